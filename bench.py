@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ray-surface intersections/sec on the north-star workload (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 With --gpus N > 1 and no launcher (no WORLD_SIZE in the environment) the process that was started
@@ -48,6 +48,12 @@ Other kinds of step, untimed side runs: `value_replay` (the same ray set again a
 `value_synchronous` (one blocking prt_trace at a time: what one RayTracer.trace(), pyrayt/_pyrayt.py:329-339, costs in
 a running design loop), `value_cold` (a fresh scene's first trace), `value_no_hints`, `value_first_trace`.
 
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step of the final repetition, right
+behind the timed region (`dump_outputs`): DIR/rows.npy, the record rows (15, R) float64 -- a frame of more than
+DUMP_ROWS_MAX rows as a fixed, seeded sample of its rows, whose indices are DIR/row_index.npy -- DIR/counts.npy (rows
+per generation) and DIR/column_sums.npy (the NaN-skipping sums of every column over the whole frame); several ranks
+write their own shard's files with a _rank<r> suffix.  The inputs are seeded: the same arguments give the same arrays.
+
 rank 0 prints ONE JSON line.  `roofline` is for the generation kernel(s): algorithmic bytes (328 B per ray alive at
 generation entry that is recorded and goes on) over the busy time above; the bytes the kernel
 actually moves (it carries 10 of the 13 state rows between generations) are reported next to it as
@@ -82,6 +88,8 @@ BYTES_PER_RAY_GENERATION = 328  # 104 B state read + 104 B
 STATE_BYTES, STATE_BYTES_LEAN, STATE_BYTES_FULL, ROW_BYTES = 80, 56, 104, 120
 HBM_PEAK_GBS = 8000.0           # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 COPY_GBS = 6300.0               # what a bare copy with the kernel's row pattern reaches (tools/ubench/copy_f64: 5.7-6.4 TB/s)
+DUMP_ROWS_MAX = 1 << 18         # --dump-outputs: rows written at most (15 x 8 B each: 31.5 MB), split over the ranks
+DUMP_SEED = 20240917            # --dump-outputs: the seed of the sample of a larger frame
 
 
 # What one rank does at the shard sizes of the 1/2/4/8 curve, measured on ONE MI355X (profiles/r6/shard_scaling.txt:
@@ -163,7 +171,37 @@ def parse_args():
                          "value_replay form)")
     ap.add_argument("--side-steps", type=int, default=40,
                     help="steps of each untimed side measurement (synchronous / no hints / changing ray count)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the rows and counts the last timed step returned as DIR/<name>.npy (a seeded sample of "
+                         "a frame over %d rows; see the module docstring)" % DUMP_ROWS_MAX)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(directory, rows, counts, rank=0, world=1):
+    """--dump-outputs: the (15, R) float64 record rows and the rows per generation of one trace, as .npy files in
+    `directory`.  Over DUMP_ROWS_MAX / world rows the rows are a sample: a seeded choice of row indices, sorted, also
+    written (row_index.npy).  column_sums.npy covers the whole frame.  Returns the names written."""
+    import numpy as np
+    import torch
+
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    total, keep = int(rows.shape[1]), max(1, DUMP_ROWS_MAX // max(world, 1))
+    if total > keep:
+        index = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=keep, replace=False))
+        picked = rows.index_select(1, torch.from_numpy(index).to(rows.device))
+    else:
+        index, picked = np.arange(total), rows
+    arrays = {"rows": picked.double().cpu().numpy(),
+              "row_index": index.astype(np.float64),
+              "counts": np.asarray(list(counts), dtype=np.float64),
+              "column_sums": torch.nansum(rows.double(), dim=1).cpu().numpy()}
+    for name, array in arrays.items():
+        np.save(os.path.join(directory, name + suffix + ".npy"), np.ascontiguousarray(array))
+    return sorted(name + suffix for name in arrays)
 
 
 def summary_file(seed):
@@ -605,6 +643,8 @@ def main():
         dist.all_reduce(slowest, op=dist.ReduceOp.MAX)
         for r, took in zip(repetitions, slowest.tolist()):
             r.elapsed = took
+    # what the last timed step handed its caller, before anything else records into its block
+    dumped = dump_outputs(args.dump_outputs, rows, counts, rank, world) if args.dump_outputs else None
     # the rows the LAST repetition's last steps left: one step per ray set of the rotation (verified further down,
     # before anything else records into those blocks)
     last_timed = {}
@@ -1142,6 +1182,8 @@ def main():
         },
         "end_to_end_trace": end_to_end,
     }
+    if dumped:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     # every repetition of the timed region (`value` / `ms_per_step` are the median one's)
     line["repetitions"] = {"n": len(repetitions), "ms_per_step": [r.elapsed / args.steps * 1e3 for r in repetitions],
                            "value_min": rows_timed / max(r.elapsed for r in repetitions),

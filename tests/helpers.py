@@ -105,3 +105,31 @@ def assert_frames_match(got, want, atol=ATOL, what="frame"):
         assert np.array_equal(got[:, col], want[:, col]), f"{what}: exact column {col} differs"
     assert np.allclose(got, want, rtol=0, atol=atol, equal_nan=True), (
         f"{what}: max abs diff {np.nanmax(np.abs(got - want))}")
+
+
+def host_rank_worker(rank, world, port, name, n, mode, result_dir, gpu_ranks):
+    """A gloo rank of tests/test_gpu_distributed.py that may stay off the GPU.  Ranks below `gpu_ranks` run that
+    module's _worker (trace their shard on cuda:0, assemble on the device); the others load the rows the parent traced
+    for their shard (shard_rows_<rank>.npy, shard_counts_<rank>.npy) and assemble on the host.  Lives here, not in the
+    test module, so that a host rank never imports that module (its skip conditions ask torch for the device count)."""
+    if rank < gpu_ranks:
+        from test_gpu_distributed import _worker
+
+        return _worker(rank, world, port, name, n, mode, result_dir)
+    import torch
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from pyrayt_amd import distributed as pdist
+
+        rows = torch.from_numpy(np.load(os.path.join(result_dir, f"shard_rows_{rank}.npy")))
+        counts = np.load(os.path.join(result_dir, f"shard_counts_{rank}.npy")).tolist()
+        full, full_counts = pdist.assemble_rows(rows, counts, 10, pdist.resolve_group(None), mode)  # (LIMIT there)
+        assert not full.is_cuda
+        np.save(os.path.join(result_dir, f"rows_{rank}.npy"), full.numpy())
+        np.save(os.path.join(result_dir, f"counts_{rank}.npy"), np.array(full_counts))
+    finally:
+        dist.destroy_process_group()

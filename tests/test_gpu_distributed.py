@@ -407,10 +407,12 @@ def _stats_worker(rank, world, port, name, n, rays_per_source, result_dir):
         dist.destroy_process_group()
 
 
+# (at most six processes may hold the GPU at once, this one included: five ranks at most; at five, shards of 8000 rays
+# split sources of 5000 between ranks)
 @pytest.mark.parametrize("name,n,rays_per_source,world", [("config2", 20011, 2500, 2), ("config3", 9001, None, 3),
-                                                          ("config2", 40000, 5000, 8)])
+                                                          ("config2", 40000, 5000, 5)])
 def test_sharded_group_stats_on_the_gpu(tmp_path, name, n, rays_per_source, world):
-    """2, 3 and 8 ranks sharing the one GPU (gloo adds the sums): every rank gets the single-rank statistics."""
+    """2, 3 and 5 ranks sharing the one GPU (gloo adds the sums): every rank gets the single-rank statistics."""
     import torch.multiprocessing as mp
 
     from pyrayt_amd import engine
@@ -570,22 +572,37 @@ def test_rccl_sharded_group_stats_across_real_devices(tmp_path):
 
 
 # ---- the BASELINE partitions at world 8 with real HIP traces: eight ranks sharing the one GPU ---------------------
+# At most six processes may hold the GPU at once, this one included: four ranks trace and assemble on the device
+# (_worker), the shards of the other four are traced here, one fresh scene each as a rank would, and those ranks
+# assemble on the host without ever opening the GPU (helpers.host_rank_worker).
+GPU_RANKS_AT_WORLD_EIGHT = 4
+
+
 @pytest.mark.parametrize("name,n,mode", [("config4", 8 * 512, "all"), ("config5", 16001, "all")])
 def test_baseline_partitions_at_world_eight_sharing_one_gpu(tmp_path, name, n, mode):
     """BASELINE config 4 (8 wavelengths, one per rank: contiguous id shards give exactly that) and config 5
-    (generation_limit 10) over 8 ranks; the blocks travel over gloo, prt_place_rows orders them on the device."""
+    (generation_limit 10) over 8 ranks; the blocks travel over gloo, prt_place_rows orders them on the device of
+    every rank that holds the GPU (the host ranks order them with the indexed copy)."""
     import torch.multiprocessing as mp
 
+    import helpers
+    from pyrayt_amd import distributed as pdist
     from pyrayt_amd import engine
 
     world = 8
     per_call = n // 8 if name == "config4" else n
-    mp.start_processes(_worker, args=(world, _free_port(), name, per_call, mode, str(tmp_path)), nprocs=world,
-                       join=True, start_method="spawn")
     snap, rays = _scene_and_rays(name, per_call)
+    for rank in range(GPU_RANKS_AT_WORLD_EIGHT, world):
+        lo, hi = pdist.shard_bounds(rays.shape[1], rank=rank, world=world)
+        scene = engine.DeviceScene(snap)
+        shard_rows, shard_counts = scene.trace(torch.from_numpy(np.ascontiguousarray(rays[:, lo:hi])).to("cuda:0"), LIMIT)
+        assert scene.trace_stats()["variant"] == 1
+        np.save(tmp_path / f"shard_rows_{rank}.npy", shard_rows.cpu().numpy())
+        np.save(tmp_path / f"shard_counts_{rank}.npy", np.array(shard_counts, dtype=np.int64))
+        scene.close()
+    mp.start_processes(helpers.host_rank_worker, args=(world, _free_port(), name, per_call, mode, str(tmp_path),
+                                                       GPU_RANKS_AT_WORLD_EIGHT), nprocs=world, join=True, start_method="spawn")
     if name == "config4":
-        from pyrayt_amd import distributed as pdist
-
         for rank in range(world):
             lo, hi = pdist.shard_bounds(rays.shape[1], rank=rank, world=world)
             assert np.all(rays[10, lo:hi] == np.linspace(0.44, 0.75, 8)[rank])  # one source / wavelength per rank
