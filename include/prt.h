@@ -170,7 +170,10 @@ void prt_scene_destroy(prt_scene* scene);
  * scene's tables in place: device buffers, pinned memory, events and what the scene learnt from its
  * previous trace stay.  Returns 0, or 1 -- scene untouched -- when the snapshot does not have the old
  * one's shape (a table or program would change size): build a new scene then.  Synchronises the
- * device (the previous trace may still be reading the tables); refused while a trace is in flight.
+ * device (the previous trace may still be reading the tables); refused while a trace is in flight.  The record plans
+ * of the scene's tickets (prt_trace_set_plan) stay in force and are resolved again against the new snapshot: they
+ * name surfaces by id, so after a reordered component list they still pass the rows of the same surfaces, and an id
+ * the new snapshot no longer has (a part replaced by a new one) passes no row.
  * options: NULL = keep the scene's. */
 int prt_scene_update(prt_scene* scene, const prt_prim* prims, int n_prims, const prt_node* nodes, int n_nodes,
                      const int32_t* roots, int n_roots, const prt_material* mats, int n_mats,
@@ -415,8 +418,10 @@ int prt_trace_batch_busy(const prt_scene* scene, int device, double* out4);
  *                                 PRT_FRAME_AXIS_INTERCEPT; < 0: none), ms_transform (0 none, 1 sin) and ms_about:
  *                                 rows with a finite v, sum v, sum v^2.
  *                     Sums are additive over generations (one set of pivots): "the rows of the last generation" are
- *                     the block of the highest generation whose count is not zero; prt_frame_finish turns a block's
- *                     first nine into the statistics of prt_frame_stats.
+ *                     the block of the highest generation whose count is not zero -- the last generation in which a row
+ *                     passed the filter, which is lower than the frame's last generation when rays that miss the
+ *                     listed surfaces live on; prt_frame_finish turns a block's first nine into the statistics of
+ *                     prt_frame_stats.
  * A plan belongs to a ticket (prt_trace = ticket 0) of a scene on a device and stays in force until replaced; NULL
  * removes it.  Traces under a plan run on the fused path only (PRT_TRACE_UNFUSED / COUNT_PATHS: PRT_ERR_ARG) and
  * learn their own dense-mode hints; without a plan nothing changes -- those kernels do not know about plans.

@@ -91,6 +91,7 @@ struct TraceTicket {
   size_t sink_slot_bytes = 0;
   double* sums_out = nullptr;         // the caller's (limit, n_groups, SINK_STATS) block
   unsigned long long plan_key = 0;    // identifies the plan the scene's plan hints were learnt under
+  int64_t plan_surfaces[8] = {0};     // the plan's surface ids: resolved to primitive indices again by every prt_scene_update
 };
 
 struct DeviceCopy {
@@ -1119,6 +1120,8 @@ extern "C" int prt_scene_set_index_tables(prt_scene* s, const int64_t* ranges, i
   return PRT_OK;
 }
 
+static void plan_resolve(const prt_scene* s, TraceTicket* t);  // (prt_trace_runtime.hpp)
+
 // The same scene with other numbers in it (a part moved, a radius or a glass changed): recompile on
 // the host and overwrite the tables in place -- device buffers, the host mirror, the events, the
 // hints of the previous trace and the telemetry all stay.  Returns 1 (and leaves the scene as it
@@ -1221,6 +1224,11 @@ extern "C" int prt_scene_update(prt_scene* s, const prt_prim* prims, int n_prims
   if (s->table_ranges.size() != 2 * s->mats.size()) {
     s->table_ranges.clear(); s->table_wavelengths.clear(); s->table_indices.clear();
   }
+  // (a record plan names surfaces by id, the kernels know them by primitive index: a reordered component list or a
+  // part replaced by another -- a new id -- moves or retires those indices, so every ticket's plan is resolved anew)
+  for (DeviceCopy& c : s->per_device)
+    for (TraceTicket& tk : c.ticket)
+      if (tk.plan_active) plan_resolve(s, &tk);
   for (size_t d = 0; d < s->per_device.size(); ++d) {
     DeviceCopy& c = s->per_device[d];
     if (!c.ready) continue;

@@ -218,6 +218,20 @@ static unsigned long long plan_key_of(const PlanDev& p) {  // what the plan's de
   return h | 1ull;
 }
 
+// The plan's surface ids as primitive indices of the scene's current tables -- at prt_trace_set_plan, and again after
+// every prt_scene_update (which may reorder the primitives or give a part a new id) -- and the key of its hints.
+static void plan_resolve(const prt_scene* s, TraceTicket* t) {
+  PlanDev& p = *t->plan_host;
+  for (int k = 0; k < p.n_rec; ++k) {
+    // (a surface id that is none of the scene's passes no row: a primitive index no ray can hit)
+    p.rec_prims[k] = -2;
+    for (size_t q = 0; q < s->dev_prims.size(); ++q)
+      if ((int64_t)s->dev_prims[q].surface_id == t->plan_surfaces[k]) p.rec_prims[k] = (int32_t)q;
+  }
+  t->plan_key = plan_key_of(p);
+  t->plan_dirty = true;
+}
+
 extern "C" int prt_trace_set_plan(prt_scene* s, int device, int ticket, const prt_record_plan* plan) {
   DeviceCopy* c;
   int rc = on_device(s, device, &c, true);
@@ -242,12 +256,6 @@ extern "C" int prt_trace_set_plan(prt_scene* s, int device, int ticket, const pr
   PlanDev p;
   memset(&p, 0, sizeof(p));
   p.n_rec = plan->n_surfaces;
-  for (int k = 0; k < plan->n_surfaces; ++k) {
-    // (a surface id that is none of the scene's passes no row: a primitive index no ray can hit)
-    p.rec_prims[k] = -2;
-    for (size_t q = 0; q < s->dev_prims.size(); ++q)
-      if ((int64_t)s->dev_prims[q].surface_id == plan->surfaces[k]) p.rec_prims[k] = (int32_t)q;
-  }
   p.store_rows = plan->store_rows ? 1 : 0;
   p.n_groups = plan->n_groups;
   p.rays_per_source = plan->rays_per_source;
@@ -278,10 +286,10 @@ extern "C" int prt_trace_set_plan(prt_scene* s, int device, int ticket, const pr
   if (!t->plan_host) t->plan_host = (PlanDev*)malloc(sizeof(PlanDev));
   if (!t->plan_host) return fail(PRT_ERR_HIP, "out of host memory");
   *t->plan_host = p;
+  for (int k = 0; k < plan->n_surfaces; ++k) t->plan_surfaces[k] = plan->surfaces[k];
   t->sums_out = plan->sums_out;
-  t->plan_key = plan_key_of(p);
-  t->plan_dirty = true;
   t->plan_active = true;
+  plan_resolve(s, t);
   return PRT_OK;
 }
 
@@ -342,6 +350,9 @@ static int fused_launch_batch(prt_scene* s, DeviceCopy* c, TraceTicket* t) {
       // lists: with no rows to place, dead lanes cost the next generation nothing but their slots).
       int assume = 0;
       if (t->use_hints && gg < (int)s->plan_hint_mode.size()) assume = s->plan_hint_mode[gg];
+      // (behind a generation launched with bit 5 the kept rays arrive dead: a tile that holds one carries less than all
+      // of its rays, so of the dense forms only "none goes on" can hold there -- anything else compacts by look-back)
+      if (gg > 0 && (t->launch_mode[gg - 1] & 32) && (assume & 15) != 2) assume = 0;
       t->launch_mode[gg] = (char)assume;
       s->plan_launches += 1;
       s->plan_dense_launches += assume ? 1 : 0;
@@ -537,7 +548,7 @@ static int64_t fused_finish(prt_scene* s, DeviceCopy* c, TraceTicket* t, int64_t
         char mode = (char)(carry_form && (rec_all || rec_none) ? (carry_form | (rec_none ? 16 : 0)) : 0);
         if (!t->plan_host->store_rows && !keep_absorbed) {
           // (no rows to place: a generation that loses only a few absorbed rays keeps them next time and stays dense;
-          // one launched that way is seen to carry everything and stays that way -- every 64th trace of the scene under
+          // one launched that way is seen to carry everything and stays that way -- every 32nd trace of the scene under
           // a plan is launched without the bit, so that a generation that has begun to absorb in numbers is found out)
           const bool kept = (t->launch_mode[t->g + b] & 32) != 0;
           const bool sparse = lost > 0 && host_gen[b].n_carry > 0 && lost * 64 <= host_gen[b].n_in;

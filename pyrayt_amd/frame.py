@@ -326,7 +326,8 @@ class SinkStats:
         self.pivots = np.zeros((self.sums.shape[1], 3)) if piv is None else np.array(piv, dtype=float)
 
     def last_generation_number(self):
-        """The highest generation that counted a row (None: no row passed)."""
+        """The highest generation that counted a row the plan let pass (None: no row passed).  With a surface filter
+        this may be lower than the frame's last generation: rays that miss the filtered surfaces can live on."""
         working = np.nonzero(self.sums[:, :, 0].sum(axis=1) > 0)[0]
         return int(working[-1]) if len(working) else None
 
@@ -344,7 +345,7 @@ class SinkStats:
     def group_stats(self, generation=None):
         """The table of ``DeviceFrame.group_stats`` (count, y, z, rms_radius, focus, focus_std, wavelength, intensity per
         source) for the rows the plan let pass, of one generation (a number, or "last": the highest that counted a
-        row) or of all of them (None).  Same arithmetic as ``k_frame_finish`` (csrc/prt_frame.hpp)."""
+        row the plan let pass -- not necessarily the frame's last generation) or of all of them (None).  Same arithmetic as ``k_frame_finish`` (csrc/prt_frame.hpp)."""
         frame = pd.DataFrame(self.values(generation))
         frame.index.name = "source_id"
         return frame
@@ -371,12 +372,13 @@ class SinkStats:
 
     def mean_square(self, generation=None, per_source=False):
         """``np.mean(np.square(f(rows) - about))`` of the plan's ``mean_square`` quantity (``DeviceFrame.mean_square``):
-        a float, or per source a DataFrame (count, mean, mean_square)."""
+        a float over the rows of every group, or per source a DataFrame (count, mean, mean_square)."""
         s = self._block(generation)
+        if not per_source:  # (over the rows of every group, as DeviceFrame.mean_square without rays_per_source)
+            count = s[:, 9].sum()
+            return float(s[:, 11].sum() / count) if count > 0 else float("nan")
         with np.errstate(invalid="ignore", divide="ignore"):
             mean, mean_square = s[:, 10] / s[:, 9], s[:, 11] / s[:, 9]
-        if not per_source:
-            return float(mean_square[0])
         frame = pd.DataFrame({"count": s[:, 9].astype(np.int64), "mean": mean, "mean_square": mean_square})
         frame.index.name = "source_id"
         return frame

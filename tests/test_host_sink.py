@@ -116,3 +116,32 @@ def test_scaling_model_of_the_bench_line():
     between = bench.scaling_model(1_000_000, 3, 3.0e6)                               # a shard size the table does not hold
     assert bench.scaling_model(1_000_000, 4, 3.0e6)["overlapped"]["ms_per_step"] < between["overlapped"]["ms_per_step"] \
         < bench.scaling_model(1_000_000, 2, 3.0e6)["overlapped"]["ms_per_step"]
+
+
+@pytest.mark.parametrize("name", ["config3", "config4", "mirrors_and_stops"])
+@pytest.mark.parametrize("n_groups", [2, 3, 4])
+def test_mean_square_over_every_group_equals_pandas_on_all_rows(name, n_groups):
+    """SinkStats.mean_square(per_source=False) with more than one group: the mean over the rows of EVERY group -- what
+    DeviceFrame.mean_square gives without rays_per_source -- not the value of group 0; NaN when no row counted."""
+    fx = helpers.load(f"scene_{name}.npz")
+    frame, limit = fx["frame"], int(fx["generation_limit"])
+    n = fx["rays0"].shape[1]
+    rays_per_source = -(-n // n_groups)                  # (every row in one of the groups)
+    column, about = "y1", 0.125
+    stats = SinkStats(sums_of(frame, None, limit, rays_per_source, n_groups, ms=(column, about)))
+    table = pd.DataFrame(frame, columns=COLUMNS)
+    groups = np.floor(table["id"] / rays_per_source)
+    assert groups.nunique() > 1                           # (the groups really split the rows)
+    last = int(table["generation"].max())
+    for generation in [None, "last"] + list(range(limit)):
+        number = last if generation == "last" else generation
+        rows = table if number is None else table.loc[table["generation"] == number]
+        v = rows[column] - about
+        v = v[np.isfinite(v)]
+        got = stats.mean_square(generation, per_source=False)
+        if len(v) == 0:
+            assert np.isnan(got), (name, generation, got)
+        else:
+            assert np.isclose(got, np.mean(np.square(v.to_numpy())), rtol=1e-12, atol=0.0), (name, generation, got)
+    # no row at all: NaN, not a division warning or 0
+    assert np.isnan(SinkStats(np.zeros((limit, n_groups, engine.SINK_STATS))).mean_square(None))
