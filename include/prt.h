@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 220 /* 0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 230 /* 0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -535,6 +535,40 @@ int prt_frame_finish(int device, const double* sums, const double* pivots, int n
 int prt_frame_mean_square(int device, const double* rows, int64_t ld, int64_t n_rows, double surface,
                           double generation, double rays_per_source, int n_groups, int quantity, int transform,
                           double about, double* out, void* stream);
+/* Histograms of the frame: what a spot diagram, an irradiance map or examples/lens_design.ipynb cell 19
+ * (`ray_set.hist('y1')`) computes from the rows, with numpy's bin rule (np.histogram / np.histogram2d): bin i takes
+ * v when edges[i] <= v < edges[i+1], the last bin also takes v == edges[n]; values outside [edges[0], edges[n]], NaN
+ * and +-inf are not counted; in two dimensions a row counts only when both of its values fall in a bin.
+ *
+ * prt_frame_range: the smallest and the largest FINITE value of one quantity (a frame column 0..14 or
+ * PRT_FRAME_AXIS_INTERCEPT) over the rows that pass the surface / generation filter (NaN = every row), into
+ * minmax_out = 2 doubles of DEVICE memory; +inf, -inf when no value is finite.  Integer atomics on an
+ * order-preserving image of the doubles: the same result on every run.  Stream-ordered.
+ *
+ * prt_frame_histogram: x_quantity (and y_quantity; -1: one dimension, y_edges / ny / y_uniform ignored) binned against
+ * x_edges[0..nx] (y_edges[0..ny]): HOST arrays, finite and non-decreasing (else PRT_ERR_ARG), copied into the
+ * workspace (prt_frame_histogram_workspace_bytes(n_groups, nx, ny, with_weights) device bytes; ny < 1 for one
+ * dimension) before the call returns.  x_uniform / y_uniform: the edges are evenly spaced (np.linspace), and the bin
+ * is guessed by arithmetic and then corrected against the edges, as numpy's own fast path does -- the answer is the
+ * edges' either way.  Rows pass the same surface / generation filter as prt_frame_reduce and are grouped by
+ * floor(id / rays_per_source) (rays_per_source <= 0: one group; a row whose group is outside [0, n_groups) is not
+ * counted).  counts_out: DEVICE int64 (n_groups, nx, ny) (ny = 1 in one dimension), overwritten: exact, and the
+ * same on every run.  weight_column 0..14: weights_out, DEVICE float64 of the same shape, overwritten with the sums
+ * of that column per bin; -1 (and weights_out NULL): counts only.  The weight sums are float64 adds whose order
+ * depends on the schedule: exact -- and then the same on every run -- when the weights are integers and every sum
+ * stays below 2^53 (every built-in source emits intensity 100), otherwise equal up to the last bits.
+ * The histogram is privatised in LDS (a window per workgroup of 65 536 bins counts only when a workgroup's share of
+ * the rows is below 2^16 -- 16-bit tallies --, else 32 768, and 10 922 with weights; one global add per non-zero bin
+ * and workgroup, or -- counts only, large windows -- per-workgroup slabs in a stream-ordered scratch block
+ * (hipMallocAsync) added up by a second kernel); more bins than a window are done in several passes over the rows.
+ * All arguments are checked before a device is touched.  Stream-ordered. */
+int prt_frame_range(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                    int quantity, double* minmax_out, void* stream);
+int64_t prt_frame_histogram_workspace_bytes(int n_groups, int nx, int ny, int with_weights);
+int prt_frame_histogram(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                        double rays_per_source, int n_groups, int x_quantity, const double* x_edges, int nx,
+                        int x_uniform, int y_quantity, const double* y_edges, int ny, int y_uniform,
+                        int weight_column, int64_t* counts_out, double* weights_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

@@ -275,6 +275,124 @@ class DeviceFrame:
         frame.index.name = "source_id"
         return frame
 
+    # --- histograms (examples/lens_design.ipynb cell 19: ``ray_set.hist('y1')``; spot diagrams, irradiance maps) --------
+    def histogram(self, x, bins=10, range=None, weights=None, density=False, surface=None, generation=None,
+                  rays_per_source=None, n_groups=None, group=None):
+        """``np.histogram`` of one quantity of the selected rows, binned on the device (``prt_frame_histogram``): returns
+        ``(hist, edges)`` as float64 numpy arrays, equal to numpy's -- counts exactly.
+
+        x: a column name or ``"axis_intercept"``; bins: an int or an edge array; range: ``(lo, hi)`` or None; weights:
+        None or a column name (the sums are float64 adds: exact for integer weights such as the built-in sources'
+        intensity 100, otherwise equal to numpy's up to the last bits); density: numpy's normalisation.  The edges are
+        numpy's own (``np.histogram_bin_edges``), with numpy's ``ValueError``s; string estimators ("auto", "fd", ...)
+        are not supported.  ``range=None`` with an int ``bins`` takes the range of the FINITE values of the selected
+        rows (``prt_frame_range``): numpy raises for input with NaN or inf instead, and pandas' ``Series.hist`` drops the
+        NaN first, which is what this matches; no finite value gives (0, 1), a single value v gives (v - 0.5, v + 0.5)
+        as in numpy.  surface / generation select rows as in ``mean_square`` (``generation="last"``: the highest
+        generation of this frame).  With ``rays_per_source`` the histogram gains a leading axis of ``n_groups`` groups
+        (``id // rays_per_source``; default as in ``group_stats``).  ``group``: a ``torch.distributed`` group whose
+        ranks each hold a share of the rows (a trace with ``gather="none"``): the automatic range is taken over every
+        rank's rows and the counts and sums are added, so every rank gets the histogram of the whole frame."""
+        hist, edges = self._histogram((x,), bins, range, weights, density, surface, generation, rays_per_source,
+                                      n_groups, group)
+        return hist, edges[0]
+
+    def histogram2d(self, x, y, bins=10, range=None, weights=None, density=False, surface=None, generation=None,
+                    rays_per_source=None, n_groups=None, group=None):
+        """``np.histogram2d`` of two quantities of the selected rows (a spot diagram: ``"y1", "z1"``; weighted by
+        ``"intensity"``, an irradiance map): returns ``(H, xedges, yedges)``, H of shape (nx, ny), or (n_groups, nx,
+        ny) with ``rays_per_source``.  bins: an int, a pair of ints, an edge array, or a pair of edge arrays (or an
+        int and an array); range: a pair of ``(lo, hi)``, either of which may be None (the finite range of that
+        quantity, as in ``histogram``).  A row counts only when both of its values fall in a bin.  Everything else as
+        in ``histogram``."""
+        hist, edges = self._histogram((x, y), bins, range, weights, density, surface, generation, rays_per_source,
+                                      n_groups, group)
+        return hist, edges[0], edges[1]
+
+    def _histogram(self, quantities, bins, range, weights, density, surface, generation, rays_per_source, n_groups,
+                   group):
+        import torch
+
+        from . import engine
+
+        codes = [15 if q == "axis_intercept" else _INDEX[q] for q in quantities]
+        needed = [name for q in quantities for name in (("x0", "y0", "x_tilt", "y_tilt") if q == "axis_intercept" else (q,))]
+        if weights is not None:
+            needed.append(weights)
+        if surface is not None:
+            needed.append("surface")
+        if rays_per_source:
+            needed.append("id")
+        self._need(*needed)
+        frame = self
+        if generation == "last":
+            generation = self.last_generation_number()
+            if group is not None:
+                generation = int(_all_reduce_max(-1.0 if generation is None else float(generation), group, None,
+                                                 self.rows.device))
+            if generation is None or generation < 0:
+                generation = 0
+        if generation is not None:
+            if self.rows_per_generation:  # (generation-major: one generation's rows are a slice, no filter needed)
+                start = sum(self.rows_per_generation[:int(generation)])
+                size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+                frame = DeviceFrame(self.rows[:, start:start + size], None, self.written)
+                generation = None
+            else:
+                self._need("generation")
+        if rays_per_source:
+            if n_groups is None:
+                top = float(self["id"].max()) if len(self) else -1.0
+                if group is not None:
+                    top = _all_reduce_max(top, group, None, self.rows.device)
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        rows = frame.rows if frame.rows.stride(1) == 1 or frame.rows.shape[1] <= 1 else frame.rows.contiguous()
+        dev = rows.device
+        ld, n_rows = max(rows.stride(0), rows.shape[1], 1), rows.shape[1]
+        nan = float("nan")
+        surface = nan if surface is None else float(surface)
+        generation = nan if generation is None else float(generation)
+        stream = engine._stream_ptr(torch, dev)
+        lib = engine.library()
+
+        def finite_range(axis):
+            box = torch.empty(2, dtype=torch.float64, device=dev)
+            engine._check(lib.prt_frame_range(dev.index or 0, rows.data_ptr(), ld, n_rows, surface, generation,
+                                              codes[axis], box.data_ptr(), stream))
+            if group is not None:
+                box[1:].neg_()
+                box = _all_reduce_min(box, group)
+                box[1:].neg_()
+            lo, hi = box.cpu().tolist()
+            return (0.0, 1.0) if lo > hi else (lo, hi)
+
+        edges, uniform = histogram_edges(bins, range, len(quantities), finite_range)
+        nx = len(edges[0]) - 1
+        ny = len(edges[1]) - 1 if len(edges) == 2 else 0
+        shape = (n_groups, nx, max(ny, 1))
+        counts = torch.empty(shape, dtype=torch.int64, device=dev)
+        sums = torch.empty(shape, dtype=torch.float64, device=dev) if weights is not None else None
+        work = torch.empty(int(engine._check(lib.prt_frame_histogram_workspace_bytes(n_groups, nx, ny, sums is not None))),
+                           dtype=torch.uint8, device=dev)
+        y_edges = edges[1] if ny else None
+        engine._check(lib.prt_frame_histogram(
+            dev.index or 0, rows.data_ptr(), ld, n_rows, surface, generation, float(rays_per_source or 0), n_groups,
+            codes[0], edges[0].ctypes.data, nx, int(uniform[0]),
+            codes[1] if ny else -1, None if y_edges is None else y_edges.ctypes.data, ny, int(ny and uniform[1]),
+            -1 if weights is None else _INDEX[weights], counts.data_ptr(), None if sums is None else sums.data_ptr(),
+            work.data_ptr(), stream))
+        out = counts if sums is None else sums
+        if group is not None:
+            out = _all_reduce_sum(out, group)
+        hist = out.cpu().numpy().astype(np.float64)
+        if not ny:
+            hist = hist[:, :, 0]
+        if density:
+            hist = np.stack([_density(h, edges) for h in hist])
+        return (hist if rays_per_source else hist[0]), edges
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -382,6 +500,68 @@ class SinkStats:
         frame = pd.DataFrame({"count": s[:, 9].astype(np.int64), "mean": mean, "mean_square": mean_square})
         frame.index.name = "source_id"
         return frame
+
+
+def histogram_edges(bins, range, dims, finite_range):
+    """The bin edges numpy's np.histogram (dims 1) / np.histogram2d (dims 2) would use, with numpy's own errors, and per
+    axis whether they are evenly spaced (bins given as a count).  finite_range(axis) -> (lo, hi): the range of an axis
+    whose bins are a count and whose range is None (numpy would take the data's min and max)."""
+    if isinstance(bins, str):
+        raise ValueError(f"string bin estimators ({bins!r}) are not supported: give a number of bins or the edges")
+    if dims == 1:
+        uniform = np.ndim(bins) == 0
+        if uniform and range is None:
+            if not bins >= 1:  # (numpy's message, before any range is looked for)
+                raise ValueError("`bins` must be positive, when an integer")
+            range = finite_range(0)
+        return [_float_edges(np.histogram_bin_edges(np.empty(0), bins, range=range))], (uniform,)
+    try:  # np.histogram2d's reading of `bins`
+        count = len(bins)
+    except TypeError:
+        count = 1
+    if count != 1 and count != 2:
+        bins = [np.asarray(bins), np.asarray(bins)]
+    per_axis = [bins, bins] if count == 1 else list(bins)
+    if any(isinstance(b, str) for b in per_axis):
+        raise ValueError("string bin estimators are not supported: give numbers of bins or the edges")
+    ranges = [None, None] if range is None else list(range)
+    if len(ranges) != 2:
+        raise ValueError("range: a pair of (lo, hi), either of which may be None")
+    uniform = tuple(np.ndim(b) == 0 for b in per_axis)
+    for axis in (0, 1):
+        if uniform[axis] and ranges[axis] is None:
+            if not per_axis[axis] >= 1:
+                raise ValueError(f"`bins[{axis}]` must be positive, when an integer")
+            ranges[axis] = finite_range(axis)
+    _, xedges, yedges = np.histogram2d(np.empty(0), np.empty(0), bins=bins, range=ranges)
+    return [_float_edges(xedges), _float_edges(yedges)], uniform
+
+
+def _float_edges(edges):
+    return np.ascontiguousarray(edges, dtype=np.float64)  # (the kernel reads float64 edges; integer edges are exact)
+
+
+def _density(hist, edges):
+    """numpy's density normalisation of one histogram (the same operations in the same order)."""
+    if len(edges) == 1:
+        return hist / np.diff(edges[0]) / hist.sum()
+    s = hist.sum()
+    hist = hist / np.diff(edges[0]).reshape(-1, 1)
+    hist = hist / np.diff(edges[1]).reshape(1, -1)
+    hist /= s
+    return hist
+
+
+def _all_reduce_min(tensor, group):
+    """Element-wise smallest of a small device tensor over the ranks of a torch.distributed group."""
+    import torch.distributed as dist
+
+    if dist.get_backend(group) == "nccl":
+        dist.all_reduce(tensor, op=dist.ReduceOp.MIN, group=group)
+        return tensor
+    host = tensor.cpu()
+    dist.all_reduce(host, op=dist.ReduceOp.MIN, group=group)
+    return host.to(tensor.device)
 
 
 def _all_reduce_sum(tensor, group):
