@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 230 /* 0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -569,6 +569,53 @@ int prt_frame_histogram(int device, const double* rows, int64_t ld, int64_t n_ro
                         double rays_per_source, int n_groups, int x_quantity, const double* x_edges, int nx,
                         int x_uniform, int y_quantity, const double* y_edges, int ny, int y_uniform,
                         int weight_column, int64_t* counts_out, double* weights_out, void* workspace, void* stream);
+/* Optical path and wavefront error of the frame (no counterpart upstream: the examples study aberrations through spot
+ * moments and axis intercepts, examples/lens_design.ipynb cells 11-20).  The rows are pyrayt/_pyrayt.py:168-186's:
+ * segment start x0..z0, end x1..z1, unit direction x_tilt..z_tilt, the index of the medium it runs through, the ray id.
+ *
+ * Definitions.
+ * Segment and OPL: a row's segment OPL is index * sqrt(dx*dx + dy*dy + dz*dz), d = (x1,y1,z1) - (x0,y0,z0), evaluated
+ *   in that order.  A row's cumulative OPL is its own segment OPL plus the cumulative OPL of the same id's row in the
+ *   previous generation; a generation-0 row has only its own.  The rows are the contract, so the 1e-6 relaunch offset
+ *   (pyrayt/_pyrayt.py:449) is part of x0 as written and not added back.
+ * Reference sphere: for a row Q = (x1,y1,z1) at surface S with direction u and index n, the ray is extended backwards to
+ *   E = Q - s u on the sphere of centre P and radius R, s the larger real root (E on the side the light came from).
+ *   OPL_E = OPL_Q - n s; OPD = OPL_E - pivot, positive when the ray's path is longer.  A ray whose line misses the
+ *   sphere gets OPD = NaN and is counted apart.
+ * Pupil: the component of E - P perpendicular to the unit axis a, in the basis (e1, e2) of the plane perpendicular to
+ *   a, divided by the pupil radius (default: the group's largest radial extent); theta runs from e1 towards e2.
+ * Zernike: Noll's order and RMS normalisation (Noll 1976), Z1 = 1, Z2 = 2 rho cos theta, Z3 = 2 rho sin theta,
+ *   Z4 = sqrt(3) (2 rho^2 - 1), ..., Z11 = sqrt(5) (6 rho^4 - 6 rho^2 + 1); n_terms <= 36.
+ * P: the mean of the group's Q, or given; R: given, or the distance from P to the mean of the group's (x0,y0,z0) at S
+ *   (where the image-space segments start: a stand-in for the exit pupil).  Pivot: OPL_E of the group's first row at S
+ *   in row order that meets the sphere.
+ *
+ * prt_frame_optical_path: the cumulative OPL of every row into opl_out (DEVICE, one double a row).  The frame is whole
+ * and generation-major: rows_per_generation (HOST, n_generations counts) gives the generations' row runs; ids are
+ * integers in [id0, id0 + n_ids) (a dense accumulator and a stamp per id, in a stream-ordered scratch block).  One
+ * launch per generation, in order; an id outside the range or repeated within a generation gives PRT_ERR_ARG.  The
+ * call reads one status word back and so returns when the stream has reached its end.
+ *
+ * prt_frame_wavefront: the wavefront at the rows that pass the surface / generation filter (NaN = every row), grouped
+ * by floor(id / rays_per_source) (<= 0: one group), opl the rows' cumulative OPL (prt_frame_optical_path).  reference:
+ * DEVICE (n_groups, 3) centres, or NULL for each group's centroid of Q; radius: DEVICE (n_groups) radii, or NULL (an
+ * entry <= 0 or NaN: the default); axes: HOST 9 doubles a, e1, e2; pupil_radius 0: the group's largest radial extent.
+ * Out, DEVICE, overwritten: opd_out / pupil_out (n_rows / (n_rows, 2) capacity) hold the selected rows in row order --
+ * the OPD with the group's weighted mean taken off (piston removed) and the normalised pupil point (e1, e2); NaN for a
+ * row that misses the sphere -- group_out (n_groups, 12): P (3), R, pivot, pupil radius, rows, rows that miss, largest
+ * and smallest OPD about the pivot, first row, largest radial extent; normal_out (n_groups, n_terms (n_terms + 1) / 2
+ * + n_terms + 3): the upper triangle of Z^T W Z by rows, Z^T W OPD, sum w, sum w OPD, sum w OPD^2 (OPD about the
+ * pivot), W = 1 or the weight_column (0..14; -1: ones).  workspace: prt_frame_wavefront_workspace_bytes(n_rows,
+ * n_groups, n_terms, with_weights) device bytes.  No floating-point atomics: every output is the same, bit for bit, on
+ * every run.  All arguments are checked before a device is touched.  Stream-ordered. */
+int prt_frame_optical_path(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                           int n_generations, double id0, int64_t n_ids, double* opl_out, void* stream);
+int64_t prt_frame_wavefront_workspace_bytes(int64_t n_rows, int n_groups, int n_terms, int with_weights);
+int prt_frame_wavefront(int device, const double* rows, int64_t ld, int64_t n_rows, const double* opl, double surface,
+                        double generation, double rays_per_source, int n_groups, const double* reference,
+                        const double* radius, const double* axes, double pupil_radius, int n_terms, int weight_column,
+                        double* opd_out, double* pupil_out, double* group_out, double* normal_out, void* workspace,
+                        void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

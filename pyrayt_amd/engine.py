@@ -75,7 +75,7 @@ AXIS_INTERCEPT = 15  # PRT_FRAME_AXIS_INTERCEPT
 ERR_ROWS_CAP = -4
 ERR_UNTRACABLE = -5
 ERR_WAVELENGTH = -6
-PRT_VERSION = 230  # include/prt.h: the ABI this binding was written for
+PRT_VERSION = 240  # include/prt.h: the ABI this binding was written for
 TABLE_KEEP_FACTOR, TABLE_KEEP_MIN = 4, 64  # index tables keep earlier wavelengths up to this multiple of a ray set's own
 UNIQUE_CAP = 4096  # distinct wavelengths looked for on the device before the host sorts the whole row
 
@@ -159,6 +159,10 @@ def _declare(lib):
         "prt_frame_histogram_workspace_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
         "prt_frame_histogram": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_int, c_p, c_int, c_int,
                                         c_int, c_p, c_int, c_int, c_int, c_p, c_p, c_p, c_p]),
+        "prt_frame_optical_path": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_p]),
+        "prt_frame_wavefront_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+        "prt_frame_wavefront": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_d, c_d, c_d, c_int, c_p, c_p, c_p, c_d, c_int,
+                                        c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -181,6 +185,7 @@ EXPORTED_SYMBOLS = (
     "prt_place_workspace_bytes", "prt_place_rows", "prt_frame_reduce", "prt_frame_stats_workspace_bytes",
     "prt_frame_stats", "prt_frame_stats_sharded", "prt_frame_pivots", "prt_frame_finish", "prt_frame_mean_square",
     "prt_frame_range", "prt_frame_histogram_workspace_bytes", "prt_frame_histogram",
+    "prt_frame_optical_path", "prt_frame_wavefront_workspace_bytes", "prt_frame_wavefront",
 )
 
 

@@ -29,6 +29,7 @@ class DeviceFrame:
         self.rows = rows
         self.rows_per_generation = list(rows_per_generation or [])
         self.written = None if columns is None or len(columns) == len(COLUMNS) else tuple(sorted(columns))
+        self.origin = None  # how the frame lost rows of its trace ("where", "select", "generation", "record_only"), if it did
         if self.written is not None:
             self.columns = tuple(COLUMNS[k] for k in self.written)  # (names of the columns THIS frame holds)
 
@@ -58,8 +59,10 @@ class DeviceFrame:
         """Rows of generation g: a contiguous slice (rows are generation-major), no kernel."""
         if g < len(self.rows_per_generation):
             start = sum(self.rows_per_generation[:g])
-            return DeviceFrame(self.rows[:, start:start + self.rows_per_generation[g]],
+            part = DeviceFrame(self.rows[:, start:start + self.rows_per_generation[g]],
                                [0] * g + [self.rows_per_generation[g]], self.written)
+            part.origin = "generation"
+            return part
         return self.where(generation=g)
 
     def last_generation(self):
@@ -88,10 +91,14 @@ class DeviceFrame:
             mask = m if mask is None else (mask & m)
         if mask is None:
             return self
-        return DeviceFrame(self.rows[:, mask], None, self.written)
+        part = DeviceFrame(self.rows[:, mask], None, self.written)
+        part.origin = "where"
+        return part
 
     def select(self, mask):
-        return DeviceFrame(self.rows[:, mask], None, self.written)
+        part = DeviceFrame(self.rows[:, mask], None, self.written)
+        part.origin = "select"
+        return part
 
     # --- reductions the notebook does on the frame -------------------------------------------------
     def group_stats(self, surface=None, generation=None, rays_per_source=None, n_groups=None, group=None, comm=None):
@@ -393,6 +400,135 @@ class DeviceFrame:
             hist = np.stack([_density(h, edges) for h in hist])
         return (hist if rays_per_source else hist[0]), edges
 
+    # --- optical path and wavefront error (no counterpart upstream) --------------------------------------------------
+    def _need_whole(self, what):
+        """The optical path sums a ray's rows over every generation before the one looked at: the frame must be the
+        whole frame of a trace."""
+        if self.origin == "record_only":
+            raise ValueError(f"{what} needs every surface's rows: this frame was recorded under record_only() / a record "
+                             "plan that keeps some surfaces only (trace_wavefront() records what it needs)")
+        if self.origin is not None:
+            raise ValueError(f"{what} needs the whole frame of a trace: this frame was made by {self.origin}()")
+        if not self.rows_per_generation or sum(self.rows_per_generation) != len(self):
+            raise ValueError(f"{what} needs the whole frame of a trace: rows_per_generation is not known for this frame")
+        self._need(*_PATH_COLUMNS)
+
+    def optical_path(self):
+        """The cumulative optical path length of every row, a device tensor of ``len(self)`` float64: the row's segment
+        ``index * sqrt(dx*dx + dy*dy + dz*dz)`` plus the cumulative OPL of the same ray's row in the previous generation
+        (``prt_frame_optical_path``, one HIP launch per generation).  The rows are the contract: the 1e-6 relaunch
+        offset of ``_pyrayt.py:449`` is part of ``x0`` as written.  Ids must be integers, unique within a generation.
+        Needs the whole frame of a trace (not one made by ``where`` / ``select`` / ``generation``, nor under
+        ``record_only``): ``ValueError`` otherwise."""
+        self._need_whole("optical_path")
+        return self._optical_path()
+
+    def _optical_path(self):
+        import torch
+
+        from . import engine
+
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        opl = torch.empty(rows.shape[1], dtype=torch.float64, device=dev)
+        if rows.shape[1] == 0:
+            return opl
+        ids = rows[_INDEX["id"]]
+        id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
+        if not (np.isfinite(id0) and np.isfinite(top)):
+            raise ValueError("optical_path: an id is not an integer in the frame's id range")
+        counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
+        engine._check(engine.library().prt_frame_optical_path(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), rows.shape[1], 1), counts.ctypes.data, len(counts),
+            id0, int(top - id0) + 1, opl.data_ptr(), engine._stream_ptr(torch, dev)))
+        return opl
+
+    def wavefront(self, surface, reference="centroid", radius=None, axis=None, basis=None, pupil_radius=None,
+                  zernike=15, weights=None, generation=None, rays_per_source=None, n_groups=None, group=None):
+        """The wavefront error at ``surface`` (an id or an object with ``get_id()``; None: every row that passes
+        ``generation``): per row the optical path difference against a reference sphere and the pupil point, per
+        group (``id // rays_per_source``) its RMS, peak-to-valley and Zernike fit.  Returns a ``Wavefront``.
+
+        Each selected row's ray is extended backwards from its end point Q along its direction to the sphere of centre
+        P and radius R (``reference``: "centroid" -- the mean of the group's Q --, a point, or an (n_groups, 3) array;
+        ``radius``: None -- the distance from P to the mean of the group's segment starts (x0, y0, z0) at the surface,
+        a stand-in for the exit pupil --, a number or one per group).  OPD = the OPL there minus the group's pivot (the
+        OPL there of its first row); a ray whose line misses the sphere has OPD NaN and counts in ``n_missed``.  The
+        pupil point is E - P in the basis (e1, e2) of the plane perpendicular to ``axis`` (default: the x axis, this
+        package's optical axis, with e1 = y and e2 = z; ``basis`` = (e1, e2) or None for one made from y / z),
+        divided by ``pupil_radius`` (None: the group's largest radial extent).  ``zernike``: J <= 36 terms in Noll's
+        order and RMS normalisation, fitted by least squares on the normal equations the device accumulates
+        (``weights``: None or a column such as "intensity"); ``rank`` reports what the pupil fill can tell apart (a
+        single ring of rays cannot tell piston from defocus).  Piston is removed from ``opd``, ``rms`` and ``pv``.
+        Needs the whole frame of a trace, like ``optical_path``.  ``group=`` (sharded frames) is not supported yet."""
+        import torch
+
+        from . import engine
+
+        if group is not None:
+            raise NotImplementedError("wavefront() of a sharded frame (group=) is not supported yet")
+        terms = int(zernike)
+        if terms != zernike or not 1 <= terms <= 36:
+            raise ValueError(f"zernike: the number of terms, 1 to 36 (got {zernike!r})")
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        if pupil_radius is not None and not (np.isfinite(pupil_radius) and pupil_radius > 0):
+            raise ValueError("pupil_radius: a positive number, or None for the group's largest radial extent")
+        axes = pupil_axes(axis, basis)
+        if isinstance(reference, str) and reference != "centroid":
+            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        self._need_whole("wavefront")
+        if weights is not None:
+            self._need(weights)
+        if rays_per_source:
+            if n_groups is None:
+                top = float(self["id"].max()) if len(self) else -1.0
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        dev = self.rows.device
+        centres = None
+        if not isinstance(reference, str):
+            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
+            if centres.shape == (3,):
+                centres = centres.expand(n_groups, 3)
+            if tuple(centres.shape) != (n_groups, 3):
+                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
+            centres = centres.to(dev, torch.float64).contiguous()
+        radii = None
+        if radius is not None:
+            radii = torch.as_tensor(np.broadcast_to(np.asarray(radius, dtype=float), (n_groups,)).copy()).to(dev)
+        opl = self._optical_path()
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if generation is not None:  # (generation-major: one generation's rows are a slice)
+            start = sum(self.rows_per_generation[:int(generation)])
+            size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+            rows, opl = rows[:, start:start + size], opl[start:start + size]
+        n_rows = rows.shape[1]
+        entries = terms * (terms + 1) // 2 + terms + 3
+        lib = engine.library()
+        opd = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        pupil = torch.empty((n_rows, 2), dtype=torch.float64, device=dev)
+        record = torch.empty((n_groups, 12), dtype=torch.float64, device=dev)
+        normal = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
+        work = torch.empty(int(engine._check(lib.prt_frame_wavefront_workspace_bytes(n_rows, n_groups, terms,
+                                                                                     weights is not None))),
+                           dtype=torch.uint8, device=dev)
+        engine._check(lib.prt_frame_wavefront(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, opl.data_ptr(),
+            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
+            None if centres is None else centres.data_ptr(), None if radii is None else radii.data_ptr(),
+            axes.ctypes.data, float(pupil_radius or 0.0), terms, -1 if weights is None else _INDEX[weights],
+            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), normal.data_ptr(), work.data_ptr(),
+            engine._stream_ptr(torch, dev)))
+        record_host = engine.to_host(record).copy()
+        normal_host = engine.to_host(normal).copy()
+        n_selected = int(record_host[:, 6].sum())
+        return Wavefront(opd[:n_selected], pupil[:n_selected], record_host, normal_host, terms)
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -500,6 +636,121 @@ class SinkStats:
         frame = pd.DataFrame({"count": s[:, 9].astype(np.int64), "mean": mean, "mean_square": mean_square})
         frame.index.name = "source_id"
         return frame
+
+
+_PATH_COLUMNS = ("index", "id", "surface", "generation", "x0", "y0", "z0", "x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")
+
+
+class Wavefront:
+    """What ``DeviceFrame.wavefront`` returns.  Per selected row, in row order (device tensors): ``opd`` -- the optical
+    path difference against the reference sphere with the group's mean taken off, NaN for a ray that misses the
+    sphere -- and ``pupil`` (n, 2), the normalised pupil point (e1, e2), ``theta = atan2(pupil[:, 1], pupil[:, 0])``.
+    Per group (numpy arrays): ``rms`` and ``pv`` of the OPD, ``zernike`` (n_groups, J) -- Noll's Z1..ZJ; Z1 is the piston
+    about the pivot --, ``rank`` of the fit's normal equations, ``n_rays`` (rows that met the sphere), ``n_missed``;
+    ``reference`` (P), ``radius`` (R), ``pivot``, ``pupil_radius``; ``normal``: the device's sums (the upper triangle
+    of Z^T W Z by rows, Z^T W OPD, sum w, sum w OPD, sum w OPD^2; OPD about the pivot)."""
+
+    def __init__(self, opd, pupil, record, normal, terms):
+        self.opd, self.pupil, self.normal, self.terms = opd, pupil, normal, terms
+        self.reference, self.radius, self.pivot = record[:, 0:3], record[:, 3], record[:, 4]
+        self.pupil_radius = record[:, 5]
+        rows, self.n_missed = record[:, 6].astype(np.int64), record[:, 7].astype(np.int64)
+        self.n_rays = rows - self.n_missed
+        self.pv = record[:, 8] - record[:, 9]
+        self.zernike, self.rank = solve_normal_equations(normal, terms)
+        w, wv, wvv = normal[:, -3], normal[:, -2], normal[:, -1]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            mean = wv / w
+            self.rms = np.where(w > 0, np.sqrt(np.maximum(wvv / w - mean * mean, 0.0)), np.nan)
+
+    def to_pandas(self):
+        """One row per group: n_rays, n_missed, rms, pv, rank, Z1..ZJ."""
+        frame = pd.DataFrame({"n_rays": self.n_rays, "n_missed": self.n_missed, "rms": self.rms, "pv": self.pv,
+                              "rank": self.rank})
+        for j in range(self.terms):
+            frame[f"Z{j + 1}"] = self.zernike[:, j]
+        frame.index.name = "source_id"
+        return frame
+
+
+RANK_RCOND = 1e-10  # singular values of Z^T W Z below this share of the largest are dropped (of Z: below 1e-5)
+
+
+def solve_normal_equations(normal, terms):
+    """Per group the least-squares Zernike coefficients from the device's sums (``numpy.linalg.lstsq`` on the J x J
+    system: the minimum-norm solution where the pupil fill leaves the terms dependent) and the system's effective
+    rank (``RANK_RCOND``: the normal equations square the design matrix's condition, so lstsq's default cut-off
+    would count rounding noise as rank)."""
+    normal = np.atleast_2d(np.asarray(normal, dtype=float))
+    upper = np.triu_indices(terms)
+    tri = len(upper[0])
+    coefficients = np.full((normal.shape[0], terms), np.nan)
+    rank = np.zeros(normal.shape[0], dtype=np.int64)
+    for g, sums in enumerate(normal):
+        if not sums[-3] > 0:
+            continue
+        a = np.zeros((terms, terms))
+        a[upper] = sums[:tri]
+        a = a + np.triu(a, 1).T
+        coefficients[g], _, rank[g], _ = np.linalg.lstsq(a, sums[tri:tri + terms], rcond=RANK_RCOND)
+    return coefficients, rank
+
+
+def noll_index(j):
+    """Noll's (1976) single index j = 1, 2, ... -> (n, m): m > 0 for cos(m theta) (even j), m < 0 for sin (odd j)."""
+    if j < 1:
+        raise ValueError("Noll indices start at 1")
+    n, k = 0, j - 1
+    while k > n:
+        n += 1
+        k -= n
+    m = n % 2 + 2 * ((k + (n + 1) % 2) // 2)
+    return n, (-m if j % 2 else m)
+
+
+def zernike_basis(terms, rho, theta):
+    """Z_1 .. Z_terms (Noll's order and RMS normalisation) at (rho, theta): an array of shape (terms,) + rho's
+    shape.  The host statement of what ``k_frame_zernike`` evaluates (there by recurrence)."""
+    from math import factorial
+
+    rho, theta = np.asarray(rho, dtype=float), np.asarray(theta, dtype=float)
+    out = []
+    for j in range(1, terms + 1):
+        n, m = noll_index(j)
+        am = abs(m)
+        radial = sum((-1) ** k * factorial(n - k) / (factorial(k) * factorial((n + am) // 2 - k)
+                                                     * factorial((n - am) // 2 - k)) * rho ** (n - 2 * k)
+                     for k in range((n - am) // 2 + 1))
+        norm = np.sqrt(n + 1.0) if m == 0 else np.sqrt(2.0 * (n + 1))
+        angular = 1.0 if m == 0 else (np.cos(am * theta) if m > 0 else np.sin(am * theta))
+        out.append(norm * radial * angular)
+    return np.array(out)
+
+
+def pupil_axes(axis=None, basis=None):
+    """The 9 doubles (a, e1, e2) the pupil projection uses: a unit axis and an orthonormal basis of the plane
+    perpendicular to it.  Default: a = x, e1 = y, e2 = z.  An axis without a basis gets e1 from y (z when the axis
+    is along y) made perpendicular to it, and e2 = a x e1."""
+    a = np.array((1.0, 0.0, 0.0) if axis is None else axis, dtype=float)
+    if a.shape != (3,) or not np.all(np.isfinite(a)) or not np.linalg.norm(a) > 0:
+        raise ValueError("axis: a finite, non-zero 3-vector")
+    a = a / np.linalg.norm(a)
+    if basis is None:
+        if axis is None:
+            e1, e2 = np.array((0.0, 1.0, 0.0)), np.array((0.0, 0.0, 1.0))
+        else:
+            seed = np.array((0.0, 1.0, 0.0)) if abs(a[1]) < 0.9 else np.array((0.0, 0.0, 1.0))
+            e1 = seed - np.dot(seed, a) * a
+            e1 /= np.linalg.norm(e1)
+            e2 = np.cross(a, e1)
+    else:
+        e1, e2 = (np.array(e, dtype=float) for e in basis)
+        if e1.shape != (3,) or e2.shape != (3,):
+            raise ValueError("basis: two 3-vectors (e1, e2)")
+        frame = np.stack([a, e1, e2])
+        if not np.allclose(frame @ frame.T, np.eye(3), atol=1e-9):
+            raise ValueError("basis: e1, e2 must be unit vectors perpendicular to each other and to the axis")
+    return np.ascontiguousarray(np.concatenate([a, e1, e2]), dtype=np.float64)
 
 
 def histogram_edges(bins, range, dims, finite_range):
