@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- ray-surface intersections/sec on the north-star workload (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: it sets up the workload, warms up, times the K
+steps, writes --dump-outputs if asked and prints the JSON line (`value`, `ms_per_step` and the `roofline` of the timed
+region itself).  --full adds everything else described below: the check of the rows against the reference's
+summaries (`verified`), the side runs (`value_replay`, `value_one_stream`, `value_synchronous`, `value_cold`,
+`value_no_hints`, `value_first_trace`, `record_plans`, `roofline.one_stream`), the result sink, the end-to-end trace,
+the re-assembly of the frame over several GPUs (`gather`) and the CPU baselines.  The timed steps are the same in both.
 
 With --gpus N > 1 and no launcher (no WORLD_SIZE in the environment) the process that was started
 becomes a launcher itself: before anything touches the GPU it picks a free port and starts N rank
@@ -38,13 +45,13 @@ flight, per step -- never more than `ms_per_step` -- and `avg_launch_ms` = that 
 kernel's duration when it has the device to itself (what `rocprofv3 --stats` averages when the steps run on one
 stream) is `roofline.one_stream`, measured right behind the timed region, with `value_one_stream` next to it.
 
-After the timed region the rows of the LAST timed step of EACH of the four ray sets are compared with the reference's
-own summary of that run (tests/golden/config2_1m_summary*.npz, written by the genuine reference: rows per generation x
-surface, the ids of the near-axial rays of SURVEY Q5, a checksum of the surface column, column sums, sampled rows to
-1e-6) -> "verified" / `verification.seeds`; a false verdict exits non-zero.  With --gpus N the ranks' shards are
-checked together (counts and sums are additive), BEFORE the timed region.
+With --full, after the timed region the rows of the LAST timed step of EACH of the four ray sets are compared with the
+reference's own summary of that run (tests/golden/config2_1m_summary*.npz, written by the genuine reference: rows per
+generation x surface, the ids of the near-axial rays of SURVEY Q5, a checksum of the surface column, column sums,
+sampled rows to 1e-6) -> "verified" / `verification.seeds`; a false verdict exits non-zero.  With --gpus N the ranks'
+shards are checked together (counts and sums are additive), BEFORE the timed region.
 
-Other kinds of step, untimed side runs: `value_replay` (the same ray set again and again: round 3's headline),
+Other kinds of step, untimed side runs of --full: `value_replay` (the same ray set again and again: round 3's headline),
 `value_synchronous` (one blocking prt_trace at a time: what one RayTracer.trace(), pyrayt/_pyrayt.py:329-339, costs in
 a running design loop), `value_cold` (a fresh scene's first trace), `value_no_hints`, `value_first_trace`.
 
@@ -57,7 +64,7 @@ write their own shard's files with a _rank<r> suffix.  The inputs are seeded: th
 rank 0 prints ONE JSON line.  `roofline` is for the generation kernel(s): algorithmic bytes (328 B per ray alive at
 generation entry that is recorded and goes on) over the busy time above; the bytes the kernel
 actually moves (it carries 10 of the 13 state rows between generations) are reported next to it as
-`moved_bytes_per_launch` / `moved_frac`.  `cpu_baseline` is the numpy oracle (a port of the reference's path,
+`moved_bytes_per_launch` / `moved_frac`.  `cpu_baseline` (--full) is the numpy oracle (a port of the reference's path,
 validated against it) timed on this host, rank 0, N=1.
 """
 import argparse
@@ -147,13 +154,17 @@ def parse_args():
                     help="rays of the job (strong scaling) / per GPU (weak scaling)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--flags", type=int, default=0, help="PRT_TRACE_* flags")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the rows against the "
+                         "reference's summaries, the side runs, the result sink, the end-to-end trace, the gather "
+                         "over several GPUs and the CPU baselines (see the module docstring)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--workload", default="config2", choices=["config2", "config3", "config4", "config5"],
                     help="informational runs of the other BASELINE scenes; the bench line is config2")
     ap.add_argument("--generation-limit", type=int, default=GENERATION_LIMIT,
                     help="experiments only: the north-star workload uses 10")
     ap.add_argument("--cpu-rays", type=int, default=1_000_000,
-                    help="rays of the same workload timed on the CPU oracle")
+                    help="rays of the same workload timed on the CPU oracle (--full)")
     ap.add_argument("--options", default="",
                     help="A/B runs only: prt_scene_options for the scene, e.g. no_tail=1,no_cull=1 (the bench line uses none)")
     ap.add_argument("--no-pipeline", action="store_true",
@@ -170,7 +181,7 @@ def parse_args():
                     help="distinct seeded ray sets the timed steps rotate through (1 = re-trace the same rays: the "
                          "value_replay form)")
     ap.add_argument("--side-steps", type=int, default=40,
-                    help="steps of each untimed side measurement (synchronous / no hints / changing ray count)")
+                    help="steps of each untimed side measurement of --full (synchronous / no hints / changing ray count)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the rows and counts the last timed step returned as DIR/<name>.npy (a seeded sample of "
                          "a frame over %d rows; see the module docstring)" % DUMP_ROWS_MAX)
@@ -522,10 +533,11 @@ def main():
     # single-GPU frame.  A mismatch ends the run, non-zero, on every rank: a scaling number for wrong rows is worth
     # nothing.  If the re-assembly itself fails (first contact with a new node), the shards are checked through their
     # additive statistics instead -- per generation x surface counts, checksum, column sums, Q5 ids -- and the line
-    # says so.  `rccl_ranks` is what ncclCommCount reports for the library's communicator.
+    # says so.  `rccl_ranks` is what ncclCommCount reports for the library's communicator.  (--full only, like the
+    # gather behind the timed region that uses the same communicator.)
     pre_verification, rccl_ranks, bench_comm = None, None, None
     verifiable_job = (args.workload == "config2" and n_job == RAYS_PER_GPU and limit == GENERATION_LIMIT and strong)
-    if distributed:
+    if distributed and args.full:
         if backend == "nccl":
             try:
                 bench_comm = pdist.LibraryComm.from_group(dist.group.WORLD, device)
@@ -648,11 +660,11 @@ def main():
     # the rows the LAST repetition's last steps left: one step per ray set of the rotation (verified further down,
     # before anything else records into those blocks)
     last_timed = {}
-    if mode == "overlap" and not args.python_loop:
+    verifiable = verifiable_job and args.full
+    if verifiable and mode == "overlap" and not args.python_loop:
         done = prepared_batch(args.steps)
         for k in range(max(0, args.steps - len(ray_sets)), args.steps):
             last_timed[k % len(ray_sets)] = done.result(k)
-    verifiable = verifiable_job
     if verifiable and world == 1:  # to the host now (one DMA each); looked at behind the side measurements
         last_timed = {k: (engine.to_host(r).T, c) for k, (r, c) in last_timed.items()}
     by_time = sorted(repetitions, key=lambda r: r.elapsed)
@@ -680,7 +692,7 @@ def main():
         torch.cuda.synchronize(device)
 
     one_stream = None
-    if mode == "overlap":
+    if mode == "overlap" and args.full:
         respin("one_stream")
         run_steps(3, how="one_stream")
         torch.cuda.synchronize(device)
@@ -704,8 +716,9 @@ def main():
     # (c) with a ray count that changes from call to call (control words re-initialised every time; the hints
     #     of the previous trace still apply -- they are checked per tile): what a design loop that resizes its
     #     ray set every iteration sees.
+    # These and everything else up to the JSON line run under --full only.
     def side(label, fn, count):
-        if count <= 0:
+        if count <= 0 or not args.full:
             return None
         respin()
         fn(3)
@@ -746,7 +759,7 @@ def main():
         if len(ray_sets) > 1 else None
     # (f) a fresh scene's first trace: scene compilation, table upload, control-word initialisation, no hints
     cold = None
-    if args.side_steps > 0:
+    if args.full and args.side_steps > 0:
         cold_times = []
         for _ in range(3):
             torch.cuda.synchronize(device)
@@ -766,7 +779,7 @@ def main():
     #     timed region (`overlapped`) and as blocking prt_trace calls (`synchronous`).  Their rows per second count the
     #     ray segments RESOLVED (what the metric counts), of which only the detector's are stored / summed.
     record_plans = None
-    if args.side_steps > 0 and args.workload == "config2" and args.flags == 0:
+    if args.full and args.side_steps > 0 and args.workload == "config2" and args.flags == 0:
         try:
             detector = int(snap.prims["surface_id"][-1])
             resolved_per_step = float(sum(set_stats[k % len(set_stats)]["rows"] for k in range(args.side_steps))) / args.side_steps
@@ -861,6 +874,8 @@ def main():
     # host right behind the timed region).  Several GPUs: checked before the timed region, see `pre_verification`.
     verified, verify_note = None, ("only BASELINE config 2 at 1M rays, generation_limit 10 (strong scaling) has "
                                    "reference summaries")
+    if not args.full:
+        verify_note = "not checked: a plain run times the steps only; --full checks the rows against the reference's summaries"
     if verifiable and world == 1:
         per_seed, what = {}, "the last timed step of each ray set (rows of the timed region's final repetition)"
         if not last_timed:  # (issue modes that do not keep a block per ray set: a synchronous trace of each set instead)
@@ -915,7 +930,7 @@ def main():
     # frame re-assembly (not in the timed region): the library's RCCL all-gathers + placement kernel
     # when the group is RCCL-backed, torch.distributed + the placement kernel otherwise
     gather = None
-    if distributed:
+    if distributed and args.full:
         try:  # an extra: its failure must not cost the benchmark line
             comm = bench_comm  # (the library's RCCL communicator made before the timed region; None on a gloo group)
             times = []
@@ -967,7 +982,7 @@ def main():
         except Exception as exc:  # noqa: BLE001
             gather = dict(gather or {}, error=f"{type(exc).__name__}: {exc}"[:300])
     result_sink = None
-    if not distributed:
+    if not distributed and args.full:
         try:
             result_sink = {"stats_ms": sink_stats(rows, counts, None, None), "groups": 8,
                            "what": "DeviceFrame.group_stats of the detector's rows, 8 source groups (prt_frame_stats), incl. the D2H of the 8 x 8 result"}
@@ -976,9 +991,9 @@ def main():
 
     # PCIe-inclusive end-to-end trace() on rank 0 (H2D rays, trace, D2H rows, DataFrame)
     end_to_end = None
-    if rank == 0 and float(n) * limit * 120 > 16e9:
+    if rank == 0 and args.full and float(n) * limit * 120 > 16e9:
         end_to_end = {"skipped": "the frame of this job is tens of GB: not brought to the host three times for a side figure"}
-    elif rank == 0:
+    elif rank == 0 and args.full:
         from pyrayt_amd.tracer import rows_to_frame
 
         try:
@@ -1103,7 +1118,8 @@ def main():
                                        "collected (prt_trace_begin / prt_trace_end)",
                          "sync": ", synchronous (prt_trace)"}[mode] +
                         "; see value_replay / value_one_stream / value_synchronous / value_cold / value_no_hints / "
-                        "value_first_trace for the other kinds of step",
+                        "value_first_trace (--full) for the other kinds of step",
+            "full": args.full,
             "ray_sets": len(ray_sets),
             "issue_mode": mode,
             "issued_by": ("prt_trace_batch (one library call per timed region)" if mode == "overlap" and not args.python_loop
@@ -1149,10 +1165,12 @@ def main():
                             "its own stream, intervals merged by the library (PRT_TRACE_BUSY / prt_trace_batch_busy) -- "
                             "kernel_ms_per_step is the time per step during which at least one of the region's traces "
                             "had launches in flight, avg_launch_ms that time per generation launch; the kernel with the "
-                            "device to itself is `one_stream`"
+                            "device to itself is `one_stream` (--full)"
                             if busy is not None else
                             "one stream, the same steps right behind the timed region (HIP events per trace): this issue "
-                            "mode has no merged intervals" if mode == "overlap" else
+                            "mode has no merged intervals" if mode == "overlap" and args.full else
+                            "nothing: this issue mode has no merged intervals, and the same steps on one stream that "
+                            "stand in for them are run by --full" if mode == "overlap" else
                             "the timed region (HIP events per trace on the launch stream; the traces do not overlap)"),
             "algorithmic_bytes_per_launch": algorithmic_bytes / launches if launches else 0,
             "avg_launch_ms": kernel_ms / kernel_launches if kernel_launches else 0,
@@ -1249,7 +1267,7 @@ def main():
         if "pipelined_ms_per_step" in gather:  # re-assembly of trace k behind trace k + 1: the steady state
             line["value_with_gather_pipelined"] = total_rows_per_step / (gather["pipelined_ms_per_step"] * 1e-3)
 
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         from oracle import prt_oracle
         import helpers
 

@@ -317,7 +317,7 @@ def test_bench_launches_its_own_ranks_on_real_devices():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     done = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                           "--rays", "100000", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                           "--rays", "100000", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [ln for ln in done.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, done.stdout
@@ -337,7 +337,7 @@ def test_bench_launches_its_own_ranks_sharing_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["PRT_DIST_BACKEND"] = "gloo"
     done = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2",
-                           "--rays", "100000", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
+                           "--rays", "100000", "--full", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=600)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [ln for ln in done.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, done.stdout
@@ -360,7 +360,7 @@ def test_bench_checks_the_shards_against_the_reference_before_it_times_them():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["PRT_DIST_BACKEND"] = "gloo"
     done = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-                           "--reps", "2", "--side-steps", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
+                           "--reps", "2", "--full", "--side-steps", "0", "--no-cpu-baseline"], capture_output=True, text=True, env=env,
                           timeout=900)
     assert done.returncode == 0, done.stderr[-2000:]
     line = json.loads([ln for ln in done.stdout.splitlines() if ln.strip()][-1])

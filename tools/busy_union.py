@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Cross-check of bench.py's roofline against a rocprofv3 kernel trace of the same command.
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o trace -- python3 bench.py --side-steps 0 --no-cpu-baseline
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o trace -- python3 bench.py --full --side-steps 0 --no-cpu-baseline
     python3 tools/busy_union.py DIR/trace_kernel_trace.csv [kernel-name-substring]
 
 bench.py's `roofline.kernel_ms_per_step` is the time the device had at least one of the timed region's traces in

@@ -6,7 +6,7 @@ for w in config2 config3 config4 config5; do
   rays=""; [ $w = config3 ] && rays="--rays 4000000"; [ $w = config4 ] && rays="--rays 8000000"; [ $w = config5 ] && rays="--rays 2000000"
   for rep in 1 2; do
   for flags in 0 512 1024; do
-    python bench.py --no-cpu-baseline --workload $w $rays --flags $flags --steps 100 --warmup 10 --side-steps 30 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --workload $w $rays --flags $flags --steps 100 --warmup 10 --side-steps 30 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 g=lambda k: ('%.4e'%d[k]) if d.get(k) else '-'

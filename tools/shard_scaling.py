@@ -30,7 +30,7 @@ for n in args.sizes:
     for mode, extra in (("overlap", []), ("overlap py", ["--python-loop"]), ("one stream", ["--streams", "1"]),
                         ("synchronous", ["--no-pipeline"])):
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rays", str(n), "--steps", str(args.steps), "--warmup", "20",
-               "--no-cpu-baseline", "--side-steps", "0", "--workload", args.workload] + extra
+               "--full", "--no-cpu-baseline", "--side-steps", "0", "--workload", args.workload] + extra
         done = subprocess.run(cmd, capture_output=True, text=True)
         try:
             d = json.loads(done.stdout.strip().splitlines()[-1])
