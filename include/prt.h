@@ -617,6 +617,50 @@ int prt_frame_wavefront(int device, const double* rows, int64_t ld, int64_t n_ro
                         double* opd_out, double* pupil_out, double* group_out, double* normal_out, void* workspace,
                         void* stream);
 
+/* Diffraction PSF and Strehl ratio of the frame: the Huygens sum over the rays that reach the reference sphere (no
+ * counterpart upstream).  It takes the wavefront's own reference sphere and OPD, so there is one definition and not two.
+ *
+ * Definitions.
+ * Rays: the rows prt_frame_wavefront selected with the same rows / ld / n_rows / surface / generation /
+ *   rays_per_source / n_groups, in its order; opd, pupil and group_record are that call's opd_out, pupil_out and
+ *   group_out.  For group g it gives P, R, the pupil radius rho and the axes (a, e1, e2).  A ray whose OPD is NaN (it
+ *   missed the sphere), or whose weight is not finite and >= 0, is left out and counted.
+ * Ray r contributes p1 = pupil_r[0] * rho and p2 = pupil_r[1] * rho (these are (E_r - P).e1 and (E_r - P).e2), OPD_r
+ *   and an amplitude a_r = sqrt(w_r), w the weight_column (-1: ones).
+ * Image plane: through P, perpendicular to a.  Pixel (i, j) lies at x = P + u_i e1 + v_j e2, where
+ *   u_i = u0 + (i - (nx-1)/2) du and v_j = v0 + (j - (ny-1)/2) dv.
+ * Distance: d_r(x) = sqrt(R^2 + u^2 + v^2 - 2 (u p1 + v p2)), exact when |E_r - P| = R; the formula is the contract.
+ * Wavelengths are in micrometres, as upstream's are (components.py:472); world units are the caller's, so
+ *   lambda_w = wavelength / world_unit_um (world_unit_um = 1000 for millimetres).
+ * Phase: phi_r(x) = (OPD_r + d_r(x) - R) / lambda_w, in cycles.  Amplitude: U_l(x) = (1/lambda_w) sum over the rays
+ *   r of wavelength l of a_r exp(2 pi i phi_r(x)).  Rays of one wavelength add coherently, wavelengths incoherently.
+ * Normalised image: I(x) = sum_l |U_l(x)|^2 / sum_l (sum over r of l of a_r / lambda_w)^2.  A perfect wave on the same
+ *   rays gives exactly 1 at P.
+ * Strehl: I at P, (u, v) = (0, 0), whether or not P is a pixel centre:
+ *   sum_l |sum a_r exp(2 pi i OPD_r / lambda_w)|^2 / lambda_w^2 / sum_l (sum a_r / lambda_w)^2; piston drops out.
+ * Amplitude factors of the Huygens-Fresnel integral other than 1/lambda (the obliquity factor, 1/r) are taken as
+ *   constant over the pupil: the error is of the order of NA^2 at the rim.  Each ray stands for an equal share of the
+ *   pupil's area, or carries its share in w; random pupil samples give a noise floor of about 1 / (number of rays).
+ *
+ * prt_frame_psf: wavelengths_um (HOST, n_wavelengths <= 16 distinct values, finite and > 0) lists every wavelength of
+ * the selected rows (a row of another wavelength: PRT_ERR_ARG once the passes have run); nx, ny in 1..1024; du, dv
+ * finite and > 0; centre_uv (HOST) = (u0, v0).  n_groups * n_wavelengths * nx * ny * 16 bytes may not pass the 256 MiB
+ * cap of the partial-sum slab.  Out, DEVICE, overwritten: image_out (n_groups, n_wavelengths, nx, ny) -- the group's
+ * normalised image per wavelength: the polychromatic image is their sum; NaN for a group without rays --; strehl_out
+ * (n_groups); record_out (n_groups, n_wavelengths, 4): rays used, rays left out, sum a, and the Strehl numerator
+ * |sum a exp(2 pi i OPD / lambda_w)|^2 / lambda_w^2.  workspace: prt_frame_psf_workspace_bytes(n_rows, n_groups,
+ * n_wavelengths) device bytes.  The sum is a grid of (pixel tile, ray slice, (group, wavelength) bucket) workgroups
+ * over rays sorted into buckets by a stable counting sort; partial sums are folded in slice order, with no
+ * floating-point atomics: every output is the same, bit for bit, on every run.  All arguments are checked before a
+ * device is touched.  Stream-ordered; the call reads one status word back and so returns when the stream has reached
+ * its end. */
+int64_t prt_frame_psf_workspace_bytes(int64_t n_rows, int n_groups, int n_wavelengths);
+int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                  double rays_per_source, int n_groups, const double* opd, const double* pupil,
+                  const double* group_record, int weight_column, const double* wavelengths_um, int n_wavelengths,
+                  double world_unit_um, int nx, int ny, double du, double dv, const double* centre_uv,
+                  double* image_out, double* strehl_out, double* record_out, void* workspace, void* stream);
+
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,
  * out[2] = GPU milliseconds spent in generation kernels (hipEvent, on the trace stream),

@@ -1,0 +1,439 @@
+// prt_psf.hpp -- the diffraction PSF (Huygens sum) and the Strehl ratio of the frame, on the device (DESIGN.md
+// section 4.5).  It builds on prt_wavefront.hpp: the rows prt_frame_wavefront selected, its OPD, pupil points and group
+// records.  Definitions: include/prt.h.
+//
+//   k_psf_count     per wave of a contiguous run of rows: how many rows the wavefront's filter selects
+//   k_psf_scan      one workgroup: the waves' output offsets (the order of the wavefront's opd_out / pupil_out)
+//   k_psf_stage     per selected row, in row order: p1, p2, c = (OPD - R) s, a = sqrt(w) and its (group, wavelength)
+//                   bucket; per wave and bucket the rays kept; rays left out counted per bucket (integer atomics)
+//   k_psf_offsets   one workgroup: each bucket's start, and each wave's offset inside each bucket
+//   k_psf_scatter   the stable counting sort: every wave writes its rays, in order, at its offsets
+//   k_psf_strehl    per (ray slice, bucket): sum a, sum a cos / sin (2 pi OPD s) in fp64, a fixed tree order
+//   k_psf_record    per group: the slices folded in order, the record, the Strehl ratio and the normalisation
+//   k_psf_huygens   per (pixel tile, ray slice, bucket): the complex amplitude sum of the slice's rays at every pixel
+//                   of the tile, the rays walked through LDS; partial sums into a slab of its own
+//   k_psf_fold      per (bucket, pixel): the slices added in slice order, |U|^2 / lambda_w^2, normalised
+// No floating-point atomics: every output is the same, bit for bit, on every run.
+#pragma once
+
+enum { PSF_MAX_WAVELENGTHS = 16, PSF_MAX_SIDE = 1024, PSF_RECORD = 4, PSF_BAD_WAVELENGTH = 1 };
+static const int kPsfBlock = 256;                 // threads of a Huygens workgroup = rays of its LDS tile
+static const int kPsfPix = 4;                     // pixels a thread owns (fp64 complex accumulators in registers)
+static const int kPsfTile = kPsfBlock * kPsfPix;  // pixels of a workgroup
+static const int kPsfMinSlice = 2048;             // rays a slice should hold at least
+static const int kPsfMaxSlices = 1024;
+static const size_t kPsfSlabBytes = 256u << 20;   // cap on the (bucket, slice, pixel) partial sums
+static const size_t kPsfCountBytes = 64u << 20;   // cap on the sort's (wave, bucket) counts
+
+struct PsfRay { double p1, p2, c, a; };
+struct PsfLambda { double value[PSF_MAX_WAVELENGTHS], s[PSF_MAX_WAVELENGTHS]; int n; };
+
+__device__ __forceinline__ bool psf_row(const double* __restrict__ rows, int64_t ld, int64_t j, double surface,
+                                        double generation, double rays_per_source, int n_groups, int& group) {
+  group = -1;
+  if (wf_selected(rows, ld, j, surface, generation)) group = wf_group(rows, ld, j, rays_per_source, n_groups);
+  return group >= 0;
+}
+
+__global__ void __launch_bounds__(PRT_BLOCK)
+k_psf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
+            double rays_per_source, int n_groups, int64_t per_wave, int64_t* __restrict__ wave_rows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
+  const int64_t first = wave * per_wave;
+  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  int64_t selected = 0;
+  for (int64_t base = first; base < last; base += 64) {
+    const int64_t j = base + lane;
+    int group;
+    selected += __popcll(__ballot(j < last && psf_row(rows, ld, j, surface, generation, rays_per_source, n_groups, group)));
+  }
+  if (lane == 0) wave_rows[wave] = selected;
+}
+
+static const int kPsfScanBlock = 512;
+__global__ void __launch_bounds__(kPsfScanBlock)
+k_psf_scan(int waves, const int64_t* __restrict__ wave_rows, int64_t* __restrict__ wave_offset) {
+  __shared__ int64_t scan[kPsfScanBlock];
+  const int per = (waves + kPsfScanBlock - 1) / kPsfScanBlock;
+  const int lo = threadIdx.x * per, hi = lo + per < waves ? lo + per : waves;
+  int64_t mine = 0;
+  for (int k = lo; k < hi; ++k) mine += wave_rows[k];
+  scan[threadIdx.x] = mine;
+  __syncthreads();
+  for (int off = 1; off < kPsfScanBlock; off <<= 1) {
+    const int64_t add = (int)threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
+    __syncthreads();
+    scan[threadIdx.x] += add;
+    __syncthreads();
+  }
+  int64_t at = scan[threadIdx.x] - mine;
+  for (int k = lo; k < hi; ++k) { wave_offset[k] = at; at += wave_rows[k]; }
+}
+
+__global__ void __launch_bounds__(PRT_BLOCK)
+k_psf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
+            double rays_per_source, int n_groups, int64_t per_wave, const int64_t* __restrict__ wave_offset,
+            const double* __restrict__ opd, const double* __restrict__ pupil, const double* __restrict__ group_record,
+            int weight_column, PsfLambda lambda, PsfRay* __restrict__ stage, int* __restrict__ bucket_of,
+            int64_t* __restrict__ counts, int buckets, unsigned long long* __restrict__ skipped,
+            int* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
+  const int64_t first = wave * per_wave;
+  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  if (first >= last) return;
+  int64_t* const mine = counts + wave * buckets;  // (only this wave writes here)
+  int64_t at = wave_offset[wave];
+  for (int64_t base = first; base < last; base += 64) {
+    const int64_t j = base + lane;
+    int group = -1;
+    const bool chosen = j < last && psf_row(rows, ld, j, surface, generation, rays_per_source, n_groups, group);
+    const unsigned long long ballot = __ballot(chosen);
+    int bucket = -1;
+    if (chosen) {
+      const int64_t pos = at + __popcll(ballot & ((1ull << lane) - 1ull));
+      const double wavelength = rows[PRT_COL_WAVELENGTH * ld + j];
+      int k = -1;
+      for (int q = 0; q < lambda.n; ++q)
+        if (k < 0 && lambda.value[q] == wavelength) k = q;
+      if (k < 0) {
+        atomicOr(status, PSF_BAD_WAVELENGTH);
+      } else {
+        const double* g = group_record + (size_t)group * WF_GROUP;
+        const double o = opd[pos], x = pupil[2 * pos], y = pupil[2 * pos + 1];
+        const double w = weight_column >= 0 ? rows[(int64_t)weight_column * ld + j] : 1.0;
+        if (o == o && x == x && y == y && w >= 0.0 && w < PRT_INF) {
+          bucket = group * lambda.n + k;
+          const double rho = g[5], s = lambda.s[k];
+          stage[pos] = PsfRay{x * rho, y * rho, (o - g[3]) * s, sqrt(w)};
+        } else {
+          atomicAdd(skipped + group * lambda.n + k, 1ull);  // (integer: the same total in any order)
+        }
+      }
+      bucket_of[pos] = bucket;
+    }
+    at += __popcll(ballot);
+    unsigned long long pending = __ballot(bucket >= 0);
+    while (pending) {  // one turn per bucket present in the slice: almost always exactly one
+      const int leader = __ffsll((long long)pending) - 1;
+      const int b = __shfl(bucket, leader);
+      const unsigned long long take = __ballot(bucket == b);
+      if (lane == 0) mine[b] += __popcll(take);
+      pending &= ~take;
+    }
+  }
+}
+
+// one workgroup: counts (waves, buckets) -> each wave's first position inside each bucket, in place
+__global__ void __launch_bounds__(kPsfScanBlock)
+k_psf_offsets(int waves, int buckets, int64_t* __restrict__ counts, int64_t* __restrict__ bucket_total,
+              int64_t* __restrict__ bucket_start) {
+  for (int b = threadIdx.x; b < buckets; b += kPsfScanBlock) {
+    int64_t sum = 0;
+    for (int w = 0; w < waves; ++w) sum += counts[(int64_t)w * buckets + b];
+    bucket_total[b] = sum;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t at = 0;
+    for (int b = 0; b < buckets; ++b) { bucket_start[b] = at; at += bucket_total[b]; }
+  }
+  __syncthreads();
+  for (int b = threadIdx.x; b < buckets; b += kPsfScanBlock) {
+    int64_t at = bucket_start[b];
+    for (int w = 0; w < waves; ++w) {
+      const int64_t c = counts[(int64_t)w * buckets + b];
+      counts[(int64_t)w * buckets + b] = at;
+      at += c;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(PRT_BLOCK)
+k_psf_scatter(const int64_t* __restrict__ wave_rows, const int64_t* __restrict__ wave_offset,
+              const int* __restrict__ bucket_of, const PsfRay* __restrict__ stage, int64_t* __restrict__ offsets,
+              int buckets, PsfRay* __restrict__ sorted) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
+  const int64_t from = wave_offset[wave], to = from + wave_rows[wave];
+  int64_t* const mine = offsets + wave * buckets;  // (only this wave reads and writes here)
+  for (int64_t base = from; base < to; base += 64) {
+    const int64_t r = base + lane;
+    const int bucket = r < to ? bucket_of[r] : -1;
+    unsigned long long pending = __ballot(bucket >= 0);
+    while (pending) {
+      const int leader = __ffsll((long long)pending) - 1;
+      const int b = __shfl(bucket, leader);
+      const unsigned long long take = __ballot(bucket == b);
+      int64_t at = lane == 0 ? mine[b] : 0;
+      at = __shfl(at, 0);
+      if (bucket == b) sorted[at + __popcll(take & ((1ull << lane) - 1ull))] = stage[r];
+      if (lane == 0) mine[b] = at + __popcll(take);
+      pending &= ~take;
+    }
+  }
+}
+
+// the rays [lo, hi) of bucket b's slice
+__device__ __forceinline__ void psf_slice(const int64_t* __restrict__ bucket_total,
+                                          const int64_t* __restrict__ bucket_start, int b, int slice, int slices,
+                                          int64_t& lo, int64_t& hi) {
+  const int64_t n = bucket_total[b], per = (n + slices - 1) / slices;
+  lo = bucket_start[b] + (int64_t)slice * per;
+  hi = bucket_start[b] + n;
+  if (lo + per < hi) hi = lo + per;
+}
+
+__global__ void __launch_bounds__(kPsfBlock)
+k_psf_strehl(const PsfRay* __restrict__ sorted, const int64_t* __restrict__ bucket_total,
+             const int64_t* __restrict__ bucket_start, const double* __restrict__ group_record, PsfLambda lambda,
+             int slices, double* __restrict__ strehl_slab) {
+  __shared__ double red[3][kPsfBlock];
+  const int t = threadIdx.x, slice = blockIdx.x, b = blockIdx.y;
+  const int g = b / lambda.n;
+  const double s = lambda.s[b - g * lambda.n], radius = group_record[(size_t)g * WF_GROUP + 3];
+  int64_t lo, hi;
+  psf_slice(bucket_total, bucket_start, b, slice, slices, lo, hi);
+  double sum_a = 0.0, sum_c = 0.0, sum_s = 0.0;
+  for (int64_t r = lo + t; r < hi; r += kPsfBlock) {
+    const PsfRay ray = sorted[r];
+    const double phase = fma(radius, s, ray.c);  // OPD / lambda_w, in cycles
+    double sn, cs;
+    sincospi(2.0 * (phase - rint(phase)), &sn, &cs);
+    sum_a += ray.a;
+    sum_c += ray.a * cs;
+    sum_s += ray.a * sn;
+  }
+  red[0][t] = sum_a; red[1][t] = sum_c; red[2][t] = sum_s;
+  for (int half = kPsfBlock / 2; half > 0; half >>= 1) {  // (a fixed tree)
+    __syncthreads();
+    if (t < half)
+      for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + half];
+  }
+  __syncthreads();
+  if (t < 3) strehl_slab[((size_t)b * slices + slice) * 3 + t] = red[t][0];
+}
+
+__global__ void __launch_bounds__(PRT_BLOCK)
+k_psf_record(const double* __restrict__ strehl_slab, int slices, int n_groups, PsfLambda lambda,
+             const int64_t* __restrict__ bucket_total, const unsigned long long* __restrict__ skipped,
+             double* __restrict__ record_out, double* __restrict__ strehl_out, double* __restrict__ norm) {
+  const int g = blockIdx.x * PRT_BLOCK + threadIdx.x;
+  if (g >= n_groups) return;
+  double numerator = 0.0, denominator = 0.0;
+  for (int k = 0; k < lambda.n; ++k) {
+    const int b = g * lambda.n + k;
+    double a = 0.0, c = 0.0, s = 0.0;
+    for (int q = 0; q < slices; ++q) {
+      const double* p = strehl_slab + ((size_t)b * slices + q) * 3;
+      a += p[0]; c += p[1]; s += p[2];
+    }
+    const double inv = lambda.s[k], num = inv * inv * (c * c + s * s), den = (inv * a) * (inv * a);
+    double* o = record_out + (size_t)b * PSF_RECORD;
+    o[0] = (double)bucket_total[b];
+    o[1] = (double)skipped[b];
+    o[2] = a;
+    o[3] = num;
+    numerator += num;
+    denominator += den;
+  }
+  norm[g] = denominator;
+  strehl_out[g] = denominator > 0.0 ? numerator / denominator : __longlong_as_double(0x7ff8000000000000ll);
+}
+
+// sqrt in fp64 for an argument far from 0 and from the denormals (|x - E|^2 ~ R^2): the hardware's reciprocal square
+// root refined by Goldschmidt's iteration, as the compiler's own expansion does without its scaling steps
+__device__ __forceinline__ double psf_sqrt(double x) {
+  const double y = __builtin_amdgcn_rsq(x);
+  double g = x * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  double d = fma(-g, g, x);
+  g = fma(d, h, g);
+  d = fma(-g, g, x);
+  return fma(d, h, g);
+}
+
+__global__ void __launch_bounds__(kPsfBlock)
+k_psf_huygens(const PsfRay* __restrict__ sorted, const int64_t* __restrict__ bucket_total,
+              const int64_t* __restrict__ bucket_start, const double* __restrict__ group_record, PsfLambda lambda,
+              int nx, int ny, double du, double dv, double u0, double v0, int slices, double* __restrict__ slab) {
+  __shared__ PsfRay tile[kPsfBlock];
+  const int t = threadIdx.x, slice = blockIdx.y, b = blockIdx.z;
+  const int g = b / lambda.n;
+  const double s = lambda.s[b - g * lambda.n], radius = group_record[(size_t)g * WF_GROUP + 3];
+  const int64_t npix = (int64_t)nx * ny;
+  double mu[kPsfPix], mv[kPsfPix], k0[kPsfPix], re[kPsfPix], im[kPsfPix];
+#pragma unroll
+  for (int q = 0; q < kPsfPix; ++q) {
+    const int64_t pix = (int64_t)blockIdx.x * kPsfTile + q * kPsfBlock + t;
+    const int i = pix < npix ? (int)(pix / ny) : 0, j = pix < npix ? (int)(pix - (int64_t)(pix / ny) * ny) : 0;
+    const double u = u0 + ((double)i - 0.5 * (nx - 1)) * du, v = v0 + ((double)j - 0.5 * (ny - 1)) * dv;
+    mu[q] = -2.0 * u;
+    mv[q] = -2.0 * v;
+    k0[q] = radius * radius + u * u + v * v;
+    re[q] = im[q] = 0.0;
+  }
+  int64_t lo, hi;
+  psf_slice(bucket_total, bucket_start, b, slice, slices, lo, hi);
+  for (int64_t base = lo; base < hi; base += kPsfBlock) {
+    __syncthreads();  // (the previous tile is read)
+    if (base + t < hi) tile[t] = sorted[base + t];
+    __syncthreads();
+    const int count = hi - base < kPsfBlock ? (int)(hi - base) : kPsfBlock;
+    for (int r = 0; r < count; ++r) {
+      const PsfRay ray = tile[r];
+#pragma unroll
+      for (int q = 0; q < kPsfPix; ++q) {
+        const double d2 = fma(mu[q], ray.p1, fma(mv[q], ray.p2, k0[q]));  // |x - E|^2
+        const double phase = fma(psf_sqrt(d2), s, ray.c);                  // (OPD + d - R) / lambda_w, cycles
+        const float turn = (float)__builtin_amdgcn_fract(phase);           // [0, 1)
+        re[q] = fma(ray.a, (double)__builtin_amdgcn_cosf(turn), re[q]);    // (v_cos_f32 / v_sin_f32 take turns)
+        im[q] = fma(ray.a, (double)__builtin_amdgcn_sinf(turn), im[q]);
+      }
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kPsfPix; ++q) {
+    const int64_t pix = (int64_t)blockIdx.x * kPsfTile + q * kPsfBlock + t;
+    if (pix < npix) {
+      double* o = slab + (((size_t)b * slices + slice) * npix + pix) * 2;
+      o[0] = re[q];
+      o[1] = im[q];
+    }
+  }
+}
+
+__global__ void __launch_bounds__(PRT_BLOCK)
+k_psf_fold(const double* __restrict__ slab, int slices, int buckets, int64_t npix, PsfLambda lambda,
+           const double* __restrict__ norm, double* __restrict__ image_out) {
+  const int64_t item = (int64_t)blockIdx.x * PRT_BLOCK + threadIdx.x;
+  if (item >= (int64_t)buckets * npix) return;
+  const int b = (int)(item / npix);
+  const int64_t pix = item - (int64_t)b * npix;
+  double re = 0.0, im = 0.0;
+  for (int q = 0; q < slices; ++q) {
+    const double* p = slab + (((size_t)b * slices + q) * npix + pix) * 2;
+    re += p[0];
+    im += p[1];
+  }
+  const int g = b / lambda.n;
+  const double inv = lambda.s[b - g * lambda.n];
+  image_out[item] = inv * inv * (re * re + im * im) / norm[g];  // (a group without rays: 0 / 0, NaN)
+}
+
+// ---- entry points ---------------------------------------------------------------------------------------------------
+static int64_t psf_buckets_bytes(int n_groups, int n_wavelengths) {
+  return (int64_t)n_groups * n_wavelengths * 8;
+}
+
+extern "C" int64_t prt_frame_psf_workspace_bytes(int64_t n_rows, int n_groups, int n_wavelengths) {
+  if (n_rows < 0 || n_groups < 1 || n_wavelengths < 1 || n_wavelengths > PSF_MAX_WAVELENGTHS) return PRT_ERR_ARG;
+  // wave counts and offsets, bucket totals / starts / skips, the status word, the groups' normalisation, the staged
+  // and the sorted rays, the rays' buckets
+  return (int64_t)2 * kWfMaxWaves * 8 + 3 * psf_buckets_bytes(n_groups, n_wavelengths) + 8 + (int64_t)n_groups * 8 +
+         n_rows * (int64_t)(2 * sizeof(PsfRay) + sizeof(int)) + 64;
+}
+
+extern "C" int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t n_rows, double surface,
+                             double generation, double rays_per_source, int n_groups, const double* opd,
+                             const double* pupil, const double* group_record, int weight_column,
+                             const double* wavelengths_um, int n_wavelengths, double world_unit_um, int nx, int ny,
+                             double du, double dv, const double* centre_uv, double* image_out, double* strehl_out,
+                             double* record_out, void* workspace, void* stream) {
+  // (everything is checked before a device is touched)
+  if (n_rows < 0 || ld < n_rows || n_groups < 1 || !group_record || !image_out || !strehl_out || !record_out ||
+      !workspace || !wavelengths_um || !centre_uv || (n_rows && (!rows || !opd || !pupil)))
+    return fail(PRT_ERR_ARG, "bad buffers");
+  if (!(rays_per_source > 0) && n_groups != 1) return fail(PRT_ERR_ARG, "one group without rays_per_source");
+  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
+  if (n_wavelengths < 1 || n_wavelengths > PSF_MAX_WAVELENGTHS)
+    return fail(PRT_ERR_ARG, "psf: 1 to 16 distinct wavelengths");
+  if (!(world_unit_um > 0 && world_unit_um < PRT_INF)) return fail(PRT_ERR_ARG, "world_unit_um: finite and > 0");
+  PsfLambda lambda;
+  lambda.n = n_wavelengths;
+  for (int k = 0; k < PSF_MAX_WAVELENGTHS; ++k) lambda.value[k] = lambda.s[k] = 0.0;
+  for (int k = 0; k < n_wavelengths; ++k) {
+    const double w = wavelengths_um[k];
+    if (!(w > 0 && w < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: finite and > 0");
+    for (int q = 0; q < k; ++q)
+      if (wavelengths_um[q] == w) return fail(PRT_ERR_ARG, "wavelengths: distinct");
+    lambda.value[k] = w;
+    lambda.s[k] = 1.0 / (w / world_unit_um);
+    if (!(lambda.s[k] < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: wavelength / world_unit_um underflows");
+  }
+  if (nx < 1 || nx > PSF_MAX_SIDE || ny < 1 || ny > PSF_MAX_SIDE) return fail(PRT_ERR_ARG, "psf: nx, ny in 1..1024");
+  if (!(du > 0 && du < PRT_INF && dv > 0 && dv < PRT_INF)) return fail(PRT_ERR_ARG, "psf: du, dv finite and > 0");
+  if (!(std::isfinite(centre_uv[0]) && std::isfinite(centre_uv[1]))) return fail(PRT_ERR_ARG, "psf: centre finite");
+  const int64_t buckets = (int64_t)n_groups * n_wavelengths, npix = (int64_t)nx * ny;
+  if (buckets > 65535) return fail(PRT_ERR_ARG, "psf: n_groups * n_wavelengths <= 65535");
+  if ((size_t)buckets * npix * 2 * sizeof(double) > kPsfSlabBytes)
+    return fail(PRT_ERR_ARG, "psf: n_groups * n_wavelengths * nx * ny * 16 bytes above the 256 MiB slab cap");
+  int rc = ops_device(device);
+  if (rc) return rc;
+  int cus = 1;
+  rc = hist_cus(device, &cus);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  // the workspace (prt_frame_psf_workspace_bytes)
+  int64_t* wave_rows = (int64_t*)workspace;
+  int64_t* wave_offset = wave_rows + kWfMaxWaves;
+  int64_t* bucket_total = wave_offset + kWfMaxWaves;
+  int64_t* bucket_start = bucket_total + buckets;
+  unsigned long long* skipped = (unsigned long long*)(bucket_start + buckets);
+  int* status = (int*)(skipped + buckets);
+  double* norm = (double*)(status + 2);
+  PsfRay* stage = (PsfRay*)(((uintptr_t)(norm + n_groups) + 31) & ~(uintptr_t)31);
+  PsfRay* sorted = stage + n_rows;
+  int* bucket_of = (int*)(sorted + n_rows);
+  // row passes: waves of contiguous rows, as many as the (wave, bucket) counts allow
+  int64_t waves = wf_waves(n_rows, 1);
+  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kPsfCountBytes / ((size_t)buckets * 8))));
+  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
+  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
+  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
+  // ray slices: enough workgroups to fill the CUs, slices of at least kPsfMinSlice rays of an average bucket
+  const int64_t tiles = (npix + kPsfTile - 1) / kPsfTile;
+  int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);
+  slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_rows / (buckets * kPsfMinSlice)));
+  slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * 16)));
+  slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));
+  const size_t count_bytes = (size_t)all_waves * buckets * 8;
+  const size_t slab_bytes = (size_t)buckets * slices * npix * 2 * sizeof(double);
+  const size_t strehl_bytes = (size_t)buckets * slices * 3 * sizeof(double);
+  char* scratch = nullptr;
+  HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + strehl_bytes + slab_bytes, st));
+  int64_t* counts = (int64_t*)scratch;
+  double* strehl_slab = (double*)(scratch + count_bytes);
+  double* slab = (double*)(scratch + count_bytes + strehl_bytes);
+  HIP_TRY(hipMemsetAsync(counts, 0, count_bytes, st));
+  HIP_TRY(hipMemsetAsync(skipped, 0, (size_t)buckets * 8 + 8, st));  // (and the status word)
+  hipLaunchKernelGGL(k_psf_count, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, per_wave, wave_rows);
+  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, wave_rows, wave_offset);
+  hipLaunchKernelGGL(k_psf_stage, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, per_wave, wave_offset, opd, pupil, group_record, weight_column, lambda,
+                     stage, bucket_of, counts, (int)buckets, skipped, status);
+  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, (int)buckets, counts,
+                     bucket_total, bucket_start);
+  hipLaunchKernelGGL(k_psf_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
+                     counts, (int)buckets, sorted);
+  hipLaunchKernelGGL(k_psf_strehl, dim3((unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st, sorted,
+                     bucket_total, bucket_start, group_record, lambda, (int)slices, strehl_slab);
+  hipLaunchKernelGGL(k_psf_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
+                     strehl_slab, (int)slices, n_groups, lambda, bucket_total, skipped, record_out, strehl_out, norm);
+  hipLaunchKernelGGL(k_psf_huygens, dim3((unsigned)tiles, (unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st,
+                     sorted, bucket_total, bucket_start, group_record, lambda, nx, ny, du, dv, centre_uv[0],
+                     centre_uv[1], (int)slices, slab);
+  hipLaunchKernelGGL(k_psf_fold, dim3((unsigned)((buckets * npix + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0,
+                     st, slab, (int)slices, (int)buckets, npix, lambda, norm, image_out);
+  int host_status = 0;
+  HIP_TRY(hipMemcpyAsync(&host_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipFreeAsync(scratch, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  if (host_status & PSF_BAD_WAVELENGTH) return fail(PRT_ERR_ARG, "psf: a selected row's wavelength is not in the list");
+  return PRT_OK;
+}

@@ -461,12 +461,19 @@ class DeviceFrame:
         (``weights``: None or a column such as "intensity"); ``rank`` reports what the pupil fill can tell apart (a
         single ring of rays cannot tell piston from defocus).  Piston is removed from ``opd``, ``rms`` and ``pv``.
         Needs the whole frame of a trace, like ``optical_path``.  ``group=`` (sharded frames) is not supported yet."""
+        if group is not None:
+            raise NotImplementedError("wavefront() of a sharded frame (group=) is not supported yet")
+        return self._wavefront(surface, reference, radius, axis, basis, pupil_radius, zernike, weights, generation,
+                               rays_per_source, n_groups)[0]
+
+    def _wavefront(self, surface, reference, radius, axis, basis, pupil_radius, zernike, weights, generation,
+                   rays_per_source, n_groups):
+        """``wavefront()``, and what the PSF passes read again: (Wavefront, the rows the passes ran on, the surface
+        filter, n_groups, the group records on the device)."""
         import torch
 
         from . import engine
 
-        if group is not None:
-            raise NotImplementedError("wavefront() of a sharded frame (group=) is not supported yet")
         terms = int(zernike)
         if terms != zernike or not 1 <= terms <= 36:
             raise ValueError(f"zernike: the number of terms, 1 to 36 (got {zernike!r})")
@@ -527,7 +534,111 @@ class DeviceFrame:
         record_host = engine.to_host(record).copy()
         normal_host = engine.to_host(normal).copy()
         n_selected = int(record_host[:, 6].sum())
-        return Wavefront(opd[:n_selected], pupil[:n_selected], record_host, normal_host, terms)
+        wave = Wavefront(opd[:n_selected], pupil[:n_selected], record_host, normal_host, terms)
+        return wave, rows, surface_id, n_groups, record
+
+    # --- diffraction PSF and Strehl ratio (no counterpart upstream) ---------------------------------------------------
+    def psf(self, surface, *, world_unit_um, pixels=128, pixel_size=None, centre=(0.0, 0.0), weights="intensity",
+            reference="centroid", radius=None, axis=None, basis=None, generation=None, rays_per_source=None,
+            n_groups=None, group=None):
+        """The diffraction image of a point at ``surface`` -- the Huygens PSF -- and its Strehl ratio, per group
+        (``id // rays_per_source``).  Returns a ``PSF``.
+
+        It runs ``wavefront()`` with the same reference-sphere arguments (``reference``, ``radius``, ``axis``,
+        ``basis``, ``generation``, ``rays_per_source``, ``n_groups``) and then one HIP pass (``prt_frame_psf``): every ray
+        that meets the reference sphere is a secondary source of amplitude ``sqrt(w)`` (``weights``: a column, default
+        "intensity", or None for ones) and phase ``(OPD + d - R) / lambda``, summed at every pixel of a grid in the plane
+        through P perpendicular to the axis; rays of one wavelength add coherently, wavelengths incoherently.  The
+        image is normalised so that a perfect wave on the same rays gives 1 at P; ``strehl`` is the image at P
+        (include/prt.h states the definitions).  world_unit_um: how many micrometres one world unit is (1000 for mm),
+        required -- wavelengths are in micrometres.  pixels: an int or (nx, ny), 1..1024; pixel_size: a number or
+        (du, dv) in world units, default lambda_min * F / 4 with F = R / (2 rho_max) the smallest over the groups with
+        rays; centre: (u0, v0), the grid's centre in world units.  The wavelengths are the distinct values of the
+        selected rows, at most 16.
+
+        Sampling: each ray stands for an equal share of the pupil's area, or carries its share in ``weights``; random
+        pupil samples leave a noise floor of about 1 / (number of rays) in the normalised image.  Obliquity and 1/r
+        are taken as constant over the pupil (an error of order NA^2 at the rim).  Needs the whole frame of a trace,
+        like ``wavefront``; ``group=`` (sharded frames) is not supported yet."""
+        import torch
+
+        from . import engine
+
+        if group is not None:
+            raise NotImplementedError("psf() of a sharded frame (group=) is not supported yet")
+        unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
+        nx, ny = _pixel_counts(pixels)
+        step = None
+        if pixel_size is not None:
+            pair = np.asarray(pixel_size, dtype=float).reshape(-1)
+            pair = np.repeat(pair, 2) if pair.size == 1 else pair
+            if pair.shape != (2,) or not np.all(np.isfinite(pair)) or not np.all(pair > 0):
+                raise ValueError(f"pixel_size: a positive number or (du, dv), or None (got {pixel_size!r})")
+            step = (float(pair[0]), float(pair[1]))
+        uv0 = np.asarray(centre, dtype=float)
+        if uv0.shape != (2,) or not np.all(np.isfinite(uv0)):
+            raise ValueError(f"centre: (u0, v0), finite (got {centre!r})")
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        self._need_whole("psf")
+        self._need("wavelength", *(() if weights is None else (weights,)))
+        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        wavelengths = self._psf_wavelengths(surface_id, generation)
+        wave, rows, surface_id, n_groups, record = self._wavefront(
+            surface_id, reference, radius, axis, basis, None, 15, weights, generation, rays_per_source, n_groups)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            f_number = np.where(wave.n_rays > 0, wave.radius / (2.0 * wave.pupil_radius), np.nan)
+        if step is None:
+            finite = f_number[np.isfinite(f_number) & (f_number > 0)]
+            if not len(finite):
+                raise ValueError("psf: no group has rays that meet the reference sphere; give pixel_size")
+            side = float(wavelengths.min()) / unit * float(finite.min()) / 4.0
+            step = (side, side)
+        dev = rows.device
+        n_rows = rows.shape[1]
+        n_w = len(wavelengths)
+        image = torch.empty((n_groups, n_w, nx, ny), dtype=torch.float64, device=dev)
+        strehl = torch.empty(n_groups, dtype=torch.float64, device=dev)
+        out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_psf_workspace_bytes(n_rows, n_groups, n_w))),
+                           dtype=torch.uint8, device=dev)
+        lam = np.ascontiguousarray(wavelengths, dtype=np.float64)
+        uv0 = np.ascontiguousarray(uv0)
+        opd = wave.opd if wave.opd.numel() else torch.empty(1, dtype=torch.float64, device=dev)
+        pupil = wave.pupil if wave.pupil.numel() else torch.empty(2, dtype=torch.float64, device=dev)
+        engine._check(lib.prt_frame_psf(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
+            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
+            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), -1 if weights is None else _INDEX[weights],
+            lam.ctypes.data, n_w, unit, nx, ny, step[0], step[1], uv0.ctypes.data, image.data_ptr(), strehl.data_ptr(),
+            out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        return PSF(engine.to_host(image).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(), wavelengths,
+                   unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave)
+
+    def _psf_wavelengths(self, surface_id, generation):
+        """The distinct wavelengths of the rows the wavefront selects (sorted), found where the rows are."""
+        rows = self.rows
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if generation is not None:
+            start = sum(self.rows_per_generation[:int(generation)])
+            size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+            rows = rows[:, start:start + size]
+        lam = rows[_INDEX["wavelength"]]
+        if surface_id is not None:
+            lam = lam[rows[_INDEX["surface"]] == surface_id]
+        if hasattr(lam, "unique"):
+            values = lam.unique().cpu().numpy().astype(np.float64)
+        else:
+            values = np.unique(np.asarray(lam, dtype=np.float64))
+        if not len(values):
+            raise ValueError("psf: no row is selected at this surface")
+        if not np.all(np.isfinite(values) & (values > 0)):
+            raise ValueError("psf: a selected row's wavelength is not finite and > 0")
+        if len(values) > 16:
+            raise ValueError(f"psf: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
+        return values
 
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
@@ -671,6 +782,79 @@ class Wavefront:
             frame[f"Z{j + 1}"] = self.zernike[:, j]
         frame.index.name = "source_id"
         return frame
+
+
+class PSF:
+    """What ``DeviceFrame.psf`` returns (numpy arrays).  ``image`` (n_groups, nx, ny): the normalised polychromatic
+    image, indexed (e1, e2) as ``np.histogram2d`` is (``imshow(image[g].T, origin="lower")`` is upright);
+    ``image_by_wavelength`` (n_groups, n_wavelengths, nx, ny), whose sum over wavelengths is ``image``; ``u`` (nx) and
+    ``v`` (ny): the pixel centres along e1 and e2, in world units, about P; per group ``strehl`` (the image at P),
+    ``peak`` and ``peak_uv`` (the brightest pixel and its centre), ``f_number`` (R / (2 rho_max)), ``n_rays`` (rays
+    summed) and ``n_missed`` (rays left out: they missed the reference sphere or had no usable weight);
+    ``wavelengths`` (micrometres); ``record`` (n_groups, n_wavelengths, 4): rays used, rays left out, sum of the
+    amplitudes, Strehl numerator; ``wavefront``: the ``Wavefront`` the image was built on."""
+
+    def __init__(self, image_by_wavelength, strehl, record, wavelengths, world_unit_um, pixels, pixel_size, centre,
+                 f_number, wavefront):
+        self.image_by_wavelength = image_by_wavelength
+        self.image = image_by_wavelength.sum(axis=1)
+        self.strehl, self.record, self.wavelengths = strehl, record, np.asarray(wavelengths, dtype=float)
+        self.world_unit_um, self.pixel_size, self.centre = world_unit_um, pixel_size, centre
+        self.f_number, self.wavefront = f_number, wavefront
+        nx, ny = pixels
+        self.u = centre[0] + (np.arange(nx) - 0.5 * (nx - 1)) * pixel_size[0]
+        self.v = centre[1] + (np.arange(ny) - 0.5 * (ny - 1)) * pixel_size[1]
+        self.n_rays = record[:, :, 0].sum(axis=1).astype(np.int64)
+        self.n_missed = record[:, :, 1].sum(axis=1).astype(np.int64)
+        flat = self.image.reshape(len(self.image), -1)
+        self.peak = np.full(len(flat), np.nan)
+        self.peak_uv = np.full((len(flat), 2), np.nan)
+        for g, values in enumerate(flat):
+            if np.all(np.isfinite(values)):
+                i, j = np.unravel_index(int(np.argmax(values)), (nx, ny))
+                self.peak[g], self.peak_uv[g] = values[i * ny + j], (self.u[i], self.v[j])
+
+    def encircled_energy(self, radii, about="reference"):
+        """Per group, the share of the window's total in the pixels whose centres lie within each radius (world units)
+        of P (``about="reference"``) or of the brightest pixel (``"peak"``): an array (n_groups, len(radii)), or
+        (n_groups,) for one radius.  A host-side sum on the image: the window must hold what is to be counted."""
+        if about not in ("reference", "peak"):
+            raise ValueError('about: "reference" or "peak"')
+        r = np.atleast_1d(np.asarray(radii, dtype=float))
+        out = np.full((len(self.image), len(r)), np.nan)
+        for g, image in enumerate(self.image):
+            cu, cv = (0.0, 0.0) if about == "reference" else self.peak_uv[g]
+            dist = np.hypot(self.u[:, None] - cu, self.v[None, :] - cv)
+            total = image.sum()
+            out[g] = [image[dist <= radius].sum() / total for radius in r]
+        return out[:, 0] if np.ndim(radii) == 0 else out
+
+    def to_pandas(self):
+        """One row per group: strehl, peak, peak_u, peak_v, f_number, n_rays, n_missed."""
+        frame = pd.DataFrame({"strehl": self.strehl, "peak": self.peak, "peak_u": self.peak_uv[:, 0],
+                              "peak_v": self.peak_uv[:, 1], "f_number": self.f_number, "n_rays": self.n_rays,
+                              "n_missed": self.n_missed})
+        frame.index.name = "source_id"
+        return frame
+
+
+def _positive(value, message):
+    try:
+        number = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{message} (got {value!r})") from None
+    if not (np.isfinite(number) and number > 0):
+        raise ValueError(f"{message} (got {value!r})")
+    return number
+
+
+def _pixel_counts(pixels):
+    """pixels: an int or (nx, ny), each 1..1024."""
+    pair = (pixels, pixels) if np.ndim(pixels) == 0 else tuple(pixels)
+    if len(pair) != 2 or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 1 <= k <= 1024
+                                 for k in pair):
+        raise ValueError(f"pixels: an int or (nx, ny), each 1..1024 (got {pixels!r})")
+    return int(pair[0]), int(pair[1])
 
 
 RANK_RCOND = 1e-10  # singular values of Z^T W Z below this share of the largest are dropped (of Z: below 1e-5)
