@@ -661,6 +661,45 @@ int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t n_rows, do
                   double world_unit_um, int nx, int ny, double du, double dv, const double* centre_uv,
                   double* image_out, double* strehl_out, double* record_out, void* workspace, void* stream);
 
+/* Geometric MTF of the frame, through focus (no counterpart upstream).  It reads only each ray's end point and
+ * direction at the surface, so it works on frames that hold the detector's rows alone.
+ *
+ * Definitions.
+ * Rays: rows at surface (NaN: any), in generation (NaN: any), in group g = floor(id / rays_per_source) with
+ *   0 <= g < n_groups (rays_per_source <= 0: one group).  Each ray has an end point Q = (x1, y1, z1), a direction
+ *   u = (x_tilt, y_tilt, z_tilt) (which need not be unit length) and a weight w (weight_column, or ones for -1).
+ * Rays left out: a ray is left out and counted (n_missed) when u.a == 0, when any value it needs is not finite, or when
+ *   w is not finite and >= 0.
+ * Axes: (a, e1, e2), the 9 doubles of frame.pupil_axes().  The default is a = x, e1 = y, e2 = z.
+ * Centre C_g: the weighted centroid of the group's Q, or a given point per group (reference).
+ * Plane at shift delta: the plane through C_g + delta a, perpendicular to a.  Ray r meets it at
+ *   X_r(delta) = Q_r + u_r ((C_g + delta a - Q_r).a) / (u_r.a).  Its coordinates in that plane are
+ *   x_r(delta) = ((X_r(delta) - C_g).e1, (X_r(delta) - C_g).e2).  These are linear in delta:
+ *   x_r(delta) = p_r + delta s_r with s_r = (u.e1, u.e2) / (u.a).
+ * Frequency vector: azimuth theta in degrees, measured from e1 towards e2, and frequency nu >= 0 in cycles per world
+ *   unit (cycles/mm for a scene in mm).  Together they give k = nu (cos theta, sin theta).
+ * OTF: OTF_g(delta, theta, nu) = sum_r w_r exp(-2 pi i k.x_r(delta)) / sum_r w_r.  Wavelengths are not separated: the
+ *   geometric MTF is polychromatic through the weights.  The MTF is |OTF| and the PTF is arg OTF, about C_g.  A group
+ *   with no rays, or with sum w = 0, gives NaN.
+ *
+ * prt_frame_mtf: reference DEVICE (n_groups, 3) or NULL for the centroids; axes HOST 9 doubles; frequencies (HOST,
+ * 1..4096, finite and >= 0), azimuths_deg (HOST, 1..16, finite), focus (HOST, 1..256 shifts delta, finite);
+ * n_groups * n_focus * n_azimuths * n_frequencies * 16 bytes may not pass the 256 MiB cap of the partial-sum slab.
+ * Out, DEVICE, overwritten: otf_out (n_groups, n_focus, n_azimuths, n_frequencies, 2) -- real and imaginary part --;
+ * record_out (n_groups, 6): C_g (3), sum w, rays used, rays left out.  workspace: prt_frame_mtf_workspace_bytes(n_rows,
+ * n_groups, n_frequencies, n_azimuths, n_focus) device bytes.  The rays are sorted into group buckets in row order by a
+ * stable counting sort; the sum is a grid of (ray slice, output tile) workgroups whose partial sums are folded in
+ * slice order.  Every partition depends only on a group's count of rays used, on the output count and on n_groups,
+ * never on n_rows, and there are no floating-point atomics: every output is the same, bit for bit, on every run and on
+ * any frame that holds the same selected rows in the same order.  sum w is added in the order of the numerators, so
+ * the OTF at nu = 0 is exactly 1.  All arguments are checked before a device is touched.  Stream-ordered; the call
+ * returns when the stream has reached its end. */
+int64_t prt_frame_mtf_workspace_bytes(int64_t n_rows, int n_groups, int n_frequencies, int n_azimuths, int n_focus);
+int prt_frame_mtf(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                  double rays_per_source, int n_groups, const double* reference, const double* axes, int weight_column,
+                  const double* frequencies, int n_frequencies, const double* azimuths_deg, int n_azimuths,
+                  const double* focus, int n_focus, double* otf_out, double* record_out, void* workspace, void* stream);
+
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,
  * out[2] = GPU milliseconds spent in generation kernels (hipEvent, on the trace stream),

@@ -640,6 +640,83 @@ class DeviceFrame:
             raise ValueError(f"psf: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
         return values
 
+    # --- geometric MTF through focus (no counterpart upstream) --------------------------------------------------------
+    def mtf(self, surface, frequencies, *, azimuths=(0.0, 90.0), focus=(0.0,), reference="centroid", axis=None,
+            basis=None, weights="intensity", generation=None, rays_per_source=None, n_groups=None, group=None):
+        """The geometric MTF at ``surface`` (an id or an object with ``get_id()``; None: every row that passes
+        ``generation``), per group (``id // rays_per_source``), at every focus shift, azimuth and frequency.  Returns
+        an ``MTF``.
+
+        Each ray's line, from its end point Q along its direction u, meets the plane through C + delta a perpendicular
+        to the axis a at x(delta) = p + delta s in the basis (e1, e2) of that plane; the OTF is the weighted mean of
+        exp(-2 pi i k.x(delta)) with k = nu (cos theta, sin theta), theta in degrees from e1 towards e2 and nu in cycles
+        per world unit (include/prt.h states the definitions).  frequencies: 1 to 4096 values >= 0; azimuths: 1 to 16
+        (default tangential and sagittal for a field along e1: 0 and 90); focus: 1 to 256 shifts delta along a, in
+        world units.  reference: "centroid" (the weighted centroid of the group's end points) or a point or an
+        (n_groups, 3) array; axis / basis as in ``wavefront``; weights: a column (default "intensity") or None for ones.
+        Past the surface a ray is a straight line, so a through-focus scan needs no re-trace.  Rays whose direction is
+        perpendicular to the axis, or with a value that is not finite, count in ``n_missed``.
+
+        One HIP pass (``prt_frame_mtf``) over the rows it selects: it reads only end points, directions and the columns
+        of the selection, so frames made by ``where``, ``select`` or under ``record_only`` work and give the same bits
+        as the whole frame.  ``group=`` (sharded frames) is not supported yet."""
+        import torch
+
+        from . import engine
+
+        if group is not None:
+            raise NotImplementedError("mtf() of a sharded frame (group=) is not supported yet")
+        nu = _mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True)
+        theta = _mtf_values(azimuths, "azimuths", 16, "finite, in degrees")
+        planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        axes = pupil_axes(axis, basis)
+        if isinstance(reference, str) and reference != "centroid":
+            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        needed = list(_MTF_COLUMNS) + ([weights] if weights is not None else []) + (["id"] if rays_per_source else [])
+        needed += (["surface"] if surface_id is not None else []) + (["generation"] if generation is not None else [])
+        try:
+            self._need(*needed)
+        except KeyError as error:
+            raise ValueError(f"mtf: {error.args[0]}") from None
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if rays_per_source:
+            if n_groups is None:
+                top = float(self["id"].max()) if len(self) else -1.0
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        n_groups = int(n_groups)
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        centres = None
+        if not isinstance(reference, str):
+            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
+            if centres.shape == (3,):
+                centres = centres.expand(n_groups, 3)
+            if tuple(centres.shape) != (n_groups, 3):
+                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
+            centres = centres.to(dev, torch.float64).contiguous()
+        n_rows = rows.shape[1]
+        otf = torch.empty((n_groups, len(planes), len(theta), len(nu), 2), dtype=torch.float64, device=dev)
+        record = torch.empty((n_groups, 6), dtype=torch.float64, device=dev)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_mtf_workspace_bytes(n_rows, n_groups, len(nu), len(theta),
+                                                                               len(planes)))),
+                           dtype=torch.uint8, device=dev)
+        engine._check(lib.prt_frame_mtf(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
+            float("nan") if surface_id is None else surface_id,
+            float("nan") if generation is None else float(generation), float(rays_per_source or 0), n_groups,
+            None if centres is None else centres.data_ptr(), axes.ctypes.data, -1 if weights is None else _INDEX[weights],
+            nu.ctypes.data, len(nu), theta.ctypes.data, len(theta), planes.ctypes.data, len(planes), otf.data_ptr(),
+            record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        pair = engine.to_host(otf)
+        return MTF(pair[..., 0] + 1j * pair[..., 1], engine.to_host(record).copy(), nu, theta, planes)
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -750,6 +827,7 @@ class SinkStats:
 
 
 _PATH_COLUMNS = ("index", "id", "surface", "generation", "x0", "y0", "z0", "x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")
+_MTF_COLUMNS = ("x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")  # (what the MTF reads of every ray)
 
 
 class Wavefront:
@@ -836,6 +914,115 @@ class PSF:
                               "n_missed": self.n_missed})
         frame.index.name = "source_id"
         return frame
+
+    def mtf(self, frequencies, azimuths=(0.0, 90.0)):
+        """The MTF of this image (the Huygens MTF, for systems near the diffraction limit where the geometric MTF does
+        not apply): per group the DFT of ``image`` at k = nu (cos theta, sin theta), normalised by the image's sum, with
+        the pixel centres (u, v) about P as coordinates.  frequencies in cycles per world unit, azimuths in degrees from
+        e1 towards e2.  A host-side sum; the window must hold the image.  Returns an ``MTF`` with one focus plane."""
+        nu = _mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True)
+        theta = _mtf_values(azimuths, "azimuths", 16, "finite, in degrees")
+        rad = np.radians(theta)
+        kc, ks = np.cos(rad)[:, None] * nu[None, :], np.sin(rad)[:, None] * nu[None, :]
+        n = len(self.image)
+        otf = np.full((n, 1, len(theta), len(nu)), np.nan, dtype=complex)
+        record = np.full((n, 6), np.nan)
+        for g, image in enumerate(self.image):
+            total = image.sum()
+            along_u = np.exp(-2j * np.pi * kc[..., None] * self.u)  # (azimuths, frequencies, nx)
+            along_v = np.exp(-2j * np.pi * ks[..., None] * self.v)  # (azimuths, frequencies, ny)
+            otf[g, 0] = np.einsum("afi,ij,afj->af", along_u, image, along_v) / total
+            record[g, 3:] = total, self.n_rays[g], self.n_missed[g]
+        return MTF(otf, record, nu, theta, np.zeros(1))
+
+
+class MTF:
+    """What ``DeviceFrame.mtf`` returns (numpy arrays).  ``otf`` (n_groups, n_focus, n_azimuths, n_frequencies),
+    complex; ``mtf`` = |otf| and ``ptf`` = arg otf (radians, about the group's centre); ``frequencies`` (cycles per world
+    unit), ``azimuths`` (degrees) and ``focus`` (shifts along the axis); per group ``centre`` (n_groups, 3), ``n_rays``
+    (rays summed), ``n_missed`` (rays left out) and ``sum_weights``.  A group without rays is NaN throughout."""
+
+    def __init__(self, otf, record, frequencies, azimuths, focus):
+        self.otf = np.asarray(otf)
+        self.mtf, self.ptf = np.abs(self.otf), np.angle(self.otf)
+        self.frequencies = np.asarray(frequencies, dtype=float)
+        self.azimuths = np.asarray(azimuths, dtype=float)
+        self.focus = np.asarray(focus, dtype=float)
+        self.record = np.asarray(record, dtype=float)
+        self.centre, self.sum_weights = self.record[:, :3], self.record[:, 3]
+        self.n_rays = np.nan_to_num(self.record[:, 4]).astype(np.int64)
+        self.n_missed = np.nan_to_num(self.record[:, 5]).astype(np.int64)
+
+    def to_pandas(self):
+        """Long form: one row per (source_id, focus, azimuth, frequency) with its mtf and ptf."""
+        g, f, a, n = self.otf.shape
+        index = np.indices((g, f, a, n)).reshape(4, -1)
+        return pd.DataFrame({"source_id": index[0], "focus": self.focus[index[1]], "azimuth": self.azimuths[index[2]],
+                             "frequency": self.frequencies[index[3]], "mtf": self.mtf.reshape(-1),
+                             "ptf": self.ptf.reshape(-1)})
+
+    def best_focus(self, frequency=None, azimuths=None):
+        """Per group, the focus shift that maximises the MTF averaged over ``azimuths`` (None: all; else values of
+        ``self.azimuths``) at ``frequency`` (a value of ``self.frequencies``; None: averaged over all of them).  The
+        best sampled plane, refined by the vertex of the parabola through it and its two neighbours when it is not at
+        an end of the scan.  NaN for a group without rays."""
+        a_index = slice(None) if azimuths is None else _positions(self.azimuths, azimuths, "azimuths")
+        f_index = slice(None) if frequency is None else _positions(self.frequencies, [frequency], "frequency")
+        merit = self.mtf[:, :, a_index][:, :, :, f_index].mean(axis=(2, 3))  # (groups, planes)
+        order = np.argsort(self.focus, kind="stable")
+        x, merit = self.focus[order], merit[:, order]
+        best = np.full(len(merit), np.nan)
+        for g, y in enumerate(merit):
+            if not np.any(np.isfinite(y)):
+                continue
+            k = int(np.nanargmax(y))
+            best[g] = x[k]
+            if 0 < k < len(x) - 1 and np.all(np.isfinite(y[k - 1:k + 2])):
+                (x0, x1, x2), (y0, y1, y2) = x[k - 1:k + 2], y[k - 1:k + 2]
+                a = ((y2 - y1) / (x2 - x1) - (y1 - y0) / (x1 - x0)) / (x2 - x0)
+                if a < 0:
+                    slope = (y1 - y0) / (x1 - x0) - a * (x0 + x1)  # (y = a x^2 + slope x + c)
+                    best[g] = float(np.clip(-slope / (2 * a), x0, x2))
+        return best
+
+
+def diffraction_mtf(frequencies, wavelength_um, f_number, world_unit_um):
+    """The diffraction-limited MTF of a circular pupil without aberrations: (2 / pi) (phi - cos phi sin phi) with
+    phi = arccos(nu lambda F), and 0 past the cutoff nu = 1 / (lambda F).  frequencies in cycles per world unit,
+    wavelength in micrometres, world_unit_um: how many micrometres one world unit is (1000 for mm)."""
+    unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
+    lam = _positive(wavelength_um, "wavelength_um: finite and > 0") / unit
+    f = _positive(f_number, "f_number: finite and > 0")
+    nu = np.asarray(frequencies, dtype=float)
+    if not np.all(np.isfinite(nu) & (nu >= 0)):
+        raise ValueError("frequencies: finite and >= 0")
+    x = np.minimum(nu * lam * f, 1.0)
+    phi = np.arccos(x)
+    return (2 / np.pi) * (phi - np.cos(phi) * np.sin(phi))
+
+
+def _mtf_values(values, name, cap, rule, non_negative=False):
+    """A 1-D float64 array of 1..cap finite values (>= 0 when non_negative)."""
+    try:
+        array = np.ascontiguousarray(np.atleast_1d(np.asarray(values, dtype=np.float64)))
+    except (TypeError, ValueError):
+        raise ValueError(f"{name}: 1 to {cap} numbers, {rule} (got {values!r})") from None
+    if array.ndim != 1 or not 1 <= len(array) <= cap:
+        raise ValueError(f"{name}: 1 to {cap} numbers, {rule} (got {array.size})")
+    if not np.all(np.isfinite(array)) or (non_negative and np.any(array < 0)):
+        raise ValueError(f"{name}: 1 to {cap} numbers, {rule}")
+    return array
+
+
+def _positions(sampled, wanted, name):
+    """Indices of the wanted values among the sampled ones."""
+    out = []
+    for value in np.atleast_1d(np.asarray(wanted, dtype=float)):
+        hits = np.flatnonzero(np.isclose(sampled, value, rtol=1e-12, atol=0))
+        if not len(hits):
+            raise ValueError(f"{name}: {value} is not one of the sampled values {list(sampled)}")
+        out.append(int(hits[0]))
+    return out
 
 
 def _positive(value, message):
