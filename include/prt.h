@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -699,6 +699,71 @@ int prt_frame_mtf(int device, const double* rows, int64_t ld, int64_t n_rows, do
                   double rays_per_source, int n_groups, const double* reference, const double* axes, int weight_column,
                   const double* frequencies, int n_frequencies, const double* azimuths_deg, int n_azimuths,
                   const double* focus, int n_focus, double* otf_out, double* record_out, void* workspace, void* stream);
+
+/* Ray-aberration curves of the frame: each ray's row at a surface joined by ray id with the row where the ray was
+ * launched (examples/lens_design.ipynb cells 12-13 join the two cuts of the frame with isin(id)), its transverse and
+ * longitudinal aberration against its pupil coordinate, a Zernike fit of the fans and the zonal curve.
+ *
+ * prt_frame_launch_index: the frame is whole and generation-major, as prt_frame_optical_path requires; its first
+ * n_launch_rows rows are generation 0.  index_out (DEVICE, int64, one per row) receives the row number of the
+ * generation-0 row with the same id, -1 when there is none; a generation-0 row maps to itself.  Ids are integers in
+ * [id0, id0 + n_ids); an id outside that range, one that is not an integer, or one repeated inside generation 0 gives
+ * PRT_ERR_ARG through one status word read back (so the call returns when the stream has reached its end).  Two
+ * passes: generation 0 writes its row numbers into a dense per-id table in a stream-ordered scratch block, then every
+ * row gathers from it.
+ *
+ * Definitions of prt_frame_ray_aberrations.
+ * Rays: rows at surface (NaN: any), in generation (NaN: any), in group g = floor(id / rays_per_source) with
+ *   0 <= g < n_groups (rays_per_source <= 0: one group).  Each has an end point Q = (x1, y1, z1), a direction
+ *   u = (x_tilt, y_tilt, z_tilt), a weight w (weight_column, or ones for -1) and a launch row (launch_index, of
+ *   prt_frame_launch_index: rows is the whole frame) with start point L = (x0, y0, z0) and direction v.
+ * Rays left out: a ray is left out and counted (n_missed) when its launch index is -1, when a value it needs is not
+ *   finite (Q, u, w, the slope, and L or v by the pupil mode), when u.a == 0, or when w is not finite and >= 0.
+ * Axes: (a, e1, e2), the 9 doubles of frame.pupil_axes().  The default is a = x, e1 = y, e2 = z.
+ * Launch (pupil) coordinate h: pupil_mode 0 (position, collimated sources) h = ((L - O).e1, (L - O).e2) with O =
+ *   launch_origin (HOST 3 doubles, NULL: the origin); pupil_mode 1 (direction, point sources) h = (v.e1, v.e2) / (v.a),
+ *   and a ray with v.a == 0 is left out.  Normalised p = h / rho, rho = pupil_radius or, when 0, the group's largest
+ *   |h| over the rays used (an extent of 0 gives rho = 1).
+ * Reference point C_g: reference_mode 0 the weighted centroid of the group's Q; 1 the given point per group
+ *   (reference, DEVICE (n_groups, 3)); 2 the chief ray: the Q of the used ray with the smallest |h|^2, ties to the first
+ *   in row order.
+ * Per ray: p, the transverse aberration eps = ((Q - C_g).e1, (Q - C_g).e2), the slope s = (u.e1, u.e2) / (u.a), and
+ *   the longitudinal aberration la = x0 - x_tilt * y0 / y_tilt of the row at the surface (PRT_FRAME_AXIS_INTERCEPT's
+ *   own device function), NaN when that is not finite; a ray with NaN la stays in everything that does not read la.  At
+ *   a plane shifted by delta along a the transverse aberration is eps + delta s (the MTF's convention).
+ * Fit: weighted least squares of the four targets eps1, eps2, s1, s2 on Z_1..Z_n_terms of p (Noll's order and RMS
+ *   normalisation, as prt_frame_wavefront; n_terms <= 36).
+ * Zones: n_zones (0..1024) rings of equal width in |p|, zone = min(floor(|p| n_zones), n_zones - 1).
+ *
+ * prt_frame_ray_aberrations: Out, DEVICE, overwritten: ray_out (capacity, 7) -- p1, p2, eps1, eps2, s1, s2, la of the
+ * rays used, compacted in row order -- and row_out (capacity, int64), their row numbers in the frame; more rays used
+ * than capacity gives PRT_ERR_ARG.  record_out (n_groups, 16): C_g (3), rho, rays used, rays left out, rays with finite
+ * la, the chief ray's row (-1: none), sum w, sum w eps (2), sum w s (2), sum w |eps|^2, sum w eps.s, sum w |s|^2 (eps
+ * about C_g, s raw).  normal_out (n_groups, n_terms (n_terms + 1) / 2 + 4 n_terms + 1): the upper triangle of Z^T W Z by
+ * rows, Z^T W eps1, Z^T W eps2, Z^T W s1, Z^T W s2, sum w.  zone_out (n_groups, n_zones, 6; may be NULL for n_zones 0):
+ * rays, then over the zone's rays with finite la sum w, sum w la, sum w la^2, then sum w |eps|^2 over all the zone's
+ * rays, then the count of rays with finite la.  workspace: prt_frame_ray_aberrations_workspace_bytes(capacity, n_groups,
+ * n_terms, n_zones) device bytes (-1 for arguments the call would refuse).  n_groups * max(n_zones, 1) * 8 bytes may
+ * not pass the 64 MiB cap of the sort's counts.  The rays are sorted into (group, zone) buckets in row order by a
+ * stable counting sort; every sum is formed per chunk of 4096 rays of a bucket in a fixed tree and the chunks are added
+ * in order.  A bucket's chunks depend only on its count of rays used, never on n_rows, and there are no floating-point
+ * atomics: every output is the same, bit for bit, on every run and on any frame that holds the same selected rows and
+ * launch rows in the same order.  All arguments are checked before a device is touched.  Stream-ordered; the call
+ * reads two counts back on the way and returns when the stream has reached its end. */
+#define PRT_PUPIL_POSITION 0
+#define PRT_PUPIL_DIRECTION 1
+#define PRT_REFERENCE_CENTROID 0
+#define PRT_REFERENCE_POINTS 1
+#define PRT_REFERENCE_CHIEF 2
+int prt_frame_launch_index(int device, const double* rows, int64_t ld, int64_t n_rows, int64_t n_launch_rows, double id0,
+                           int64_t n_ids, int64_t* index_out, void* stream);
+int64_t prt_frame_ray_aberrations_workspace_bytes(int64_t capacity, int n_groups, int n_terms, int n_zones);
+int prt_frame_ray_aberrations(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* launch_index,
+                              double surface, double generation, double rays_per_source, int n_groups,
+                              const double* reference, int reference_mode, const double* axes, int pupil_mode,
+                              const double* launch_origin, double pupil_radius, int n_terms, int n_zones,
+                              int weight_column, int64_t capacity, double* ray_out, int64_t* row_out,
+                              double* record_out, double* normal_out, double* zone_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

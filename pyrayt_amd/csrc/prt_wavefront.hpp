@@ -49,6 +49,13 @@ __host__ __device__ constexpr int noll_m(int j) {
   return (j % 2) ? -m : m;
 }
 
+struct NollTable { int n[WF_MAX_TERMS], m[WF_MAX_TERMS]; };
+__host__ __device__ constexpr NollTable noll_table() {
+  NollTable t{};
+  for (int j = 1; j <= WF_MAX_TERMS; ++j) { t.n[j - 1] = noll_n(j); t.m[j - 1] = noll_m(j); }
+  return t;
+}
+
 __device__ __forceinline__ bool wf_selected(const double* __restrict__ rows, int64_t ld, int64_t j, double surface,
                                             double generation) {
   return (surface != surface || rows[PRT_COL_SURFACE * ld + j] == surface) &&
@@ -363,9 +370,10 @@ __device__ __forceinline__ void wf_zernike(double x, double y, double (&z)[WF_MA
       radial[n][m] = ((k2 * rho2 + k3) * radial[n - 2][m] + k4 * radial[n - 4][m]) / k1;
     }
   }
+  constexpr NollTable noll = noll_table();  // (constants once the loop is unrolled: radial, cm, sm stay in registers)
 #pragma unroll
   for (int j = 1; j <= WF_MAX_TERMS; ++j) {
-    const int n = noll_n(j), m = noll_m(j), am = m < 0 ? -m : m;
+    const int n = noll.n[j - 1], m = noll.m[j - 1], am = m < 0 ? -m : m;
     const double norm = am == 0 ? sqrt((double)(n + 1)) : sqrt(2.0 * (n + 1));
     z[j - 1] = norm * radial[n][am] * (m > 0 ? cm[am] : m < 0 ? sm[am] : 1.0);
   }

@@ -401,7 +401,7 @@ class DeviceFrame:
         return (hist if rays_per_source else hist[0]), edges
 
     # --- optical path and wavefront error (no counterpart upstream) --------------------------------------------------
-    def _need_whole(self, what):
+    def _need_whole(self, what, columns=None):
         """The optical path sums a ray's rows over every generation before the one looked at: the frame must be the
         whole frame of a trace."""
         if self.origin == "record_only":
@@ -411,7 +411,7 @@ class DeviceFrame:
             raise ValueError(f"{what} needs the whole frame of a trace: this frame was made by {self.origin}()")
         if not self.rows_per_generation or sum(self.rows_per_generation) != len(self):
             raise ValueError(f"{what} needs the whole frame of a trace: rows_per_generation is not known for this frame")
-        self._need(*_PATH_COLUMNS)
+        self._need(*(columns or _PATH_COLUMNS))
 
     def optical_path(self):
         """The cumulative optical path length of every row, a device tensor of ``len(self)`` float64: the row's segment
@@ -717,6 +717,176 @@ class DeviceFrame:
         pair = engine.to_host(otf)
         return MTF(pair[..., 0] + 1j * pair[..., 1], engine.to_host(record).copy(), nu, theta, planes)
 
+    # --- ray-aberration curves: the frame joined by ray id (examples/lens_design.ipynb cells 12-13) ---------------------
+    def launch_index(self):
+        """Per row, the row number of the generation-0 row with the same ray id (-1: none; a generation-0 row maps to
+        itself): a device tensor of ``len(self)`` int64 (``prt_frame_launch_index``: generation 0 writes a dense per-id
+        table, every row gathers from it).  It is the notebook's join of two cuts of the frame,
+        ``results.loc[(generation == 0) & id.isin(selected.id)]``, as an index.  Ids must be integers, unique within
+        generation 0.  Needs the whole frame of a trace, like ``optical_path``."""
+        self._need_whole("launch_index", _JOIN_COLUMNS)
+        return self._launch_index()
+
+    def _launch_index(self):
+        import torch
+
+        from . import engine
+
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        index = torch.empty(rows.shape[1], dtype=torch.int64, device=dev)
+        if rows.shape[1] == 0:
+            return index
+        ids = rows[_INDEX["id"]]
+        id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
+        if not (np.isfinite(id0) and np.isfinite(top)):
+            raise ValueError("launch_index: an id is not an integer in the frame's id range")
+        engine._check(engine.library().prt_frame_launch_index(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), rows.shape[1], 1), rows.shape[1],
+            int(self.rows_per_generation[0]), id0, int(top - id0) + 1, index.data_ptr(), engine._stream_ptr(torch, dev)))
+        return index
+
+    def _selection(self, surface, generation):
+        """The mask of the rows at ``surface`` (None: any) in ``generation`` (None: any; "last": the highest)."""
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        mask = None
+        if surface is not None:
+            mask = self["surface"] == float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        if generation is not None:
+            m = self["generation"] == float(generation)
+            mask = m if mask is None else (mask & m)
+        return mask
+
+    def launch(self, surface=None, generation=None):
+        """The launch rows of the selected rows (at ``surface``, in ``generation``; "last": the highest), in the
+        selected rows' order: a ``DeviceFrame`` aligned row for row with ``where(...)`` of the same selection, without
+        the rows that have no launch row.  The notebook's ``results.loc[(generation == 0) & id.isin(selected.id)]``."""
+        index = self.launch_index()
+        mask = self._selection(surface, generation)
+        if mask is not None:
+            index = index[mask]
+        part = DeviceFrame(self.rows[:, index[index >= 0]], None, self.written)
+        part.origin = "launch"
+        return part
+
+    def ray_aberrations(self, surface, *, pupil="position", launch_origin=(0.0, 0.0, 0.0), reference="centroid",
+                        axis=None, basis=None, pupil_radius=None, zernike=21, zones=64, weights=None, generation=None,
+                        rays_per_source=None, n_groups=None, group=None):
+        """The ray aberrations at ``surface`` (an id or an object with ``get_id()``; None: every row that passes
+        ``generation``) against the pupil coordinate each ray was launched at, per group (``id // rays_per_source``).
+        Returns a ``RayAberrations``.
+
+        Every selected row is joined by ray id with its generation-0 row (``launch_index``).  pupil: "position" for
+        collimated sources -- h = ((L - O).e1, (L - O).e2), L the launch row's start point, O ``launch_origin`` -- or
+        "direction" for point sources -- h = (v.e1, v.e2) / (v.a), v the launch direction.  p = h / rho with rho
+        ``pupil_radius`` (None: the group's largest |h|).  Per ray: p, the transverse aberration eps = (Q - C) in
+        (e1, e2) about C (``reference``: "centroid" -- the weighted centroid of the group's end points Q --, "chief"
+        -- the Q of the ray with the smallest |h| --, a point or an (n_groups, 3) array), the slope
+        s = (u.e1, u.e2) / (u.a), and the longitudinal aberration ``axis_intercept`` of the row.  At a plane shifted by
+        delta along the axis the transverse aberration is eps + delta s: a through-focus study needs no re-trace.
+        ``zernike``: J <= 36 Noll terms fitted to eps1, eps2, s1, s2 over p; ``zones``: 0..1024 rings of equal width in
+        |p| for the longitudinal curve; axis / basis / weights as in ``mtf`` (include/prt.h states the definitions).
+        Rays without a launch row, with a value that is not finite, with a direction perpendicular to the axis or a
+        weight that is not finite and >= 0 count in ``n_missed``.  One HIP pass (``prt_frame_ray_aberrations``), no
+        floating-point atomics: the same bits on every run.  Needs the whole frame of a trace, like ``optical_path``;
+        ``group=`` (sharded frames) is not supported yet."""
+        import torch
+
+        from . import engine
+
+        if group is not None:
+            raise NotImplementedError("ray_aberrations() of a sharded frame (group=) is not supported yet")
+        if pupil not in ("position", "direction"):
+            raise ValueError(f'pupil: "position" or "direction" (got {pupil!r})')
+        terms = zernike
+        if isinstance(terms, bool) or not isinstance(terms, (int, np.integer)) or not 1 <= terms <= 36:
+            raise ValueError(f"zernike: the number of terms, 1 to 36 (got {zernike!r})")
+        if isinstance(zones, bool) or not isinstance(zones, (int, np.integer)) or not 0 <= zones <= 1024:
+            raise ValueError(f"zones: the number of rings, 0 to 1024 (got {zones!r})")
+        terms, zones = int(terms), int(zones)
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        if pupil_radius is not None and not (np.isfinite(pupil_radius) and pupil_radius > 0):
+            raise ValueError("pupil_radius: a positive number, or None for the group's largest extent")
+        origin = np.ascontiguousarray(np.asarray(launch_origin, dtype=np.float64))
+        if origin.shape != (3,) or not np.all(np.isfinite(origin)):
+            raise ValueError(f"launch_origin: a finite 3-vector (got {launch_origin!r})")
+        axes = pupil_axes(axis, basis)
+        if isinstance(reference, str) and reference not in ("centroid", "chief"):
+            raise ValueError('reference: "centroid", "chief", a point or an (n_groups, 3) array')
+        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        try:
+            self._need_whole("ray_aberrations", _JOIN_COLUMNS)
+            if weights is not None:
+                self._need(weights)
+        except KeyError as error:
+            raise ValueError(f"ray_aberrations: {error.args[0]}") from None
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if rays_per_source:
+            if n_groups is None:
+                top = float(self["id"].max()) if len(self) else -1.0
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        n_groups = int(n_groups)
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        centres, mode = None, {"centroid": 0, "chief": 2}.get(reference if isinstance(reference, str) else None, 1)
+        if mode == 1:
+            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
+            if centres.shape == (3,):
+                centres = centres.expand(n_groups, 3)
+            if tuple(centres.shape) != (n_groups, 3):
+                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
+            centres = centres.to(dev, torch.float64).contiguous()
+        index = self._launch_index()
+        n_rows = rows.shape[1]
+        if generation is not None:  # (generation-major: at most one generation's rows are selected)
+            g = int(generation)
+            capacity = self.rows_per_generation[g] if 0 <= g < len(self.rows_per_generation) else 0
+        elif surface_id is not None:
+            capacity = int((rows[_INDEX["surface"]] == surface_id).sum())
+        else:
+            capacity = n_rows
+        entries = terms * (terms + 1) // 2 + 4 * terms + 1
+        lib = engine.library()
+        rays = torch.empty((capacity, 7), dtype=torch.float64, device=dev)
+        row_numbers = torch.empty(capacity, dtype=torch.int64, device=dev)
+        record = torch.empty((n_groups, 16), dtype=torch.float64, device=dev)
+        normal = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
+        zone = torch.empty((n_groups, zones, 6), dtype=torch.float64, device=dev)
+        work = torch.empty(int(engine._check(lib.prt_frame_ray_aberrations_workspace_bytes(capacity, n_groups, terms,
+                                                                                           zones))),
+                           dtype=torch.uint8, device=dev)
+        engine._check(lib.prt_frame_ray_aberrations(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, index.data_ptr(),
+            float("nan") if surface_id is None else surface_id,
+            float("nan") if generation is None else float(generation), float(rays_per_source or 0), n_groups,
+            None if centres is None else centres.data_ptr(), mode, axes.ctypes.data, 0 if pupil == "position" else 1,
+            origin.ctypes.data, float(pupil_radius or 0.0), terms, zones, -1 if weights is None else _INDEX[weights],
+            capacity, rays.data_ptr() if capacity else None, row_numbers.data_ptr() if capacity else None,
+            record.data_ptr(), normal.data_ptr(), zone.data_ptr() if zones else None, work.data_ptr(),
+            engine._stream_ptr(torch, dev)))
+        record_host = engine.to_host(record).copy()
+        used = int(record_host[:, 4].sum())
+        row_numbers = row_numbers[:used]
+        # the launch coordinate itself, gathered from the launch rows (p * rho would round twice)
+        launch = rows[:, index[row_numbers]]
+        if pupil == "position":
+            d = [launch[_INDEX[name]] - float(o) for name, o in zip(("x0", "y0", "z0"), origin)]
+            h = [d[0] * float(e[0]) + d[1] * float(e[1]) + d[2] * float(e[2]) for e in (axes[3:6], axes[6:9])]
+        else:
+            v = [launch[_INDEX[name]] for name in ("x_tilt", "y_tilt", "z_tilt")]
+            va = v[0] * float(axes[0]) + v[1] * float(axes[1]) + v[2] * float(axes[2])
+            h = [(v[0] * float(e[0]) + v[1] * float(e[1]) + v[2] * float(e[2])) / va for e in (axes[3:6], axes[6:9])]
+        groups = None
+        if rays_per_source:
+            groups = torch.floor(rows[_INDEX["id"]][row_numbers] / float(rays_per_source)).to(torch.int64)
+        return RayAberrations(rays[:used], row_numbers, record_host, engine.to_host(normal).copy(),
+                              engine.to_host(zone).copy(), terms, h=torch.stack(h, 1), group=groups)
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -827,6 +997,7 @@ class SinkStats:
 
 
 _PATH_COLUMNS = ("index", "id", "surface", "generation", "x0", "y0", "z0", "x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")
+_JOIN_COLUMNS = tuple(name for name in _PATH_COLUMNS if name != "index")  # (what the ray-aberration passes read)
 _MTF_COLUMNS = ("x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")  # (what the MTF reads of every ray)
 
 
@@ -984,6 +1155,118 @@ class MTF:
                     slope = (y1 - y0) / (x1 - x0) - a * (x0 + x1)  # (y = a x^2 + slope x + c)
                     best[g] = float(np.clip(-slope / (2 * a), x0, x2))
         return best
+
+
+class RayAberrations:
+    """What ``DeviceFrame.ray_aberrations`` returns.  Per ray used, in row order (device tensors): ``pupil`` (n, 2), the
+    normalised launch coordinate p; ``transverse`` (n, 2), eps about the group's reference point; ``slope`` (n, 2), s;
+    ``longitudinal`` (n), la (NaN for a ray parallel to the axis); ``rows`` (n), the ray's row number in the frame;
+    ``launch`` (n, 2), the launch coordinate h itself, and ``group`` (n).  Per group (numpy arrays): ``centre``
+    (n_groups, 3), ``pupil_radius`` (rho), ``n_rays``, ``n_missed``, ``n_longitudinal`` (rays with a finite la),
+    ``chief_row`` (-1: none), ``sum_weights``, ``coefficients`` (n_groups, 4, J) -- Noll's Z1..ZJ fitted to eps1, eps2,
+    s1, s2 over p --, ``rank`` of the fit's normal equations and ``residual`` (n_groups, 4), the weighted RMS of what the
+    fit leaves of each target; ``record`` (n_groups, 16), ``normal`` and ``zones`` (n_groups, n_zones, 6): the device's
+    sums (include/prt.h)."""
+
+    def __init__(self, rays, rows, record, normal, zones, terms, h=None, group=None):
+        self.rays, self.rows, self.terms = rays, rows, int(terms)
+        self.pupil, self.transverse, self.slope, self.longitudinal = rays[:, 0:2], rays[:, 2:4], rays[:, 4:6], rays[:, 6]
+        self.record = np.atleast_2d(np.asarray(record, dtype=float))
+        self.normal = np.atleast_2d(np.asarray(normal, dtype=float))
+        self.zones = np.asarray(zones, dtype=float).reshape(len(self.record), -1, 6)
+        self.launch, self.group = h, group
+        r = self.record
+        self.centre, self.pupil_radius = r[:, 0:3], r[:, 3]
+        self.n_rays, self.n_missed = r[:, 4].astype(np.int64), r[:, 5].astype(np.int64)
+        self.n_longitudinal, self.chief_row = r[:, 6].astype(np.int64), r[:, 7].astype(np.int64)
+        self.sum_weights = r[:, 8]
+        tri = self.terms * (self.terms + 1) // 2
+        n = len(r)
+        self.coefficients = np.full((n, 4, self.terms), np.nan)
+        self.rank = np.zeros(n, dtype=np.int64)
+        for k in range(4):  # (one right-hand side at a time through the wavefront's solver)
+            system = np.concatenate([self.normal[:, :tri], self.normal[:, tri + k * self.terms:tri + (k + 1) * self.terms],
+                                     self.normal[:, -1:], np.zeros((n, 2))], axis=1)
+            self.coefficients[:, k], self.rank = solve_normal_equations(system, self.terms)
+        # what the fit leaves: sum w t^2 - c.(Z^T W t), for eps (both components, about C) and s (raw)
+        rhs = self.normal[:, tri:tri + 4 * self.terms].reshape(n, 4, self.terms)
+        explained = (self.coefficients * rhs).sum(axis=2)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            left_eps = np.maximum(r[:, 13] - explained[:, 0] - explained[:, 1], 0.0) / r[:, 8]
+            left_s = np.maximum(r[:, 15] - explained[:, 2] - explained[:, 3], 0.0) / r[:, 8]
+        self.residual = np.stack([np.sqrt(left_eps), np.sqrt(left_s)], axis=1)
+
+    def _moments(self):
+        r = self.record
+        with np.errstate(invalid="ignore", divide="ignore"):
+            w = np.where(r[:, 8] > 0, r[:, 8], np.nan)
+            m_eps, m_s = r[:, 9:11] / w[:, None], r[:, 11:13] / w[:, None]
+            ee = r[:, 13] / w - (m_eps ** 2).sum(axis=1)
+            es = r[:, 14] / w - (m_eps * m_s).sum(axis=1)
+            ss = r[:, 15] / w - (m_s ** 2).sum(axis=1)
+        return ee, es, ss
+
+    def rms_radius(self, focus=0.0):
+        """Per group, the RMS spot radius about the spot's own centroid at the plane shifted by ``focus`` along the
+        axis: sqrt(var eps + 2 focus cov(eps, s) + focus^2 var s), from the group sums."""
+        ee, es, ss = self._moments()
+        return np.sqrt(np.maximum(ee + 2.0 * focus * es + focus * focus * ss, 0.0))
+
+    def best_focus(self):
+        """Per group, the shift along the axis that minimises the RMS spot radius, in closed form:
+        -cov(eps, s) / var(s) (NaN when every ray has the same slope)."""
+        _, es, ss = self._moments()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(ss > 0, -es / ss, np.nan)
+
+    def fan(self, azimuth_deg, samples=65, focus=0.0):
+        """The fitted transverse aberration eps + focus * s along the pupil diameter at ``azimuth_deg`` (0: the
+        tangential fan along e1; 90: the sagittal fan along e2): ``(t, along, across)`` with t the ``samples``
+        positions from -1 to 1 on the diameter and, per group, the components of the aberration along the diameter
+        and across it (arrays (n_groups, samples))."""
+        t = np.linspace(-1.0, 1.0, int(samples))
+        angle = np.radians(float(azimuth_deg))
+        c, s = np.cos(angle), np.sin(angle)
+        basis = zernike_basis(self.terms, np.abs(t), np.where(t >= 0, angle, angle + np.pi))  # (terms, samples)
+        value = np.einsum("gkj,js->gks", self.coefficients, basis)
+        e1 = value[:, 0] + focus * value[:, 2]
+        e2 = value[:, 1] + focus * value[:, 3]
+        return t, c * e1 + s * e2, -s * e1 + c * e2
+
+    def longitudinal_curve(self):
+        """The zonal curve of the longitudinal aberration (the notebook's cell 13 for any number of rays): a dict of
+        arrays (n_groups, n_zones) -- ``radius`` (the zones' centres in world units, (zone + 1/2) / n_zones * rho),
+        ``mean`` and ``std`` (weighted, over the zone's rays with a finite la; NaN for a zone without one), ``count``
+        (those rays) and ``rays`` (all the zone's rays)."""
+        z = self.zones
+        n_zones = z.shape[1]
+        centres = (np.arange(n_zones) + 0.5) / max(n_zones, 1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            w = np.where(z[:, :, 1] > 0, z[:, :, 1], np.nan)
+            mean = z[:, :, 2] / w
+            std = np.sqrt(np.maximum(z[:, :, 3] / w - mean * mean, 0.0))
+        return {"radius": centres[None, :] * self.pupil_radius[:, None], "mean": mean, "std": std,
+                "count": z[:, :, 5].astype(np.int64), "rays": z[:, :, 0].astype(np.int64)}
+
+    def to_pandas(self):
+        """One row per ray used, in row order: row, source_id, radius (= h1) and h2, p1, p2, eps1, eps2, s1, s2 and
+        focus (= la) -- ``table['radius'], table['focus']`` are the two columns the notebook's ``spherical_aberration()``
+        returns."""
+        from . import engine
+
+        def host(x):
+            return engine.to_host(x) if hasattr(x, "is_cuda") else np.asarray(x)
+
+        rays = host(self.rays)
+        rows = host(self.rows)
+        group = np.zeros(len(rows), dtype=np.int64) if self.group is None else host(self.group)
+        if self.launch is not None:
+            h = host(self.launch)
+        else:
+            h = rays[:, 0:2] * self.pupil_radius[group][:, None]
+        return pd.DataFrame({"row": rows, "source_id": group, "radius": h[:, 0], "h2": h[:, 1], "p1": rays[:, 0],
+                             "p2": rays[:, 1], "eps1": rays[:, 2], "eps2": rays[:, 3], "s1": rays[:, 4], "s2": rays[:, 5],
+                             "focus": rays[:, 6]})
 
 
 def diffraction_mtf(frequencies, wavelength_um, f_number, world_unit_um):
