@@ -765,6 +765,63 @@ int prt_frame_ray_aberrations(int device, const double* rows, int64_t ld, int64_
                               int weight_column, int64_t capacity, double* ray_out, int64_t* row_out,
                               double* record_out, double* normal_out, double* zone_out, void* workspace, void* stream);
 
+/* Geometric encircled / ensquared energy of the frame, through focus, and its inverse: the radius that encloses a
+ * fraction of the energy.  Like prt_frame_mtf it reads only each ray's end point and direction at the surface, so it
+ * works on frames that hold the detector's rows alone.
+ *
+ * Definitions.
+ * Rays, groups, rays left out (n_missed), axes (a, e1, e2), weight column, centre C_g (the weighted centroid of the
+ *   group's Q, or a given point per group), p_r, s_r and the plane at shift delta: exactly prt_frame_mtf's, computed by
+ *   its device code.  Ray r meets the plane at shift delta at x_r(delta) = p_r + delta s_r.
+ * Centre of a plane: with follow_centroid != 0, distances at shift delta are measured from the plane's own weighted
+ *   centroid c(delta) = pbar + delta sbar, with pbar = sum w p / sum w and sbar = sum w s / sum w; each sum is formed
+ *   per chunk of 4096 rays of the group in a fixed tree and the chunks are added in order.  With follow_centroid == 0,
+ *   c = 0: distances are measured from C_g.
+ * Distance: x = (p + delta s) - c(delta), per component, the product, the sum and the difference each rounded, in that
+ *   order, without fused multiply-add.  d_r(delta) is
+ *     PRT_ENERGY_CIRCLE   sqrt(x1 * x1 + x2 * x2)   (each product rounded, then the sum, then the square root)
+ *     PRT_ENERGY_SQUARE   max(|x1|, |x2|), a half-width
+ *     PRT_ENERGY_SLIT_E2  |x1|   (a slit along e2)
+ *     PRT_ENERGY_SLIT_E1  |x2|   (a slit along e1)
+ *   d lies in [0, +inf].  An overflow gives +inf, which lies outside every finite radius and sorts last.  p, s and
+ *   delta are finite, so d is never NaN as long as c(delta) is finite; where c(delta) itself overflows, a coordinate
+ *   that comes out NaN counts as d = +inf.
+ * Integer weights: every sum that decides an output is an integer sum, exact and independent of order.  Per group,
+ *   m = rays used and w_max = the largest weight = f 2^E with 0.5 <= f < 1, B = bit_length(m); then
+ *   q_r = (uint64) floor(ldexp(w_r, 62 - E - B)), so q_r < 2^(62 - B) and W = sum q_r < 2^62.  The scaling is a power of
+ *   two: q is w truncated below w_max 2^-(61 - B) (41 bits at 1M rays), and a weight smaller than that counts 0.  With
+ *   weight_column -1, w = 1.  W == 0, or no rays, gives NaN outputs.
+ * Energy: EE_g(delta, R_j) = (double)(sum over d_r <= R_j of q_r) / (double) W, for radii R_j >= 0, finite and strictly
+ *   ascending.
+ * Enclosed radius: for a fraction 0 < phi_k <= 1, T_k = clamp((uint64) ceil(phi_k * (double) W), 1, W); the radius is
+ *   the smallest d among the group's distances at that plane with sum over d_r <= d of q_r >= T_k.  It is a ray's own
+ *   distance, not an interpolation.
+ *
+ * prt_frame_energy: reference DEVICE (n_groups, 3) or NULL for the centroids; axes HOST 9 doubles; radii (HOST, 0..4096),
+ * fractions (HOST, 0..16), not both empty; focus (HOST, 1..256 shifts delta, finite).  n_groups * n_focus * n_radii * 8
+ * bytes (the radius bins) and n_groups * n_focus * n_fractions * 16 KiB (the select's digit windows) may each not pass a
+ * 256 MiB cap.  Out, DEVICE, overwritten: energy_out (n_groups, n_focus, n_radii) (may be NULL when n_radii == 0),
+ * radius_out (n_groups, n_focus, n_fractions) (may be NULL when n_fractions == 0), record_out (n_groups, 10): C_g (3),
+ * pbar (2), sbar (2), sum w, rays used, rays left out.  workspace: prt_frame_energy_workspace_bytes(n_rows, n_groups,
+ * n_radii, n_fractions, n_focus) device bytes (-1 for arguments the call would refuse).  The energy is a cumulative
+ * count: each ray's d is searched in the radii and q added to a (plane, radius) bin.  The radius is an exact selection: a
+ * most-significant-digit-first radix select on the bit image of d (for non-negative doubles, bit order is numeric
+ * order), six digits of 11, 11, 11, 10, 10 and 10 bits, after which the selected prefix is the radius.  No
+ * floating-point atomics; partitions depend on a group's count of rays used and on the output counts, never on n_rows:
+ * every output is the same, bit for bit, on every run and on any frame that holds the same selected rows in the same
+ * order.  All arguments are checked before a device is touched.  Stream-ordered; the call returns when the stream has
+ * reached its end. */
+#define PRT_ENERGY_CIRCLE 0
+#define PRT_ENERGY_SQUARE 1
+#define PRT_ENERGY_SLIT_E1 2
+#define PRT_ENERGY_SLIT_E2 3
+int64_t prt_frame_energy_workspace_bytes(int64_t n_rows, int n_groups, int n_radii, int n_fractions, int n_focus);
+int prt_frame_energy(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                     double rays_per_source, int n_groups, const double* reference, const double* axes,
+                     int weight_column, int shape, int follow_centroid, const double* radii, int n_radii,
+                     const double* fractions, int n_fractions, const double* focus, int n_focus, double* energy_out,
+                     double* radius_out, double* record_out, void* workspace, void* stream);
+
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,
  * out[2] = GPU milliseconds spent in generation kernels (hipEvent, on the trace stream),

@@ -717,6 +717,97 @@ class DeviceFrame:
         pair = engine.to_host(otf)
         return MTF(pair[..., 0] + 1j * pair[..., 1], engine.to_host(record).copy(), nu, theta, planes)
 
+    # --- geometric encircled / ensquared energy through focus (no counterpart upstream) -------------------------------
+    def enclosed_energy(self, surface, radii=None, *, fractions=(0.5, 0.8, 0.9), shape="circle", focus=(0.0,),
+                        reference="centroid", follow_centroid=True, axis=None, basis=None, weights="intensity",
+                        generation=None, rays_per_source=None, n_groups=None, group=None):
+        """The geometric enclosed energy at ``surface`` (an id or an object with ``get_id()``; None: every row that
+        passes ``generation``), per group (``id // rays_per_source``) and focus shift: the fraction of the energy within
+        each of ``radii`` and, the other way round, the radius that holds each of ``fractions``.  Returns an
+        ``EnclosedEnergy``.
+
+        Rays, groups, axes, weights, the centre C_g (``reference``) and each ray's position x(delta) = p + delta s at
+        the plane shifted by delta are ``mtf``'s.  Distances are measured from the plane's own weighted centroid
+        (``follow_centroid``, the default) or from C_g.  shape: "circle" (sqrt(x1^2 + x2^2)), "square" (max(|x1|, |x2|),
+        a half-width), "slit_e2" (|x1|: a slit along e2) or "slit_e1" (|x2|).  radii: None or 1 to 4096 values, finite,
+        >= 0 and strictly ascending; fractions: None or 1 to 16 values in (0, 1]; not both None; focus: 1 to 256 shifts.
+        The weights are scaled by a power of two to integers, so every sum is exact: the energy is an exact count and
+        the radius is the distance of the ray at which the count reaches ceil(fraction * total) -- a ray's own
+        distance, not an interpolation (include/prt.h states the definitions).  A weight below 2^-41 of the largest
+        (at 1M rays) counts nothing.
+
+        One HIP pass (``prt_frame_energy``) over the rows it selects: frames made by ``where``, ``select`` or under
+        ``record_only`` work and give the same bits as the whole frame.  ``group=`` (sharded frames) is not supported
+        yet."""
+        import torch
+
+        from . import engine
+
+        if group is not None:
+            raise NotImplementedError("enclosed_energy() of a sharded frame (group=) is not supported yet")
+        edges = np.zeros(0) if radii is None else _mtf_values(radii, "radii", 4096, "finite, >= 0 and strictly ascending",
+                                                              non_negative=True)
+        if len(edges) > 1 and not np.all(np.diff(edges) > 0):
+            raise ValueError("radii: 1 to 4096 numbers, finite, >= 0 and strictly ascending")
+        phi = np.zeros(0) if fractions is None else _mtf_values(fractions, "fractions", 16, "in (0, 1]")
+        if np.any(phi <= 0) or np.any(phi > 1):
+            raise ValueError("fractions: 1 to 16 numbers, in (0, 1]")
+        if not len(edges) and not len(phi):
+            raise ValueError("radii: give radii, fractions or both")
+        if not isinstance(shape, str) or shape not in _ENERGY_SHAPES:
+            raise ValueError(f"shape: one of {sorted(_ENERGY_SHAPES)} (got {shape!r})")
+        planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        axes = pupil_axes(axis, basis)
+        if isinstance(reference, str) and reference != "centroid":
+            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        needed = list(_MTF_COLUMNS) + ([weights] if weights is not None else []) + (["id"] if rays_per_source else [])
+        needed += (["surface"] if surface_id is not None else []) + (["generation"] if generation is not None else [])
+        try:
+            self._need(*needed)
+        except KeyError as error:
+            raise ValueError(f"enclosed_energy: {error.args[0]}") from None
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if rays_per_source:
+            if n_groups is None:
+                top = float(self["id"].max()) if len(self) else -1.0
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        n_groups = int(n_groups)
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        centres = None
+        if not isinstance(reference, str):
+            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
+            if centres.shape == (3,):
+                centres = centres.expand(n_groups, 3)
+            if tuple(centres.shape) != (n_groups, 3):
+                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
+            centres = centres.to(dev, torch.float64).contiguous()
+        n_rows = rows.shape[1]
+        energy = torch.empty((n_groups, len(planes), len(edges)), dtype=torch.float64, device=dev)
+        radius = torch.empty((n_groups, len(planes), len(phi)), dtype=torch.float64, device=dev)
+        record = torch.empty((n_groups, 10), dtype=torch.float64, device=dev)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_energy_workspace_bytes(n_rows, n_groups, len(edges), len(phi),
+                                                                                  len(planes)))),
+                           dtype=torch.uint8, device=dev)
+        engine._check(lib.prt_frame_energy(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
+            float("nan") if surface_id is None else surface_id,
+            float("nan") if generation is None else float(generation), float(rays_per_source or 0), n_groups,
+            None if centres is None else centres.data_ptr(), axes.ctypes.data, -1 if weights is None else _INDEX[weights],
+            _ENERGY_SHAPES[shape], 1 if follow_centroid else 0, edges.ctypes.data if len(edges) else None, len(edges),
+            phi.ctypes.data if len(phi) else None, len(phi), planes.ctypes.data, len(planes),
+            energy.data_ptr() if len(edges) else None, radius.data_ptr() if len(phi) else None, record.data_ptr(),
+            work.data_ptr(), engine._stream_ptr(torch, dev)))
+        return EnclosedEnergy(engine.to_host(energy).copy(), engine.to_host(radius).copy(),
+                              engine.to_host(record).copy(), edges, phi, planes, shape)
+
     # --- ray-aberration curves: the frame joined by ray id (examples/lens_design.ipynb cells 12-13) ---------------------
     def launch_index(self):
         """Per row, the row number of the generation-0 row with the same ray id (-1: none; a generation-0 row maps to
@@ -999,6 +1090,7 @@ class SinkStats:
 _PATH_COLUMNS = ("index", "id", "surface", "generation", "x0", "y0", "z0", "x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")
 _JOIN_COLUMNS = tuple(name for name in _PATH_COLUMNS if name != "index")  # (what the ray-aberration passes read)
 _MTF_COLUMNS = ("x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")  # (what the MTF reads of every ray)
+_ENERGY_SHAPES = {"circle": 0, "square": 1, "slit_e1": 2, "slit_e2": 3}  # (PRT_ENERGY_* of include/prt.h)
 
 
 class Wavefront:
@@ -1140,21 +1232,72 @@ class MTF:
         a_index = slice(None) if azimuths is None else _positions(self.azimuths, azimuths, "azimuths")
         f_index = slice(None) if frequency is None else _positions(self.frequencies, [frequency], "frequency")
         merit = self.mtf[:, :, a_index][:, :, :, f_index].mean(axis=(2, 3))  # (groups, planes)
-        order = np.argsort(self.focus, kind="stable")
-        x, merit = self.focus[order], merit[:, order]
-        best = np.full(len(merit), np.nan)
-        for g, y in enumerate(merit):
-            if not np.any(np.isfinite(y)):
-                continue
-            k = int(np.nanargmax(y))
-            best[g] = x[k]
-            if 0 < k < len(x) - 1 and np.all(np.isfinite(y[k - 1:k + 2])):
-                (x0, x1, x2), (y0, y1, y2) = x[k - 1:k + 2], y[k - 1:k + 2]
-                a = ((y2 - y1) / (x2 - x1) - (y1 - y0) / (x1 - x0)) / (x2 - x0)
-                if a < 0:
-                    slope = (y1 - y0) / (x1 - x0) - a * (x0 + x1)  # (y = a x^2 + slope x + c)
-                    best[g] = float(np.clip(-slope / (2 * a), x0, x2))
-        return best
+        return _best_plane(self.focus, merit)
+
+
+class EnclosedEnergy:
+    """What ``DeviceFrame.enclosed_energy`` returns (numpy arrays).  ``energy`` (n_groups, n_focus, n_radii): the
+    fraction of the energy within each of ``radii``; ``radius`` (n_groups, n_focus, n_fractions): the radius (half-width
+    for a square or a slit) that holds each of ``fractions``, a ray's own distance; ``focus`` (shifts along the axis)
+    and ``shape``; per group ``centre`` (n_groups, 3), ``centroid_shift`` (n_groups, 2, 2): pbar and sbar, the weighted
+    means of p and of the slope s about the centre (the centroid of the plane at shift delta is pbar + delta sbar);
+    ``n_rays`` (rays used), ``n_missed`` (rays left out) and ``sum_weights``.  A group without rays, or whose weights
+    are all zero, is NaN throughout."""
+
+    def __init__(self, energy, radius, record, radii, fractions, focus, shape="circle"):
+        self.energy, self.radius = np.asarray(energy, dtype=float), np.asarray(radius, dtype=float)
+        self.radii = np.asarray(radii, dtype=float)
+        self.fractions = np.asarray(fractions, dtype=float)
+        self.focus = np.asarray(focus, dtype=float)
+        self.shape = shape
+        self.record = np.asarray(record, dtype=float)
+        self.centre, self.sum_weights = self.record[:, :3], self.record[:, 7]
+        self.centroid_shift = self.record[:, 3:7].reshape(-1, 2, 2)
+        self.n_rays = np.nan_to_num(self.record[:, 8]).astype(np.int64)
+        self.n_missed = np.nan_to_num(self.record[:, 9]).astype(np.int64)
+
+    def to_pandas(self):
+        """Long form: one row per (source_id, focus, quantity, value) -- quantity "energy" with its radius in
+        ``radius`` and the enclosed fraction in ``energy``, then quantity "radius" likewise for each of ``fractions``."""
+        parts = []
+        for name, block, radius_of, energy_of in (
+                ("energy", self.energy, lambda j, v: self.radii[j], lambda j, v: v),
+                ("radius", self.radius, lambda j, v: v, lambda j, v: self.fractions[j])):
+            index = np.indices(block.shape).reshape(3, -1)
+            values = block.reshape(-1)
+            parts.append(pd.DataFrame({"source_id": index[0], "focus": self.focus[index[1]], "quantity": name,
+                                       "radius": radius_of(index[2], values), "energy": energy_of(index[2], values)}))
+        return pd.concat(parts, ignore_index=True)
+
+    def best_focus(self, fraction=None):
+        """Per group, the focus shift of the smallest enclosed radius at ``fraction`` (a value of ``self.fractions``;
+        None: the mean over all of them).  The best sampled plane, refined by the vertex of the parabola through it
+        and its two neighbours when it is not at an end of the scan (``MTF.best_focus``'s rule).  NaN for a group
+        without rays."""
+        if not len(self.fractions):
+            raise ValueError("fraction: this result holds no enclosed radius (it was made without fractions)")
+        index = slice(None) if fraction is None else _positions(self.fractions, [fraction], "fraction")
+        return _best_plane(self.focus, -self.radius[:, :, index].mean(axis=2))
+
+
+def _best_plane(focus, merit):
+    """Per group the focus shift of the largest merit (groups, planes): the best sampled plane, refined by the vertex
+    of the parabola through it and its two neighbours when it is interior.  NaN where no plane is finite."""
+    order = np.argsort(focus, kind="stable")
+    x, merit = focus[order], merit[:, order]
+    best = np.full(len(merit), np.nan)
+    for g, y in enumerate(merit):
+        if not np.any(np.isfinite(y)):
+            continue
+        k = int(np.nanargmax(y))
+        best[g] = x[k]
+        if 0 < k < len(x) - 1 and np.all(np.isfinite(y[k - 1:k + 2])):
+            (x0, x1, x2), (y0, y1, y2) = x[k - 1:k + 2], y[k - 1:k + 2]
+            a = ((y2 - y1) / (x2 - x1) - (y1 - y0) / (x1 - x0)) / (x2 - x0)
+            if a < 0:
+                slope = (y1 - y0) / (x1 - x0) - a * (x0 + x1)  # (y = a x^2 + slope x + c)
+                best[g] = float(np.clip(-slope / (2 * a), x0, x2))
+    return best
 
 
 class RayAberrations:
