@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -821,6 +821,61 @@ int prt_frame_energy(int device, const double* rows, int64_t ld, int64_t n_rows,
                      int weight_column, int shape, int follow_centroid, const double* radii, int n_radii,
                      const double* fractions, int n_fractions, const double* focus, int n_focus, double* energy_out,
                      double* radius_out, double* record_out, void* workspace, void* stream);
+
+/* ---- ray-path analysis of the frame: which surfaces every ray met, in order (no counterpart upstream) -----------------
+ * The passes above describe the spot at a surface and take "the rays there" as given.  The engine is a non-sequential
+ * tracer: a ray may miss the lens and still reach the detector, be clipped by a stop, bounce between two mirrors or leave
+ * through a lens's edge.  This pass joins the frame by ray id on the device and says how every ray got where it is and
+ * where the others went (on the host: results.groupby("id")["surface"].agg(tuple) and what follows from it).
+ *
+ * Definitions.
+ * Frame: whole and generation-major, as prt_frame_optical_path requires: rows_per_generation gives the generations'
+ *   runs; ids are integers in [id0, id0 + n_ids), unique within a generation.
+ * Surface values: the surface column of a row must be an integer in [0, 2^31).  The frame never holds -1, since
+ *   _pyrayt.py:428-435 records living rays only.
+ * Path of a ray: the tuple of the surface values of its rows in generation order.  A ray with a row in generation g > 0
+ *   and none in g - 1 means the frame is not whole: PRT_ERR_ARG through the status word, like a repeated id.
+ * Node: a distinct non-empty prefix of some ray's path.  The root (the empty prefix) is not a node.  A node has a parent
+ *   (-1 for a first surface), a surface and a depth, which is the generation of the rows at it.
+ * Node numbering: nodes are numbered 0 .. n_nodes - 1 in ascending order of their sequences compared as tuples -- Python's
+ *   sorted(set(prefixes)).  That is depth-first preorder with children in ascending surface id, so a node's subtree is the
+ *   contiguous range [k, k + subtree_size[k]).  This numbering is the contract; it does not depend on scheduling.
+ * Groups: g = floor(id / rays_per_source), as elsewhere; rays_per_source <= 0 means one group.  A row of a group outside
+ *   [0, n_groups) is left out of the per-group tables; it is still given its node.
+ * Counts per (group, node): through -- rows at the node, i.e. rays whose path has this prefix; ended -- rays whose last
+ *   row is at the node; dark -- ended rays whose last row has sqrt(x_tilt^2 + y_tilt^2 + z_tilt^2) <= 1e-8 (np.isclose's
+ *   absolute tolerance at _pyrayt.py:415, where upstream decides that a ray was absorbed).  An ended ray that is not dark
+ *   escaped or ran into the generation limit.
+ * Weights: weight_column is a column index, or -1 for ones.  A weight that is not finite and >= 0 counts 0 and is tallied
+ *   apart as n_bad_weight (rows).
+ * Energy per (group, node): energy_through and energy_ended are sums of the weight of the rows at the node, respectively
+ *   of the last rows of the rays that ended there.  The weights become integers by prt_frame_energy's power-of-two rule,
+ *   computed by its device function: q = floor(ldexp(w, 62 - E - B)) with w_max = f 2^E the largest weight of the frame
+ *   and B = bit_length(n_rows).  Every sum that reaches an output is then an integer sum, exact in any order, and is
+ *   converted back to a double once at the end: ldexp((double) sum, -(62 - E - B)).  For integer weights with a total
+ *   below 2^53 (the built-in sources' intensity 100) the energy is the exact sum.
+ * Too many nodes: more than max_paths distinct nodes gives PRT_ERR_ARG with a message that names the cap, never a
+ *   truncated table; nothing is ever written out of bounds.
+ *
+ * prt_frame_paths: max_paths in [1, 65536]; the tree is a table of 2^c >= 4 * max_paths slots, and n_groups * 2^c * 40
+ * bytes (the per-(group, slot) tallies) may not pass a 256 MiB cap.  Out, overwritten: row_node_out DEVICE n_rows int32
+ * (the node of each row's prefix), ray_node_out DEVICE n_ids int32 (the node where the ray ended; -1: the id has no row),
+ * ray_last_row_out DEVICE n_ids int64 (the ray's last row; -1), node_out DEVICE (max_paths, 4) int32 (parent, surface,
+ * depth, subtree size; -1 past n_nodes), count_out DEVICE (n_groups, max_paths, 3) int64 (through, ended, dark; 0 past
+ * n_nodes), energy_out DEVICE (n_groups, max_paths, 2) double (through, ended), record_out HOST 4 int64: n_nodes, rays
+ * with rows, n_bad_weight, deepest depth + 1.  workspace: prt_frame_paths_workspace_bytes(n_rows, n_ids, n_groups,
+ * max_paths) device bytes (-1 for arguments the call would refuse).  One launch per generation in order on the stream;
+ * a node's device-side name is the slot its (parent slot, surface) key took in the table with one compare-and-swap, so
+ * no lane waits for another; every loop is bounded at launch.  The call reads the status word and the nodes' keys back
+ * (12 bytes a node), orders them on the host and renumbers on the device.  No floating-point atomics: every output is
+ * the same, bit for bit, on every run, and unchanged by any permutation of the rows inside a generation, apart from
+ * row_node_out and ray_last_row_out being permuted with them.  All arguments are checked before a device is touched.
+ * Stream-ordered; the call returns when the stream has reached its end. */
+int64_t prt_frame_paths_workspace_bytes(int64_t n_rows, int64_t n_ids, int n_groups, int max_paths);
+int prt_frame_paths(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation, int n_generations,
+                    double id0, int64_t n_ids, double rays_per_source, int n_groups, int weight_column, int max_paths,
+                    int32_t* row_node_out, int32_t* ray_node_out, int64_t* ray_last_row_out, int32_t* node_out,
+                    int64_t* count_out, double* energy_out, int64_t* record_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

@@ -57,6 +57,15 @@ __device__ __forceinline__ void energy_slice(const int64_t* __restrict__ slice_s
   hi = lo + per < bucket_start[g] + n ? lo + per : bucket_start[g] + n;
 }
 
+// the power-of-two rule that makes the weights integers: with w_max = f 2^E (0.5 <= f < 1; its bit image is given) and
+// B = bit_length(count), the shift is 62 - E - B and q = floor(ldexp(w, shift)) -- count such q sum to less than 2^62
+__device__ __forceinline__ int energy_shift(u64 w_max_bits, long long count) {
+  int e = 0;
+  frexp(__longlong_as_double((long long)w_max_bits), &e);
+  return 62 - e - (64 - __clzll(count));
+}
+__device__ __forceinline__ u64 energy_quantum(double w, int shift) { return (u64)floor(ldexp(w, shift)); }
+
 // per (group, chunk): [0] sum w  [1..2] sum w p  [3..4] sum w s -- each thread over its strided rays in order, then a
 // fixed tree; the largest weight of the chunk into w_max[g]
 __global__ void __launch_bounds__(kEnergyBlock)
@@ -116,10 +125,7 @@ k_energy_record(int n_groups, const int64_t* __restrict__ chunk_start, const dou
   r[7] = s[0];
   r[8] = (double)bucket_total[g];
   r[9] = (double)missed[g];
-  int e = 0;
-  frexp(__longlong_as_double((long long)w_max[g]), &e);  // w_max = f 2^e, 0.5 <= f < 1
-  const int bits = 64 - __clzll((long long)bucket_total[g]);  // bit_length(m)
-  shift[g] = 62 - e - bits;
+  shift[g] = energy_shift(w_max[g], (long long)bucket_total[g]);
 }
 
 // per (group, chunk): q_r = (uint64) floor(ldexp(w_r, shift)); W[g] += the chunk's sum
@@ -137,7 +143,7 @@ k_energy_scale(int n_groups, const int64_t* __restrict__ chunk_start, const int6
   const int by = shift[g];
   u64 mine = 0;
   for (int64_t r = lo + t; r < hi; r += kEnergyBlock) {
-    const u64 v = (u64)floor(ldexp(stage[r].w, by));
+    const u64 v = energy_quantum(stage[r].w, by);
     q[r] = v;
     mine += v;
   }

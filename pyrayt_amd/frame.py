@@ -978,6 +978,82 @@ class DeviceFrame:
         return RayAberrations(rays[:used], row_numbers, record_host, engine.to_host(normal).copy(),
                               engine.to_host(zone).copy(), terms, h=torch.stack(h, 1), group=groups)
 
+    # --- ray paths: which surfaces every ray met, in order (the frame joined by ray id, for every ray at once) -----------
+    def paths(self, weights="intensity", rays_per_source=None, n_groups=None, max_paths=4096):
+        """The ray paths of the frame: every ray's ordered sequence of surfaces -- on the host,
+        ``results.groupby("id")["surface"].agg(tuple)`` -- put into a tree of prefixes.  Returns a ``Paths``: per node
+        (a distinct non-empty prefix of some ray's path) its parent, surface, depth and subtree size, per group
+        (``id // rays_per_source``) and node the rays and the energy that went through it, ended there and were
+        absorbed there, and per row and per ray the number of its node, so that the frame can be cut by path
+        (``frame.select(paths.rows(node))``) and handed to the other passes.
+
+        Nodes are numbered in ascending order of their sequences compared as tuples (``sorted(set(prefixes))``): a
+        node's subtree is the range ``[k, k + subtree_size[k])``.  through: the rows at the node; ended: the rays whose
+        last row is there; dark: the ended rays whose last row has a direction of length <= 1e-8 (absorbed, as
+        ``_pyrayt.py:415`` decides it).  weights: a column name or None for ones; a weight that is not finite and >= 0
+        counts 0 (``n_bad_weight``).  The weights are scaled by a power of two to integers, as ``enclosed_energy``
+        does, so every sum is exact and the same bits on every run and in any order of the rows of a generation
+        (include/prt.h states the definitions).  More than ``max_paths`` (1 to 65536) distinct nodes: ``ValueError``.
+
+        One HIP launch per generation (``prt_frame_paths``).  Ids must be integers, unique within a generation, and
+        surfaces integers in [0, 2^31).  Needs the whole frame of a trace, like ``optical_path``."""
+        import torch
+
+        from . import engine
+
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        if isinstance(max_paths, bool) or not isinstance(max_paths, (int, np.integer)) or not 1 <= max_paths <= 65536:
+            raise ValueError(f"max_paths: the most nodes the tree may have, 1 to 65536 (got {max_paths!r})")
+        columns = [name for name in _PATHS_COLUMNS if name != "intensity" or weights == "intensity"]
+        columns += [weights] if weights is not None and weights not in columns else []
+        try:
+            self._need_whole("paths", columns=columns)
+        except KeyError as error:
+            raise ValueError(f"paths: {error.args[0]}") from None
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        n_rows = rows.shape[1]
+        ids = rows[_INDEX["id"]]
+        if n_rows:
+            id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
+            if not (np.isfinite(id0) and np.isfinite(top)):
+                raise ValueError("paths: an id is not an integer in the frame's id range")
+        else:
+            id0 = top = 0.0
+        n_ids = int(top - id0) + 1
+        if rays_per_source:
+            if n_groups is None:
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        n_groups, max_paths = int(n_groups), int(max_paths)
+        lib = engine.library()
+        work_bytes = int(engine._check(lib.prt_frame_paths_workspace_bytes(n_rows, n_ids, n_groups, max_paths)))
+        row_node = torch.empty(n_rows, dtype=torch.int32, device=dev)
+        ray_node = torch.empty(n_ids, dtype=torch.int32, device=dev)
+        ray_last_row = torch.empty(n_ids, dtype=torch.int64, device=dev)
+        node = torch.empty((max_paths, 4), dtype=torch.int32, device=dev)
+        count = torch.empty((n_groups, max_paths, 3), dtype=torch.int64, device=dev)
+        energy = torch.empty((n_groups, max_paths, 2), dtype=torch.float64, device=dev)
+        record = np.zeros(4, dtype=np.int64)
+        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
+        engine._check(lib.prt_frame_paths(
+            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
+            len(counts), id0, n_ids, float(rays_per_source or 0), n_groups, -1 if weights is None else _INDEX[weights],
+            max_paths, row_node.data_ptr() if n_rows else None, ray_node.data_ptr(), ray_last_row.data_ptr(),
+            node.data_ptr(), count.data_ptr(), energy.data_ptr(), record.ctypes.data, work.data_ptr(),
+            engine._stream_ptr(torch, dev)))
+        n_nodes = int(record[0])
+        node_host = engine.to_host(node[:n_nodes]).copy()
+        count_host = engine.to_host(count[:, :n_nodes].contiguous()).copy()
+        energy_host = engine.to_host(energy[:, :n_nodes].contiguous()).copy()
+        return Paths(node_host[:, 0], node_host[:, 1], node_host[:, 2], node_host[:, 3], count_host[:, :, 0],
+                     count_host[:, :, 1], count_host[:, :, 2], energy_host[:, :, 0], energy_host[:, :, 1],
+                     row_node=row_node, ray_node=ray_node, ray_last_row=ray_last_row, id0=id0,
+                     n_bad_weight=int(record[2]), n_rays=int(record[1]), ids=ids)
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -1090,6 +1166,7 @@ class SinkStats:
 _PATH_COLUMNS = ("index", "id", "surface", "generation", "x0", "y0", "z0", "x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")
 _JOIN_COLUMNS = tuple(name for name in _PATH_COLUMNS if name != "index")  # (what the ray-aberration passes read)
 _MTF_COLUMNS = ("x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")  # (what the MTF reads of every ray)
+_PATHS_COLUMNS = ("generation", "intensity", "id", "surface", "x_tilt", "y_tilt", "z_tilt")  # (what paths() reads)
 _ENERGY_SHAPES = {"circle": 0, "square": 1, "slit_e1": 2, "slit_e2": 3}  # (PRT_ENERGY_* of include/prt.h)
 
 
@@ -1410,6 +1487,172 @@ class RayAberrations:
         return pd.DataFrame({"row": rows, "source_id": group, "radius": h[:, 0], "h2": h[:, 1], "p1": rays[:, 0],
                              "p2": rays[:, 1], "eps1": rays[:, 2], "eps2": rays[:, 3], "s1": rays[:, 4], "s2": rays[:, 5],
                              "focus": rays[:, 6]})
+
+
+class Paths:
+    """The ray paths of a frame (``DeviceFrame.paths``): a tree of the prefixes of every ray's sequence of surfaces.
+
+    ``sequences`` (a list of tuples in the canonical order: ascending as tuples), ``parent`` (-1 for a first surface),
+    ``surface``, ``depth`` and ``subtree_size`` describe the ``n_nodes`` nodes; ``through``, ``ended``, ``dark``,
+    ``energy_through`` and ``energy_ended`` are (n_groups, n_nodes) tables.  ``row_node`` (per row of the frame),
+    ``ray_node`` and ``ray_last_row`` (per id, from ``id0``; -1 for an id without rows) are device tensors -- None on
+    an object made by ``merge`` -- and ``rays`` / ``rows`` turn nodes into masks for ``frame.select``."""
+
+    def __init__(self, parent, surface, depth, subtree_size, through, ended, dark, energy_through, energy_ended,
+                 row_node=None, ray_node=None, ray_last_row=None, id0=0.0, n_bad_weight=0, n_rays=None, ids=None,
+                 launched=None):
+        self.parent = np.asarray(parent, dtype=np.int64)
+        self.surface = np.asarray(surface)
+        self.depth = np.asarray(depth, dtype=np.int64)
+        self.subtree_size = np.asarray(subtree_size, dtype=np.int64)
+        n = len(self.parent)
+        self.through = np.asarray(through, dtype=np.int64).reshape(-1, n)
+        self.ended = np.asarray(ended, dtype=np.int64).reshape(-1, n)
+        self.dark = np.asarray(dark, dtype=np.int64).reshape(-1, n)
+        self.energy_through = np.asarray(energy_through, dtype=np.float64).reshape(-1, n)
+        self.energy_ended = np.asarray(energy_ended, dtype=np.float64).reshape(-1, n)
+        self.row_node, self.ray_node, self.ray_last_row = row_node, ray_node, ray_last_row
+        self.id0, self.n_bad_weight = id0, int(n_bad_weight)
+        self.n_rays = int(self.ended.sum()) if n_rays is None else int(n_rays)
+        self.launched = launched  # (rays per source, where the tracer knows it: trace_paths)
+        self._ids = ids
+        self.sequences = []
+        for k in range(n):  # (a parent comes before its children)
+            head = self.sequences[self.parent[k]] if self.parent[k] >= 0 else ()
+            self.sequences.append(head + (self.surface[k].item() if hasattr(self.surface[k], "item") else self.surface[k],))
+        self._number = {sequence: k for k, sequence in enumerate(self.sequences)}
+
+    @property
+    def n_nodes(self):
+        return len(self.parent)
+
+    @property
+    def n_groups(self):
+        return self.through.shape[0]
+
+    def to_pandas(self):
+        """One line per (source, node), with the node's sequence."""
+        g, k = np.divmod(np.arange(self.n_groups * self.n_nodes), max(self.n_nodes, 1))
+        return pd.DataFrame({"source_id": g, "node": k, "parent": self.parent[k], "depth": self.depth[k],
+                             "surface": self.surface[k], "sequence": [self.sequences[n] for n in k],
+                             "through": self.through.reshape(-1), "ended": self.ended.reshape(-1),
+                             "dark": self.dark.reshape(-1), "energy_through": self.energy_through.reshape(-1),
+                             "energy_ended": self.energy_ended.reshape(-1)})
+
+    def complete(self):
+        """The nodes where rays ended: the complete paths."""
+        return np.flatnonzero(self.ended.sum(axis=0) > 0)
+
+    def index(self, sequence):
+        """The number of the node with this sequence of surfaces (ids or objects with ``get_id()``)."""
+        key = tuple(_surface_id(item) for item in sequence)
+        if key not in self._number:
+            raise ValueError(f"no ray went through {key}")
+        return self._number[key]
+
+    def find(self, through=None, ends_at=None, avoids=None):
+        """The numbers of the nodes whose sequence holds every surface of ``through``, ends at ``ends_at`` and holds
+        none of ``avoids`` (each a surface id, an object with ``get_id()`` or several of them; None: no condition)."""
+        need, stop, last = _surface_ids(through), _surface_ids(avoids), _surface_ids(ends_at)
+        return np.array([k for k, sequence in enumerate(self.sequences)
+                         if need <= set(sequence) and not (stop & set(sequence)) and (not last or sequence[-1] in last)],
+                        dtype=np.int64)
+
+    def _range(self, node, complete):
+        node = int(node)
+        if not 0 <= node < self.n_nodes:
+            raise ValueError(f"node: 0 to {self.n_nodes - 1} (got {node})")
+        return node, node + (1 if complete else int(self.subtree_size[node]))
+
+    def rays(self, node, complete=True):
+        """A device mask over the ids (from ``id0``): the rays whose complete path is ``node`` (a number or several),
+        or, with complete=False, every ray whose path has the node as a prefix -- the range test
+        ``node <= ray_node < node + subtree_size[node]``."""
+        if self.ray_node is None:
+            raise ValueError("this Paths holds no per-ray tensors (it was made by merge())")
+        mask = None
+        for k in np.atleast_1d(np.asarray(node)):
+            lo, hi = self._range(k, complete)
+            m = (self.ray_node >= lo) & (self.ray_node < hi)
+            mask = m if mask is None else (mask | m)
+        return mask if mask is not None else self.ray_node < -1
+
+    def rows(self, node, complete=True):
+        """The same as a mask over the frame's rows, for ``frame.select(...)``: every row of the rays ``rays`` picks."""
+        picked = self.rays(node, complete)
+        index = self._ids - self.id0
+        return picked[index.long() if hasattr(index, "long") else np.asarray(index, dtype=np.int64)]
+
+    def fates(self, launched=None):
+        """Per source and final surface the rays that ended there, those of them that were absorbed (dark) and those
+        that escaped or ran into the generation limit, with the energy of their last rows.  launched: the rays per
+        source (a number or one per source; by default what ``trace_paths`` knows): the table then also gives, as
+        surface -1, the rays that never met a surface -- launched minus the rays through the first surfaces."""
+        launched = self.launched if launched is None else launched
+        surfaces = sorted(set(self.surface[self.ended.sum(axis=0) > 0].tolist()))
+        lines = []
+        for g in range(self.n_groups):
+            if launched is not None:
+                missed = int(np.broadcast_to(np.asarray(launched), (self.n_groups,))[g]) - int(
+                    self.through[g, self.depth == 0].sum())
+                lines.append((g, -1, missed, 0, missed, 0.0))
+            for surface in surfaces:
+                at = self.surface == surface
+                ended, dark = int(self.ended[g, at].sum()), int(self.dark[g, at].sum())
+                if ended:
+                    lines.append((g, surface, ended, dark, ended - dark, float(self.energy_ended[g, at].sum())))
+        return pd.DataFrame(lines, columns=["source_id", "surface", "ended", "dark", "escaped", "energy_ended"])
+
+    def merge(self, labels, collapse_repeats=False):
+        """A coarser tree, on the host: every surface relabelled through the dict ``labels`` (surface id -> a
+        component's label, say; a surface that is not in it keeps its id), consecutive repeats of a label dropped when
+        ``collapse_repeats``, and the tables of the nodes that fall together added (a ray counts once in a merged
+        node: where it entered it).  Returns a ``Paths`` without device tensors; its ``node_map`` gives each old
+        node's new number."""
+        relabelled = []
+        for sequence in self.sequences:
+            out = []
+            for surface in sequence:
+                label = labels.get(surface, surface)
+                if not (collapse_repeats and out and out[-1] == label):
+                    out.append(label)
+            relabelled.append(tuple(out))
+        merged = sorted(set(relabelled))
+        number = {sequence: k for k, sequence in enumerate(merged)}
+        node_map = np.array([number[sequence] for sequence in relabelled], dtype=np.int64)
+        n = len(merged)
+        tables = [np.zeros((self.n_groups, n), dtype=t.dtype)
+                  for t in (self.through, self.ended, self.dark, self.energy_through, self.energy_ended)]
+        for k, m in enumerate(node_map):
+            entered = self.parent[k] < 0 or node_map[self.parent[k]] != m
+            for table, old in zip(tables, (self.through, self.ended, self.dark, self.energy_through, self.energy_ended)):
+                if entered or old is self.ended or old is self.dark or old is self.energy_ended:
+                    table[:, m] += old[:, k]
+        parent = np.array([number[sequence[:-1]] if len(sequence) > 1 else -1 for sequence in merged], dtype=np.int64)
+        size = np.ones(n, dtype=np.int64)
+        for k in range(n - 1, -1, -1):
+            if parent[k] >= 0:
+                size[parent[k]] += size[k]
+        surface = np.empty(n, dtype=object)
+        surface[:] = [sequence[-1] for sequence in merged]
+        if n and all(isinstance(v, (int, np.integer)) for v in surface):
+            surface = surface.astype(np.int64)
+        out = Paths(parent, surface, [len(sequence) - 1 for sequence in merged], size, *tables, id0=self.id0,
+                    n_bad_weight=self.n_bad_weight, n_rays=self.n_rays, launched=self.launched)
+        out.node_map = node_map
+        return out
+
+
+def _surface_id(item):
+    return item.get_id() if hasattr(item, "get_id") else item
+
+
+def _surface_ids(items):
+    if items is None:
+        return set()
+    if isinstance(items, (str, bytes)) or hasattr(items, "get_id") or not hasattr(items, "__iter__"):
+        items = (items,)
+    return {_surface_id(item) for item in items}
 
 
 def diffraction_mtf(frequencies, wavelength_um, f_number, world_unit_um):

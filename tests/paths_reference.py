@@ -1,0 +1,92 @@
+"""A numpy / dict restatement of the ray-path definitions of include/prt.h: every ray's rows collected by id, its path
+the tuple of their surfaces in generation order, the nodes the sorted set of the paths' prefixes, the tables plain
+counts and math.fsum sums.  tests/test_host_paths.py checks it against the figures known of the golden frames and runs
+the Paths object on it; tests/test_gpu_paths.py checks the device against it."""
+import math
+
+import numpy as np
+
+COLUMNS = ("generation", "intensity", "wavelength", "index", "id", "surface",
+           "x0", "y0", "z0", "x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")
+IX = {name: k for k, name in enumerate(COLUMNS)}
+
+
+def ray_rows(frame):
+    """id -> its rows in generation order; ValueError where the definitions refuse the frame."""
+    rows_of = {}
+    for row in np.argsort(frame[:, IX["generation"]], kind="stable"):
+        ray, surface = frame[row, IX["id"]], frame[row, IX["surface"]]
+        if ray != np.floor(ray) or not np.isfinite(ray):
+            raise ValueError("an id is not an integer")
+        if not (0 <= surface < 2 ** 31 and surface == np.floor(surface)):
+            raise ValueError("a surface is not an integer in [0, 2^31)")
+        rows_of.setdefault(int(ray), []).append(int(row))
+    for ray, rows in rows_of.items():
+        generations = frame[rows, IX["generation"]]
+        if len(set(generations)) != len(generations):
+            raise ValueError("an id repeats within a generation")
+        if list(generations) != list(range(len(rows))):
+            raise ValueError("a ray has a row in a generation and none in the one before")
+    return rows_of
+
+
+def paths(frame, rays_per_source=None, n_groups=1, weights="intensity"):
+    """Everything prt_frame_paths reports, as a dict of numpy arrays (energies by math.fsum)."""
+    frame = np.asarray(frame, dtype=np.float64)
+    rows_of = ray_rows(frame)
+    surfaces = frame[:, IX["surface"]].astype(np.int64)
+    path_of = {ray: tuple(int(surfaces[row]) for row in rows) for ray, rows in rows_of.items()}
+    sequences = sorted({path[:k] for path in path_of.values() for k in range(1, len(path) + 1)})
+    number = {sequence: k for k, sequence in enumerate(sequences)}
+    n = len(sequences)
+    parent = np.array([number[s[:-1]] if len(s) > 1 else -1 for s in sequences], dtype=np.int64)
+    subtree = np.array([sum(1 for t in sequences if t[:len(s)] == s) for s in sequences], dtype=np.int64)
+    w = np.ones(len(frame)) if weights is None else frame[:, IX[weights]].copy()
+    bad = ~(np.isfinite(w) & (w >= 0))
+    w[bad] = 0.0
+    tilt = frame[:, 12:15]
+    with np.errstate(over="ignore", invalid="ignore"):
+        is_dark = np.sqrt(tilt[:, 0] * tilt[:, 0] + tilt[:, 1] * tilt[:, 1] + tilt[:, 2] * tilt[:, 2]) <= 1e-8
+    ids = frame[:, IX["id"]]
+    id0 = ids.min() if len(frame) else 0.0
+    n_ids = int(ids.max() - id0) + 1 if len(frame) else 1
+    group = np.floor(ids / rays_per_source).astype(np.int64) if rays_per_source else np.zeros(len(frame), dtype=np.int64)
+    through, ended, dark = (np.zeros((n_groups, n), dtype=np.int64) for _ in range(3))
+    parts_through = [[[] for _ in range(n)] for _ in range(n_groups)]
+    parts_ended = [[[] for _ in range(n)] for _ in range(n_groups)]
+    row_node = np.full(len(frame), -1, dtype=np.int64)
+    ray_node = np.full(n_ids, -1, dtype=np.int64)
+    ray_last_row = np.full(n_ids, -1, dtype=np.int64)
+    for ray, rows in rows_of.items():
+        path = path_of[ray]
+        for k, row in enumerate(rows):
+            node = number[path[:k + 1]]
+            row_node[row] = node
+            if 0 <= group[row] < n_groups:
+                through[group[row], node] += 1
+                parts_through[group[row]][node].append(w[row])
+        last, node = rows[-1], number[path]
+        ray_node[int(ray - id0)] = node
+        ray_last_row[int(ray - id0)] = last
+        if 0 <= group[last] < n_groups:
+            ended[group[last], node] += 1
+            dark[group[last], node] += int(is_dark[last])
+            parts_ended[group[last]][node].append(w[last])
+    return dict(sequences=sequences, parent=parent, surface=np.array([s[-1] for s in sequences], dtype=np.int64),
+                depth=np.array([len(s) - 1 for s in sequences], dtype=np.int64), subtree_size=subtree,
+                through=through, ended=ended, dark=dark,
+                energy_through=np.array([[math.fsum(v) for v in line] for line in parts_through]).reshape(n_groups, n),
+                energy_ended=np.array([[math.fsum(v) for v in line] for line in parts_ended]).reshape(n_groups, n),
+                row_node=row_node, ray_node=ray_node, ray_last_row=ray_last_row, id0=float(id0),
+                n_bad_weight=int(bad.sum()), n_rays=len(rows_of), integer_weights=bool(np.all(w == np.floor(w))),
+                shift=62 - int(np.frexp(w.max())[1] if len(w) and w.max() > 0 else 0) - int(len(frame)).bit_length())
+
+
+def paths_object(frame, **kwargs):
+    """The reference as a pyrayt_amd.frame.Paths (host arrays in place of the device tensors)."""
+    from pyrayt_amd.frame import Paths
+
+    ref = paths(frame, **kwargs)
+    return Paths(ref["parent"], ref["surface"], ref["depth"], ref["subtree_size"], ref["through"], ref["ended"],
+                 ref["dark"], ref["energy_through"], ref["energy_ended"], id0=ref["id0"],
+                 n_bad_weight=ref["n_bad_weight"], n_rays=ref["n_rays"]), ref
