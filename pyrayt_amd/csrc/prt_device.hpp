@@ -420,10 +420,13 @@ __device__ __forceinline__ void object_normal(int type, const double* __restrict
 }
 
 // ---- TracerSurface.get_world_normals (world_objects.py:401-418) -------------------------------
-// p = world-space point (4 comps).  Returns the world-space unit normal times normal_scale.
+// p = world-space point (4 comps).  Returns the world-space unit normal times normal_scale, and the length |n_w| it
+// was divided by: the reference zeroes the fourth component BEFORE it normalises (world_objects.py:414-417), so that
+// component is 0 / |n_w| -- NaN where the length is 0 or NaN (the centre of a sphere, a non-finite point) -- which the
+// stand-alone entry point writes out.
 template <class PrimPtr>
-__device__ __forceinline__ void world_normal(PrimPtr p, double px, double py, double pz, double pw,
-                                             double& nx, double& ny, double& nz) {
+__device__ __forceinline__ void world_normal_len(PrimPtr p, double px, double py, double pz, double pw,
+                                                 double& nx, double& ny, double& nz, double& len_out) {
   const auto m = p->minv;
   const double lx = row_dot(m, 0, px, py, pz, pw);
   const double ly = row_dot(m, 1, px, py, pz, pw);
@@ -467,6 +470,14 @@ __device__ __forceinline__ void world_normal(PrimPtr p, double px, double py, do
   nx = wx * sgn;
   ny = wy * sgn;
   nz = wz * sgn;
+  len_out = len;
+}
+// ... without the length (the generation kernels: the value is dead there, the code the same)
+template <class PrimPtr>
+__device__ __forceinline__ void world_normal(PrimPtr p, double px, double py, double pz, double pw,
+                                             double& nx, double& ny, double& nz) {
+  double len;
+  world_normal_len(p, px, py, pz, pw, nx, ny, nz, len);
 }
 
 // ---- materials --------------------------------------------------------------------------------

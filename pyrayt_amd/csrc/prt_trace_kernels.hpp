@@ -1336,12 +1336,12 @@ k_normals(const DevPrim* __restrict__ prim, const double* __restrict__ pts, int6
           double* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * PRT_BLOCK + threadIdx.x;
   if (i >= k) return;
-  double nx, ny, nz;
-  world_normal(prim, pts[i], pts[ld + i], pts[2 * ld + i], pts[3 * ld + i], nx, ny, nz);
+  double nx, ny, nz, len;
+  world_normal_len(prim, pts[i], pts[ld + i], pts[2 * ld + i], pts[3 * ld + i], nx, ny, nz, len);
   out[i] = nx;
   out[ld + i] = ny;
   out[2 * ld + i] = nz;
-  out[3 * ld + i] = 0.0 * (double)prim->normal_scale;
+  out[3 * ld + i] = (0.0 / len) * (double)prim->normal_scale;  // (0 / |n_w|, as the reference: NaN where the normal is)
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)

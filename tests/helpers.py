@@ -89,6 +89,13 @@ class FixtureSnapshot:
         self.roots = scene["roots"].astype(np.int32)
 
 
+def device_scene(scene_dict, options=None):
+    """A DeviceScene of an oracle-format scene dict."""
+    from pyrayt_amd.engine import DeviceScene
+
+    return DeviceScene(FixtureSnapshot(scene_dict), options=options)
+
+
 def snapshot_of(fixture, prefix=""):
     """A fixture's scene as the structured tables the library takes."""
     return FixtureSnapshot(scene_of(fixture, prefix))
@@ -105,6 +112,94 @@ def assert_frames_match(got, want, atol=ATOL, what="frame"):
         assert np.array_equal(got[:, col], want[:, col]), f"{what}: exact column {col} differs"
     assert np.allclose(got, want, rtol=0, atol=atol, equal_nan=True), (
         f"{what}: max abs diff {np.nanmax(np.abs(got - want))}")
+
+
+def _ordered(bits):
+    """uint64 views of doubles -> int64 keys whose order is the doubles' order (-0.0 and +0.0 one apart)."""
+    bits = bits.astype(np.uint64)
+    negative = (bits >> np.uint64(63)).astype(bool)
+    magnitude = (bits & np.uint64(0x7FFFFFFFFFFFFFFF)).astype(np.int64)
+    return np.where(negative, -magnitude - 1, magnitude)
+
+
+def differing_bits(got, want):
+    """Boolean mask of the elements of two equal-shaped float64 arrays that are not the same double: another bit
+    pattern, unless both are NaN (any payload).  -0.0 and +0.0 differ."""
+    got = np.ascontiguousarray(got, dtype=np.float64)
+    want = np.ascontiguousarray(want, dtype=np.float64)
+    return (got.view(np.uint64) != want.view(np.uint64)) & ~(np.isnan(got) & np.isnan(want))
+
+
+def assert_same_bits(got, want, what="array"):
+    """Both arrays hold the same doubles: equal shapes, every element equal as a uint64 view (so a zero's sign
+    counts), except that a NaN matches any NaN.  The failure message counts the differing elements, names their
+    columns (last axis), lists the first few and gives the worst ulp distance over the finite ones."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} != {want.shape}"
+    if got.size == 0:
+        return
+    got = np.ascontiguousarray(got, dtype=np.float64)
+    want = np.ascontiguousarray(want, dtype=np.float64)
+    differ = differing_bits(got, want)
+    if not differ.any():
+        return
+    where = np.argwhere(differ)
+    columns = sorted(set(where[:, -1].tolist())) if got.ndim > 1 else []
+    first = [(*(int(i) for i in index), float(got[tuple(index)]), float(want[tuple(index)])) for index in where[:5]]
+    finite = differ & np.isfinite(got) & np.isfinite(want)
+    worst = int(np.abs(_ordered(got.view(np.uint64)[finite]) - _ordered(want.view(np.uint64)[finite])).max()) if finite.any() else None
+    raise AssertionError(
+        f"{what}: {int(differ.sum())} of {got.size} elements differ in their bits, columns {columns}; "
+        f"first (index..., got, want): {first}; worst distance over the finite ones: {worst} ulp")
+
+
+def assert_frames_identical(got, want, what="frame"):
+    """Result frames (R,15) that hold the same doubles in every column (assert_same_bits)."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.ndim == 2 and got.shape[1] == 15, f"{what}: not a frame, shape {got.shape}"
+    assert_same_bits(got, want, what)
+
+
+# the bar against values the genuine reference (or the numpy oracle, which runs numpy's own sums) wrote: what
+# tests/test_c_oracle.py::test_two_oracles_agree holds the two oracles to, three orders above the worst distance
+# between the C oracle and any golden frame (8.9e-16, scene_adv_short_c)
+REFERENCE_RTOL = REFERENCE_ATOL = 1e-12
+
+
+def assert_close_to_reference(got, want, what="array"):
+    """`got` against values of the reference: finite where it is, equal where it is not finite (same infinity, NaN
+    where it has NaN), and within rtol = atol = 1e-12 where it is."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    assert got.shape == want.shape, f"{what}: shape {got.shape} != {want.shape}"
+    if got.size == 0:
+        return
+    finite = np.isfinite(want)
+    assert np.array_equal(np.isfinite(got), finite), f"{what}: finite in other places than the reference"
+    assert np.array_equal(got[~finite], want[~finite], equal_nan=True), f"{what}: differs where the reference is not finite"
+    error = np.abs(got[finite] - want[finite])
+    bad = error > REFERENCE_ATOL + REFERENCE_RTOL * np.abs(want[finite])
+    assert not bad.any(), (f"{what}: {int(bad.sum())} of {got.size} elements beyond rtol = atol = 1e-12 of the reference, "
+                           f"max abs diff {error.max()}")
+
+
+# the scene fixtures whose golden frame (written by the genuine reference) the C oracle -- and so the engine --
+# reproduces in every bit, and the four on which a few elements of the float columns 6-14 differ by some ulp
+# (tests/test_c_oracle.py::test_trace_matches_reference pins which, how many and why)
+EXACT_SCENE_FIXTURES = ("config1", "config2", "config3", "config4", "config5", "two_mirrors", "tutorial",
+                        "mirrors_and_stops", "stopped_lens", "stale_box", "adv_lens", "adv_prism", "adv_condenser",
+                        "adv_still", "adv_bench_a", "adv_bench_b", "adv_bench_c")
+CLOSE_SCENE_FIXTURES = ("adv_short_a", "adv_short_b", "adv_short_c", "adv_stop")
+
+
+def assert_matches_golden_frame(got, name, want, what=None):
+    """A frame against (rows of) the golden frame of scene fixture `name` ("config2" or "scene_config2.npz"): the
+    same bits on the fixtures the reference's own frame is reproduced exactly, within 1e-12 of it on the others
+    (the four above and those with user materials, which the C oracle does not trace)."""
+    short = name[len("scene_"):-len(".npz")] if name.endswith(".npz") else name
+    if short in EXACT_SCENE_FIXTURES:
+        assert_frames_identical(got, want, what or name)
+    else:
+        assert_close_to_reference(got, want, what or name)
 
 
 def host_rank_worker(rank, world, port, name, n, mode, result_dir, gpu_ranks):

@@ -19,16 +19,32 @@ def built():
         subprocess.run(["make", "-C", os.path.join(ROOT, "oracle")], check=True)
 
 
-@pytest.mark.parametrize("name", ["config1", "config2", "config3", "config4", "config5",
-                                  "two_mirrors", "tutorial", "mirrors_and_stops", "stopped_lens",
-                                  "adv_lens", "adv_stop", "adv_prism", "adv_condenser", "adv_still", "adv_short_a", "adv_short_b", "adv_short_c", "adv_bench_a", "adv_bench_b", "adv_bench_c", "stale_box"])
+# elements of the golden frame that the C oracle does not reproduce bit for bit, per fixture: an upper bound (measured
+# with gcc 11.4 / glibc 2.35 on x86-64 with FMA; write another toolchain's counts beside these if it gives
+# others). All of them are in the float columns 6-14, the worst 232 ulp / 8.9e-16 (adv_short_c).
+INEXACT_ELEMENTS = {"adv_short_a": 2, "adv_short_b": 7, "adv_short_c": 36, "adv_stop": 13}
+
+
+@pytest.mark.parametrize("name", helpers.EXACT_SCENE_FIXTURES + helpers.CLOSE_SCENE_FIXTURES)
 def test_trace_matches_reference(name):
+    """The C oracle's frame IS the reference's on 17 fixtures: every bit of every column, zero signs and NaNs included.
+    On the other four a few elements differ by some ulp, and no reordering in a per-ray function can change that:
+    every differing row descends from a generation in which its ray was the ONLY one on its surface, where the
+    reference's `np.matmul(minv, rays)` on a single column goes to another BLAS routine (gemv, not gemm) whose
+    rounding differs -- the reference's bits there depend on how many other rays hit the same surface (the numpy
+    oracle, which runs the same calls on the same subsets, gives the golden bits on all 21)."""
     fx = helpers.load(f"scene_{name}.npz")
     frame, counts = c_oracle.trace(helpers.scene_of(fx), fx["rays0"], int(fx["generation_limit"]))
-    helpers.assert_frames_match(frame, fx["frame"], what=name)
+    if name in helpers.EXACT_SCENE_FIXTURES:
+        helpers.assert_frames_identical(frame, fx["frame"], what=name)
+    else:
+        helpers.assert_close_to_reference(frame, fx["frame"], what=name)
+        differ = helpers.differing_bits(frame, fx["frame"])
+        assert differ.sum() <= INEXACT_ELEMENTS[name], (name, int(differ.sum()))
+        assert not differ[:, :6].any(), f"{name}: an exact column differs"
     t, surf = c_oracle.propagate(helpers.scene_of(fx), fx["rays0"])
     assert np.array_equal(surf, fx["surf_0"])
-    assert np.allclose(t, fx["t_0"], rtol=0, atol=helpers.ATOL)
+    helpers.assert_same_bits(t, np.where(np.isnan(fx["t_0"]), np.inf, fx["t_0"]), what=f"{name}: t of generation 0")
 
 
 @pytest.mark.parametrize("name", ["union_spheres", "intersect_spheres", "difference_spheres",
@@ -45,7 +61,7 @@ def test_csg_nearest_hit(name):
     want_s = np.where(np.isfinite(want_t), ids[row, cols], -1)
     t, surf = c_oracle.propagate(helpers.scene_of(fx, key), fx[key + "rays"])
     assert np.array_equal(surf, want_s)
-    assert np.allclose(t, want_t, rtol=0, atol=helpers.ATOL)
+    helpers.assert_close_to_reference(t, want_t, what=name)
 
 
 @pytest.mark.parametrize("name,args,limit", [("config3", (5000,), 10), ("mirrors_and_stops", (20000,), 8),

@@ -78,7 +78,7 @@ def test_fixture_traced_from_c_equals_the_golden_frame(tmp_path, name, depth):
     done = subprocess.run([host, src, dst, str(depth)], capture_output=True, text=True, timeout=300)
     assert done.returncode == 0, done.stderr[-600:]
     rows, counts = read_output(dst, limit)
-    helpers.assert_frames_match(rows.T, fx["frame"], what=f"{name} traced from C")
+    helpers.assert_matches_golden_frame(rows.T, name, fx["frame"], what=f"{name} traced from C")
     # ... and what the Python binding returns for the same tables is the same bytes
     ds = engine.DeviceScene(snap)
     py_rows, py_counts = ds.trace(torch.from_numpy(rays).to("cuda:0"), limit)
@@ -111,7 +111,7 @@ def test_record_plan_set_from_c(tmp_path, name):
     rows = np.frombuffer(raw, dtype="<f8", count=15 * total, offset=8 * (1 + limit)).reshape(15, total)
     sums = np.frombuffer(raw, dtype="<f8", offset=8 * (1 + limit) + 8 * 15 * total).reshape(limit, 12)
     want = frame[frame[:, 5] == surface]
-    helpers.assert_frames_match(rows.T, want, what=f"{name}: rows of surface {surface} from C")
+    helpers.assert_matches_golden_frame(rows.T, name, want, what=f"{name}: rows of surface {surface} from C")
     for g in range(limit):
         ref = frame_oracle.reduce_sums(want.T, None, float(g), None, 1)[0]
         assert np.allclose(sums[g, :9], ref, rtol=1e-11, atol=1e-12), (name, g)

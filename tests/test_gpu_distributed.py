@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import helpers
 import scenes
 
 pytestmark = pytest.mark.gpu
@@ -79,7 +80,7 @@ def test_sharded_hip_trace_assembles_to_the_single_rank_frame(tmp_path, name, n,
         assert np.load(tmp_path / f"counts_{rank}.npy").tolist() == counts
         if mode == "all" or rank == 0:
             assert got.shape == want.shape
-            assert np.array_equal(got, want, equal_nan=True)  # sharded == unsharded, same row order
+            helpers.assert_same_bits(got, want, what=f"rank {rank}: sharded against unsharded")  # (same row order too)
         else:
             assert got.shape[1] == 0
 
@@ -302,7 +303,7 @@ def test_rccl_allgather_rows_across_real_devices(tmp_path, name, n, mode):
         assert np.load(tmp_path / f"counts_{rank}.npy").tolist() == counts
         if mode == "all" or rank == 0:
             assert got.shape == want.shape
-            assert np.array_equal(got, want, equal_nan=True)
+            helpers.assert_same_bits(got, want, what=f"rank {rank}: sharded against unsharded")
         else:
             assert got.shape[1] == 0
 
@@ -489,7 +490,7 @@ def test_record_plans_of_a_sharded_tracer(tmp_path, world):
     for rank in range(world):
         assert np.allclose(np.load(tmp_path / f"table_{rank}.npy"), want_table, rtol=1e-9, atol=1e-12, equal_nan=True), rank
         assert np.allclose(np.load(tmp_path / f"ms_{rank}.npy"), want_ms, rtol=1e-10, atol=1e-300, equal_nan=True), rank
-        assert np.array_equal(np.load(tmp_path / f"rows_{rank}.npy"), want_rows, equal_nan=True), rank
+        helpers.assert_same_bits(np.load(tmp_path / f"rows_{rank}.npy"), want_rows, what=f"rank {rank}: rows of the detector")
 
 
 def test_sharded_group_stats_over_a_one_rank_rccl_communicator():
@@ -610,4 +611,4 @@ def test_baseline_partitions_at_world_eight_sharing_one_gpu(tmp_path, name, n, m
     want = rows.cpu().numpy()
     for rank in range(world):
         assert np.load(tmp_path / f"counts_{rank}.npy").tolist() == counts
-        assert np.array_equal(np.load(tmp_path / f"rows_{rank}.npy"), want, equal_nan=True)
+        helpers.assert_same_bits(np.load(tmp_path / f"rows_{rank}.npy"), want, what=f"rank {rank}: assembled against unsharded")

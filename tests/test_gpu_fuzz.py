@@ -1,7 +1,9 @@
 """Randomised scenes: HIP engine vs the C oracle on seeded random CSG trees, transforms and
 materials -- shapes the part factories never build (unions, right-nested and balanced trees,
-anisotropic scales, every primitive as any child).  Surface ids must agree exactly, values to
-1e-6 (they agree far tighter; the assertion keeps the north-star tolerance)."""
+anisotropic scales, every primitive as any child).  Surface ids, t and every column of the frames
+must be the C oracle's doubles, bit for bit (helpers.assert_same_bits: a NaN matches any NaN, a
+zero's sign counts); the components' hit lists, whose expectation is the numpy oracle's, within
+rtol = atol = 1e-12 (their parameters reach 1e12, hence the relative term)."""
 import numpy as np
 import pytest
 
@@ -85,7 +87,7 @@ def test_random_scene(seed):
     t, surf = ds.propagate(device_rays)
     want_t, want_surf = c_oracle.propagate(flat, rays)
     assert np.array_equal(surf.cpu().numpy(), want_surf)
-    assert np.allclose(t.cpu().numpy(), want_t, rtol=0, atol=helpers.ATOL)
+    helpers.assert_same_bits(t.cpu().numpy(), want_t, what=f"seed {seed}: t")
     # every component's own hit list (component.intersect(), csg.py:118-160) on a slice that holds all
     # the degenerate families: values where finite, ids where the list has an entry
     from oracle import prt_oracle
@@ -99,7 +101,7 @@ def test_random_scene(seed):
         want_hits = np.where(np.isnan(want_hits), np.inf, want_hits)       # upstream's NaN = miss
         finite = np.isfinite(want_hits)
         assert np.array_equal(np.isfinite(got_hits), finite), (seed, root)
-        assert np.allclose(got_hits[finite], want_hits[finite], rtol=1e-12, atol=helpers.ATOL), (seed, root)
+        assert np.allclose(got_hits[finite], want_hits[finite], rtol=1e-12, atol=1e-12), (seed, root)
         assert np.array_equal(np.isneginf(got_hits), np.isneginf(want_hits)), (seed, root)
         assert np.array_equal(got_ids[finite], np.asarray(want_ids)[finite]), (seed, root)
     # whole trace, reference-faithful bookkeeping (absorbed rays carried) and the default; every fifth
@@ -112,7 +114,7 @@ def test_random_scene(seed):
     for flags in (0, 1, 2):
         rows, counts = ds.trace(device_rays, 6, flags=flags)
         assert counts == want_counts, (seed, flags)
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"seed {seed} flags {flags}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"seed {seed} flags {flags}")
     ds.close()
 
 
@@ -163,11 +165,11 @@ def test_random_bench(seed):
     for turn, buffer in enumerate((device_rays, twin, device_rays, device_rays, device_rays)):
         rows, counts = ds.trace(buffer, limit)
         assert counts == want_counts, (seed, turn)
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"bench seed {seed} turn {turn}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"bench seed {seed} turn {turn}")
     assert ds.telemetry()["speculation_misses"] == 0
     rows, counts = ds.trace(device_rays, limit, flags=2)       # and the three-kernel path
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"bench seed {seed} unfused")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"bench seed {seed} unfused")
     ds.close()
 
 
@@ -191,7 +193,7 @@ def test_random_scene_traced_again_from_the_same_buffers(seed):
     for k in range(2):
         rows, counts = ds.trace(buf, 6, out=block)
         assert counts == want_counts, (seed, k)
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"seed {seed} pass {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"seed {seed} pass {k}")
     from pyrayt_amd import engine
 
     if not engine.DEFAULT_OPTIONS and not engine.DEFAULT_TRACE_FLAGS and want_counts:
@@ -210,7 +212,7 @@ def test_random_scene_traced_again_from_the_same_buffers(seed):
     for k in range(2):
         rows, counts = ds.trace(buf, 6, out=block)
         assert counts == want_counts, (seed, "changed", k)
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"seed {seed} changed pass {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"seed {seed} changed pass {k}")
     ds.close()
 
 

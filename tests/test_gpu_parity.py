@@ -3,8 +3,14 @@
   (2) the CPU oracle on seeded inputs the fixtures do not cover,
 plus size-independent properties at the north-star size.
 
-Bar (BASELINE.json north_star): intersected-surface index bit-exact; hit point / direction /
-refractive index within 1e-6 abs in float64.  helpers.ATOL = 1e-6.
+Bar: far inside BASELINE.json's north_star (surface index exact, the rest within 1e-6) -- the bits the engine claims.
+  * against the C oracle, and between two paths of the engine itself: the same doubles (helpers.assert_same_bits /
+    assert_frames_identical; a NaN matches any NaN, a zero's sign counts);
+  * against the golden frames the genuine reference wrote: the same doubles on the 17 fixtures of
+    helpers.EXACT_SCENE_FIXTURES, rtol = atol = 1e-12 on the four of helpers.CLOSE_SCENE_FIXTURES (where the
+    reference's own bits depend on how many rays share a surface, tests/test_c_oracle.py);
+  * against the per-entry-point golden vectors and the numpy oracle: rtol = atol = 1e-12
+    (helpers.assert_close_to_reference).
 """
 import ctypes
 
@@ -36,10 +42,27 @@ def dev(array):
 FixtureSnapshot = helpers.FixtureSnapshot  # (kept importable from here: the render tests and tools take it from this module)
 
 
-def device_scene(scene_dict, options=None):
-    from pyrayt_amd.engine import DeviceScene
+device_scene = helpers.device_scene
 
-    return DeviceScene(FixtureSnapshot(scene_dict), options=options)
+
+_DEFAULT_PATH = {}
+
+
+def default_path(name):
+    """(frame (R,15), t of generation 0) of scene fixture `name` from the engine's default path (lane-per-ray nearest
+    hit, fused generations, default program form): computed once per fixture, read-only, what every other path of
+    the engine is compared with bit for bit."""
+    if name not in _DEFAULT_PATH:
+        fx = helpers.load(f"scene_{name}.npz")
+        ds = device_scene(helpers.scene_of(fx))
+        rows, counts = ds.trace(dev(fx["rays0"]), int(fx["generation_limit"]))
+        t, surf = ds.propagate(dev(fx["rays0"]))
+        frame, t = rows.cpu().numpy().T.copy(), t.cpu().numpy().copy()
+        ds.close()
+        frame.setflags(write=False)
+        t.setflags(write=False)
+        _DEFAULT_PATH[name] = (frame, t)
+    return _DEFAULT_PATH[name]
 
 
 def test_library_loads_on_gpu():
@@ -54,12 +77,30 @@ def test_library_loads_on_gpu():
 # golden scenes: whole trace and the stepwise propagate / interact entry points
 # ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", SCENE_FIXTURES)
+def test_trace_is_the_c_oracles_frame_in_every_bit(name):
+    """The default path against the C oracle (built beside the library, no reference needed): the same doubles in
+    all 15 columns and in t; against the reference's own frame the same doubles on the 17 fixtures the C oracle
+    reproduces exactly, 1e-12 on the other four."""
+    fx = helpers.load(f"scene_{name}.npz")
+    frame, t = default_path(name)
+    want, want_counts = c_oracle.trace(helpers.scene_of(fx), fx["rays0"], int(fx["generation_limit"]))
+    helpers.assert_frames_identical(frame, want, what=f"{name} against the C oracle")
+    want_t, want_surf = c_oracle.propagate(helpers.scene_of(fx), fx["rays0"])
+    helpers.assert_same_bits(t, want_t, what=f"{name}: t against the C oracle")
+    assert (name in helpers.EXACT_SCENE_FIXTURES) != (name in helpers.CLOSE_SCENE_FIXTURES)
+    helpers.assert_matches_golden_frame(frame, name, fx["frame"], what=f"{name} against the golden frame")
+    helpers.assert_close_to_reference(t, fx["t_0"], what=f"{name}: t against the golden t")
+
+
+@pytest.mark.parametrize("name", SCENE_FIXTURES)
 @pytest.mark.parametrize("flags", [0, 1, 2, 3])
 def test_trace_matches_reference(name, flags):
     fx = helpers.load(f"scene_{name}.npz")
     ds = device_scene(helpers.scene_of(fx))
     rows, counts = ds.trace(dev(fx["rays0"]), int(fx["generation_limit"]), flags=flags)
-    helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what=f"{name} flags={flags}")
+    got = rows.cpu().numpy().T
+    helpers.assert_frames_identical(got, default_path(name)[0], what=f"{name} flags={flags} against the default path")
+    helpers.assert_matches_golden_frame(got, name, fx["frame"], what=f"{name} flags={flags}")
     assert sum(counts) == fx["frame"].shape[0]
     ds.close()
 
@@ -78,9 +119,12 @@ def test_trace_matches_reference_on_every_program_form(name, knob):
     if knob == "no_cull":
         assert info["cull_steps"] == 0
     rows, counts = ds.trace(dev(fx["rays0"]), int(fx["generation_limit"]))
-    helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what=f"{name} {knob}")
+    got = rows.cpu().numpy().T
+    helpers.assert_frames_identical(got, default_path(name)[0], what=f"{name} {knob} against the default path")
+    helpers.assert_matches_golden_frame(got, name, fx["frame"], what=f"{name} {knob}")
     t, surf = ds.propagate(dev(fx["rays0"]))
     assert np.array_equal(surf.cpu().numpy(), fx["surf_0"]), f"{name} {knob}: surfaces"
+    helpers.assert_same_bits(t.cpu().numpy(), default_path(name)[1], what=f"{name} {knob}: t against the default path")
     ds.close()
 
 
@@ -96,9 +140,12 @@ def test_surface_parallel_variants_match_reference(name, variant):
                                                      "hit_staged": int("lds" in variant)})
     t, surf = ds.propagate(dev(fx["rays0"]))
     assert np.array_equal(surf.cpu().numpy(), fx["surf_0"]), f"{name} {variant}: surfaces"
-    assert np.allclose(t.cpu().numpy(), fx["t_0"], rtol=0, atol=helpers.ATOL), f"{name} {variant}: t"
+    helpers.assert_same_bits(t.cpu().numpy(), default_path(name)[1], what=f"{name} {variant}: t against the default path")
+    helpers.assert_close_to_reference(t.cpu().numpy(), fx["t_0"], what=f"{name} {variant}: t")
     rows, counts = ds.trace(dev(fx["rays0"]), int(fx["generation_limit"]), flags=2)
-    helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what=f"{name} {variant}")
+    got = rows.cpu().numpy().T
+    helpers.assert_frames_identical(got, default_path(name)[0], what=f"{name} {variant} against the default path")
+    helpers.assert_matches_golden_frame(got, name, fx["frame"], what=f"{name} {variant}")
     assert ds.trace_stats()["variant"] == (3 if "lanes" in variant else 2)
     ds.close()
 
@@ -115,16 +162,16 @@ def test_stepwise_matches_reference(name):
     for g in range(int(fx["n_generations"])):
         t, surf = ds.propagate(rays)
         assert np.array_equal(surf.cpu().numpy(), fx[f"surf_{g}"]), f"{name}: surfaces gen {g}"
-        assert np.allclose(t.cpu().numpy(), fx[f"t_{g}"], rtol=0, atol=helpers.ATOL), f"{name}: t gen {g}"
+        helpers.assert_close_to_reference(t.cpu().numpy(), fx[f"t_{g}"], what=f"{name}: t gen {g}")
         rows, nxt = ds.interact(rays, t, surf, g, limit)
         if rows.shape[1] == 0:  # every ray dead: nothing recorded, the loop ends
             assert g == int(fx["n_generations"]) - 1
             break
         blocks.append(rows.cpu().numpy().T)
-        assert np.allclose(nxt.cpu().numpy(), fx[f"next_{g}"], rtol=0, atol=helpers.ATOL,
-                           equal_nan=True), f"{name}: state after gen {g}"
+        helpers.assert_close_to_reference(nxt.cpu().numpy(), fx[f"next_{g}"], what=f"{name}: state after gen {g}")
         rays = nxt.contiguous()
-    helpers.assert_frames_match(np.vstack(blocks), fx["frame"], what=name)
+    helpers.assert_frames_identical(np.vstack(blocks), default_path(name)[0], what=f"{name}: stepwise against the fused trace")
+    helpers.assert_matches_golden_frame(np.vstack(blocks), name, fx["frame"], what=name)
     ds.close()
 
 
@@ -140,12 +187,10 @@ def test_primitive_intersect_and_normals(kind, variant):
     hits, ids = ds.intersect(0, dev(fx[key + "rays"][:8]))
     hits = hits.cpu().numpy()
     want = np.where(np.isnan(fx[key + "hits"]), np.inf, fx[key + "hits"])  # NaN == miss
-    assert np.array_equal(np.isfinite(hits), np.isfinite(want))
-    assert np.allclose(hits, want, rtol=0, atol=helpers.ATOL)
+    helpers.assert_close_to_reference(hits, want, what=f"{kind} {variant}: hits")
     has = fx[key + "has_hit"]
     normals = ds.world_normals(0, dev(fx[key + "points"])).cpu().numpy()
-    assert np.allclose(normals[:, has], fx[key + "normals"][:, has], rtol=0, atol=helpers.ATOL,
-                       equal_nan=True)
+    helpers.assert_close_to_reference(normals[:, has], fx[key + "normals"][:, has], what=f"{kind} {variant}: normals")
     ds.close()
 
 
@@ -157,7 +202,7 @@ def test_csg_component_intersect(name):
     ds = device_scene(helpers.scene_of(fx, key))
     hits, ids = ds.intersect(0, dev(fx[key + "rays"][:8]))
     assert np.array_equal(ids.cpu().numpy(), fx[key + "ids"])
-    assert np.allclose(hits.cpu().numpy(), fx[key + "hits"], rtol=0, atol=helpers.ATOL)
+    helpers.assert_close_to_reference(hits.cpu().numpy(), fx[key + "hits"], what=f"{name}: hits")
     ds.close()
 
 
@@ -169,7 +214,7 @@ def test_material_trace(kind, material):
     ds = device_scene(helpers.scene_of(fx, key))
     rays = dev(fx[key + "in"])
     ds.material_trace(0, rays)
-    assert np.allclose(rays.cpu().numpy(), fx[key + "out"], rtol=0, atol=helpers.ATOL, equal_nan=True)
+    helpers.assert_close_to_reference(rays.cpu().numpy(), fx[key + "out"], what=f"{kind} {material}: rays after trace()")
     ds.close()
 
 
@@ -273,7 +318,10 @@ def test_trace_matches_oracle(name, args, limit):
     ds = DeviceScene(snap)
     rows, counts = ds.trace(dev(rays), limit)
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what=name)
+    exact, exact_counts = c_oracle.trace(helpers.flat_scene(snap), rays, limit)
+    assert counts == exact_counts
+    helpers.assert_frames_identical(rows.cpu().numpy().T, exact, what=f"{name} against the C oracle")
+    helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what=f"{name} against the numpy oracle")
     ds.close()
 
 
@@ -290,13 +338,13 @@ def test_empty_ragged_and_tiny_inputs():
         rows, counts = ds.trace(dev(sub), 10)
         want, want_counts = orc.trace(flat, sub, 10) if n else (np.zeros((0, 15)), [])
         assert counts == want_counts, n
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"n={n}")
+        helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what=f"n={n}")
     # strided input (a column slice of a wider buffer) and generation_limit 1
     wide = dev(rays)
     rows, counts = ds.trace(wide[:, 100:400], 1)
     want, want_counts = orc.trace(flat, rays[:, 100:400], 1)
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what="strided")
+    helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what="strided")
     # rays that all miss: nothing recorded
     away = rays.copy()
     away[4] = -1.0
@@ -318,7 +366,8 @@ def test_config2_one_million_rays():
     n = int(fx["n"])
     CountedObject.reset_ids()
     parts, rays = scenes.config2(scenes.product_api(), n)
-    ds = DeviceScene(SceneSnapshot(parts))
+    snap = SceneSnapshot(parts)
+    ds = DeviceScene(snap)
     rows, counts = ds.trace(dev(rays), 10)
     frame = rows.cpu().numpy().T
     assert frame.shape[0] == int(fx["rows"]) == 2999991
@@ -332,7 +381,12 @@ def test_config2_one_million_rays():
     assert np.array_equal(frame[(gens == 1) & (surf == detector), 4].astype(np.int64), fx["q5_ids"])
     assert int((surf * (gens + 1)).sum()) == int(fx["surface_checksum"])
     assert np.allclose(frame.sum(axis=0), fx["column_sums"], rtol=1e-9, atol=1e-3)
-    assert np.allclose(frame[fx["sample_index"]], fx["sample_rows"], rtol=0, atol=helpers.ATOL)
+    # (rows the genuine reference wrote at this size; the C oracle gives the same doubles for them on the CPU)
+    helpers.assert_same_bits(frame[fx["sample_index"]], fx["sample_rows"], what="sampled rows of the reference's 1M-ray frame")
+    # every 64th ray through the C oracle: rays are independent, their rows are the rows of the full trace
+    pick = np.arange(0, n, 64)
+    want, want_counts = c_oracle.trace(helpers.flat_scene(snap), np.ascontiguousarray(rays[:, pick]), 10)
+    helpers.assert_frames_identical(frame[np.isin(frame[:, 4], pick)], want, what="every 64th ray against the C oracle")
     # invariants: generation-major, ids ascending inside a generation, unit tilts,
     # segment end of generation g == segment start of generation g+1 (minus the 1e-6 re-launch)
     assert np.all(np.diff(gens) >= 0)
@@ -529,7 +583,7 @@ def test_baseline_configs_at_full_size(name, args, limit):
     want, want_counts = c_oracle.trace(helpers.flat_scene(snap), np.ascontiguousarray(rays[:, pick]), limit)
     keep = torch.isin(ids, torch.from_numpy(pick.astype(np.float64)).to(ids.device))
     got = rows[:, keep].cpu().numpy().T
-    helpers.assert_frames_match(got, want, what=f"{name} subsample")
+    helpers.assert_frames_identical(got, want, what=f"{name} subsample")
     # and tracing the subset alone gives exactly those rows (independence of rays)
     sub_rows, sub_counts = ds.trace(dev(rays[:, pick]), limit)
     assert sub_counts == want_counts and np.array_equal(sub_rows.cpu().numpy().T, got)
@@ -591,7 +645,7 @@ def test_scene_update_in_place_equals_a_new_scene():
         for turn in range(2):
             rows, counts = ds.trace(device_rays, 10)
             assert counts == want_counts, (step, turn)
-            helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"updated scene step {step} turn {turn}")
+            helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what=f"updated scene step {step} turn {turn}")
         fresh = DeviceScene(snap)
         rows_fresh, _ = fresh.trace(device_rays, 10)
         assert np.array_equal(rows_fresh.cpu().numpy(), rows.cpu().numpy(), equal_nan=True)
@@ -778,13 +832,13 @@ def test_ray_sets_that_need_all_state_rows(kind):
     assert ds.telemetry()["full_rows_fallbacks"] == 0        # RaySet defaults: compact state
     want_good, want_good_counts = orc.trace(flat, rays, 10)
     assert good_counts == want_good_counts
-    helpers.assert_frames_match(good.cpu().numpy().T, want_good, what="config3 compact")
+    helpers.assert_close_to_reference(good.cpu().numpy().T, want_good, what="config3 compact")
     odd = _odd_rays(kind, rays)
     want, want_counts = orc.trace(flat, odd, 10)
     for turn in range(2):                                     # the repeat, then straight with all rows
         rows, counts = ds.trace(dev(odd), 10)
         assert counts == want_counts and ds.telemetry()["full_rows_fallbacks"] == 1, (kind, turn)
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"{kind} turn {turn}")
+        helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what=f"{kind} turn {turn}")
     again, _ = ds.trace(dev(rays), 10)                        # the scene stays on all rows: same frame
     assert np.array_equal(again.cpu().numpy(), good.cpu().numpy())
     ds.close()
@@ -800,7 +854,7 @@ def test_compact_and_full_state_rows_give_the_same_frame():
         compact, counts = ds.trace(rays, limit)
         full, full_counts = ds.trace(rays, limit, flags=engine.TRACE_FULL_ROWS)
         assert counts == full_counts and np.array_equal(compact.cpu().numpy(), full.cpu().numpy(), equal_nan=True)
-        helpers.assert_frames_match(compact.cpu().numpy().T, fx["frame"], what=name)
+        helpers.assert_matches_golden_frame(compact.cpu().numpy().T, name, fx["frame"])
         ds.close()
 
 
@@ -826,7 +880,7 @@ def test_dense_mode_hints_repeat_and_miss():
     tele = ds.telemetry()
     assert tele["dense_launches"] >= 2 and tele["speculation_misses"] == 0
     assert counts == want_counts and np.array_equal(again.cpu().numpy(), first)
-    helpers.assert_frames_match(first.T, want, what="config2 hinted")
+    helpers.assert_close_to_reference(first.T, want, what="config2 hinted")
     # same ray count, but a third of the rays now miss everything: generation 0 is no longer dense
     other = rays.copy()
     other[5, ::3] = 5.0
@@ -835,7 +889,7 @@ def test_dense_mode_hints_repeat_and_miss():
     got2, counts2 = ds.trace(dev(other), 10)
     assert ds.telemetry()["speculation_misses"] == 1
     assert counts2 == want2_counts
-    helpers.assert_frames_match(got2.cpu().numpy().T, want2, what="config2 after a missed hint")
+    helpers.assert_close_to_reference(got2.cpu().numpy().T, want2, what="config2 after a missed hint")
     before = ds.telemetry()["dense_launches"]
     for _ in range(3):                                    # after a miss the hints rest for two traces ...
         got3, counts3 = ds.trace(dev(other), 10)
@@ -866,7 +920,7 @@ def test_dense_mode_miss_in_the_generation_that_ends_the_trace(n):
     for _ in range(3):                                    # one generation: it is first and last at once
         got, counts = ds.trace(dev(rays), 1)
         assert counts == want_counts
-    helpers.assert_frames_match(got.cpu().numpy().T, want, what="one dense generation")
+    helpers.assert_close_to_reference(got.cpu().numpy().T, want, what="one dense generation")
     assert ds.telemetry()["dense_launches"] == 2 and ds.telemetry()["speculation_misses"] == 0
     for victim in (0, n // 2, n - 1):                     # one ray of one tile misses everything
         other = rays.copy()
@@ -878,7 +932,7 @@ def test_dense_mode_miss_in_the_generation_that_ends_the_trace(n):
             ds2.trace(dev(rays), 1)
         got2, counts2 = ds2.trace(dev(other), 1)
         assert ds2.telemetry()["speculation_misses"] == 1 and counts2 == want2_counts
-        helpers.assert_frames_match(got2.cpu().numpy().T, want2, what=f"ray {victim} misses")
+        helpers.assert_close_to_reference(got2.cpu().numpy().T, want2, what=f"ray {victim} misses")
         ds2.close()
     ds.close()
 
@@ -896,14 +950,14 @@ def test_dense_mode_hints_across_limits_flags_and_sizes():
         rows, counts = ds.trace(rays, limit, flags=flags)
         got = rows.cpu().numpy().T
         keep = want[:, 0] < limit                   # rows of the first `limit` generations
-        helpers.assert_frames_match(got, want[keep], what=f"config3 limit {limit} flags {flags}")
+        helpers.assert_matches_golden_frame(got, "config3", want[keep], what=f"config3 limit {limit} flags {flags}")
     assert ds.telemetry()["speculation_misses"] == 0 and ds.telemetry()["dense_launches"] > 0
     # a record block that is too small is reported from the dense generations as from the others
     # (the wrapper then grows it and repeats), and an exact-fit block works
     total = want.shape[0]
     for cap in (rays.shape[1] * 2, total, total - 1):
         rows, counts = ds.trace(rays, 10, rows_cap=cap)
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"config3 rows_cap {cap}")
+        helpers.assert_matches_golden_frame(rows.cpu().numpy().T, "config3", want, what=f"config3 rows_cap {cap}")
     block = torch.empty((15, total - 1), dtype=torch.float64, device="cuda:0")
     with pytest.raises(RuntimeError, match="rows_cap"):
         ds.trace(rays, 10, out=block)              # a caller's block is never replaced
@@ -926,7 +980,7 @@ def test_traces_in_flight_equal_synchronous_traces(name):
     n = rays.shape[1]
     want, want_counts = ds.trace(rays, limit)
     want = want.cpu().numpy().copy()
-    helpers.assert_frames_match(want.T, fx["frame"], what=name)
+    helpers.assert_matches_golden_frame(want.T, name, fx["frame"])
     blocks = [torch.full((15, n * limit), float("nan"), dtype=torch.float64, device="cuda:0") for _ in range(2)]
     steps = 7
     ds.trace_begin(0, rays, limit, blocks[0])
@@ -959,7 +1013,7 @@ def test_tickets_reject_misuse_and_every_flag_goes_through_them():
     with pytest.raises(ValueError, match="own workspace and record block"):
         ds.trace_begin(1, rays, limit, a)                      # same record block as the trace in flight
     rows, counts = ds.trace_end(0)
-    helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what="ticket 0")
+    helpers.assert_matches_golden_frame(rows.cpu().numpy().T, "config3", fx["frame"], what="ticket 0")
     with pytest.raises(ValueError, match="no trace in flight"):
         eng._check(eng.library().prt_trace_end(ds.handle, 0, 0, (ctypes.c_int64 * limit)()))
     # keep-absorbed, the three-kernel path, no hints, all state rows, kernel publish, the stall fallback, sync
@@ -970,7 +1024,7 @@ def test_tickets_reject_misuse_and_every_flag_goes_through_them():
             ds.trace_begin(0, rays, limit, a, flags=flags)
             for ticket, block in ((1, b), (0, a)):
                 rows, counts = ds.trace_end(ticket)
-                helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what=f"flags {flags} ticket {ticket}")
+                helpers.assert_matches_golden_frame(rows.cpu().numpy().T, "config3", fx["frame"], what=f"flags {flags} ticket {ticket}")
     # (the stall hook lives in the fused kernels: two flag sets carry it, two traces each, on two tickets)
     assert ds.telemetry()["lookback_fallbacks"] == (0 if engine.DEFAULT_TRACE_FLAGS & engine.TRACE_UNFUSED else 4)
     # a record block one column short is reported by prt_trace_end
@@ -1006,8 +1060,8 @@ def test_a_missed_hint_in_flight_repeats_only_that_trace():
     rows_b, got_b = ds.trace_end(0)
     rows_a, got_a = ds.trace_end(1)
     assert got_b == counts_b and got_a == counts_a
-    helpers.assert_frames_match(rows_b.cpu().numpy().T, want_b, what="missed hint in flight")
-    helpers.assert_frames_match(rows_a.cpu().numpy().T, want_a, what="the trace queued behind it")
+    helpers.assert_close_to_reference(rows_b.cpu().numpy().T, want_b, what="missed hint in flight")
+    helpers.assert_close_to_reference(rows_a.cpu().numpy().T, want_a, what="the trace queued behind it")
     assert ds.telemetry()["speculation_misses"] == 1
     ds.close()
 
@@ -1036,7 +1090,7 @@ def test_a_missed_hint_with_an_exact_fit_record_block_is_repeated_not_reported()
         block = torch.empty((15, sum(want_counts)), dtype=torch.float64, device="cuda:0")  # fits `other` exactly
         rows, counts = ds.trace(dev(other), limit, out=block)
         assert counts == want_counts and ds.telemetry()["speculation_misses"] == 1
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"exact fit after a miss, stride {stride}")
+        helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what=f"exact fit after a miss, stride {stride}")
         ds.close()
 
 
@@ -1059,7 +1113,7 @@ def test_path_counters_tell_well_formed_rays_from_the_others():
     ds = DeviceScene(snap)
     want, want_counts = orc.trace(flat, rays, limit)
     rows, counts = ds.trace(dev(rays), limit, flags=engine.TRACE_COUNT_PATHS)
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what="counted trace")
+    helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what="counted trace")
     tele = ds.telemetry()
     assert tele["counted_traces"] == 1 and ds.trace_stats()["variant"] == 2  # (a counted trace runs on the three-kernel path)
     assert tele["rays_not_well_formed"] == 0                                   # unit directions, w = 1 / 0
@@ -1072,7 +1126,7 @@ def test_path_counters_tell_well_formed_rays_from_the_others():
     want2, want2_counts = orc.trace(flat, odd, limit)
     rows2, counts2 = ds.trace(dev(odd), limit, flags=engine.TRACE_COUNT_PATHS)
     assert counts2 == want2_counts
-    helpers.assert_frames_match(rows2.cpu().numpy().T, want2, what="counted trace, odd rays")
+    helpers.assert_close_to_reference(rows2.cpu().numpy().T, want2, what="counted trace, odd rays")
     tele2 = ds.telemetry()
     gen0_bad = len(set(range(0, n, 4)) | set(range(0, n, 5)))
     assert tele2["counted_traces"] == 2 and tele2["rays_not_well_formed"] >= gen0_bad
@@ -1170,7 +1224,7 @@ def test_ticket_edges_update_in_flight_bad_ticket_varying_sizes():
     rows, counts = ds.trace_end(2)
     want, want_counts = orc.trace(flat, rays, limit)
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what="ticket 2")
+    helpers.assert_close_to_reference(rows.cpu().numpy().T, want, what="ticket 2")
     moved = SceneSnapshot(parts)
     assert ds.update(moved)                                 # ... and afterwards they are
     # ray sets of different sizes through all four tickets
@@ -1180,7 +1234,7 @@ def test_ticket_edges_update_in_flight_bad_ticket_varying_sizes():
     for k, (rows_k, counts_k) in enumerate(got):
         want_k, want_counts_k = orc.trace(flat2, sets[k], limit)
         assert counts_k == want_counts_k, k
-        helpers.assert_frames_match(rows_k.T, want_k, what=f"trace_many set {k}")
+        helpers.assert_close_to_reference(rows_k.T, want_k, what=f"trace_many set {k}")
     ds.close()
 
 
@@ -1539,7 +1593,7 @@ def test_trace_batch_under_the_trace_flags(flags):
     for rows, counts in got:
         assert counts == want_counts
         assert torch.equal(rows, want)
-    helpers.assert_frames_match(want.cpu().numpy().T, fx["frame"], what="mirrors_and_stops")
+    helpers.assert_matches_golden_frame(want.cpu().numpy().T, "mirrors_and_stops", fx["frame"])
     ds.close()
 
 
@@ -1579,7 +1633,7 @@ def test_a_ray_buffer_that_loses_rays_in_numbers_is_replayed_and_refilled():
     for k in range(4):
         rows, counts = ds.trace(buf, 10, out=block)
         assert counts == want_counts
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"replayed, trace {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"replayed, trace {k}")
     # same lossy rays, one of them swapped with a surviving one: equal totals, two tiles with other counts
     lost = int(np.nonzero(np.abs(rays[5]) > 0.25)[0][0])
     kept = int(np.nonzero(np.abs(rays[5]) < 0.05)[0][-1])
@@ -1592,7 +1646,7 @@ def test_a_ray_buffer_that_loses_rays_in_numbers_is_replayed_and_refilled():
         for k in range(3):
             rows, counts = ds.trace(buf, 10, out=block)
             assert counts == want_counts
-            helpers.assert_frames_match(rows.cpu().numpy().T, want, what="refilled buffer")
+            helpers.assert_frames_identical(rows.cpu().numpy().T, want, what="refilled buffer")
     assert ds.telemetry()["speculation_misses"] == 0
     ds.close()
 
@@ -1647,7 +1701,7 @@ def test_sparse_loss_generations_run_dense_with_their_absorbed_rays_kept(with_ho
     for k in range(3):                                           # another buffer every time: no per-tile records
         rows, counts = ds.trace(buffers[k], 10, out=block)
         assert counts == want_counts
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"absorbed rays kept, trace {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"absorbed rays kept, trace {k}")
     told = ds.telemetry()
     assert told["sparse_keep_launches"] == 3 and told["speculation_misses"] == 0
     # other rays, lost elsewhere and in other numbers: the hint holds for them as well
@@ -1656,7 +1710,7 @@ def test_sparse_loss_generations_run_dense_with_their_absorbed_rays_kept(with_ho
     other_buffer = dev(other)
     rows, counts = ds.trace(other_buffer, 10, out=block)
     assert counts == counts_other
-    helpers.assert_frames_match(rows.cpu().numpy().T, want_other, what="other rays on the same hint")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want_other, what="other rays on the same hint")
     assert ds.telemetry()["sparse_keep_launches"] == 4 and ds.telemetry()["speculation_misses"] == 0
     # the same buffer again and again: nothing but the hints is kept between traces (the per-tile records of earlier
     # rounds are retired), so a replayed buffer is served like any other
@@ -1664,7 +1718,7 @@ def test_sparse_loss_generations_run_dense_with_their_absorbed_rays_kept(with_ho
     for k in range(4):
         rows, counts = ds.trace(buf, 10, out=block)
         assert counts == want_counts
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"same buffer, trace {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"same buffer, trace {k}")
     assert ds.telemetry()["sparse_keep_launches"] == 8 and ds.telemetry()["speculation_misses"] == 0
     # not with the flag; upstream's bookkeeping for the whole trace is the other flag and has its own hints
     before = ds.telemetry()["sparse_keep_launches"]
@@ -1672,7 +1726,7 @@ def test_sparse_loss_generations_run_dense_with_their_absorbed_rays_kept(with_ho
         for k in range(2):
             rows, counts = ds.trace(buffers[3 + k], 10, out=block, flags=flags)
             assert counts == want_counts
-            helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"flags {flags}")
+            helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"flags {flags}")
     assert ds.telemetry()["sparse_keep_launches"] == before
     ds.close()
 
@@ -1698,15 +1752,15 @@ def test_a_sparse_loss_hint_that_does_not_hold_repeats_the_trace():
     astray_buffer = dev(astray)
     rows, counts = ds.trace(astray_buffer, 10, out=block)
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what="after a sparse-loss hint that did not hold")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want, what="after a sparse-loss hint that did not hold")
     assert ds.telemetry()["speculation_misses"] == 1
     # the first ray set again, and in flight on two tickets
     want, want_counts = c_oracle.trace(flat, rays, 10)
     got = ds.trace_batch([dev(rays), dev(astray), dev(rays)], 10, depth=2)
     torch.cuda.synchronize()
     assert got[0][1] == want_counts and got[2][1] == want_counts
-    helpers.assert_frames_match(got[0][0].cpu().numpy().T, want, what="in flight, ticket 0")
-    helpers.assert_frames_match(got[2][0].cpu().numpy().T, want, what="in flight, ticket 0 again")
+    helpers.assert_frames_identical(got[0][0].cpu().numpy().T, want, what="in flight, ticket 0")
+    helpers.assert_frames_identical(got[2][0].cpu().numpy().T, want, what="in flight, ticket 0 again")
     ds.close()
 
 
@@ -1783,7 +1837,7 @@ def test_the_generation_behind_a_sparse_loss_runs_on_its_dead_list(which):
         before = ds.telemetry()
         rows, counts = ds.trace(buffers[k], 10, out=block)
         assert counts == want_counts
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"dead list, trace {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"dead list, trace {k}")
         told = ds.telemetry()
         assert told["dense_launches"] - before["dense_launches"] == generations, (told, before)
         assert told["sparse_keep_launches"] - before["sparse_keep_launches"] == 1 and told["speculation_misses"] == 0
@@ -1793,23 +1847,23 @@ def test_the_generation_behind_a_sparse_loss_runs_on_its_dead_list(which):
     other_buffer = dev(other)
     rows, counts = ds.trace(other_buffer, 10, out=block)
     assert counts == counts_other and ds.telemetry()["speculation_misses"] == 0
-    helpers.assert_frames_match(rows.cpu().numpy().T, want_other, what="other rays on the same hints")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want_other, what="other rays on the same hints")
     # in flight on two tickets and two streams, and under the flags that switch the forms off
     got = ds.trace_batch([buffers[4], other_buffer, buffers[5]], 10, depth=2)
     torch.cuda.synchronize()
     for (rows, counts), (frame, frame_counts) in zip(got, ((want, want_counts), (want_other, counts_other), (want, want_counts))):
         assert counts == frame_counts
-        helpers.assert_frames_match(rows.cpu().numpy().T, frame, what="in flight")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, frame, what="in flight")
     for flags in (engine.TRACE_NO_SPARSE_KEEP, engine.TRACE_NO_HINTS, engine.TRACE_KEEP_ABSORBED):
         for k in (6, 7):
             rows, counts = ds.trace(buffers[k], 10, out=block, flags=flags)
             assert counts == want_counts
-            helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"flags {flags}")
+            helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"flags {flags}")
     # the same buffer again and again
     for k in range(4):
         rows, counts = ds.trace(buffers[7], 10, out=block)
         assert counts == want_counts
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"same buffer, trace {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"same buffer, trace {k}")
     assert ds.telemetry()["speculation_misses"] == 0
     ds.close()
 
@@ -1835,12 +1889,12 @@ def test_a_dead_list_hint_that_does_not_hold_repeats_the_trace():
     astray_buffer = dev(astray)
     rows, counts = ds.trace(astray_buffer, 10, out=block)
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what="after a dead-list hint that did not hold")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want, what="after a dead-list hint that did not hold")
     assert ds.telemetry()["speculation_misses"] == 1
     want, want_counts = c_oracle.trace(flat, rays, 10)
     rows, counts = ds.trace(buffers[2], 10, out=block)
     assert counts == want_counts
-    helpers.assert_frames_match(rows.cpu().numpy().T, want, what="the first rays again")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want, what="the first rays again")
     ds.close()
 
 
@@ -1868,12 +1922,12 @@ def test_a_dead_list_that_overflows_costs_one_repeat_and_rests():
         assert counts == counts_few, k
     told = ds.telemetry()
     assert told["sparse_keep_launches"] == 2 and told["dense_launches"] == 2 * 3 and told["speculation_misses"] == 0
-    helpers.assert_frames_match(rows.cpu().numpy().T, want_few, what="a short dead list")
+    helpers.assert_frames_identical(rows.cpu().numpy().T, want_few, what="a short dead list")
     buffers = [dev(many) for _ in range(3)]
     for k, buffer in enumerate(buffers):
         rows, counts = ds.trace(buffer, 10, out=block)
         assert counts == want_counts, k
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"overflowing dead list, trace {k}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"overflowing dead list, trace {k}")
         told = ds.telemetry()
         assert told["speculation_misses"] == 1, (k, told)        # (the first of them found out)
     assert told["sparse_keep_launches"] == 2 + 3                 # generation 1 keeps its rays all the same
@@ -1902,7 +1956,7 @@ def test_a_generation_that_keeps_too_many_rays_goes_back_to_compacting():
         rows, counts = ds.trace(buffers[-1], 10, out=block)
         want, want_counts = frames[which]
         assert counts == want_counts, which
-        helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"{which}, trace {len(kept)}")
+        helpers.assert_frames_identical(rows.cpu().numpy().T, want, what=f"{which}, trace {len(kept)}")
         kept.append(ds.telemetry()["sparse_keep_launches"])
     # first trace: no hints; second: kept; third: still kept (3000 rays of them); fourth: dropped; fifth: compacts and
     # sees a sparse loss again; sixth: kept

@@ -101,7 +101,7 @@ def check(rows, counts, plan, frame, ids, what):
     and the fused sums per generation to the bound of tests/test_gpu_record_plan.py."""
     sel = filtered(frame, ids)
     if plan.rows:
-        helpers.assert_frames_match(rows.cpu().numpy().T, sel, what=what)
+        helpers.assert_close_to_reference(rows.cpu().numpy().T, sel, what=what)
         assert counts == counts_of(sel), (what, counts, counts_of(sel))
     else:
         assert rows.shape[1] == 0 and sum(counts) == 0, what
@@ -254,7 +254,7 @@ def fresh_full(pyrayt, sources, components):
 
 def assert_rows_of(got, full, ids, what):
     want = full.loc[full["surface"].isin(list(ids))].reset_index(drop=True)
-    helpers.assert_frames_match(got.to_numpy(), want.to_numpy(), what=what)
+    helpers.assert_same_bits(got.to_numpy(), want.to_numpy(), what=what)
 
 
 def assert_stats_of(stats, device_full, ids, n_groups, what):
@@ -351,7 +351,7 @@ def test_a_failed_update_is_not_taken_for_a_current_scene(monkeypatch):
         tracer.trace()
     got = tracer.trace()
     want, _ = fresh_full(pyrayt, sources, tracer.get_system())
-    helpers.assert_frames_match(got.to_numpy(), want.to_numpy(), what="after a failed update")
+    helpers.assert_same_bits(got.to_numpy(), want.to_numpy(), what="after a failed update")
     monkeypatch.undo()
 
     # the update does not fit, and building the new scene fails once
@@ -372,7 +372,7 @@ def test_a_failed_update_is_not_taken_for_a_current_scene(monkeypatch):
     got = tracer.trace()
     monkeypatch.undo()
     want, _ = fresh_full(pyrayt, sources, tracer.get_system())
-    helpers.assert_frames_match(got.to_numpy(), want.to_numpy(), what="after a failed rebuild")
+    helpers.assert_same_bits(got.to_numpy(), want.to_numpy(), what="after a failed rebuild")
 
 
 def test_trace_ray_set_records_everything_after_plans():
@@ -387,11 +387,11 @@ def test_trace_ray_set_records_everything_after_plans():
     assert set(np.unique(want["surface"])) != {det.get_id()}             # (more than the detector's rows)
     tracer.trace_stats(surface=det)
     got = tracer.trace_ray_set(rays_host, device)
-    helpers.assert_frames_match(got.to_numpy(), want.to_numpy(), what="trace_ray_set after trace_stats")
+    helpers.assert_same_bits(got.to_numpy(), want.to_numpy(), what="trace_ray_set after trace_stats")
     tracer.record_only(det)
     tracer.trace()
     got = tracer.trace_ray_set(rays_host, device)
-    helpers.assert_frames_match(got.to_numpy(), want.to_numpy(), what="trace_ray_set after record_only")
+    helpers.assert_same_bits(got.to_numpy(), want.to_numpy(), what="trace_ray_set after record_only")
 
 
 # --- what "last" means for the fused sums ----------------------------------------------------------------------------

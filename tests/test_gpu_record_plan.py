@@ -78,11 +78,11 @@ def test_filtered_frame_is_the_reference_frame_filtered(name):
         plan = engine.RecordPlan(surfaces=ids, rows=True, generation_limit=limit)
         for attempt in range(3):  # (a first trace, then two on the plan's own hints)
             rows, counts = ds.trace(rays, limit, plan=plan)
-            helpers.assert_frames_match(rows.cpu().numpy().T, want, what=f"{name} surfaces={ids} attempt {attempt}")
+            helpers.assert_matches_golden_frame(rows.cpu().numpy().T, name, want, what=f"{name} surfaces={ids} attempt {attempt}")
             assert counts == counts_of(want, limit), (name, ids, attempt)
     # ... and without a plan the scene traces as ever
     rows, counts = ds.trace(rays, limit, plan=None)
-    helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what=f"{name} after the plans")
+    helpers.assert_matches_golden_frame(rows.cpu().numpy().T, name, fx["frame"], what=f"{name} after the plans")
     ds.close()
 
 
@@ -108,7 +108,7 @@ def test_fused_sums_equal_the_frame_oracle_on_the_reference_frame(name, store_ro
                     got = plan.sums.cpu().numpy()
                     sel = filtered(frame, ids) if ids else frame
                     if store_rows:
-                        helpers.assert_frames_match(rows.cpu().numpy().T, sel, what=f"{name} {ids} rows beside the sums")
+                        helpers.assert_matches_golden_frame(rows.cpu().numpy().T, name, sel, what=f"{name} {ids} rows beside the sums")
                     else:
                         assert rows.shape[1] == 0 and sum(counts) == 0
                     for g in range(limit):
@@ -187,12 +187,12 @@ def test_plans_of_two_tickets_in_flight_together():
             ds.trace_begin(ticket, rays, limit, outs[ticket], stream=streams[ticket])
         results = [ds.trace_end(ticket) for ticket in range(3)]
         torch.cuda.synchronize()
-        helpers.assert_frames_match(results[0][0].cpu().numpy().T, want_rows, what="ticket 0 (rows of the imager)")
+        helpers.assert_matches_golden_frame(results[0][0].cpu().numpy().T, "config3", want_rows, what="ticket 0 (rows of the imager)")
         assert results[1][0].shape[1] == 0
         want = frame_oracle.reduce_sums(want_rows.T, None, None, None, 1)
         got = plan_sums.sums.cpu().numpy().sum(axis=0)[:, :9]
         assert np.allclose(got, want, rtol=1e-11, atol=1e-12), (got, want)
-        helpers.assert_frames_match(results[2][0].cpu().numpy().T, fx["frame"], what="ticket 2 (no plan)")
+        helpers.assert_matches_golden_frame(results[2][0].cpu().numpy().T, "config3", fx["frame"], what="ticket 2 (no plan)")
     ds.close()
 
 
@@ -326,7 +326,7 @@ def test_a_column_list_writes_those_columns_and_no_others(name):
         with pytest.raises(KeyError):
             view.group_stats()
     rows, counts = ds.trace(rays, limit, plan=None)
-    helpers.assert_frames_match(rows.cpu().numpy().T, frame, what=f"{name} after the column plans")
+    helpers.assert_matches_golden_frame(rows.cpu().numpy().T, name, frame, what=f"{name} after the column plans")
     ds.close()
 
 
@@ -343,7 +343,7 @@ def test_plan_arguments_are_checked():
     with pytest.raises(ValueError):
         engine.RecordPlan(surfaces=tuple(range(9)))
     rows, counts = ds.trace(rays, 10, plan=None)
-    helpers.assert_frames_match(rows.cpu().numpy().T, fx["frame"], what="after the refused plans")
+    helpers.assert_matches_golden_frame(rows.cpu().numpy().T, "config2", fx["frame"], what="after the refused plans")
     ds.close()
 
 

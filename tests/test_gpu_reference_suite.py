@@ -1,6 +1,7 @@
 """The reference's own unit / integration tests for the path, re-stated against pyrayt_amd's API so
 that a maintainer can read them side by side (same scenarios, same analytic expectations, same
-tolerances -- np.allclose defaults unless the reference states otherwise):
+tolerances -- np.allclose defaults unless the reference states otherwise; where a CSG node's hit list is compared
+with its children's, engine against engine, the same doubles):
 
     test/integration_tests/int_test_thick_lenses.py:8-113      six thick-lens families
     test/test_tinygfx/test_g3d/test_csg.py:38-209              two offset unit spheres under each operation
@@ -11,6 +12,8 @@ tolerances -- np.allclose defaults unless the reference states otherwise):
 Everything below runs on the HIP engine (component.intersect / Material.trace / RayTracer.trace)."""
 import numpy as np
 import pytest
+
+import helpers
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -99,9 +102,9 @@ def test_csg_union(pyrayt):  # :38-92
     r_hits, _ = right.intersect(rays)
     l_hits, _ = left.intersect(rays)
     low, high = y_vals < -0.5, y_vals > -0.5
-    assert np.allclose(hits[:2, low], r_hits[:, low])
+    helpers.assert_same_bits(hits[:2, low], r_hits[:, low], what="the node's hits against its child's")
     assert np.all(surfaces[:2, low & ~missed] == right.get_id())
-    assert np.allclose(hits[:2, high], l_hits[:, high])
+    helpers.assert_same_bits(hits[:2, high], l_hits[:, high], what="the node's hits against its child's")
     assert np.all(surfaces[:2, high & ~missed] == left.get_id())
 
 
@@ -121,9 +124,9 @@ def test_csg_intersect(pyrayt):  # :99-150
     r_hits, _ = right.intersect(rays)
     l_hits, _ = left.intersect(rays)
     low, high = y_vals < -0.5, y_vals > -0.5
-    assert np.allclose(hits[:2, low], l_hits[:, low])
+    helpers.assert_same_bits(hits[:2, low], l_hits[:, low], what="the node's hits against its child's")
     assert np.all(surfaces[:2, low & ~missed] == left.get_id())
-    assert np.allclose(hits[:2, high], r_hits[:, high])
+    helpers.assert_same_bits(hits[:2, high], r_hits[:, high], what="the node's hits against its child's")
     assert np.all(surfaces[:2, high & ~missed] == right.get_id())
 
 
@@ -146,11 +149,11 @@ def test_csg_difference(pyrayt):  # :152-209
     assert np.allclose(hits, np.sort(hits, axis=0))
     l_hits, _ = left.intersect(rays)
     r_hits, _ = right.intersect(rays)
-    assert np.allclose(hits[:2, y_vals > 0], l_hits[:, y_vals > 0])
+    helpers.assert_same_bits(hits[:2, y_vals > 0], l_hits[:, y_vals > 0], what="the node's hits against its child's")
     assert np.all(surfaces[:2, (y_vals > 0) & ~missed] == left.get_id())
-    assert np.allclose(hits[[[0], [3]], bitten], l_hits[:, bitten])
+    helpers.assert_same_bits(hits[[[0], [3]], bitten], l_hits[:, bitten], what="the node's hits against its child's")
     assert np.all(surfaces[[[0], [3]], bitten] == left.get_id())
-    assert np.allclose(hits[1:3, bitten], r_hits[:, bitten])
+    helpers.assert_same_bits(hits[1:3, bitten], r_hits[:, bitten], what="the node's hits against its child's")
     assert np.all(surfaces[1:3, bitten] == right.get_id())
 
 
