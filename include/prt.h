@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -876,6 +876,73 @@ int prt_frame_paths(int device, const double* rows, int64_t ld, const int64_t* r
                     double id0, int64_t n_ids, double rays_per_source, int n_groups, int weight_column, int max_paths,
                     int32_t* row_node_out, int32_t* ray_node_out, int64_t* ray_last_row_out, int32_t* node_out,
                     int64_t* count_out, double* energy_out, int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Fresnel transmittance and polarisation of the frame (no counterpart upstream) ------------------------------------
+ * refract() (tinygfx/g3d/operations.py:110-162) bends a ray and does nothing else: the intensity column leaves the source
+ * at 100 and arrives at 100 however many glass surfaces the ray crossed.  This pass joins the frame by ray id, carries
+ * two field vectors per ray through every interface its rows describe and gives every row the share of the launch
+ * energy that is left.  The frame holds what Fresnel's equations need: the surface normal follows from the directions
+ * before and after, so none has to be recorded.
+ *
+ * Definitions.
+ * Frame: whole and generation-major.  Ids are integers in [id0, id0 + n_ids) and unique within a generation.  These are
+ *   prt_frame_optical_path's rules; a repeated id, an id out of range, and a row in generation g without one in g - 1
+ *   give PRT_ERR_ARG through the status word.
+ * Interface quantities: for a ray's row in generation g >= 1 and its row in g - 1, ui and ut are the two rows'
+ *   directions (x_tilt, y_tilt, z_tilt), normalised; ni, nt are their index values; S is row g - 1's surface.
+ * Interface kind, decided from the rows alone, with eps_dir = 1e-12:
+ *   lossless: S is in the caller's list of lossless surfaces (ideally coated; at most 64 ids).  The ray is treated as
+ *     one of the kinds below, but with all amplitude coefficients of magnitude 1 (ts = tp = 1).
+ *   undeviated: |ui - ut|^2 <= eps_dir and ni == nt.  The field and the transmittance pass unchanged.
+ *   refraction: ni != nt.  N = ni ui - nt ut, normalised and oriented so that ci = ui.N > 0; ct = ut.N.  If not
+ *     (ci > 0 and ct > 0) -- which covers values that are not finite -- the interface is invalid.  Otherwise, with
+ *     a = ni ci, b = nt ct, c = nt ci, d = ni ct, the power-normalised amplitude coefficients are
+ *     ts = 2 sqrt(a b) / (a + b) and tp = 2 sqrt(a b) / (c + d); ts^2, tp^2 are the power transmittances T_s, T_p.
+ *   reflection: ni == nt and the ray is deviated: mirrors, and total internal reflection as the reference writes it (it
+ *     keeps n1, operations.py:159-161).  N = ui - ut, normalised.  An ideal reflector: rs = -1, rp = +1.  The
+ *     retardance of total internal reflection and of metals is NOT modelled; such interfaces are counted.
+ *   invalid, besides: a direction that cannot be normalised (zero or not finite), an index that is not finite and > 0.
+ * eps_dir = 1e-12: two rows of one undeviated ray differ by roundings, |ui - ut|^2 ~ 1e-31, and a real deviation below
+ *   1e-6 rad is no optical interface, so any threshold between works for `undeviated`.  For normal incidence the choice
+ *   balances two errors.  Below the threshold s and p are not told apart, which is wrong by the relative difference of
+ *   ts and tp, O(sin^2 theta) <= 1e-12: the suite's own bar.  Above it s = ui x N is a difference of products of size 1
+ *   with a result of size sin theta, so its direction is good to 1e-16 / sin theta <= 1e-10 at the threshold and to
+ *   1e-14 from sin theta = 0.01 on; within the transverse plane that error is harmless (it multiplies ts - tp), along
+ *   the ray it is what |E.ut| / |E| can reach.
+ * Field update: s = ui x N normalised, pi = ui x s, pt = ut x s; E' = ts (E.s) s + tp (E.pi) pt, for a reflection with
+ *   rs, rp.  At normal incidence (|ui x N|^2 <= eps_dir) s and p coincide: refraction E' = ts E, reflection E' = -E.
+ * Field state and transmittance: each ray carries two real field vectors Ea, Eb.
+ *   Unpolarised input (the default): at generation 0 they are an orthonormal pair perpendicular to the launch
+ *     direction u0: Ea = u0 x e normalised, with e the world axis of the smallest |u0| component (ties to the first),
+ *     Eb = u0 x Ea.  T = (|Ea|^2 + |Eb|^2) / 2.
+ *   Polarised input (a world vector v, normalised by the call): Ea = v minus its component along u0, normalised when
+ *     its squared length is above eps_dir, Eb = 0.  T = |Ea|^2.  A ray with v parallel to u0 is invalid.
+ *   Generation-0 rows have T = 1.  A row's T is computed from the updated fields by the formula above at a refraction
+ *   that is not lossless; at every other interface (undeviated, reflection, lossless: all coefficients of magnitude 1)
+ *   it is the previous row's T handed on as it is, since a rotation keeps |E| only to rounding: a mirror or a coated
+ *   surface leaves T unchanged to the bit.
+ *   An invalid interface makes the ray's T and field NaN from that row on, and the ray is counted once.
+ * Arithmetic: every step is rounded on its own (no FMA contraction), dot products as (x x' + y y') + z z', in the order
+ *   the kernel writes them, so that a numpy restatement can follow it operation for operation.
+ * Counters: interfaces that are reflections, interfaces whose S is in the lossless list (of any kind), undeviated
+ *   interfaces, invalid rays.
+ *
+ * prt_frame_fresnel: polarization HOST 3 doubles (finite, not zero) or NULL for unpolarised input; lossless HOST
+ * n_lossless <= 64 surface ids.  Out, overwritten: transmittance_out DEVICE n_rows doubles; field_out DEVICE (6, n_rows)
+ * doubles, Ea then Eb by component, or NULL; record_out HOST 4 int64: the counters.  workspace:
+ * prt_frame_fresnel_workspace_bytes(n_rows, n_ids) device bytes (-1 for arguments the call would refuse): per id the
+ * fields (six planes), its previous row and a generation stamp, 60 bytes.  Caps: n_ids in [1, 2^31], a generation's
+ * rows fit one launch, at most 64 lossless surfaces; PRT_ERR_ARG otherwise, never a truncated result, and nothing is
+ * ever written out of bounds.  One launch per generation in order on the stream, one row a thread; no two lanes touch
+ * one ray's state, there are no floating-point atomics and no floating-point sums across rays, the only atomics are the
+ * stamp and the integer counters (one add per workgroup): every output is the same, bit for bit, on every run, and
+ * unchanged by any permutation of the rows inside a generation apart from being permuted with them.  All arguments are
+ * checked before a device is touched.  Stream-ordered; the call reads the status word and the counters back and so
+ * returns when the stream has reached its end. */
+int64_t prt_frame_fresnel_workspace_bytes(int64_t n_rows, int64_t n_ids);
+int prt_frame_fresnel(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation, int n_generations,
+                      double id0, int64_t n_ids, const double* polarization, const int64_t* lossless, int n_lossless,
+                      double* transmittance_out, double* field_out, int64_t* record_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

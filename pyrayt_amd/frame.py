@@ -1054,6 +1054,70 @@ class DeviceFrame:
                      row_node=row_node, ray_node=ray_node, ray_last_row=ray_last_row, id0=id0,
                      n_bad_weight=int(record[2]), n_rays=int(record[1]), ids=ids)
 
+    def fresnel(self, polarization=None, lossless=(), fields=False):
+        """Fresnel transmittance and polarisation of every ray, joined by ray id on the device: a ``Fresnel`` with per row
+        the share ``transmittance`` of the ray's launch energy that is left when it runs that row's segment -- after
+        every interface before it -- and, with ``fields``, the two field vectors carried there.
+
+        An interface is read off two consecutive rows of a ray: the directions and indices before and after, and the
+        surface of the earlier row; the normal follows from the two directions.  Unequal indices are a refraction with
+        the power-normalised coefficients ts, tp of an uncoated surface; equal indices with a deviated ray are an ideal
+        reflection (rs = -1, rp = +1: mirrors, and total internal reflection as the engine writes it; its retardance is
+        not modelled); an undeviated ray passes as it is.  ``lossless``: surfaces (ids or objects with ``get_id()`` /
+        ``surface_ids``, at most 64 ids) taken as ideally coated: the field is still rotated, with coefficients of
+        magnitude 1.  ``polarization``: None for unpolarised input (two orthogonal fields per ray, T their mean), or a
+        world vector: each ray starts with its component perpendicular to the launch direction, normalised.  An
+        interface the rows cannot describe (a direction or index that is not finite, a transmitted ray on the wrong side)
+        makes the ray NaN from there on and counts in ``n_invalid``.  include/prt.h states the definitions.
+
+        One HIP launch per generation (``prt_frame_fresnel``).  Ids must be integers, unique within a generation.  Needs
+        the whole frame of a trace, like ``optical_path``."""
+        import torch
+
+        from . import engine
+
+        try:
+            self._need_whole("fresnel", columns=_FRESNEL_COLUMNS)
+        except KeyError as error:
+            raise ValueError(f"fresnel: {error.args[0]}") from None
+        ids_lossless = sorted(_lossless_ids(lossless))
+        if len(ids_lossless) > 64:
+            raise ValueError(f"fresnel: at most 64 lossless surfaces (got {len(ids_lossless)})")
+        v = None
+        if polarization is not None:
+            try:
+                v = np.ascontiguousarray(polarization, dtype=np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                v = np.zeros(0)
+            if v.shape != (3,) or not np.all(np.isfinite(v)) or not np.any(v != 0):
+                raise ValueError("fresnel: polarization is None or a world vector of three finite numbers, not all zero")
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        n_rows = rows.shape[1]
+        if n_rows:
+            ids = rows[_INDEX["id"]]
+            id0, top = (float(x) for x in torch.stack([ids.min(), ids.max()]).cpu())
+            if not (np.isfinite(id0) and np.isfinite(top)):
+                raise ValueError("fresnel: an id is not an integer in the frame's id range")
+        else:
+            id0 = top = 0.0
+        n_ids = int(top - id0) + 1
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_fresnel_workspace_bytes(n_rows, n_ids))), dtype=torch.uint8,
+                           device=dev)
+        transmittance = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        field = torch.empty((6, n_rows), dtype=torch.float64, device=dev) if fields else None
+        record = np.zeros(4, dtype=np.int64)
+        counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
+        coated = np.ascontiguousarray(ids_lossless, dtype=np.int64)
+        engine._check(lib.prt_frame_fresnel(
+            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
+            len(counts), id0, n_ids, None if v is None else v.ctypes.data, coated.ctypes.data if len(coated) else None,
+            len(coated), transmittance.data_ptr() if n_rows else None,
+            field.data_ptr() if field is not None and n_rows else None, record.ctypes.data, work.data_ptr(),
+            engine._stream_ptr(torch, dev)))
+        return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -1167,6 +1231,7 @@ _PATH_COLUMNS = ("index", "id", "surface", "generation", "x0", "y0", "z0", "x1",
 _JOIN_COLUMNS = tuple(name for name in _PATH_COLUMNS if name != "index")  # (what the ray-aberration passes read)
 _MTF_COLUMNS = ("x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")  # (what the MTF reads of every ray)
 _PATHS_COLUMNS = ("generation", "intensity", "id", "surface", "x_tilt", "y_tilt", "z_tilt")  # (what paths() reads)
+_FRESNEL_COLUMNS = ("generation", "intensity", "index", "id", "surface", "x_tilt", "y_tilt", "z_tilt")  # (fresnel())
 _ENERGY_SHAPES = {"circle": 0, "square": 1, "slit_e1": 2, "slit_e2": 3}  # (PRT_ENERGY_* of include/prt.h)
 
 
@@ -1641,6 +1706,68 @@ class Paths:
                     n_bad_weight=self.n_bad_weight, n_rays=self.n_rays, launched=self.launched)
         out.node_map = node_map
         return out
+
+
+class Fresnel:
+    """What ``DeviceFrame.fresnel`` returns.  ``transmittance``: a device tensor, per row of the frame the share of the
+    ray's launch energy left on that row's segment (1 at generation 0; NaN for a ray past an invalid interface);
+    ``field``: None, or a device (6, n_rows) tensor, Ea then Eb by component; the counters ``n_reflections`` (interfaces
+    with equal indices and a deviated ray: their retardance is not modelled), ``n_lossless`` (interfaces at a surface of
+    the ``lossless`` list), ``n_undeviated`` and ``n_invalid`` (rays); ``polarization`` and ``lossless`` as given."""
+
+    def __init__(self, frame, transmittance, field, record, polarization=None, lossless=()):
+        self.frame, self.transmittance, self.field = frame, transmittance, field
+        self.n_reflections, self.n_lossless, self.n_undeviated, self.n_invalid = (int(v) for v in record)
+        self.polarization, self.lossless = polarization, tuple(lossless)
+        self._paths = {}
+
+    def to_pandas(self):
+        """One line per row of the frame: generation, id, surface, intensity, transmittance (and the fields)."""
+        from . import engine
+
+        table = pd.DataFrame({name: engine.to_host(self.frame[name]) for name in ("generation", "id", "surface", "intensity")})
+        table["transmittance"] = engine.to_host(self.transmittance)
+        if self.field is not None:
+            for k, name in enumerate(("ea_x", "ea_y", "ea_z", "eb_x", "eb_y", "eb_z")):
+                table[name] = engine.to_host(self.field[k])
+        return table
+
+    def apply(self):
+        """A new whole frame, a copy of the rows with ``intensity`` replaced by ``intensity * transmittance`` (one
+        multiply per row), with the same ``rows_per_generation``: every pass that weighs by intensity then sees the
+        losses.  The frame the transmittance was computed on is left as it is."""
+        rows = self.frame.rows.clone()
+        rows[_INDEX["intensity"]] = self.frame.rows[_INDEX["intensity"]] * self.transmittance
+        return DeviceFrame(rows, self.frame.rows_per_generation, self.frame.written)
+
+    def transmission(self, surface, rays_per_source=None):
+        """Per source (``id // rays_per_source``; None: one), the energy that arrives at ``surface`` (an id or an object
+        with ``get_id()``) in the applied frame over the energy launched -- the intensity of the generation-0 rows of
+        the original frame.  Both are ``paths()``' exact integer sums, so the ratio is the same bits on every run."""
+        wanted = _surface_id(surface)
+        if rays_per_source not in self._paths:
+            options = dict(weights="intensity", rays_per_source=rays_per_source)
+            self._paths[rays_per_source] = (self.apply().paths(**options), self.frame.paths(**options))
+        applied, original = self._paths[rays_per_source]
+        arrived = applied.energy_through[:, applied.surface == wanted].sum(axis=1)
+        launched = original.energy_through[:, original.depth == 0].sum(axis=1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return arrived / launched
+
+
+def _lossless_ids(items):
+    """Surface ids of ``lossless``: ids, objects with ``get_id()``, components with ``surface_ids``, or several of them."""
+    if items is None:
+        return set()
+    if isinstance(items, (str, bytes)) or hasattr(items, "get_id") or hasattr(items, "surface_ids") or not hasattr(items, "__iter__"):
+        items = (items,)
+    out = set()
+    for item in items:
+        if hasattr(item, "surface_ids"):
+            out.update(int(sid) for sid, _ in item.surface_ids)
+        else:
+            out.add(int(_surface_id(item)))
+    return out
 
 
 def _surface_id(item):
