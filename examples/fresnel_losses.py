@@ -44,8 +44,11 @@ def main():
     losses = frame.fresnel()
     report("uncoated (Fresnel)", losses.apply(), losses.transmission(detector, rays_per_source=rays), detector, rays)
     report("lens declared lossless", coated.apply(), coated.transmission(detector, rays_per_source=rays), detector, rays)
-    print(f"interfaces: {losses.n_reflections} reflections (retardance not modelled), {losses.n_undeviated} undeviated, "
+    print(f"interfaces: {losses.n_reflections} reflections (ideal unless coated), {losses.n_undeviated} undeviated, "
           f"{losses.n_invalid} invalid rays; {coated.n_lossless} at coated surfaces")
+    layer = pyrayt.materials.Coating.quarter_wave(1.38, float(frame["wavelength"][0]))  # (MgF2, a quarter wave thick)
+    quarter = frame.fresnel(coatings={lens: layer})
+    report("quarter-wave MgF2", quarter.apply(), quarter.transmission(detector, rays_per_source=rays), detector, rays)
     polarised = frame.fresnel(polarization=(0.0, 1.0, 0.0)).transmission(detector, rays_per_source=rays)
     print(f"input polarised along y: throughput {polarised[0]:.4f} / {polarised[1]:.4f}")
 

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -900,7 +900,8 @@ int prt_frame_paths(int device, const double* rows, int64_t ld, const int64_t* r
  *     ts = 2 sqrt(a b) / (a + b) and tp = 2 sqrt(a b) / (c + d); ts^2, tp^2 are the power transmittances T_s, T_p.
  *   reflection: ni == nt and the ray is deviated: mirrors, and total internal reflection as the reference writes it (it
  *     keeps n1, operations.py:159-161).  N = ui - ut, normalised.  An ideal reflector: rs = -1, rp = +1.  The
- *     retardance of total internal reflection and of metals is NOT modelled; such interfaces are counted.
+ *     retardance of total internal reflection and of metals is NOT modelled here (prt_frame_fresnel_coated models it at
+ *     the surfaces the caller coats); such interfaces are counted.
  *   invalid, besides: a direction that cannot be normalised (zero or not finite), an index that is not finite and > 0.
  * eps_dir = 1e-12: two rows of one undeviated ray differ by roundings, |ui - ut|^2 ~ 1e-31, and a real deviation below
  *   1e-6 rad is no optical interface, so any threshold between works for `undeviated`.  For normal incidence the choice
@@ -943,6 +944,83 @@ int64_t prt_frame_fresnel_workspace_bytes(int64_t n_rows, int64_t n_ids);
 int prt_frame_fresnel(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation, int n_generations,
                       double id0, int64_t n_ids, const double* polarization, const int64_t* lossless, int n_lossless,
                       double* transmittance_out, double* field_out, int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Thin-film coatings, metals and the phase of total internal reflection in the Fresnel pass -------------------------
+ * prt_frame_fresnel knows the bare dielectric interface and the ideal surface.  prt_frame_fresnel_coated is the same
+ * pass with complex fields and, at the surfaces the caller coats, the coefficients of a layer stack.  prt_frame_fresnel
+ * and its outputs are left exactly as they are.
+ *
+ * Definitions.
+ * Coating: belongs to one or more surface ids and has three parts.  layers: 0 to 16 pairs (material, thickness), listed
+ *   from the AMBIENT side to the SUBSTRATE side; thickness in the unit of the frame's wavelength column (micrometres, as
+ *   the Sellmeier glasses take them).  ambient: a material, default the constant 1.0.  substrate: a material or none.
+ *   A material is a real or complex constant n + ik, with k >= 0 absorbing (fields as exp(-i omega t)), or a function of
+ *   the wavelength.  The host evaluates materials on the distinct wavelengths of the frame; their values travel as a
+ *   table, and the kernel looks a row's wavelength up in it exactly.
+ * Coated interface: a refraction or a reflection (the kinds of prt_frame_fresnel, decided as there) at a surface S that
+ *   has a coating.  An undeviated ray passes a coated surface as it passes any other.  The wavelength is that of the
+ *   ray's row in generation g - 1.
+ * Which side the ray comes from: the ray arrives from the ambient side iff its ni equals the real part of ambient at its
+ *   wavelength; an exact comparison.  Otherwise it arrives from the substrate side and the layers are traversed in
+ *   reverse.
+ * The far medium: refraction (ni != nt): nt from the rows.  Reflection (ni == nt, deviated) from the ambient side:
+ *   substrate; if there is none the interface is invalid.  Reflection from the substrate side: ambient.  So a bare face
+ *   of total internal reflection is a coating without layers and with ambient 1.0 on a prism face; an aluminium mirror
+ *   is a coating without layers and with substrate 1.2 + 7.0i; a protected-silver mirror is one layer over a complex
+ *   substrate.
+ * Coefficients: the Snell invariant is ni sin thetai, with N and cos thetai = ui.N as prt_frame_fresnel has them and
+ *   sin^2 thetai = |ui x N|^2.  Per layer j, cos thetaj = sqrt(1 - (ni sin thetai / nj)^2): the square root is complex,
+ *   on the branch with Im(nj cos thetaj) >= 0; the far medium's cosine likewise.  The phase is
+ *   deltaj = 2 pi nj dj cos thetaj / lambda.  The tilted admittances are eta_s = n cos theta and eta_p = n / cos theta.
+ *   Per polarisation, (B, C) = M_1 ... M_L (1, eta_far) with the characteristic matrix of a layer
+ *   M_j = [[cos deltaj, -i sin deltaj / eta_j], [-i eta_j sin deltaj, cos deltaj]], layer 1 next to the near medium;
+ *   r = (eta_near B - C) / (eta_near B + C), t = 2 eta_near / (eta_near B + C), eta_near of the real ni.
+ *   Transmitted coefficients are power-normalised, as ts, tp of prt_frame_fresnel are: ts, tp = t sqrt(Re eta_far /
+ *   Re eta_near) of their polarisation; then |E|^2 carries power and the phase is kept.  Reflected coefficients are
+ *   rs = r_s and rp = -r_p: the signs in the basis s, pi, pt, in which a substrate of infinite |n| gives the ideal
+ *   mirror of prt_frame_fresnel, rs = -1, rp = +1.  Without layers ts, tp are those of prt_frame_fresnel.
+ * Fields: Ea, Eb are complex 3-vectors.  The field update is prt_frame_fresnel's with complex cs, cp:
+ *   E' = cs (E.s) s + cp (E.pi) pt, the dot products without conjugation (s, pi, pt are real); at normal incidence
+ *   E' = ts E, respectively E' = rs E.  T = (|Ea|^2 + |Eb|^2) / 2, respectively |Ea|^2, with complex moduli.  T is
+ *   computed from the fields at every coated interface.
+ * Surfaces without a coating follow prt_frame_fresnel's rules and arithmetic, operation for operation, on the real and
+ *   on the imaginary parts, `lossless` and the handing-on of T included; |E|^2 is the real parts' sum plus the imaginary
+ *   parts' sum.  Without coatings and with a real polarization, T and the real parts are prt_frame_fresnel's bits and the
+ *   imaginary parts are zero.
+ * Polarised input: polarization is a complex 3-vector, (0, 1, i) for circular input.  It is normalised with the complex
+ *   norm; the transverse part is taken as in prt_frame_fresnel, on both parts, and normalised with the complex norm.
+ * Invalid interfaces, besides prt_frame_fresnel's: a reflection that needs a substrate and has none; a NaN or
+ *   non-positive (or infinite) wavelength at a coated interface; a table value of the far medium or of a layer crossed
+ *   that is not finite, or coefficients that are not finite.  The ray is NaN from there on and counted once.
+ * Refused calls: a row's wavelength that is not in the table at a coated interface sets a status bit and the call
+ *   returns PRT_ERR_ARG: the caller's table was wrong.
+ * Counters: prt_frame_fresnel's four, then coated interfaces, then interfaces of total internal reflection: a valid
+ *   coated reflection whose far index is real and below the Snell invariant, so that |r| = 1 by construction.
+ * Caps, PRT_ERR_ARG beyond them, never a truncated result: 64 coated surface ids, 16 coatings, 16 layers, 256 distinct
+ *   wavelengths (a continuous Monte-Carlo spectrum is out of scope).
+ *
+ * prt_frame_fresnel_coated: the arguments of prt_frame_fresnel, except: polarization HOST 6 doubles (real part, then
+ * imaginary part) or NULL.  The HOST tables: coated_surfaces n_coated <= 64 surface ids, none listed twice, none also
+ * lossless; surface_coating n_coated int32, the coating of each, in [0, n_coatings); n_coatings <= 16; layer_counts
+ * n_coatings int32 in [0, 16]; has_substrate n_coatings int32; thicknesses (n_coatings, 16) doubles, finite and >= 0 for
+ * the layers counted; wavelengths n_wavelengths <= 256 doubles, finite, > 0, ascending and distinct; indices
+ * (n_coatings, 18, n_wavelengths, 2) doubles: per coating the slots ambient, layer 0..15, substrate, per wavelength
+ * (real, imaginary).  Out, overwritten: transmittance_out DEVICE n_rows doubles; field_out DEVICE (12, n_rows) doubles or
+ * NULL: the real parts of Ea then Eb by component, then the imaginary parts; record_out HOST 6 int64: the counters.
+ * workspace: prt_frame_fresnel_coated_workspace_bytes(n_rows, n_ids) device bytes (-1 for arguments the call would
+ * refuse): the tables at their caps, and per id the fields (twelve planes), its previous row and a generation stamp, 108
+ * bytes.  The guarantees of prt_frame_fresnel hold: one launch per generation in order on the stream, one row a thread,
+ * no two lanes touch one ray's state, no floating-point atomics and no sums across rays, nothing read or written out of
+ * bounds on a refused frame, every output the same bits on every run and under any permutation of a generation's rows.
+ * All arguments, the tables included, are checked before a device is touched. */
+int64_t prt_frame_fresnel_coated_workspace_bytes(int64_t n_rows, int64_t n_ids);
+int prt_frame_fresnel_coated(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                             int n_generations, double id0, int64_t n_ids, const double* polarization,
+                             const int64_t* lossless, int n_lossless, const int64_t* coated_surfaces,
+                             const int32_t* surface_coating, int n_coated, int n_coatings, const int32_t* layer_counts,
+                             const int32_t* has_substrate, const double* thicknesses, const double* wavelengths,
+                             int n_wavelengths, const double* indices, double* transmittance_out, double* field_out,
+                             int64_t* record_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

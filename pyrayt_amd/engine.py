@@ -182,6 +182,9 @@ def _declare(lib):
                                     c_p, c_p, c_p, c_p, c_p, c_p]),
         "prt_frame_fresnel_workspace_bytes": (c_i64, [c_i64, c_i64]),
         "prt_frame_fresnel": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_fresnel_coated_workspace_bytes": (c_i64, [c_i64, c_i64]),
+        "prt_frame_fresnel_coated": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_p, c_int, c_p, c_p, c_int,
+                                             c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -209,6 +212,7 @@ EXPORTED_SYMBOLS = (
     "prt_frame_launch_index", "prt_frame_ray_aberrations_workspace_bytes", "prt_frame_ray_aberrations",
     "prt_frame_energy_workspace_bytes", "prt_frame_energy", "prt_frame_paths_workspace_bytes", "prt_frame_paths",
     "prt_frame_fresnel_workspace_bytes", "prt_frame_fresnel",
+    "prt_frame_fresnel_coated_workspace_bytes", "prt_frame_fresnel_coated",
 )
 
 

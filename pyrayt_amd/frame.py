@@ -1054,7 +1054,7 @@ class DeviceFrame:
                      row_node=row_node, ray_node=ray_node, ray_last_row=ray_last_row, id0=id0,
                      n_bad_weight=int(record[2]), n_rays=int(record[1]), ids=ids)
 
-    def fresnel(self, polarization=None, lossless=(), fields=False):
+    def fresnel(self, polarization=None, lossless=(), fields=False, coatings=None):
         """Fresnel transmittance and polarisation of every ray, joined by ray id on the device: a ``Fresnel`` with per row
         the share ``transmittance`` of the ray's launch energy that is left when it runs that row's segment -- after
         every interface before it -- and, with ``fields``, the two field vectors carried there.
@@ -1070,19 +1070,38 @@ class DeviceFrame:
         interface the rows cannot describe (a direction or index that is not finite, a transmitted ray on the wrong side)
         makes the ray NaN from there on and counts in ``n_invalid``.  include/prt.h states the definitions.
 
-        One HIP launch per generation (``prt_frame_fresnel``).  Ids must be integers, unique within a generation.  Needs
-        the whole frame of a trace, like ``optical_path``."""
+        ``coatings``: a mapping from a surface (an id, or an object with ``get_id()`` / ``surface_ids``) to a
+        ``pyrayt_amd.materials.Coating``: a thin-film stack, a metal (a complex substrate) or a bare face whose total
+        internal reflection keeps its phase.  At such a surface the complex amplitude coefficients of the stack replace
+        the rules above (characteristic matrices, include/prt.h), the fields are complex and T is computed from them.
+        The materials are evaluated on the distinct wavelengths of the frame, at most 256: a continuous Monte-Carlo
+        spectrum is out of scope.  At most 64 coated surface ids, 16 coatings of 16 layers.  ``polarization`` may then be
+        a complex vector, ``(0, 1, 1j)`` for circular input.  With ``coatings=None`` and a real ``polarization`` the call
+        is the one described above, unchanged; otherwise ``field`` is a (6, n) complex128 tensor, the surfaces without
+        a coating follow the rules above with the same arithmetic, and the result counts ``n_coated`` and ``n_tir``.
+
+        One HIP launch per generation (``prt_frame_fresnel``, ``prt_frame_fresnel_coated``).  Ids must be integers,
+        unique within a generation.  Needs the whole frame of a trace, like ``optical_path``."""
         import torch
 
         from . import engine
 
+        complex_input = False
+        if polarization is not None:
+            try:
+                complex_input = bool(np.iscomplexobj(np.asarray(polarization)))
+            except (TypeError, ValueError):
+                complex_input = False
+        is_coated = coatings is not None or complex_input
         try:
-            self._need_whole("fresnel", columns=_FRESNEL_COLUMNS)
+            self._need_whole("fresnel", columns=_FRESNEL_COATED_COLUMNS if coatings else _FRESNEL_COLUMNS)
         except KeyError as error:
             raise ValueError(f"fresnel: {error.args[0]}") from None
         ids_lossless = sorted(_lossless_ids(lossless))
         if len(ids_lossless) > 64:
             raise ValueError(f"fresnel: at most 64 lossless surfaces (got {len(ids_lossless)})")
+        if is_coated:
+            return self._fresnel_coated(polarization, ids_lossless, fields, coatings or {})
         v = None
         if polarization is not None:
             try:
@@ -1117,6 +1136,92 @@ class DeviceFrame:
             field.data_ptr() if field is not None and n_rows else None, record.ctypes.data, work.data_ptr(),
             engine._stream_ptr(torch, dev)))
         return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
+
+    def _fresnel_coated(self, polarization, ids_lossless, fields, coatings):
+        """``fresnel()`` through ``prt_frame_fresnel_coated``: complex fields, the coated surfaces' tables."""
+        import torch
+
+        from . import engine
+        from .materials import Coating
+
+        if not hasattr(coatings, "items"):
+            raise ValueError("fresnel: coatings is a mapping from a surface to a Coating")
+        stacks, surface_coating = [], {}
+        for key, coating in coatings.items():
+            if not isinstance(coating, Coating):
+                raise ValueError(f"fresnel: coatings maps a surface to a Coating (got {coating!r})")
+            known = [k for k, other in enumerate(stacks) if other is coating]
+            if not known:
+                stacks.append(coating)
+            for sid in sorted(_lossless_ids(key)):
+                if sid in surface_coating:
+                    raise ValueError(f"fresnel: surface {sid} is given two coatings")
+                surface_coating[sid] = known[0] if known else len(stacks) - 1
+        both = sorted(set(surface_coating) & set(ids_lossless))
+        if both:
+            raise ValueError(f"fresnel: surfaces {both} are both lossless and coated")
+        if len(surface_coating) > 64:
+            raise ValueError(f"fresnel: at most 64 coated surfaces (got {len(surface_coating)})")
+        if len(stacks) > 16:
+            raise ValueError(f"fresnel: at most 16 coatings (got {len(stacks)})")
+        v = None
+        if polarization is not None:
+            try:
+                v = np.asarray(polarization, dtype=np.complex128).reshape(-1)
+            except (TypeError, ValueError):
+                v = np.zeros(0, dtype=np.complex128)
+            if v.shape != (3,) or not np.all(np.isfinite(v)) or not np.any(v != 0):
+                raise ValueError("fresnel: polarization is None or a world vector of three finite numbers, not all zero")
+        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        dev = rows.device
+        n_rows = rows.shape[1]
+        if n_rows:
+            ids = rows[_INDEX["id"]]
+            id0, top = (float(x) for x in torch.stack([ids.min(), ids.max()]).cpu())
+            if not (np.isfinite(id0) and np.isfinite(top)):
+                raise ValueError("fresnel: an id is not an integer in the frame's id range")
+        else:
+            id0 = top = 0.0
+        n_ids = int(top - id0) + 1
+        # the materials on the distinct wavelengths of the frame (as DeviceScene.ensure_tables does for table glasses)
+        wavelengths = np.zeros(0)
+        if stacks and n_rows:
+            wavelengths = engine.to_host(torch.unique(rows[_INDEX["wavelength"]])).astype(np.float64)
+            wavelengths = np.ascontiguousarray(wavelengths[np.isfinite(wavelengths) & (wavelengths > 0)])
+            if len(wavelengths) > 256:
+                raise ValueError(f"fresnel: at most 256 distinct wavelengths with coatings (got {len(wavelengths)})")
+        table = np.ones((max(len(stacks), 1), 18, max(len(wavelengths), 1)), dtype=np.complex128)
+        thickness = np.zeros((max(len(stacks), 1), 16))
+        for k, coating in enumerate(stacks):
+            if len(wavelengths):
+                table[k] = coating.table(wavelengths)
+            thickness[k, :len(coating.layers)] = [d for _, d in coating.layers]
+        table = np.ascontiguousarray(table)
+        layer_counts = np.array([len(c.layers) for c in stacks] or [0], dtype=np.int32)
+        has_substrate = np.array([c.substrate is not None for c in stacks] or [0], dtype=np.int32)
+        coated_ids = np.array(sorted(surface_coating) or [0], dtype=np.int64)
+        coating_of = np.array([surface_coating[sid] for sid in sorted(surface_coating)] or [0], dtype=np.int32)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_fresnel_coated_workspace_bytes(n_rows, n_ids))),
+                           dtype=torch.uint8, device=dev)
+        transmittance = torch.empty(n_rows, dtype=torch.float64, device=dev)
+        planes = torch.empty((12, n_rows), dtype=torch.float64, device=dev) if fields else None
+        record = np.zeros(6, dtype=np.int64)
+        counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
+        lossless_ids = np.ascontiguousarray(ids_lossless, dtype=np.int64)
+        v6 = None if v is None else np.ascontiguousarray(np.concatenate([v.real, v.imag]))
+        engine._check(lib.prt_frame_fresnel_coated(
+            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
+            len(counts), id0, n_ids, None if v6 is None else v6.ctypes.data,
+            lossless_ids.ctypes.data if len(lossless_ids) else None, len(lossless_ids), coated_ids.ctypes.data,
+            coating_of.ctypes.data, len(surface_coating), len(stacks), layer_counts.ctypes.data, has_substrate.ctypes.data,
+            thickness.ctypes.data, wavelengths.ctypes.data if len(wavelengths) else None, len(wavelengths),
+            table.view(np.float64).ctypes.data, transmittance.data_ptr() if n_rows else None,
+            planes.data_ptr() if planes is not None and n_rows else None, record.ctypes.data, work.data_ptr(),
+            engine._stream_ptr(torch, dev)))
+        field = torch.complex(planes[:6], planes[6:]) if planes is not None else None
+        return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless),
+                       coatings=dict(coatings))
 
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
@@ -1232,6 +1337,7 @@ _JOIN_COLUMNS = tuple(name for name in _PATH_COLUMNS if name != "index")  # (wha
 _MTF_COLUMNS = ("x1", "y1", "z1", "x_tilt", "y_tilt", "z_tilt")  # (what the MTF reads of every ray)
 _PATHS_COLUMNS = ("generation", "intensity", "id", "surface", "x_tilt", "y_tilt", "z_tilt")  # (what paths() reads)
 _FRESNEL_COLUMNS = ("generation", "intensity", "index", "id", "surface", "x_tilt", "y_tilt", "z_tilt")  # (fresnel())
+_FRESNEL_COATED_COLUMNS = _FRESNEL_COLUMNS + ("wavelength",)  # (fresnel(coatings=...))
 _ENERGY_SHAPES = {"circle": 0, "square": 1, "slit_e1": 2, "slit_e2": 3}  # (PRT_ENERGY_* of include/prt.h)
 
 
@@ -1713,13 +1819,47 @@ class Fresnel:
     ray's launch energy left on that row's segment (1 at generation 0; NaN for a ray past an invalid interface);
     ``field``: None, or a device (6, n_rows) tensor, Ea then Eb by component; the counters ``n_reflections`` (interfaces
     with equal indices and a deviated ray: their retardance is not modelled), ``n_lossless`` (interfaces at a surface of
-    the ``lossless`` list), ``n_undeviated`` and ``n_invalid`` (rays); ``polarization`` and ``lossless`` as given."""
+    the ``lossless`` list), ``n_undeviated`` and ``n_invalid`` (rays); ``polarization`` and ``lossless`` as given.
+    From ``fresnel(coatings=...)`` or a complex ``polarization``: ``field`` is complex128, and ``n_coated`` (interfaces
+    at a coated surface) and ``n_tir`` (of them, total internal reflections: a real far index below the Snell invariant)
+    are counted as well; both are 0 otherwise."""
 
-    def __init__(self, frame, transmittance, field, record, polarization=None, lossless=()):
+    def __init__(self, frame, transmittance, field, record, polarization=None, lossless=(), coatings=None):
         self.frame, self.transmittance, self.field = frame, transmittance, field
-        self.n_reflections, self.n_lossless, self.n_undeviated, self.n_invalid = (int(v) for v in record)
-        self.polarization, self.lossless = polarization, tuple(lossless)
+        self.n_reflections, self.n_lossless, self.n_undeviated, self.n_invalid = (int(v) for v in record[:4])
+        self.n_coated, self.n_tir = (int(v) for v in record[4:6]) if len(record) >= 6 else (0, 0)
+        self.polarization, self.lossless, self.coatings = polarization, tuple(lossless), coatings
         self._paths = {}
+
+    def stokes(self, rows=None):
+        """Per row (``rows``: an index tensor or slice; None: all) the Stokes parameters S0..S3 of ``Ea`` -- the field of
+        polarised input -- as a (4, n) device tensor.  The transverse basis is the one launch fields use: for the row's
+        direction u, e1 = u x e normalised with e the world axis of the smallest |u| component (ties to the first),
+        e2 = u x e1; with E1 = Ea.e1, E2 = Ea.e2: S0 = |E1|^2 + |E2|^2, S1 = |E1|^2 - |E2|^2, S2 = 2 Re(conj(E1) E2),
+        S3 = 2 Im(conj(E1) E2).  Needs ``fields=True``."""
+        import torch
+
+        if self.field is None:
+            raise ValueError("stokes: the fields were not kept (fresnel(fields=True))")
+        pick = slice(None) if rows is None else rows
+        u = torch.stack([self.frame[name] for name in ("x_tilt", "y_tilt", "z_tilt")])[:, pick]
+        u = u / torch.sqrt((u * u).sum(dim=0))
+        magnitude = u.abs()
+        axis = torch.zeros(u.shape[1], dtype=torch.long, device=u.device)
+        least = magnitude[0].clone()
+        second = magnitude[1] < least
+        axis[second] = 1
+        least = torch.where(second, magnitude[1], least)
+        axis[magnitude[2] < least] = 2
+        e = torch.nn.functional.one_hot(axis, 3).T.to(u.dtype)
+        e1 = torch.linalg.cross(u, e, dim=0)
+        e1 = e1 / torch.sqrt((e1 * e1).sum(dim=0))
+        e2 = torch.linalg.cross(u, e1, dim=0)
+        ea = self.field[:3][:, pick].to(torch.complex128)
+        c1, c2 = (ea * e1).sum(dim=0), (ea * e2).sum(dim=0)
+        cross = torch.conj(c1) * c2
+        p1, p2 = c1.real ** 2 + c1.imag ** 2, c2.real ** 2 + c2.imag ** 2
+        return torch.stack([p1 + p2, p1 - p2, 2.0 * cross.real, 2.0 * cross.imag])
 
     def to_pandas(self):
         """One line per row of the frame: generation, id, surface, intensity, transmittance (and the fields)."""
@@ -1729,7 +1869,7 @@ class Fresnel:
         table["transmittance"] = engine.to_host(self.transmittance)
         if self.field is not None:
             for k, name in enumerate(("ea_x", "ea_y", "ea_z", "eb_x", "eb_y", "eb_z")):
-                table[name] = engine.to_host(self.field[k])
+                table[name] = engine.to_host(self.field[k].contiguous())
         return table
 
     def apply(self):

@@ -199,6 +199,82 @@ def table_indices(material, wavelengths):
     return np.ascontiguousarray(np.broadcast_to(out, wavelengths.shape))
 
 
+class Coating:
+    """A thin-film stack on a surface, for ``DeviceFrame.fresnel(coatings=...)`` (include/prt.h states the physics).
+
+    ``layers``: 0 to 16 pairs (material, thickness), listed from the **ambient** side to the **substrate** side;
+    thickness in the unit of the frame's ``wavelength`` column (micrometres, as the Sellmeier glasses take them).
+    ``ambient``: the medium on the outer side, default the constant 1.0.  ``substrate``: the medium behind the stack, or
+    None.  A refracted ray takes its far medium from the frame; ``substrate`` is what a ray reflected on the ambient
+    side sees (a metal mirror: ``Coating((), substrate=1.2 + 7.0j)``), ``ambient`` what a ray reflected on the
+    substrate side sees (a bare face of total internal reflection: ``Coating(())``).
+
+    A material is a real or complex constant ``n + ik`` (``k >= 0`` absorbing), anything with ``index_at(wavelength)``
+    such as the glasses of this module, or a callable of the wavelength."""
+
+    MAX_LAYERS = 16
+
+    def __init__(self, layers=(), ambient=1.0, substrate=None):
+        layers = tuple(layers)
+        if len(layers) > self.MAX_LAYERS:
+            raise ValueError(f"Coating: at most {self.MAX_LAYERS} layers (got {len(layers)})")
+        out = []
+        for layer in layers:
+            try:
+                material, thickness = layer
+                thickness = float(thickness)
+            except (TypeError, ValueError):
+                raise ValueError("Coating: layers are pairs (material, thickness)") from None
+            if not (np.isfinite(thickness) and thickness >= 0):
+                raise ValueError(f"Coating: a thickness is finite and >= 0 (got {thickness})")
+            _check_material(material)
+            out.append((material, thickness))
+        _check_material(ambient)
+        if substrate is not None:
+            _check_material(substrate)
+        self.layers, self.ambient, self.substrate = tuple(out), ambient, substrate
+
+    @classmethod
+    def quarter_wave(cls, material, wavelength, ambient=1.0, substrate=None):
+        """One layer of ``material`` whose optical thickness at normal incidence is a quarter of ``wavelength``."""
+        n = complex(material_index(material, np.array([float(wavelength)]))[0]).real
+        return cls([(material, float(wavelength) / (4.0 * n))], ambient=ambient, substrate=substrate)
+
+    def table(self, wavelengths):
+        """The complex indices on ``wavelengths``, (18, n) complex128: ambient, the layers (unused slots 1), substrate
+        (1 where there is none)."""
+        wavelengths = np.asarray(wavelengths, dtype=float)
+        out = np.ones((self.MAX_LAYERS + 2, len(wavelengths)), dtype=np.complex128)
+        out[0] = material_index(self.ambient, wavelengths)
+        for k, (material, _) in enumerate(self.layers):
+            out[1 + k] = material_index(material, wavelengths)
+        if self.substrate is not None:
+            out[-1] = material_index(self.substrate, wavelengths)
+        return out
+
+
+def _check_material(material):
+    if hasattr(material, "index_at") or callable(material):
+        return
+    try:
+        complex(material)
+    except (TypeError, ValueError):
+        raise ValueError(f"Coating: a material is a number n + ik, has index_at(wavelength) or is callable (got "
+                         f"{material!r})") from None
+
+
+def material_index(material, wavelengths):
+    """A coating material on an array of wavelengths, as complex128 of the same shape."""
+    wavelengths = np.asarray(wavelengths, dtype=float)
+    if hasattr(material, "index_at"):
+        value = material.index_at(wavelengths.copy())
+    elif callable(material):
+        value = material(wavelengths.copy())
+    else:
+        value = complex(material)
+    return np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=np.complex128), wavelengths.shape))
+
+
 absorber = _AbsorbingMaterial()
 """A bulk absorbing material"""
 
