@@ -25,7 +25,6 @@
 #pragma once
 
 enum { AB_RECORD = 16, AB_RAY = 7, AB_ZONE = 6, AB_MAX_ZONES = 1024, AB_SUMS = 12 };
-enum { AB_BAD_ID = 1, AB_REPEATED_ID = 2 };
 static const int kAbBlock = 256;                  // threads of a chunk workgroup = rays of its LDS tile
 static const size_t kAbCountBytes = 64u << 20;    // cap on the sort's (wave, bucket) counts
 static const size_t kAbSlabBytes = 256u << 20;    // cap on the chunks' partial sums
@@ -39,13 +38,13 @@ k_aberration_table(const double* __restrict__ rows, int64_t ld, int64_t n_launch
                    unsigned long long* __restrict__ table, int* __restrict__ status) {
   const int64_t j = (int64_t)blockIdx.x * PRT_BLOCK + threadIdx.x;
   if (j >= n_launch_rows) return;
-  const double k = rows[PRT_COL_ID * ld + j] - id0;
-  if (!(k >= 0.0 && k < (double)n_ids && k == floor(k))) {
-    atomicOr(status, AB_BAD_ID);
+  const int64_t i = join_id(rows, ld, j, id0, n_ids);
+  if (i < 0) {
+    atomicOr(status, JOIN_BAD_ID);
     return;
   }
   // (the table starts as all ones: an entry taken before is an id seen twice in generation 0)
-  if (atomicCAS(table + (int64_t)k, ~0ull, (unsigned long long)j) != ~0ull) atomicOr(status, AB_REPEATED_ID);
+  if (atomicCAS(table + i, ~0ull, (unsigned long long)j) != ~0ull) atomicOr(status, JOIN_REPEATED_ID);
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
@@ -54,23 +53,23 @@ k_aberration_gather(const double* __restrict__ rows, int64_t ld, int64_t n_rows,
                     int* __restrict__ status) {
   const int64_t j = (int64_t)blockIdx.x * PRT_BLOCK + threadIdx.x;
   if (j >= n_rows) return;
-  const double k = rows[PRT_COL_ID * ld + j] - id0;
-  if (!(k >= 0.0 && k < (double)n_ids && k == floor(k))) {
-    atomicOr(status, AB_BAD_ID);
+  const int64_t i = join_id(rows, ld, j, id0, n_ids);
+  if (i < 0) {
+    atomicOr(status, JOIN_BAD_ID);
     index_out[j] = -1;
     return;
   }
-  index_out[j] = (int64_t)table[(int64_t)k];  // (all ones: -1, no launch row)
+  index_out[j] = (int64_t)table[i];  // (all ones: -1, no launch row)
 }
 
 extern "C" int prt_frame_launch_index(int device, const double* rows, int64_t ld, int64_t n_rows, int64_t n_launch_rows,
                                       double id0, int64_t n_ids, int64_t* index_out, void* stream) {
   if (n_rows < 0 || ld < n_rows || n_launch_rows < 0 || n_launch_rows > n_rows || (n_rows && (!rows || !index_out)))
     return fail(PRT_ERR_ARG, "bad buffers");
-  if (!(n_ids >= 1 && n_ids <= ((int64_t)1 << 31)) || !(id0 == id0 && std::fabs(id0) < 9.0e15))
-    return fail(PRT_ERR_ARG, "ids: n_ids in [1, 2^31], id0 finite");
+  int rc = join_ids(id0, n_ids);
+  if (rc) return rc;
   if (n_rows == 0) return PRT_OK;
-  int rc = ops_device(device);
+  rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* scratch = nullptr;
@@ -90,8 +89,8 @@ extern "C" int prt_frame_launch_index(int device, const double* rows, int64_t ld
   HIP_TRY(hipFreeAsync(scratch, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
-  if (host_status & AB_BAD_ID) return fail(PRT_ERR_ARG, "launch index: an id is not an integer in [id0, id0 + n_ids)");
-  if (host_status & AB_REPEATED_ID) return fail(PRT_ERR_ARG, "launch index: an id repeats within generation 0");
+  if (host_status & JOIN_BAD_ID) return join_refusal(JOIN_BAD_ID, "launch index");
+  if (host_status & JOIN_REPEATED_ID) return fail(PRT_ERR_ARG, "launch index: an id repeats within generation 0");
   return PRT_OK;
 }
 

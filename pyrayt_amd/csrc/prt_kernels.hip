@@ -12,7 +12,7 @@
 //   prt_abi_states.hpp      extern "C": per-state entry points (+ prt_host_shade.hpp: a caller's own Material.trace())
 //   prt_trace_runtime.hpp   extern "C": prt_trace*, the ticket runtime
 //   prt_abi_render_ops.hpp  extern "C": renderers, operations
-//   prt_gather.hpp, prt_frame.hpp, prt_histogram.hpp, prt_wavefront.hpp, prt_psf.hpp, prt_mtf.hpp, prt_aberrations.hpp, prt_energy.hpp, prt_paths.hpp, prt_fresnel.hpp, prt_coatings.hpp   extern "C" + kernels: frame
+//   prt_gather.hpp, prt_join.hpp (the join by ray id of the passes after it), prt_frame.hpp, prt_histogram.hpp, prt_wavefront.hpp, prt_psf.hpp, prt_mtf.hpp, prt_aberrations.hpp, prt_energy.hpp, prt_paths.hpp, prt_fresnel.hpp, prt_coatings.hpp   extern "C" + kernels: frame
 //                    re-assembly across ranks, reductions, histograms, optical path and wavefront over the frame
 //
 // Data layout in HBM
@@ -85,6 +85,7 @@ static int raise_lds_limits() {
 // ------------------------------------------------------------------------------------------------
 // reductions over the result frame
 // ------------------------------------------------------------------------------------------------
+#include "prt_join.hpp"
 #include "prt_frame.hpp"
 #include "prt_histogram.hpp"
 #include "prt_wavefront.hpp"

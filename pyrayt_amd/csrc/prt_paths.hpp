@@ -25,7 +25,7 @@
 // outputs are the same bits on every run and under any order of the rows inside a generation.
 #pragma once
 
-enum { PATHS_BAD_ID = 1, PATHS_REPEATED_ID = 2, PATHS_BAD_SURFACE = 4, PATHS_NOT_WHOLE = 8, PATHS_OVERFLOW = 16 };
+enum { PATHS_BAD_SURFACE = JOIN_OWN_BIT, PATHS_OVERFLOW = JOIN_OWN_BIT << 1 };  // (after the join's bits, prt_join.hpp)
 enum { PATHS_MAX_PATHS = 65536, PATHS_TALLIES = 5 };  // tallies: through, energy through, ended, dark, energy ended
 static const int kPathsBlock = 256;
 static const int kPathsWaves = kPathsBlock / 64;
@@ -166,19 +166,18 @@ k_paths_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_
     int64_t i = -1;
     bool weight_ok = true;
     if (live) {
-      const double k = rows[PRT_COL_ID * ld + j] - id0, s = rows[PRT_COL_SURFACE * ld + j];
-      const bool id_ok = k >= 0.0 && k < (double)n_ids && k == floor(k);
+      const int64_t id = join_id(rows, ld, j, id0, n_ids);
+      const double s = rows[PRT_COL_SURFACE * ld + j];
       const bool surface_ok = s >= 0.0 && s < 2147483648.0 && s == floor(s);
-      if (!id_ok) atomicOr(&words->status, PATHS_BAD_ID);
+      if (id < 0) atomicOr(&words->status, JOIN_BAD_ID);
       if (!surface_ok) atomicOr(&words->status, PATHS_BAD_SURFACE);
-      if (id_ok && surface_ok) {
-        i = (int64_t)k;
-        // (stamp: the generation that wrote node_of[i] last, + 1)
-        const int before = atomicExch(stamp + i, generation + 1);
+      if (id >= 0 && surface_ok) {  // (an id is claimed only by a row whose surface is good too)
+        i = id;
+        // (the stamp: the generation that wrote node_of[i] last, + 1)
+        const int bits = join_status(join_claim(stamp, i, generation), generation);
         int parent = -1;
-        bool ok = before == generation;
-        if (before == generation + 1) atomicOr(&words->status, PATHS_REPEATED_ID);
-        else if (!ok) atomicOr(&words->status, PATHS_NOT_WHOLE);  // (no row in generation - 1)
+        bool ok = !bits;
+        if (bits) atomicOr(&words->status, bits);
         if (ok && generation > 0) {
           parent = node_of[i];
           ok = parent >= 0 && parent < capacity;  // (-1: its node overflowed)
@@ -308,7 +307,7 @@ k_paths_remap(int64_t n_rows, int64_t n_ids, int n_groups, int max_paths, int n_
 // ---- entry points ---------------------------------------------------------------------------------------------------
 static bool paths_sizes_ok(int64_t n_rows, int64_t n_ids, int n_groups, int max_paths) {
   if (n_rows < 0 || n_groups < 1 || max_paths < 1 || max_paths > PATHS_MAX_PATHS) return false;
-  if (!(n_ids >= 1 && n_ids <= ((int64_t)1 << 31))) return false;
+  if (!join_n_ids_ok(n_ids)) return false;
   return ((size_t)n_groups << paths_capacity_bits(max_paths)) * PATHS_TALLIES * 8 <= kPathsTableBytes;
 }
 
@@ -327,17 +326,13 @@ extern "C" int prt_frame_paths(int device, const double* rows, int64_t ld, const
                                int64_t* ray_last_row_out, int32_t* node_out, int64_t* count_out, double* energy_out,
                                int64_t* record_out, void* workspace, void* stream) {
   // (everything is checked before a device is touched)
-  if (n_generations < 0 || (n_generations && !rows_per_generation) || ld < 0) return fail(PRT_ERR_ARG, "bad buffers");
-  int64_t n_rows = 0;
-  for (int g = 0; g < n_generations; ++g) {
-    if (rows_per_generation[g] < 0) return fail(PRT_ERR_ARG, "rows_per_generation: counts >= 0");
-    n_rows += rows_per_generation[g];
-  }
-  if (ld < n_rows || n_groups < 1 || !ray_node_out || !ray_last_row_out || !node_out || !count_out || !energy_out ||
+  const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld);
+  if (n_rows < 0) return (int)n_rows;
+  if (n_groups < 1 || !ray_node_out || !ray_last_row_out || !node_out || !count_out || !energy_out ||
       !record_out || !workspace || (n_rows && (!rows || !row_node_out)))
     return fail(PRT_ERR_ARG, "bad buffers");
-  if (!(n_ids >= 1 && n_ids <= ((int64_t)1 << 31)) || !(id0 == id0 && std::fabs(id0) < 9.0e15))
-    return fail(PRT_ERR_ARG, "ids: n_ids in [1, 2^31], id0 finite");
+  int rc = join_ids(id0, n_ids);
+  if (rc) return rc;
   if (!(rays_per_source > 0) && n_groups != 1) return fail(PRT_ERR_ARG, "one group without rays_per_source");
   if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
   if (max_paths < 1 || max_paths > PATHS_MAX_PATHS) return fail(PRT_ERR_ARG, "paths: max_paths in [1, 65536]");
@@ -346,7 +341,7 @@ extern "C" int prt_frame_paths(int device, const double* rows, int64_t ld, const
   const int bits = paths_capacity_bits(max_paths), capacity = 1 << bits;
   const int64_t items = n_rows + n_ids + (int64_t)n_groups * max_paths;
   if ((items + PRT_BLOCK - 1) / PRT_BLOCK > 0x7fffffff) return fail(PRT_ERR_ARG, "paths: too many rows for one launch");
-  int rc = ops_device(device);
+  rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_paths_workspace_bytes)
@@ -395,11 +390,10 @@ extern "C" int prt_frame_paths(int device, const double* rows, int64_t ld, const
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
   const int status = host_words.status;
-  if (status & PATHS_BAD_ID) return fail(PRT_ERR_ARG, "paths: an id is not an integer in [id0, id0 + n_ids)");
-  if (status & PATHS_BAD_SURFACE) return fail(PRT_ERR_ARG, "paths: a surface is not an integer in [0, 2^31)");
-  if (status & PATHS_REPEATED_ID) return fail(PRT_ERR_ARG, "paths: an id repeats within a generation");
-  if (status & PATHS_NOT_WHOLE)
-    return fail(PRT_ERR_ARG, "paths: a ray has a row in a generation and none in the one before: the frame is not whole");
+  if (!(status & JOIN_BAD_ID) && (status & PATHS_BAD_SURFACE))  // (a bad id first, a bad surface before the join's others)
+    return fail(PRT_ERR_ARG, "paths: a surface is not an integer in [0, 2^31)");
+  rc = join_refusal(status, "paths");
+  if (rc) return rc;
   if ((status & PATHS_OVERFLOW) || host_words.nodes > max_paths || host_words.nodes < 0)
     return fail(PRT_ERR_ARG, "paths: more than max_paths = " + std::to_string(max_paths) + " distinct nodes");
   // the nodes in the order they were made: a parent comes before its children (the generations ran in order)

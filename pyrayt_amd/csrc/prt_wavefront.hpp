@@ -70,7 +70,6 @@ __device__ __forceinline__ int wf_group(const double* __restrict__ rows, int64_t
 }
 
 // ---- optical path -------------------------------------------------------------------------------------------------
-enum { WF_BAD_ID = 1, WF_REPEATED_ID = 2 };
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_frame_optical_path(const double* __restrict__ rows, int64_t ld, int64_t start, int64_t count, int generation,
                      double id0, int64_t n_ids, double* __restrict__ acc, int* __restrict__ stamp,
@@ -81,16 +80,16 @@ k_frame_optical_path(const double* __restrict__ rows, int64_t ld, int64_t start,
   const double dy = rows[PRT_COL_Y1 * ld + j] - rows[PRT_COL_Y0 * ld + j];
   const double dz = rows[PRT_COL_Z1 * ld + j] - rows[PRT_COL_Z0 * ld + j];
   const double segment = rows[PRT_COL_INDEX * ld + j] * sqrt(dx * dx + dy * dy + dz * dz);
-  const double k = rows[PRT_COL_ID * ld + j] - id0;
-  if (!(k >= 0.0 && k < (double)n_ids && k == floor(k))) {
-    atomicOr(status, WF_BAD_ID);
+  const int64_t i = join_id(rows, ld, j, id0, n_ids);
+  if (i < 0) {
+    atomicOr(status, JOIN_BAD_ID);
     opl[j] = __longlong_as_double(0x7ff8000000000000ll);
     return;
   }
-  const int64_t i = (int64_t)k;
-  const int last = atomicExch(stamp + i, generation + 1);  // (stamp: the generation that wrote acc[i] last, + 1)
-  if (last == generation + 1) atomicOr(status, WF_REPEATED_ID);
-  const double cumulative = (generation > 0 && last == generation ? acc[i] : 0.0) + segment;
+  const int bits = join_status(join_claim(stamp, i, generation), generation);  // (0: acc[i] is generation - 1's)
+  if (bits & JOIN_REPEATED_ID) atomicOr(status, JOIN_REPEATED_ID);
+  // (a missing generation is not refused here: the sum starts again)
+  const double cumulative = (generation > 0 && !bits ? acc[i] : 0.0) + segment;
   acc[i] = cumulative;
   opl[j] = cumulative;
 }
@@ -534,18 +533,13 @@ k_frame_wavefront_piston(int64_t capacity, const int64_t* __restrict__ total, co
 // ---- entry points ---------------------------------------------------------------------------------------------------
 extern "C" int prt_frame_optical_path(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
                                       int n_generations, double id0, int64_t n_ids, double* opl_out, void* stream) {
-  if (n_generations < 0 || (n_generations && !rows_per_generation) || ld < 0)
-    return fail(PRT_ERR_ARG, "bad buffers");
-  int64_t n_rows = 0;
-  for (int g = 0; g < n_generations; ++g) {
-    if (rows_per_generation[g] < 0) return fail(PRT_ERR_ARG, "rows_per_generation: counts >= 0");
-    n_rows += rows_per_generation[g];
-  }
-  if (ld < n_rows || (n_rows && (!rows || !opl_out))) return fail(PRT_ERR_ARG, "bad buffers");
-  if (!(n_ids >= 1 && n_ids <= ((int64_t)1 << 31)) || !(id0 == id0 && std::fabs(id0) < 9.0e15))
-    return fail(PRT_ERR_ARG, "ids: n_ids in [1, 2^31], id0 finite");
+  const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld);
+  if (n_rows < 0) return (int)n_rows;
+  if (n_rows && (!rows || !opl_out)) return fail(PRT_ERR_ARG, "bad buffers");
+  int rc = join_ids(id0, n_ids);
+  if (rc) return rc;
   if (n_rows == 0) return PRT_OK;
-  int rc = ops_device(device);
+  rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   char* scratch = nullptr;
@@ -568,9 +562,7 @@ extern "C" int prt_frame_optical_path(int device, const double* rows, int64_t ld
   HIP_TRY(hipFreeAsync(scratch, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
-  if (host_status & WF_BAD_ID) return fail(PRT_ERR_ARG, "optical path: an id is not an integer in [id0, id0 + n_ids)");
-  if (host_status & WF_REPEATED_ID) return fail(PRT_ERR_ARG, "optical path: an id repeats within a generation");
-  return PRT_OK;
+  return join_refusal(host_status, "optical path");
 }
 
 static int64_t wf_waves(int64_t n_rows, int n_groups) {

@@ -167,7 +167,7 @@ class DeviceFrame:
 
         from . import engine
 
-        rows = self.rows if self.rows.stride(1) == 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         sums = torch.empty((n_groups, 9), dtype=torch.float64, device=dev)
         nan = float("nan")
@@ -187,7 +187,7 @@ class DeviceFrame:
         lib = engine.library()
         nan = float("nan")
         if comm is not None:  # one library call: both passes, two ncclAllReduce of (n_groups, 9) doubles
-            rows = self.rows if self.rows.stride(1) == 1 else self.rows.contiguous()
+            rows = self._contiguous_rows()
             dev = rows.device
             out = torch.empty((n_groups, 8), dtype=torch.float64, device=dev)
             work = torch.empty(int(lib.prt_frame_stats_workspace_bytes(n_groups)), dtype=torch.uint8, device=dev)
@@ -262,7 +262,7 @@ class DeviceFrame:
                 n_groups = max(1, int(top // rays_per_source) + 1)
         else:
             n_groups = 1
-        rows = self.rows if self.rows.stride(1) == 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         sums = torch.empty((n_groups, 3), dtype=torch.float64, device=dev)
         nan = float("nan")
@@ -355,7 +355,7 @@ class DeviceFrame:
                 n_groups = max(1, int(top // rays_per_source) + 1)
         else:
             n_groups = 1
-        rows = frame.rows if frame.rows.stride(1) == 1 or frame.rows.shape[1] <= 1 else frame.rows.contiguous()
+        rows = frame._contiguous_rows()
         dev = rows.device
         ld, n_rows = max(rows.stride(0), rows.shape[1], 1), rows.shape[1]
         nan = float("nan")
@@ -413,6 +413,24 @@ class DeviceFrame:
             raise ValueError(f"{what} needs the whole frame of a trace: rows_per_generation is not known for this frame")
         self._need(*(columns or _PATH_COLUMNS))
 
+    def _contiguous_rows(self):
+        """The rows as the library reads them: contiguous along the row axis."""
+        rows = self.rows
+        return rows if rows.stride(1) == 1 or rows.shape[1] <= 1 else rows.contiguous()
+
+    def _id_range(self, what, rows):
+        """``(id0, n_ids, top)``: the smallest id of ``rows``, the length of the dense per-id arrays of a join by ray id,
+        the largest id; ``(0.0, 1, 0.0)`` for an empty frame."""
+        import torch
+
+        if rows.shape[1] == 0:
+            return 0.0, 1, 0.0
+        ids = rows[_INDEX["id"]]
+        id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
+        if not (np.isfinite(id0) and np.isfinite(top)):
+            raise ValueError(f"{what}: an id is not an integer in the frame's id range")
+        return id0, int(top - id0) + 1, top
+
     def optical_path(self):
         """The cumulative optical path length of every row, a device tensor of ``len(self)`` float64: the row's segment
         ``index * sqrt(dx*dx + dy*dy + dz*dz)`` plus the cumulative OPL of the same ray's row in the previous generation
@@ -428,19 +446,16 @@ class DeviceFrame:
 
         from . import engine
 
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         opl = torch.empty(rows.shape[1], dtype=torch.float64, device=dev)
         if rows.shape[1] == 0:
             return opl
-        ids = rows[_INDEX["id"]]
-        id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
-        if not (np.isfinite(id0) and np.isfinite(top)):
-            raise ValueError("optical_path: an id is not an integer in the frame's id range")
+        id0, n_ids, _ = self._id_range("optical_path", rows)
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
         engine._check(engine.library().prt_frame_optical_path(
             dev.index or 0, rows.data_ptr(), max(rows.stride(0), rows.shape[1], 1), counts.ctypes.data, len(counts),
-            id0, int(top - id0) + 1, opl.data_ptr(), engine._stream_ptr(torch, dev)))
+            id0, n_ids, opl.data_ptr(), engine._stream_ptr(torch, dev)))
         return opl
 
     def wavefront(self, surface, reference="centroid", radius=None, axis=None, basis=None, pupil_radius=None,
@@ -507,7 +522,7 @@ class DeviceFrame:
         if radius is not None:
             radii = torch.as_tensor(np.broadcast_to(np.asarray(radius, dtype=float), (n_groups,)).copy()).to(dev)
         opl = self._optical_path()
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         if generation == "last":
             generation = self.last_generation_number() or 0
         if generation is not None:  # (generation-major: one generation's rows are a slice)
@@ -690,7 +705,7 @@ class DeviceFrame:
         else:
             n_groups = 1
         n_groups = int(n_groups)
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         centres = None
         if not isinstance(reference, str):
@@ -778,7 +793,7 @@ class DeviceFrame:
         else:
             n_groups = 1
         n_groups = int(n_groups)
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         centres = None
         if not isinstance(reference, str):
@@ -823,18 +838,15 @@ class DeviceFrame:
 
         from . import engine
 
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         index = torch.empty(rows.shape[1], dtype=torch.int64, device=dev)
         if rows.shape[1] == 0:
             return index
-        ids = rows[_INDEX["id"]]
-        id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
-        if not (np.isfinite(id0) and np.isfinite(top)):
-            raise ValueError("launch_index: an id is not an integer in the frame's id range")
+        id0, n_ids, _ = self._id_range("launch_index", rows)
         engine._check(engine.library().prt_frame_launch_index(
             dev.index or 0, rows.data_ptr(), max(rows.stride(0), rows.shape[1], 1), rows.shape[1],
-            int(self.rows_per_generation[0]), id0, int(top - id0) + 1, index.data_ptr(), engine._stream_ptr(torch, dev)))
+            int(self.rows_per_generation[0]), id0, n_ids, index.data_ptr(), engine._stream_ptr(torch, dev)))
         return index
 
     def _selection(self, surface, generation):
@@ -922,7 +934,7 @@ class DeviceFrame:
         else:
             n_groups = 1
         n_groups = int(n_groups)
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         centres, mode = None, {"centroid": 0, "chief": 2}.get(reference if isinstance(reference, str) else None, 1)
         if mode == 1:
@@ -1011,17 +1023,11 @@ class DeviceFrame:
             self._need_whole("paths", columns=columns)
         except KeyError as error:
             raise ValueError(f"paths: {error.args[0]}") from None
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         n_rows = rows.shape[1]
         ids = rows[_INDEX["id"]]
-        if n_rows:
-            id0, top = (float(v) for v in torch.stack([ids.min(), ids.max()]).cpu())
-            if not (np.isfinite(id0) and np.isfinite(top)):
-                raise ValueError("paths: an id is not an integer in the frame's id range")
-        else:
-            id0 = top = 0.0
-        n_ids = int(top - id0) + 1
+        id0, n_ids, top = self._id_range("paths", rows)
         if rays_per_source:
             if n_groups is None:
                 n_groups = max(1, int(top // rays_per_source) + 1)
@@ -1092,7 +1098,8 @@ class DeviceFrame:
                 complex_input = bool(np.iscomplexobj(np.asarray(polarization)))
             except (TypeError, ValueError):
                 complex_input = False
-        is_coated = coatings is not None or complex_input
+        # the field type: complex (twelve planes, six counters, the coated entry) or real (six planes, four counters)
+        is_complex = coatings is not None or complex_input
         try:
             self._need_whole("fresnel", columns=_FRESNEL_COATED_COLUMNS if coatings else _FRESNEL_COLUMNS)
         except KeyError as error:
@@ -1100,128 +1107,45 @@ class DeviceFrame:
         ids_lossless = sorted(_lossless_ids(lossless))
         if len(ids_lossless) > 64:
             raise ValueError(f"fresnel: at most 64 lossless surfaces (got {len(ids_lossless)})")
-        if is_coated:
-            return self._fresnel_coated(polarization, ids_lossless, fields, coatings or {})
+        if is_complex:
+            stacks, surface_coating = _coating_stacks(coatings or {}, ids_lossless)
         v = None
         if polarization is not None:
             try:
-                v = np.ascontiguousarray(polarization, dtype=np.float64).reshape(-1)
+                v = np.ascontiguousarray(polarization, dtype=np.complex128 if is_complex else np.float64).reshape(-1)
             except (TypeError, ValueError):
                 v = np.zeros(0)
             if v.shape != (3,) or not np.all(np.isfinite(v)) or not np.any(v != 0):
                 raise ValueError("fresnel: polarization is None or a world vector of three finite numbers, not all zero")
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
+        rows = self._contiguous_rows()
         dev = rows.device
         n_rows = rows.shape[1]
-        if n_rows:
-            ids = rows[_INDEX["id"]]
-            id0, top = (float(x) for x in torch.stack([ids.min(), ids.max()]).cpu())
-            if not (np.isfinite(id0) and np.isfinite(top)):
-                raise ValueError("fresnel: an id is not an integer in the frame's id range")
-        else:
-            id0 = top = 0.0
-        n_ids = int(top - id0) + 1
+        id0, n_ids, _ = self._id_range("fresnel", rows)
         lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_fresnel_workspace_bytes(n_rows, n_ids))), dtype=torch.uint8,
-                           device=dev)
+        tables, arrays = (), ()  # (arrays: what the table arguments point into, alive over the call)
+        entry, workspace_bytes, planes, counters = lib.prt_frame_fresnel, lib.prt_frame_fresnel_workspace_bytes, 6, 4
+        if is_complex:
+            entry, workspace_bytes, planes, counters = (lib.prt_frame_fresnel_coated,
+                                                        lib.prt_frame_fresnel_coated_workspace_bytes, 12, 6)
+            tables, arrays = _coating_tables(stacks, surface_coating, rows if n_rows else None)
+        work = torch.empty(int(engine._check(workspace_bytes(n_rows, n_ids))), dtype=torch.uint8, device=dev)
         transmittance = torch.empty(n_rows, dtype=torch.float64, device=dev)
-        field = torch.empty((6, n_rows), dtype=torch.float64, device=dev) if fields else None
-        record = np.zeros(4, dtype=np.int64)
-        counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
-        coated = np.ascontiguousarray(ids_lossless, dtype=np.int64)
-        engine._check(lib.prt_frame_fresnel(
-            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
-            len(counts), id0, n_ids, None if v is None else v.ctypes.data, coated.ctypes.data if len(coated) else None,
-            len(coated), transmittance.data_ptr() if n_rows else None,
-            field.data_ptr() if field is not None and n_rows else None, record.ctypes.data, work.data_ptr(),
-            engine._stream_ptr(torch, dev)))
-        return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
-
-    def _fresnel_coated(self, polarization, ids_lossless, fields, coatings):
-        """``fresnel()`` through ``prt_frame_fresnel_coated``: complex fields, the coated surfaces' tables."""
-        import torch
-
-        from . import engine
-        from .materials import Coating
-
-        if not hasattr(coatings, "items"):
-            raise ValueError("fresnel: coatings is a mapping from a surface to a Coating")
-        stacks, surface_coating = [], {}
-        for key, coating in coatings.items():
-            if not isinstance(coating, Coating):
-                raise ValueError(f"fresnel: coatings maps a surface to a Coating (got {coating!r})")
-            known = [k for k, other in enumerate(stacks) if other is coating]
-            if not known:
-                stacks.append(coating)
-            for sid in sorted(_lossless_ids(key)):
-                if sid in surface_coating:
-                    raise ValueError(f"fresnel: surface {sid} is given two coatings")
-                surface_coating[sid] = known[0] if known else len(stacks) - 1
-        both = sorted(set(surface_coating) & set(ids_lossless))
-        if both:
-            raise ValueError(f"fresnel: surfaces {both} are both lossless and coated")
-        if len(surface_coating) > 64:
-            raise ValueError(f"fresnel: at most 64 coated surfaces (got {len(surface_coating)})")
-        if len(stacks) > 16:
-            raise ValueError(f"fresnel: at most 16 coatings (got {len(stacks)})")
-        v = None
-        if polarization is not None:
-            try:
-                v = np.asarray(polarization, dtype=np.complex128).reshape(-1)
-            except (TypeError, ValueError):
-                v = np.zeros(0, dtype=np.complex128)
-            if v.shape != (3,) or not np.all(np.isfinite(v)) or not np.any(v != 0):
-                raise ValueError("fresnel: polarization is None or a world vector of three finite numbers, not all zero")
-        rows = self.rows if self.rows.stride(1) == 1 or self.rows.shape[1] <= 1 else self.rows.contiguous()
-        dev = rows.device
-        n_rows = rows.shape[1]
-        if n_rows:
-            ids = rows[_INDEX["id"]]
-            id0, top = (float(x) for x in torch.stack([ids.min(), ids.max()]).cpu())
-            if not (np.isfinite(id0) and np.isfinite(top)):
-                raise ValueError("fresnel: an id is not an integer in the frame's id range")
-        else:
-            id0 = top = 0.0
-        n_ids = int(top - id0) + 1
-        # the materials on the distinct wavelengths of the frame (as DeviceScene.ensure_tables does for table glasses)
-        wavelengths = np.zeros(0)
-        if stacks and n_rows:
-            wavelengths = engine.to_host(torch.unique(rows[_INDEX["wavelength"]])).astype(np.float64)
-            wavelengths = np.ascontiguousarray(wavelengths[np.isfinite(wavelengths) & (wavelengths > 0)])
-            if len(wavelengths) > 256:
-                raise ValueError(f"fresnel: at most 256 distinct wavelengths with coatings (got {len(wavelengths)})")
-        table = np.ones((max(len(stacks), 1), 18, max(len(wavelengths), 1)), dtype=np.complex128)
-        thickness = np.zeros((max(len(stacks), 1), 16))
-        for k, coating in enumerate(stacks):
-            if len(wavelengths):
-                table[k] = coating.table(wavelengths)
-            thickness[k, :len(coating.layers)] = [d for _, d in coating.layers]
-        table = np.ascontiguousarray(table)
-        layer_counts = np.array([len(c.layers) for c in stacks] or [0], dtype=np.int32)
-        has_substrate = np.array([c.substrate is not None for c in stacks] or [0], dtype=np.int32)
-        coated_ids = np.array(sorted(surface_coating) or [0], dtype=np.int64)
-        coating_of = np.array([surface_coating[sid] for sid in sorted(surface_coating)] or [0], dtype=np.int32)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_fresnel_coated_workspace_bytes(n_rows, n_ids))),
-                           dtype=torch.uint8, device=dev)
-        transmittance = torch.empty(n_rows, dtype=torch.float64, device=dev)
-        planes = torch.empty((12, n_rows), dtype=torch.float64, device=dev) if fields else None
-        record = np.zeros(6, dtype=np.int64)
+        field = torch.empty((planes, n_rows), dtype=torch.float64, device=dev) if fields else None
+        record = np.zeros(counters, dtype=np.int64)
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
         lossless_ids = np.ascontiguousarray(ids_lossless, dtype=np.int64)
-        v6 = None if v is None else np.ascontiguousarray(np.concatenate([v.real, v.imag]))
-        engine._check(lib.prt_frame_fresnel_coated(
+        parts = None if v is None else np.ascontiguousarray(np.concatenate([v.real, v.imag]) if is_complex else v)
+        engine._check(entry(
             dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
-            len(counts), id0, n_ids, None if v6 is None else v6.ctypes.data,
-            lossless_ids.ctypes.data if len(lossless_ids) else None, len(lossless_ids), coated_ids.ctypes.data,
-            coating_of.ctypes.data, len(surface_coating), len(stacks), layer_counts.ctypes.data, has_substrate.ctypes.data,
-            thickness.ctypes.data, wavelengths.ctypes.data if len(wavelengths) else None, len(wavelengths),
-            table.view(np.float64).ctypes.data, transmittance.data_ptr() if n_rows else None,
-            planes.data_ptr() if planes is not None and n_rows else None, record.ctypes.data, work.data_ptr(),
-            engine._stream_ptr(torch, dev)))
-        field = torch.complex(planes[:6], planes[6:]) if planes is not None else None
+            len(counts), id0, n_ids, None if parts is None else parts.ctypes.data,
+            lossless_ids.ctypes.data if len(lossless_ids) else None, len(lossless_ids), *tables,
+            transmittance.data_ptr() if n_rows else None, field.data_ptr() if field is not None and n_rows else None,
+            record.ctypes.data, work.data_ptr(), engine._stream_ptr(torch, dev)))
+        if not is_complex:
+            return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
+        field = torch.complex(field[:6], field[6:]) if field is not None else None
         return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless),
-                       coatings=dict(coatings))
+                       coatings=dict(coatings or {}))
 
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
@@ -1893,6 +1817,63 @@ class Fresnel:
         launched = original.energy_through[:, original.depth == 0].sum(axis=1)
         with np.errstate(invalid="ignore", divide="ignore"):
             return arrived / launched
+
+
+def _coating_stacks(coatings, ids_lossless):
+    """``coatings`` of ``fresnel()`` as (the distinct Coatings, {surface id: its number among them})."""
+    from .materials import Coating
+
+    if not hasattr(coatings, "items"):
+        raise ValueError("fresnel: coatings is a mapping from a surface to a Coating")
+    stacks, surface_coating = [], {}
+    for key, coating in coatings.items():
+        if not isinstance(coating, Coating):
+            raise ValueError(f"fresnel: coatings maps a surface to a Coating (got {coating!r})")
+        known = [k for k, other in enumerate(stacks) if other is coating]
+        if not known:
+            stacks.append(coating)
+        for sid in sorted(_lossless_ids(key)):
+            if sid in surface_coating:
+                raise ValueError(f"fresnel: surface {sid} is given two coatings")
+            surface_coating[sid] = known[0] if known else len(stacks) - 1
+    both = sorted(set(surface_coating) & set(ids_lossless))
+    if both:
+        raise ValueError(f"fresnel: surfaces {both} are both lossless and coated")
+    if len(surface_coating) > 64:
+        raise ValueError(f"fresnel: at most 64 coated surfaces (got {len(surface_coating)})")
+    if len(stacks) > 16:
+        raise ValueError(f"fresnel: at most 16 coatings (got {len(stacks)})")
+    return stacks, surface_coating
+
+
+def _coating_tables(stacks, surface_coating, rows):
+    """The table arguments of ``prt_frame_fresnel_coated``, in its order, and the arrays they point into: the
+    materials on the distinct wavelengths of the frame (as DeviceScene.ensure_tables does for table glasses)."""
+    import torch
+
+    from . import engine
+
+    wavelengths = np.zeros(0)
+    if stacks and rows is not None:
+        wavelengths = engine.to_host(torch.unique(rows[_INDEX["wavelength"]])).astype(np.float64)
+        wavelengths = np.ascontiguousarray(wavelengths[np.isfinite(wavelengths) & (wavelengths > 0)])
+        if len(wavelengths) > 256:
+            raise ValueError(f"fresnel: at most 256 distinct wavelengths with coatings (got {len(wavelengths)})")
+    table = np.ones((max(len(stacks), 1), 18, max(len(wavelengths), 1)), dtype=np.complex128)
+    thickness = np.zeros((max(len(stacks), 1), 16))
+    for k, coating in enumerate(stacks):
+        if len(wavelengths):
+            table[k] = coating.table(wavelengths)
+        thickness[k, :len(coating.layers)] = [d for _, d in coating.layers]
+    table = np.ascontiguousarray(table).view(np.float64)
+    layer_counts = np.array([len(c.layers) for c in stacks] or [0], dtype=np.int32)
+    has_substrate = np.array([c.substrate is not None for c in stacks] or [0], dtype=np.int32)
+    coated_ids = np.array(sorted(surface_coating) or [0], dtype=np.int64)
+    coating_of = np.array([surface_coating[sid] for sid in sorted(surface_coating)] or [0], dtype=np.int32)
+    arguments = (coated_ids.ctypes.data, coating_of.ctypes.data, len(surface_coating), len(stacks), layer_counts.ctypes.data,
+                 has_substrate.ctypes.data, thickness.ctypes.data, wavelengths.ctypes.data if len(wavelengths) else None,
+                 len(wavelengths), table.ctypes.data)
+    return arguments, (coated_ids, coating_of, layer_counts, has_substrate, thickness, wavelengths, table)
 
 
 def _lossless_ids(items):

@@ -236,3 +236,19 @@ def test_fresnel_kernel_uses_no_scratch_and_the_registers_design_states():
         assert res["private_segment_fixed_size"] == 0 and res["vgpr_spill_count"] == 0, (name, res)
         assert res["sgpr_spill_count"] == 0 and res["group_segment_fixed_size"] <= 1024, (name, res)
         assert res["vgpr_count"] == int(stated.group(1)), (name, res)
+
+
+@pytest.mark.parametrize("n_ids", [1, 65, 2 ** 31])
+def test_the_workspaces_of_both_entries_keep_their_sizes(n_ids):
+    """The two entries share their workspace's carve-up: the words, the coated entry's tables at their caps (thicknesses,
+    wavelengths, complex indices per coating, slot and wavelength), per id the planes of Ea and Eb (6 real, 12 complex),
+    the previous row and the stamp, and the slack to align by."""
+    from pyrayt_amd import engine
+
+    if not os.path.exists(engine.LIB_PATH):
+        pytest.skip("libprt_hip.so is not built")
+    lib = engine.library()
+    for n_rows in (0, n_ids, 3 * n_ids):
+        assert lib.prt_frame_fresnel_workspace_bytes(n_rows, n_ids) == 64 + n_ids * 60 + 64
+        assert lib.prt_frame_fresnel_coated_workspace_bytes(n_rows, n_ids) == \
+            64 + 8 * (16 * 16 + 256 + 2 * 16 * 18 * 256) + n_ids * 108 + 64
