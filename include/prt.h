@@ -979,6 +979,14 @@ int prt_frame_fresnel(int device, const double* rows, int64_t ld, const int64_t*
  *   Re eta_near) of their polarisation; then |E|^2 carries power and the phase is kept.  Reflected coefficients are
  *   rs = r_s and rp = -r_p: the signs in the basis s, pi, pt, in which a substrate of infinite |n| gives the ideal
  *   mirror of prt_frame_fresnel, rs = -1, rp = +1.  Without layers ts, tp are those of prt_frame_fresnel.
+ *   A finite stack never makes an interface invalid by its thickness or absorption: the kernel carries every M_j scaled
+ *   by exp(-Im deltaj), which r does not see, and multiplies t by exp(-sum Im deltaj) at the end; a layer that is opaque
+ *   many times over (a metal film of micrometres, an evanescent gap of many waves) gives the r of its bulk material and
+ *   t = 0, not NaN.  Conditioning: the far medium's n cos theta is sqrt(n^2 - q) of the Snell invariant, not the cosine
+ *   of the transmitted row, so next to the far medium's critical angle, and for a ray that leaves at grazing exit, one
+ *   ulp of q moves n cos theta by 1.1e-16 n^2 / (2 n cos theta), and r, t with it (t, which goes with its square
+ *   root, by more): at 1e-9 relative from the critical angle the coefficients are defined to some 1e-9, no better.
+ *   A layer next to ITS critical angle is no such case: M_j is even in n cos thetaj.
  * Fields: Ea, Eb are complex 3-vectors.  The field update is prt_frame_fresnel's with complex cs, cp:
  *   E' = cs (E.s) s + cp (E.pi) pt, the dot products without conjugation (s, pi, pt are real); at normal incidence
  *   E' = ts E, respectively E' = rs E.  T = (|Ea|^2 + |Eb|^2) / 2, respectively |Ea|^2, with complex moduli.  T is
@@ -991,7 +999,9 @@ int prt_frame_fresnel(int device, const double* rows, int64_t ld, const int64_t*
  *   norm; the transverse part is taken as in prt_frame_fresnel, on both parts, and normalised with the complex norm.
  * Invalid interfaces, besides prt_frame_fresnel's: a reflection that needs a substrate and has none; a NaN or
  *   non-positive (or infinite) wavelength at a coated interface; a table value of the far medium or of a layer crossed
- *   that is not finite, or coefficients that are not finite.  The ray is NaN from there on and counted once.
+ *   that is not finite, or coefficients that are not finite (a far medium exactly at its critical angle, an index
+ *   whose square overflows: never a finite thickness or absorption, see Coefficients).  The ray is NaN from there on and
+ *   counted once.
  * Refused calls: a row's wavelength that is not in the table at a coated interface sets a status bit and the call
  *   returns PRT_ERR_ARG: the caller's table was wrong.
  * Counters: prt_frame_fresnel's four, then coated interfaces, then interfaces of total internal reflection: a valid

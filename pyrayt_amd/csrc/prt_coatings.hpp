@@ -62,7 +62,8 @@ __device__ __forceinline__ Cx cx_ncos(Cx n, double q) {
 __device__ __forceinline__ bool cx_finite(Cx a) { return fabs(a.re) < PRT_INF && fabs(a.im) < PRT_INF; }
 
 // one layer applied to (B, C) of one polarisation: (B, C) <- [[cos d, -i sin d / eta], [-i eta sin d, cos d]] (B, C)
-// (the sign of i that goes with n + ik absorbing, fields as exp(-i omega t)); isind is -i sin d
+// (the sign of i that goes with n + ik absorbing, fields as exp(-i omega t)); isind is -i sin d.  coat_stack hands in
+// cos d and -i sin d times exp(-Im d), so (B, C) come out scaled by that: see there
 __device__ __forceinline__ void coat_layer(Cx& b, Cx& c, Cx cosd, Cx isind, Cx eta) {
   const Cx nb = cx_add(cx_mul(cosd, b), cx_mul(cx_div(isind, eta), c));
   const Cx nc = cx_add(cx_mul(cx_mul(isind, eta), b), cx_mul(cosd, c));
@@ -115,7 +116,13 @@ __device__ __forceinline__ int coat_of(const CoatingTables& tb, double surface) 
 }
 
 // r or t of the stack `coating` at wavelength lambda for light that arrives in the index ni at cos(theta) = ci,
-// sin^2(theta) = xx, and leaves in nt; from the characteristic matrices of its layers
+// sin^2(theta) = xx, and leaves in nt; from the characteristic matrices of its layers.
+// Every layer's matrix is carried scaled by exp(-Im delta) (Im delta >= 0 on the branch of cx_ncos): cosh and sinh of
+// Im delta become (1 + e) / 2 and (1 - e) / 2 with e = exp(-2 Im delta), which lie in [0, 1] whatever the thickness or
+// the absorption, and 1 - e comes from expm1, so a faintly absorbing or faintly evanescent layer does not lose its sinh
+// to cancellation.  r is a quotient of (B, C) and does not see the common scale; t is multiplied by exp(-sum Im delta)
+// at the end, which underflows to 0 for an opaque stack, as it should.  What is left to grow in (B, C) is a factor of
+// at most max(|eta|, 1 / |eta|) a layer, so the squares in cx_div, where it divides by eta0 B + C, stay in range.
 __device__ __forceinline__ CoatCoefficients coat_stack(const CoatingTables& tb, int coating, double lambda, double ni,
                                                        double nt, double ci, double xx, bool reflection) {
   CoatCoefficients r = {{-1.0, 0.0}, {1.0, 0.0}, false, false, false};
@@ -151,6 +158,7 @@ __device__ __forceinline__ CoatCoefficients coat_stack(const CoatingTables& tb, 
   const Cx far_s = far_ncos, far_p = cx_div(cx_mul(far, far), far_ncos);
   Cx bs = {1.0, 0.0}, cs = far_s, bp = {1.0, 0.0}, cp = far_p;
   bool finite = cx_finite(far);
+  double damping = 0.0;  // (sum of Im delta over the layers)
   // (from the layer next to the far medium to the one next to the near medium)
   for (int step = 0; step < COATING_MAX_LAYERS; ++step) {
     if (step >= layers) break;
@@ -162,8 +170,9 @@ __device__ __forceinline__ CoatCoefficients coat_stack(const CoatingTables& tb, 
     const Cx delta = cx_scale(ncos, 6.283185307179586 * thick / lambda);
     double sn, cn;
     sincos(delta.re, &sn, &cn);
-    const double ep = exp(delta.im), em = 1.0 / ep;
-    const double ch = (ep + em) / 2.0, sh = (ep - em) / 2.0;
+    const double less = expm1(-2.0 * delta.im);  // (e - 1)
+    const double ch = (2.0 + less) / 2.0, sh = -less / 2.0;
+    damping += delta.im;
     const Cx cosd = {cn * ch, -(sn * sh)};
     const Cx isind = {cn * sh, -(sn * ch)};  // -i sin(delta), sin(a + ib) = sin a cosh b + i cos a sinh b
     coat_layer(bs, cs, cosd, isind, ncos);
@@ -175,8 +184,9 @@ __device__ __forceinline__ CoatCoefficients coat_stack(const CoatingTables& tb, 
     r.zp = cx_div(cx_sub(cp, cx_scale(bp, eta0p)), den_p);
     r.tir = far.im == 0.0 && far.re * far.re < q;
   } else {  // (power-normalised: sqrt(Re eta_far / eta_near))
-    r.zs = cx_scale(cx_div(Cx{2.0 * eta0s, 0.0}, den_s), sqrt(far_s.re / eta0s));
-    r.zp = cx_scale(cx_div(Cx{2.0 * eta0p, 0.0}, den_p), sqrt(far_p.re / eta0p));
+    const double dim = exp(-damping);
+    r.zs = cx_scale(cx_div(Cx{2.0 * eta0s, 0.0}, den_s), sqrt(far_s.re / eta0s) * dim);
+    r.zp = cx_scale(cx_div(Cx{2.0 * eta0p, 0.0}, den_p), sqrt(far_p.re / eta0p) * dim);
   }
   if (!(finite && cx_finite(r.zs) && cx_finite(r.zp))) r.invalid = true;
   r.tir = r.tir && !r.invalid;

@@ -90,8 +90,10 @@ def project_coefficients(raw, reflection):
     return ts * np.sqrt(far_s.real / near_s.real), tp * np.sqrt(far_p.real / near_p.real)
 
 
-def interface_coefficients(stack, ni, nt, cos_i, reflection, lam, formulation=matrix_coefficients):
-    """(cs, cp, total internal reflection?) of a coated interface, or None where the definitions call it invalid."""
+def interface_coefficients(stack, ni, nt, cos_i, reflection, lam, formulation=matrix_coefficients, sin2=None):
+    """(cs, cp, total internal reflection?) of a coated interface, or None where the definitions call it invalid.  A
+    formulation with a method `projected` (tests/thinfilm_reference.py) takes sin^2 of the angle of incidence as the
+    kernel has it, |ui x N|^2, as well, projects for itself and adds a fourth number, its margin."""
     if not (np.isfinite(lam) and lam > 0):
         return None
     ambient = index(stack.ambient, lam)
@@ -110,12 +112,18 @@ def interface_coefficients(stack, ni, nt, cos_i, reflection, lam, formulation=ma
     values = [far] + [n for n, _ in layers]
     if not np.all(np.isfinite(values)):
         return None
+    extra = ()
     with np.errstate(all="ignore"):
-        cs, cp = project_coefficients(formulation(ni, cos_i, far, layers, lam), reflection)
+        if hasattr(formulation, "projected"):
+            cs, cp, margin = formulation.projected(ni, cos_i, 1.0 - cos_i * cos_i if sin2 is None else sin2, far, layers,
+                                                   lam, reflection)
+            extra = (margin,)
+        else:
+            cs, cp = project_coefficients(formulation(ni, cos_i, far, layers, lam), reflection)
     if not (np.isfinite(cs) and np.isfinite(cp)):
         return None
     invariant = ni * np.sqrt(1.0 - cos_i * cos_i)
-    return cs, cp, bool(reflection and far.imag == 0 and far.real < invariant)
+    return (cs, cp, bool(reflection and far.imag == 0 and far.real < invariant)) + extra
 
 
 def transverse_basis(u):
@@ -138,13 +146,15 @@ def stokes(direction, ea):
 
 def fresnel(frame, polarization=None, lossless=(), coatings=None, formulation=matrix_coefficients):
     """Everything prt_frame_fresnel_coated reports for a frame given as (n_rows, 15): transmittance (n_rows), field
-    (6, n_rows) complex and the six counters.  coatings: {surface id: Stack or Coating}."""
+    (6, n_rows) complex and the six counters.  coatings: {surface id: Stack or Coating}.  `margin` (n_rows): the sum of
+    the margins of the coated interfaces a ray has crossed, zero with a formulation that states none."""
     frame = np.asarray(frame, dtype=np.float64)
     coatings = coatings or {}
     n_rows = len(frame)
     generation = frame[:, IX["generation"]].astype(np.int64)
     t_out = np.full(n_rows, np.nan)
     field = np.full((6, n_rows), np.nan + 0j)
+    margin = np.zeros(n_rows)
     names = ("n_reflections", "n_lossless", "n_undeviated", "n_invalid", "n_coated", "n_tir")
     count = dict.fromkeys(names, 0)
     previous = {}
@@ -176,6 +186,7 @@ def fresnel(frame, polarization=None, lossless=(), coatings=None, formulation=ma
             is_lossless = surface in lossless
             count["n_lossless"] += int(is_lossless)
             ea, eb, t = field[:3, before], field[3:, before], t_out[before]
+            margin[row] = margin[before]
             d = ui - ut
             dd = d @ d
             bad = not (dd < np.inf and 0 < ni < np.inf and 0 < nt < np.inf)
@@ -203,12 +214,14 @@ def fresnel(frame, polarization=None, lossless=(), coatings=None, formulation=ma
                 if surface in coatings:
                     count["n_coated"] += 1
                     from_fields = True
+                    x = np.cross(ui, normal)
                     found = None if bad else interface_coefficients(coatings[surface], ni, nt, min(cos_i, 1.0), reflection,
-                                                                    frame[before, IX["wavelength"]], formulation)
+                                                                    frame[before, IX["wavelength"]], formulation, x @ x)
                     if found is None:
                         bad = True
                     else:
-                        cs, cp, tir = found
+                        cs, cp, tir = found[:3]
+                        margin[row] += sum(found[3:])
                         count["n_tir"] += int(tir)
                 if not bad:
                     x = np.cross(ui, normal)
@@ -228,7 +241,7 @@ def fresnel(frame, polarization=None, lossless=(), coatings=None, formulation=ma
             if not (bad or was_dead):
                 field[:3, row], field[3:, row], t_out[row] = ea, eb, t
         previous = now
-    return dict(transmittance=t_out, field=field, **count)
+    return dict(transmittance=t_out, field=field, margin=margin, **count)
 
 
 def launch(raw, u0, polarization):
