@@ -641,6 +641,11 @@ int prt_frame_wavefront(int device, const double* rows, int64_t ld, int64_t n_ro
  * Amplitude factors of the Huygens-Fresnel integral other than 1/lambda (the obliquity factor, 1/r) are taken as
  *   constant over the pupil: the error is of the order of NA^2 at the rim.  Each ray stands for an equal share of the
  *   pupil's area, or carries its share in w; random pupil samples give a noise floor of about 1 / (number of rays).
+ * Accuracy: the phase is reduced in fp64 and its sine and cosine come from the fp32 instructions, so a ray's phasor is
+ *   within eps = 3e-7 + 2 pi 2^-25 + 16 pi ulp(R / lambda_w) of the definition's (3e-7: twice the instructions' measured
+ *   error) and a bucket's normalised intensity within 2 eps sqrt(I) + eps^2: about 1e-6 at the peak, 2e-13 where the
+ *   image is dark.  The Strehl ratio is summed with fp64 sines and cosines: within 4 pi 2 ulp(R / lambda_w) and a few
+ *   hundred ulps.  tests/diffraction_reference.py derives both and states what is counted.
  *
  * prt_frame_psf: wavelengths_um (HOST, n_wavelengths <= 16 distinct values, finite and > 0) lists every wavelength of
  * the selected rows (a row of another wavelength: PRT_ERR_ARG once the passes have run); nx, ny in 1..1024; du, dv
@@ -681,6 +686,10 @@ int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t n_rows, do
  * OTF: OTF_g(delta, theta, nu) = sum_r w_r exp(-2 pi i k.x_r(delta)) / sum_r w_r.  Wavelengths are not separated: the
  *   geometric MTF is polychromatic through the weights.  The MTF is |OTF| and the PTF is arg OTF, about C_g.  A group
  *   with no rays, or with sum w = 0, gives NaN.
+ * Accuracy: the phase k.x is formed and reduced in fp64, its sine and cosine come from the fp32 instructions with the
+ *   conversion's rounding put back to first order: |OTF - definition| <= 3e-7 + 2e-14 + 2 pi 13 2^-53 T, T the weighted
+ *   mean of the magnitudes of the phase's terms in cycles (3e-7: twice the instructions' measured error).
+ *   tests/diffraction_reference.py derives it and states what is counted.
  *
  * prt_frame_mtf: reference DEVICE (n_groups, 3) or NULL for the centroids; axes HOST 9 doubles; frequencies (HOST,
  * 1..4096, finite and >= 0), azimuths_deg (HOST, 1..16, finite), focus (HOST, 1..256 shifts delta, finite);

@@ -228,3 +228,54 @@ def host_rank_worker(rank, world, port, name, n, mode, result_dir, gpu_ranks):
         np.save(os.path.join(result_dir, f"counts_{rank}.npy"), np.array(full_counts))
     finally:
         dist.destroy_process_group()
+
+
+def psf_synthetic_frame(n=3000, seed=5):
+    """Three generations of rays through an index-1.5 slab converging near a focus, two wavelengths, varied weights."""
+    rng = np.random.default_rng(seed)
+    ids = np.sort(rng.choice(4 * n, n, replace=False)).astype(float)
+    r, t = np.sqrt(rng.random(n)), rng.random(n) * 2 * np.pi
+    p0 = np.stack([np.full(n, -5.0), r * np.cos(t), r * np.sin(t)], 1)
+    p1 = p0 + np.array([4.0, 0, 0])
+    p2 = p1 + np.array([0.5, 0, 0])
+    focus = np.array([10.0, 0.02, -0.01])
+    dirn = focus - p2
+    dirn /= np.linalg.norm(dirn, axis=1)[:, None]
+    p3 = p2 + dirn * ((focus[0] + 0.3 - p2[:, 0]) / dirn[:, 0])[:, None] + rng.normal(0, 2e-5, (n, 3)) * [0, 1, 1]
+    wavelength = np.where(rng.random(n) < 0.5, 0.55, 0.65)
+    rows = []
+    for g, (a, b, index, surf) in enumerate(((p0, p1, 1.0, 1.0), (p1, p2, 1.5, 2.0), (p2, p3, 1.0, 5.0))):
+        u = (b - a) / np.linalg.norm(b - a, axis=1)[:, None]
+        block = np.zeros((n, 15))
+        block[:, 0], block[:, 1], block[:, 2], block[:, 3] = g, 50 + 50 * rng.random(n), wavelength, index
+        block[:, 4], block[:, 5], block[:, 6:9], block[:, 9:12], block[:, 12:15] = ids, surf, a, b, u
+        rows.append(block)
+    return np.concatenate(rows)
+
+
+def mtf_synthetic_frame(n=3000, seed=7):
+    """Two generations; the second ends near a focus at surface 5 along a tilted axis, varied weights, and a few rows
+    that must be left out: NaN end points, a NaN weight, directions perpendicular to the axis."""
+    rng = np.random.default_rng(seed)
+    ids = np.sort(rng.choice(4 * n, n, replace=False)).astype(float)
+    axis = np.array([1.0, 0.2, 0.0]) / np.linalg.norm([1.0, 0.2, 0.0])  # (u = z is exactly perpendicular to it)
+    start = rng.normal(0, 1, (n, 3)) * 0.5 - 5 * axis
+    focus = np.array([0.01, -0.02, 0.03])
+    u = focus - start + rng.normal(0, 2e-3, (n, 3))
+    end = start + u * (0.98 + 0.04 * rng.random(n))[:, None]
+    rows = []
+    for g, (a, b, surf) in enumerate(((start - u, start, 2.0), (start, end, 5.0))):
+        block = np.zeros((n, 15))
+        block[:, 0], block[:, 1], block[:, 2], block[:, 3] = g, 50 + 50 * rng.random(n), 0.55, 1.0
+        block[:, 4], block[:, 5], block[:, 6:9], block[:, 9:12], block[:, 12:15] = ids, surf, a, b, b - a
+        rows.append(block)
+    frame = np.concatenate(rows)
+    last = frame[:, 0] == 1
+    picks = np.flatnonzero(last)[[3, 10, 500, 2000, 2900]]
+    frame[picks[0], 10] = np.nan
+    frame[picks[1], 1] = np.nan
+    perpendicular = np.array([0.0, 0.0, 1.0])
+    frame[picks[2], 12:15] = perpendicular
+    frame[picks[3], 12:15] = perpendicular * 3
+    frame[picks[4], 14] = np.inf
+    return frame, axis

@@ -5,6 +5,7 @@ bit, and run twice for bit-identical outputs."""
 import numpy as np
 import pytest
 
+import diffraction_reference
 import helpers
 import scenes
 
@@ -85,35 +86,23 @@ def check_mtf(frame, device, surface, frequencies, **options):
     assert np.nanmax(np.abs(got.otf - otf)) <= 1e-6
     np.testing.assert_allclose(got.centre, centre, rtol=0, atol=1e-12, equal_nan=True)
     assert np.array_equal(got.n_rays, used) and np.array_equal(got.n_missed, missed)
+    # ... and every output against the longdouble reference, within the derived budget (tests/diffraction_reference.py),
+    # which on these frames is tighter than the flat 1e-6 (tests/test_host_diffraction_reference.py)
+    from pyrayt_amd.frame import pupil_axes
+
+    rows, groups = diffraction_reference.select_rows(frame, surface, options.get("rays_per_source"), n_groups)
+    weight = np.ones(len(rows)) if options.get("weights", "intensity") is None else rows[:, IX[options.get("weights", "intensity")]]
+    ref = diffraction_reference.mtf_reference(rows[:, 9:12], rows[:, 12:15], weight, groups, n_groups,
+                                              np.asarray(frequencies, dtype=float), options.get("azimuths", (0.0, 90.0)),
+                                              options.get("focus", (0.0,)), pupil_axes() if axes is None else axes,
+                                              centre=got.centre)
+    held = ~np.isnan(otf)
+    assert np.all(diffraction_reference.otf_deviation(got.otf, ref)[held] <= ref.bound[held]) and ref.bound[held].max() < 1e-6
+    assert np.array_equal(got.n_rays, ref.n_rays) and np.array_equal(got.n_missed, ref.n_missed)
     return got
 
 
-def synthetic_frame(n=3000, seed=7):
-    """Two generations; the second ends near a focus at surface 5 along a tilted axis, varied weights, and a few rows
-    that must be left out: NaN end points, a NaN weight, directions perpendicular to the axis."""
-    rng = np.random.default_rng(seed)
-    ids = np.sort(rng.choice(4 * n, n, replace=False)).astype(float)
-    axis = np.array([1.0, 0.2, 0.0]) / np.linalg.norm([1.0, 0.2, 0.0])  # (u = z is exactly perpendicular to it)
-    start = rng.normal(0, 1, (n, 3)) * 0.5 - 5 * axis
-    focus = np.array([0.01, -0.02, 0.03])
-    u = focus - start + rng.normal(0, 2e-3, (n, 3))
-    end = start + u * (0.98 + 0.04 * rng.random(n))[:, None]
-    rows = []
-    for g, (a, b, surf) in enumerate(((start - u, start, 2.0), (start, end, 5.0))):
-        block = np.zeros((n, 15))
-        block[:, 0], block[:, 1], block[:, 2], block[:, 3] = g, 50 + 50 * rng.random(n), 0.55, 1.0
-        block[:, 4], block[:, 5], block[:, 6:9], block[:, 9:12], block[:, 12:15] = ids, surf, a, b, b - a
-        rows.append(block)
-    frame = np.concatenate(rows)
-    last = frame[:, 0] == 1
-    picks = np.flatnonzero(last)[[3, 10, 500, 2000, 2900]]
-    frame[picks[0], IX["y1"]] = np.nan
-    frame[picks[1], IX["intensity"]] = np.nan
-    perpendicular = np.array([0.0, 0.0, 1.0])
-    frame[picks[2], 12:15] = perpendicular
-    frame[picks[3], 12:15] = perpendicular * 3
-    frame[picks[4], IX["z_tilt"]] = np.inf
-    return frame, axis
+synthetic_frame = helpers.mtf_synthetic_frame
 
 
 def test_mtf_against_numpy_on_a_synthetic_frame():

@@ -7,6 +7,7 @@ import math
 import numpy as np
 import pytest
 
+import diffraction_reference
 import helpers
 import scenes
 
@@ -77,30 +78,23 @@ def check_psf(frame, device, surface, unit, **options):
     np.testing.assert_allclose(got.image_by_wavelength, image, rtol=0, atol=1e-5, equal_nan=True)
     np.testing.assert_allclose(got.image, image.sum(axis=1), rtol=0, atol=2e-5, equal_nan=True)
     np.testing.assert_allclose(got.strehl, strehl, rtol=0, atol=1e-9, equal_nan=True)
+    # ... and every pixel against the longdouble reference, within the derived budget (tests/diffraction_reference.py),
+    # which on these frames is tighter than the flat figures above (tests/test_host_diffraction_reference.py)
+    n_groups = options.get("n_groups", 1)
+    inputs = diffraction_reference.psf_inputs_from(frame, got, surface, options.get("rays_per_source"), n_groups,
+                                                   options.get("weights", "intensity"))
+    ref = diffraction_reference.psf_reference(inputs)
+    for value, want, bound in ((got.image_by_wavelength, ref.image_by_wavelength, ref.bound_by_wavelength),
+                               (got.image, ref.image, ref.bound), (got.strehl, ref.strehl, ref.strehl_bound)):
+        nan = np.isnan(want.astype(float))
+        assert np.array_equal(np.isnan(value), nan)
+        assert np.all(np.abs(value.astype(np.longdouble) - want)[~nan] <= bound[~nan])
+    assert np.nanmax(ref.bound_by_wavelength) < 1e-5 and np.nanmax(ref.bound) < 2e-5 and np.nanmax(ref.strehl_bound) < 1e-9
+    assert np.array_equal(got.record[:, :, 0], ref.n_rays) and np.array_equal(got.record[:, :, 1], ref.n_missed)
     return got
 
 
-def synthetic_frame(n=3000, seed=5):
-    """Three generations of rays through an index-1.5 slab converging near a focus, two wavelengths, varied weights."""
-    rng = np.random.default_rng(seed)
-    ids = np.sort(rng.choice(4 * n, n, replace=False)).astype(float)
-    r, t = np.sqrt(rng.random(n)), rng.random(n) * 2 * np.pi
-    p0 = np.stack([np.full(n, -5.0), r * np.cos(t), r * np.sin(t)], 1)
-    p1 = p0 + np.array([4.0, 0, 0])
-    p2 = p1 + np.array([0.5, 0, 0])
-    focus = np.array([10.0, 0.02, -0.01])
-    dirn = focus - p2
-    dirn /= np.linalg.norm(dirn, axis=1)[:, None]
-    p3 = p2 + dirn * ((focus[0] + 0.3 - p2[:, 0]) / dirn[:, 0])[:, None] + rng.normal(0, 2e-5, (n, 3)) * [0, 1, 1]
-    wavelength = np.where(rng.random(n) < 0.5, 0.55, 0.65)
-    rows = []
-    for g, (a, b, index, surf) in enumerate(((p0, p1, 1.0, 1.0), (p1, p2, 1.5, 2.0), (p2, p3, 1.0, 5.0))):
-        u = (b - a) / np.linalg.norm(b - a, axis=1)[:, None]
-        block = np.zeros((n, 15))
-        block[:, 0], block[:, 1], block[:, 2], block[:, 3] = g, 50 + 50 * rng.random(n), wavelength, index
-        block[:, 4], block[:, 5], block[:, 6:9], block[:, 9:12], block[:, 12:15] = ids, surf, a, b, u
-        rows.append(block)
-    return np.concatenate(rows)
+synthetic_frame = helpers.psf_synthetic_frame
 
 
 def test_psf_against_numpy_on_a_synthetic_frame():
