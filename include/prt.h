@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -1040,6 +1040,71 @@ int prt_frame_fresnel_coated(int device, const double* rows, int64_t ld, const i
                              const int32_t* has_substrate, const double* thicknesses, const double* wavelengths,
                              int n_wavelengths, const double* indices, double* transmittance_out, double* field_out,
                              int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Sensitivities of the frame: differential ray tracing (no counterpart upstream) -----------------------------------
+ * d(landing point)/d(parameter) of every ray, for K rigid motions of surfaces, from ONE trace: the rows of a ray, joined
+ * by id, are its whole path, `surface` names the primitive each segment ended on, and the surface table below says what
+ * that primitive is.  A tangent (do, dd) per ray and parameter is pushed through the recorded interfaces.  The result is
+ * the derivative AT FIXED PATH, as in every differential ray trace: a ray whose sequence of surfaces changes under the
+ * motion (the edge of an aperture) is outside it.  Sources do not move; shape and index parameters and derivatives of
+ * anything but the landing point and its moments (the optical path, for one) are not computed.
+ *
+ * Definitions.
+ * Frame: whole and generation-major, ids as prt_frame_optical_path wants them (a repeated id, an id out of range, a row
+ *   in generation g without one in g - 1: PRT_ERR_ARG through the status word).
+ * Surface table: n_surfaces prt_prim records (type, normal_scale, params, minv; `material` is not read), ascending in
+ *   surface_id, ids distinct.
+ * Parameter k: a twist (v, w, c), 9 doubles, and a list of at most 64 surface ids of the table (parameter_ids
+ *   [parameter_first[k], parameter_first[k + 1])).  A moved surface has the velocity u = v + w x (x - c) at x per unit
+ *   parameter; every other surface has u = 0.
+ * A row: start o = (x0, y0, z0), unit direction d = tilt / |tilt|, landing point x = (x1, y1, z1), t = (x - o).d, and n
+ *   the world normal of the row's primitive at x, as the trace computes it, turned against d (n.d < 0).
+ * Landing, per parameter, from the segment's (do, dd):  dt = n.(u - do - t dd) / (n.d),  dx = do + t dd + d dt.
+ *   Generation 0: do = dd = 0.
+ * Normal: dn = w x n (only where the surface is moved) + W (dx - u), W = s (I - n n^T) A^T H A / |A^T g|, A the 3x3 of
+ *   minv, g half the gradient of the primitive's implicit function in object coordinates at A x + b, H half its Hessian
+ *   (sphere: I; cylinder wall and paraboloid: diag(1, 1, 0); planes, cube faces and end caps: 0), s = normal_scale,
+ *   negated where n was turned.
+ * Interface between a ray's row in g - 1 (d, n, dn there, index ni) and its row in g (d', index nt), eps_dir = 1e-12:
+ *   refraction, ni != nt: mu = ni / nt, ci = -n.d, ct = sqrt(1 - mu^2 (1 - ci^2)), gamma = mu ci - ct;
+ *     dci = -(dn.d + n.dd), dct = mu^2 ci dci / ct, dd' = mu dd + (mu dci - dct) n + gamma dn;
+ *   reflection, ni == nt and |d - d'|^2 > eps_dir: dd' = dd - 2 [(dd.n + d.dn) n + (d.n) dn];
+ *   undeviated: dd' = dd.
+ *   The rows must fit the rule: |mu d + gamma n - d'|^2 <= eps_dir for a refraction, |d + 2 ci n - d'|^2 <= eps_dir for
+ *   a reflection; a ray whose rows fit neither (a caller-shaded surface) is NaN from there on and counts as unfit.
+ * Next segment: it starts at x + 1e-6 d', so do' = dx + 1e-6 dd'.  dd' is tangent to the unit sphere analytically and is
+ *   not renormalised.
+ * Rays that end: a ray absent from a generation ends; its state is never read again.  A row whose surface is not in the
+ *   table makes the ray NaN from there on (unknown); so does a row that is not finite or has n.d = 0, or an index that
+ *   is not finite and > 0 (invalid).  Each ray is counted once.
+ * Selection: row_slot DEVICE n_rows int64: the position of a selected row in the outputs, -1 for the others;
+ *   selected DEVICE n_selected int64: the rows in output order; group_first HOST n_groups + 1 int64: the outputs of
+ *   group q are [group_first[q], group_first[q + 1]).  The sums run in that order, so a caller that orders the selection
+ *   by (group, generation, id) gets the same bits under any order of the rows inside a generation.
+ * Sums, per group, E = 6 + 4 K + K (K + 1) / 2 doubles, over the selected rows whose weight, landing point and 3 K
+ *   derivatives are all finite, w = the weight column's value or 1 (weight_column < 0):  count, sum w, sum w x (3),
+ *   sum w |x - pivot|^2, sum w dx_k (k-major, 3 K), sum w (x - pivot).dx_k (K; pivots HOST (n_groups, 3)), sum w dx_j.dx_k for k <= j (row-major
+ *   lower triangle).  Each workgroup writes the partial sums of its 256 outputs; a second kernel adds a group's partials
+ *   in a fixed order (a wave an entry: lane l takes partials l, l + 64, ..., then the lanes are added pairwise).
+ *
+ * prt_frame_sensitivity: out, overwritten: jacobian_out DEVICE (K, 3, n_selected) doubles; sums_out DEVICE (n_groups, E);
+ * record_out HOST 4 int64: unknown, invalid, unfit rays, reflections.  workspace:
+ * prt_frame_sensitivity_workspace_bytes(n_ids, n_surfaces, K, n_groups, max rows of a group) device bytes (-1 for
+ * arguments the call would refuse): the table, per id 48 K bytes of state, its previous row and a stamp, the partials.
+ * Caps: K in [1, 16], n_ids in [1, 2^31], n_groups in [1, 65535], a generation's rows fit one launch; PRT_ERR_ARG
+ * otherwise, never a truncated result, nothing written out of bounds.  One launch per generation in order on the stream,
+ * one row a thread, the loop over the parameters inside the thread with its state in memory; no two lanes touch one
+ * ray's state; no floating-point atomics; every output is the same bits on every run, and the result for a parameter does
+ * not depend on which others are in the call.  All arguments are checked before a device is touched.  Stream-ordered; the
+ * call reads the status word and the counters back and so returns when the stream has reached its end. */
+int64_t prt_frame_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                                              int64_t max_group_rows);
+int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                          int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
+                          const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
+                          int n_parameters, const int64_t* row_slot, const int64_t* selected, int64_t n_selected,
+                          const int64_t* group_first, int n_groups, int weight_column, const double* pivots,
+                          double* jacobian_out, double* sums_out, int64_t* record_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

@@ -1,0 +1,529 @@
+// prt_sensitivity.hpp -- sensitivities of the frame, on the device: differential ray tracing.  A
+// tangent (d position, d direction) per ray and parameter is pushed through the interfaces the ray's rows describe; out
+// comes d(landing point)/d(parameter) of the selected rows and, per group, the sums a least-squares step needs.  It uses
+// the join by ray id (prt_join.hpp) and has the Fresnel pass's shape: one launch per generation, one row a thread.
+// Definitions: include/prt.h.
+//
+//   sens_row        the work of one row.  Per id: the stamp, the row it had in the previous generation (negative: the ray
+//                   cannot be followed any more) and, per parameter, six planes of doubles: dx of the ray's last landing
+//                   point and dd of the segment that ended there.  A row of generation g >= 1 reads its ray's previous
+//                   row, finishes that row's interface (refraction, reflection, none), starts the new segment 1e-6 along
+//                   the new direction and lands it on its own surface.  Everything that does not depend on the parameter
+//                   (both normals, the curvature operator of the previous surface, the interface's kind) is worked out
+//                   once, in registers; the loop over the parameters runs inside the thread with its state in memory, so
+//                   the register count does not grow with K.
+//   k_sens_step     one launch per generation, in generation order on one stream: sens_row, then the counters
+//   k_sens_partials the group sums of the selected rows as per-workgroup partials, written in workgroup order
+//   k_sens_fold     the partials of a group added in a fixed order: one wave per (group, entry)
+// n, and the decision "wall or cap", come from the functions the trace uses: world_normal_len and object_normal of
+// prt_device.hpp.  No two lanes touch one ray's state, there are no floating-point atomics; the sums run over the
+// selection in the order the caller gave it (pyrayt_amd gives (group, generation, id)), so they do not depend on the
+// order of the rows within a generation.  The library is built with -ffp-contract=off.
+// Two things are not as the first design had them.  The surface table is NOT read through the scalar cache as the
+// coating tables are: those are at most 64 entries in the kernel arguments, scanned by every lane alike; this table has
+// no such cap (a system of a hundred lenses has three hundred surfaces) and the lanes of a wave meet different surfaces,
+// so each lane bisects the table in the workspace and loads its own 200-byte entry with vector loads, which hit in the
+// cache after the first wave.  And k_sens_partials keeps 206 x 4 doubles (6.5 KB) of LDS so that a workgroup needs one
+// barrier for all its entries instead of two an entry; k_sens_step itself uses the 64 bytes of the counters and no more.
+#pragma once
+
+enum { SENS_BAD_SELECTION = JOIN_OWN_BIT };
+enum { SENS_MAX_PARAMETERS = 16, SENS_MAX_IDS = 64, SENS_COUNTERS = 4, SENS_FIXED = 6 };
+enum { SENS_MAX_ENTRIES = SENS_FIXED + 4 * SENS_MAX_PARAMETERS + SENS_MAX_PARAMETERS * (SENS_MAX_PARAMETERS + 1) / 2 };
+static const int kSensBlock = 256;
+static const int kSensWaves = kSensBlock / 64;
+#define PRT_SENS_EPS_DIR 1e-12   // eps_dir of include/prt.h, as in the Fresnel pass
+#define PRT_SENS_OFFSET 1e-6     // the relaunch offset
+
+// a surface of the table: the fields of prt_prim that world_normal_len reads, and which parameters move it (bit k)
+struct SensSurface {
+  double minv[16];
+  double params[6];
+  double surface_id;
+  int32_t type, normal_scale;
+  uint32_t moved_by;
+  int32_t pad;
+};
+struct SensTwist { double v[3], w[3], c[3]; };
+struct SensArgs { SensTwist twist[SENS_MAX_PARAMETERS]; int n_parameters, n_surfaces; };
+struct SensWords { u64 count[SENS_COUNTERS]; int status; };  // unknown, invalid, unfit, reflections
+struct SensVec { double x, y, z; };
+
+__device__ __forceinline__ double sv_dot(const SensVec& a, const SensVec& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ SensVec sv_cross(const SensVec& a, const SensVec& b) {
+  return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
+}
+__device__ __forceinline__ SensVec sv_sub(const SensVec& a, const SensVec& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ SensVec sv_add(const SensVec& a, const SensVec& b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ SensVec sv_scale(double c, const SensVec& a) { return {c * a.x, c * a.y, c * a.z}; }
+__device__ __forceinline__ SensVec sv_col(const double* __restrict__ rows, int64_t ld, int first, int64_t j) {
+  return {rows[first * ld + j], rows[(first + 1) * ld + j], rows[(first + 2) * ld + j]};
+}
+__device__ __forceinline__ bool sv_finite(const SensVec& a) { return is_finite(a.x) && is_finite(a.y) && is_finite(a.z); }
+
+// the table's entry of a surface id (ascending ids), or -1
+__device__ __forceinline__ int sens_find(const SensSurface* __restrict__ table, int n, double surface) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (table[mid].surface_id < surface) lo = mid + 1; else hi = mid;
+  }
+  return lo < n && table[lo].surface_id == surface ? lo : -1;
+}
+
+// A surface met at x by a ray along the unit vector d: n is the trace's world normal turned against d, nd = n.d < 0.
+// The curvature operator dn = sign * (m - n (n.m)), m = A^T (h * (A y)) / denom for y = dx - u, is kept as h, sign
+// and denom; h == 0 on flat pieces.
+struct SensHit {
+  SensVec n;
+  double nd, sign, denom;
+  int h;  // bit r: row r of A enters the Hessian (sphere 7, cylinder wall and paraboloid 3, flat 0)
+  bool ok;
+};
+
+__device__ __forceinline__ SensHit sens_hit(const SensSurface* __restrict__ s, const SensVec& x, const SensVec& d) {
+  SensHit hit;
+  double len;
+  world_normal_len(s, x.x, x.y, x.z, 1.0, hit.n.x, hit.n.y, hit.n.z, len);
+  const double lx = row_dot(s->minv, 0, x.x, x.y, x.z, 1.0);
+  const double ly = row_dot(s->minv, 1, x.x, x.y, x.z, 1.0);
+  const double lz = row_dot(s->minv, 2, x.x, x.y, x.z, 1.0);
+  double ax, ay, az;
+  object_normal(s->type, s->params, lx, ly, lz, ax, ay, az);  // (wall or cap: what the trace decided)
+  double g = 1.0;
+  hit.h = 0;
+  if (s->type == PRIM_SPHERE) {
+    hit.h = 7;
+    g = norm3(lx, ly, lz);
+  } else if (s->type == PRIM_CYLINDER && az == 0.0) {
+    hit.h = 3;
+    g = norm3(lx, ly, 0.0);
+  } else if (s->type == PRIM_PARABOLOID && az < 0.0) {
+    hit.h = 3;
+    g = norm3(lx, ly, 2 * s->params[0]);
+  }
+  hit.denom = len * g;
+  hit.sign = (double)s->normal_scale;
+  hit.nd = sv_dot(hit.n, d);
+  if (hit.nd > 0.0) {
+    hit.n = {-hit.n.x, -hit.n.y, -hit.n.z};
+    hit.nd = -hit.nd;
+    hit.sign = -hit.sign;
+  }
+  hit.ok = hit.nd < 0.0 && hit.nd >= -2.0 && (hit.h == 0 || (hit.denom > 0.0 && hit.denom < PRT_INF));
+  return hit;
+}
+
+// the velocity of surface s under parameter k at x: v + w x (x - c) where k moves s, else 0
+__device__ __forceinline__ SensVec sens_velocity(const SensTwist& tw, bool moved, const SensVec& x) {
+  if (!moved) return {0.0, 0.0, 0.0};
+  const SensVec r = {x.x - tw.c[0], x.y - tw.c[1], x.z - tw.c[2]};
+  const SensVec w = {tw.w[0], tw.w[1], tw.w[2]};
+  const SensVec t = sv_cross(w, r);
+  return {tw.v[0] + t.x, tw.v[1] + t.y, tw.v[2] + t.z};
+}
+
+enum { SENS_NONE = 0, SENS_REFRACT = 1, SENS_REFLECT = 2 };
+
+// row j of `generation`; flag: what the row adds to the counters
+__device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t j,
+                                         int generation, double id0, int64_t n_ids, const SensArgs& args,
+                                         const SensSurface* __restrict__ table, double* __restrict__ state,
+                                         int64_t* __restrict__ last_row, int* __restrict__ stamp, int* status,
+                                         const int64_t* __restrict__ row_slot, int64_t n_selected,
+                                         double* __restrict__ jacobian, bool (&flag)[SENS_COUNTERS]) {
+  const double nan = __longlong_as_double(0x7ff8000000000000ll);
+  const int K = args.n_parameters;
+  bool unknown = false, invalid = false, unfit = false, reflection = false;
+  int64_t slot = row_slot[j];
+  if (slot >= n_selected) { atomicOr(status, SENS_BAD_SELECTION); slot = -1; }
+  const int64_t i = join_id(rows, ld, j, id0, n_ids);
+  bool joined = false, dead = true;
+  if (i < 0) {
+    atomicOr(status, JOIN_BAD_ID);
+  } else {
+    const int bits = join_status(join_claim(stamp, i, generation), generation);
+    joined = !bits;
+    if (bits) atomicOr(status, bits);
+  }
+  if (joined) {
+    int64_t p = -1;
+    bool was_dead = false;
+    if (generation > 0) {
+      p = last_row[i];  // (written by the launch of generation - 1: the stamp said so)
+      was_dead = p < 0;
+      p = was_dead ? -1 - p : p;
+      p = p < n_rows ? p : j;
+    }
+    // this row: start, unit direction, landing point, surface
+    const SensVec o = sv_col(rows, ld, PRT_COL_X0, j), x = sv_col(rows, ld, PRT_COL_X1, j);
+    const SensVec raw = sv_col(rows, ld, PRT_COL_XTILT, j);
+    const double mm = sv_dot(raw, raw);
+    const SensVec d = sv_scale(1.0 / sqrt(mm), raw);
+    const SensVec run = sv_sub(x, o);
+    const double t = sv_dot(run, d);
+    const int e = sens_find(table, args.n_surfaces, rows[PRT_COL_SURFACE * ld + j]);
+    SensHit here = {};
+    if (!(mm > 0.0 && mm < PRT_INF && sv_finite(o) && sv_finite(x))) {
+      invalid = true;
+    } else if (e < 0) {
+      unknown = true;
+    } else {
+      here = sens_hit(table + e, x, d);
+      invalid = !here.ok;
+    }
+    const uint32_t moved_here = e >= 0 ? table[e].moved_by : 0u;
+    // the interface behind the previous row
+    int kind = SENS_NONE;
+    SensVec xp = {0, 0, 0}, dp = {0, 0, 0};
+    SensHit there = {};
+    double mu = 1.0, ci = 0.0, ct = 0.0, gamma = 0.0;
+    double a0[3] = {0, 0, 0}, a1[3] = {0, 0, 0}, a2[3] = {0, 0, 0};
+    uint32_t moved_there = 0u;
+    if (generation > 0 && !was_dead && !invalid && !unknown) {
+      xp = sv_col(rows, ld, PRT_COL_X1, p);
+      const SensVec rawp = sv_col(rows, ld, PRT_COL_XTILT, p);
+      dp = sv_scale(1.0 / sqrt(sv_dot(rawp, rawp)), rawp);
+      const double ni = rows[PRT_COL_INDEX * ld + p], nt = rows[PRT_COL_INDEX * ld + j];
+      const int ep = sens_find(table, args.n_surfaces, rows[PRT_COL_SURFACE * ld + p]);
+      // (the previous row was landed by its own launch: its surface is in the table and its normal is good)
+      if (ep < 0 || !(ni > 0.0 && ni < PRT_INF && nt > 0.0 && nt < PRT_INF)) {
+        invalid = true;
+      } else {
+        const SensSurface* __restrict__ sp = table + ep;
+        there = sens_hit(sp, xp, dp);
+        moved_there = sp->moved_by;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { a0[c] = sp->minv[c]; a1[c] = sp->minv[4 + c]; a2[c] = sp->minv[8 + c]; }
+        const SensVec turn = sv_sub(dp, d);
+        const double dd = sv_dot(turn, turn);
+        ci = -there.nd;
+        SensVec want;
+        if (!there.ok || !(dd < PRT_INF)) {
+          invalid = true;
+          want = d;
+        } else if (ni != nt) {
+          kind = SENS_REFRACT;
+          mu = ni / nt;
+          const double radicand = 1.0 - (mu * mu) * (1.0 - ci * ci);
+          ct = sqrt(radicand);
+          gamma = mu * ci - ct;
+          want = sv_add(sv_scale(mu, dp), sv_scale(gamma, there.n));
+          unfit = !(radicand > 0.0);
+        } else if (dd <= PRT_SENS_EPS_DIR) {
+          want = d;
+        } else {
+          kind = SENS_REFLECT;
+          reflection = true;
+          want = sv_add(dp, sv_scale(2.0 * ci, there.n));
+        }
+        const SensVec miss = sv_sub(want, d);
+        unfit = !invalid && (unfit || !(sv_dot(miss, miss) <= PRT_SENS_EPS_DIR));
+        reflection = reflection && !unfit && !invalid;
+      }
+    }
+    dead = was_dead || invalid || unknown || unfit;
+    if (!dead) {
+#pragma unroll 1
+      for (int k = 0; k < K; ++k) {
+        const SensTwist& tw = args.twist[k];
+        SensVec dx = {0.0, 0.0, 0.0}, dd = {0.0, 0.0, 0.0}, start = {0.0, 0.0, 0.0};
+        if (generation > 0) {
+          double* __restrict__ s = state + (int64_t)k * 6 * n_ids + i;
+          dx = {s[0], s[n_ids], s[2 * n_ids]};
+          dd = {s[3 * n_ids], s[4 * n_ids], s[5 * n_ids]};
+          // dn = w x n (a moved surface) + W (dx - u)
+          const bool moved = (moved_there >> k) & 1u;
+          SensVec dn = {0.0, 0.0, 0.0};
+          if (there.h) {
+            const SensVec y = sv_sub(dx, sens_velocity(tw, moved, xp));
+            const double z0 = (there.h & 1) ? (a0[0] * y.x + a0[1] * y.y) + a0[2] * y.z : 0.0;
+            const double z1 = (there.h & 2) ? (a1[0] * y.x + a1[1] * y.y) + a1[2] * y.z : 0.0;
+            const double z2 = (there.h & 4) ? (a2[0] * y.x + a2[1] * y.y) + a2[2] * y.z : 0.0;
+            const SensVec m = {((a0[0] * z0 + a1[0] * z1) + a2[0] * z2) / there.denom,
+                               ((a0[1] * z0 + a1[1] * z1) + a2[1] * z2) / there.denom,
+                               ((a0[2] * z0 + a1[2] * z1) + a2[2] * z2) / there.denom};
+            const double along = sv_dot(there.n, m);
+            dn = sv_scale(there.sign, sv_sub(m, sv_scale(along, there.n)));
+          }
+          if (moved) dn = sv_add(sv_cross({tw.w[0], tw.w[1], tw.w[2]}, there.n), dn);
+          if (kind == SENS_REFRACT) {
+            const double dci = -(sv_dot(dn, dp) + sv_dot(there.n, dd));
+            const double dct = ((mu * mu) * ci) * dci / ct;
+            const double dgamma = mu * dci - dct;
+            dd = sv_add(sv_add(sv_scale(mu, dd), sv_scale(dgamma, there.n)), sv_scale(gamma, dn));
+          } else if (kind == SENS_REFLECT) {
+            const double turn = sv_dot(dd, there.n) + sv_dot(dp, dn);
+            const SensVec back = sv_add(sv_scale(turn, there.n), sv_scale(there.nd, dn));
+            dd = sv_sub(dd, sv_scale(2.0, back));
+          }
+          start = sv_add(dx, sv_scale(PRT_SENS_OFFSET, dd));
+        }
+        // the landing: dt = n.(u - do - t dd) / (n.d), dx = do + t dd + d dt
+        const SensVec u = sens_velocity(tw, (moved_here >> k) & 1u, x);
+        const SensVec reach = sv_add(start, sv_scale(t, dd));
+        const double dt = sv_dot(here.n, sv_sub(u, reach)) / here.nd;
+        dx = sv_add(reach, sv_scale(dt, d));
+        double* __restrict__ s = state + (int64_t)k * 6 * n_ids + i;
+        s[0] = dx.x; s[n_ids] = dx.y; s[2 * n_ids] = dx.z;
+        s[3 * n_ids] = dd.x; s[4 * n_ids] = dd.y; s[5 * n_ids] = dd.z;
+        if (slot >= 0) {
+          double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
+          out[0] = dx.x; out[n_selected] = dx.y; out[2 * n_selected] = dx.z;
+        }
+      }
+    }
+    // a ray is counted once: it is NaN from there on
+    unknown = unknown && !was_dead;
+    invalid = invalid && !was_dead && !unknown;
+    unfit = unfit && !was_dead;
+  }
+  if (dead && slot >= 0)
+    for (int k = 0; k < K; ++k) {
+      double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
+      out[0] = nan; out[n_selected] = nan; out[2 * n_selected] = nan;
+    }
+  if (i >= 0) last_row[i] = dead ? -1 - j : j;  // (also for a row the status word refuses: the next launch reads this one's)
+  flag[0] = unknown; flag[1] = invalid; flag[2] = unfit; flag[3] = reflection;
+}
+
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t start, int64_t count, int generation,
+            double id0, int64_t n_ids, SensArgs args, const SensSurface* __restrict__ table, double* __restrict__ state,
+            int64_t* __restrict__ last_row, int* __restrict__ stamp, SensWords* __restrict__ words,
+            const int64_t* __restrict__ row_slot, int64_t n_selected, double* __restrict__ jacobian) {
+  const int64_t j = start + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
+  bool flag[SENS_COUNTERS] = {};
+  if (j < start + count)
+    sens_row(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status, row_slot,
+             n_selected, jacobian, flag);
+  fresnel_count(flag, words->count);
+}
+
+// ---- the group sums ------------------------------------------------------------------------------------------------------
+// entries of a group, K parameters: count, sum w, sum w x (3), sum w |x - pivot|^2, sum w dx_k (3 K, k-major), sum w (x - pivot).dx_k (K),
+// sum w dx_j.dx_k for k <= j (K (K + 1) / 2, row-major lower triangle)
+static int sens_entries(int K) { return SENS_FIXED + 3 * K + K + K * (K + 1) / 2; }
+
+// what slot s (row r, finite throughout) adds to entry e
+__device__ __forceinline__ double sens_entry(int e, int K, double w, const SensVec& x, const SensVec& pivot,
+                                             const double* __restrict__ jacobian, int64_t n_selected, int64_t s) {
+  if (e == 0) return 1.0;
+  if (e == 1) return w;
+  if (e < 5) return w * (e == 2 ? x.x : e == 3 ? x.y : x.z);
+  if (e == 5) { const SensVec r = sv_sub(x, pivot); return w * sv_dot(r, r); }
+  e -= SENS_FIXED;
+  if (e < 3 * K) return w * jacobian[(int64_t)e * n_selected + s];
+  e -= 3 * K;
+  const auto column = [&](int k) -> SensVec {
+    const double* __restrict__ c = jacobian + (int64_t)k * 3 * n_selected + s;
+    return {c[0], c[n_selected], c[2 * n_selected]};
+  };
+  if (e < K) return w * sv_dot(sv_sub(x, pivot), column(e));
+  e -= K;
+  int row = 0;
+  while ((row + 1) * (row + 2) / 2 <= e) ++row;
+  return w * sv_dot(column(row), column(e - row * (row + 1) / 2));
+}
+
+// workgroup (chunk, group): slots [first[group] + 256 chunk, ...) of the group; its partial sums to
+// partials[(group * chunks + chunk) * entries + e], waves added in order
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_partials(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const int64_t* __restrict__ selected,
+                int64_t n_selected, const int64_t* __restrict__ first, int K, int weight_column,
+                const double* __restrict__ pivots, const double* __restrict__ jacobian, double* __restrict__ partials,
+                int* status) {
+  __shared__ double red[SENS_MAX_ENTRIES][kSensWaves];
+  const int group = blockIdx.y, entries = SENS_FIXED + 3 * K + K + K * (K + 1) / 2;
+  const int64_t s = first[group] + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
+  double* __restrict__ out = partials + ((int64_t)group * gridDim.x + blockIdx.x) * entries;
+  bool live = s < first[group + 1] && s < n_selected;
+  double w = 0.0;
+  SensVec x = {0.0, 0.0, 0.0};
+  const SensVec pivot = {pivots[3 * group], pivots[3 * group + 1], pivots[3 * group + 2]};
+  if (live) {
+    const int64_t r = selected[s];
+    if (r < 0 || r >= n_rows) {
+      atomicOr(status, SENS_BAD_SELECTION);
+      live = false;
+    } else {
+      w = weight_column < 0 ? 1.0 : rows[weight_column * ld + r];
+      x = sv_col(rows, ld, PRT_COL_X1, r);
+      live = is_finite(w) && sv_finite(x);
+      for (int c = 0; c < 3 * K; ++c) live = live && is_finite(jacobian[(int64_t)c * n_selected + s]);
+    }
+  }
+  for (int e = 0; e < entries; ++e) {
+    double v = live ? sens_entry(e, K, w, x, pivot, jacobian, n_selected, s) : 0.0;
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) red[e][threadIdx.x >> 6] = v;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < entries; e += kSensBlock) {
+    double sum = red[e][0];
+    for (int wave = 1; wave < kSensWaves; ++wave) sum += red[e][wave];
+    out[e] = sum;
+  }
+}
+
+// one wave per (group, entry): lane l adds the group's partials l, l + 64, ... in that order, then the butterfly: a fixed
+// order, and no lane walks thousands of workgroups alone
+__global__ void __launch_bounds__(64)
+k_sens_fold(const double* __restrict__ partials, int chunks, int entries, int n_groups, double* __restrict__ sums) {
+  const int64_t at = blockIdx.x;
+  if (at >= (int64_t)n_groups * entries) return;
+  const int64_t group = at / entries, e = at % entries;
+  double sum = 0.0;
+  for (int chunk = threadIdx.x; chunk < chunks; chunk += 64) sum += partials[(group * chunks + chunk) * entries + e];
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  if (threadIdx.x == 0) sums[at] = sum;
+}
+
+// ---- entry points ----------------------------------------------------------------------------------------------------------
+struct SensWork { SensWords* words; SensSurface* table; int64_t* first; double* pivots; double* state; int64_t* last_row; int* stamp; double* partials; };
+
+static int64_t sens_chunks(int64_t max_group_rows) { return (max_group_rows + kSensBlock - 1) / kSensBlock; }
+
+static bool sens_sizes_ok(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups, int64_t max_group_rows) {
+  return join_n_ids_ok(n_ids) && n_surfaces >= 1 && n_surfaces <= (1 << 20) && n_parameters >= 1 &&
+         n_parameters <= SENS_MAX_PARAMETERS && n_groups >= 1 && n_groups <= 65535 && max_group_rows >= 0 &&
+         sens_chunks(max_group_rows) <= 0x7fffffff;
+}
+
+static SensWork sens_carve(void* workspace, int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                           int64_t max_group_rows, char** end) {
+  SensWork w;
+  w.words = (SensWords*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
+  w.table = (SensSurface*)((char*)w.words + 64);
+  w.first = (int64_t*)(w.table + n_surfaces);
+  w.pivots = (double*)(w.first + n_groups + 1);
+  w.state = w.pivots + 3 * (int64_t)n_groups;
+  w.last_row = (int64_t*)(w.state + 6 * (int64_t)n_parameters * n_ids);
+  w.partials = (double*)(w.last_row + n_ids);
+  w.stamp = (int*)(w.partials + (int64_t)n_groups * sens_chunks(max_group_rows) * sens_entries(n_parameters));
+  *end = (char*)(w.stamp + n_ids);
+  return w;
+}
+
+extern "C" int64_t prt_frame_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                                                         int64_t max_group_rows) {
+  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows)) return PRT_ERR_ARG;
+  char* end;
+  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end);
+  (void)w;
+  return (int64_t)(uintptr_t)end + 64;
+}
+
+extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                                     int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces,
+                                     int n_surfaces, const double* twists, const int64_t* parameter_ids,
+                                     const int32_t* parameter_first, int n_parameters, const int64_t* row_slot,
+                                     const int64_t* selected, int64_t n_selected, const int64_t* group_first,
+                                     int n_groups, int weight_column, const double* pivots, double* jacobian_out,
+                                     double* sums_out, int64_t* record_out, void* workspace, void* stream) {
+  const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld, kSensBlock, "sensitivity");
+  if (n_rows < 0) return (int)n_rows;
+  if (!record_out || !workspace || !sums_out || !surfaces || !twists || !parameter_first || !group_first || !pivots ||
+      n_selected < 0 || n_selected > n_rows || (n_rows && (!rows || !row_slot)) ||
+      (n_selected && (!selected || !jacobian_out)))
+    return fail(PRT_ERR_ARG, "bad buffers");
+  int rc = join_ids(id0, n_ids);
+  if (rc) return rc;
+  if (n_parameters < 1 || n_parameters > SENS_MAX_PARAMETERS)
+    return fail(PRT_ERR_ARG, "sensitivity: 1 to 16 parameters a call");
+  if (n_groups < 1 || n_groups > 65535) return fail(PRT_ERR_ARG, "sensitivity: 1 to 65535 groups");
+  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "sensitivity: weight_column");
+  if (n_surfaces < 1 || n_surfaces > (1 << 20)) return fail(PRT_ERR_ARG, "sensitivity: 1 to 2^20 surfaces in the table");
+  int64_t max_group_rows = 0;
+  if (group_first[0] != 0 || group_first[n_groups] != n_selected)
+    return fail(PRT_ERR_ARG, "sensitivity: group_first runs from 0 to n_selected");
+  for (int g = 0; g < n_groups; ++g) {
+    if (group_first[g + 1] < group_first[g]) return fail(PRT_ERR_ARG, "sensitivity: group_first ascends");
+    max_group_rows = std::max(max_group_rows, group_first[g + 1] - group_first[g]);
+  }
+  for (int k = 0; k < 3 * n_groups; ++k)
+    if (!(std::fabs(pivots[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: pivots finite");
+  std::vector<SensSurface> table((size_t)n_surfaces);
+  for (int s = 0; s < n_surfaces; ++s) {
+    const prt_prim& pr = surfaces[s];
+    if (pr.type < PRT_PRIM_SPHERE || pr.type > PRT_PRIM_PARABOLOID || (pr.normal_scale != 1 && pr.normal_scale != -1))
+      return fail(PRT_ERR_ARG, "sensitivity: a surface of unknown kind or normal_scale");
+    if (s && !(surfaces[s - 1].surface_id < pr.surface_id))
+      return fail(PRT_ERR_ARG, "sensitivity: the surface table is sorted by id, ids distinct");
+    SensSurface& out = table[s];
+    std::memset(&out, 0, sizeof(out));
+    for (int k = 0; k < 16; ++k) {
+      if (!(std::fabs(pr.minv[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: a surface's minv is not finite");
+      out.minv[k] = pr.minv[k];
+    }
+    for (int k = 0; k < 6; ++k) out.params[k] = pr.params[k];
+    out.surface_id = (double)pr.surface_id;
+    out.type = pr.type;
+    out.normal_scale = pr.normal_scale;
+  }
+  SensArgs args;
+  std::memset(&args, 0, sizeof(args));
+  args.n_parameters = n_parameters;
+  args.n_surfaces = n_surfaces;
+  if (parameter_first[0] != 0) return fail(PRT_ERR_ARG, "sensitivity: parameter_first starts at 0");
+  for (int k = 0; k < n_parameters; ++k) {
+    const int from = parameter_first[k], to = parameter_first[k + 1];
+    if (to < from || to - from > SENS_MAX_IDS || (to > from && !parameter_ids))
+      return fail(PRT_ERR_ARG, "sensitivity: at most 64 surface ids a parameter");
+    for (int c = 0; c < 9; ++c) {
+      const double value = twists[9 * k + c];
+      if (!(std::fabs(value) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: a twist is not finite");
+      (c < 3 ? args.twist[k].v[c] : c < 6 ? args.twist[k].w[c - 3] : args.twist[k].c[c - 6]) = value;
+    }
+    for (int at = from; at < to; ++at) {
+      int lo = 0, hi = n_surfaces;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (surfaces[mid].surface_id < parameter_ids[at]) lo = mid + 1; else hi = mid;
+      }
+      if (lo == n_surfaces || surfaces[lo].surface_id != parameter_ids[at])
+        return fail(PRT_ERR_ARG, "sensitivity: a parameter moves a surface that is not in the table");
+      table[lo].moved_by |= 1u << k;
+    }
+  }
+  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows))
+    return fail(PRT_ERR_ARG, "sensitivity: too many rows in a group");
+  for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = 0;
+  rc = ops_device(device);
+  if (rc) return rc;
+  char* end;
+  const SensWork w = sens_carve(workspace, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end);
+  hipStream_t st = (hipStream_t)stream;
+  const int entries = sens_entries(n_parameters);
+  HIP_TRY(hipMemsetAsync(w.words, 0, 64, st));
+  HIP_TRY(hipMemsetAsync(w.stamp, 0, (size_t)n_ids * sizeof(int), st));
+  HIP_TRY(hipMemcpyAsync(w.table, table.data(), table.size() * sizeof(SensSurface), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.first, group_first, (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.pivots, pivots, (size_t)n_groups * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  int64_t start = 0;
+  for (int g = 0; g < n_generations; ++g) {
+    const int64_t count = rows_per_generation[g];
+    if (count)
+      hipLaunchKernelGGL(k_sens_step, dim3((unsigned)((count + kSensBlock - 1) / kSensBlock)), dim3(kSensBlock), 0, st,
+                         rows, ld, n_rows, start, count, g, id0, n_ids, args, w.table, w.state, w.last_row, w.stamp,
+                         w.words, row_slot, n_selected, jacobian_out);
+    start += count;
+  }
+  const int chunks = (int)sens_chunks(max_group_rows);
+  if (chunks)
+    hipLaunchKernelGGL(k_sens_partials, dim3((unsigned)chunks, (unsigned)n_groups), dim3(kSensBlock), 0, st, rows, ld,
+                       n_rows, selected, n_selected, w.first, n_parameters, weight_column, w.pivots, jacobian_out,
+                       w.partials, &w.words->status);
+  hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)n_groups * entries)), dim3(64), 0, st, w.partials, chunks,
+                     entries, n_groups, sums_out);
+  SensWords host_words;
+  HIP_TRY(hipMemcpyAsync(&host_words, w.words, sizeof(SensWords), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipGetLastError());
+  rc = join_refusal(host_words.status, "sensitivity");
+  if (rc) return rc;
+  if (host_words.status & SENS_BAD_SELECTION)
+    return fail(PRT_ERR_ARG, "sensitivity: row_slot or selected points outside the selection or the frame");
+  for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = (int64_t)host_words.count[k];
+  return PRT_OK;
+}

@@ -185,6 +185,9 @@ def _declare(lib):
         "prt_frame_fresnel_coated_workspace_bytes": (c_i64, [c_i64, c_i64]),
         "prt_frame_fresnel_coated": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_p, c_int, c_p, c_p, c_int,
                                              c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_sensitivity_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_i64]),
+        "prt_frame_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p, c_int,
+                                          c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -213,6 +216,7 @@ EXPORTED_SYMBOLS = (
     "prt_frame_energy_workspace_bytes", "prt_frame_energy", "prt_frame_paths_workspace_bytes", "prt_frame_paths",
     "prt_frame_fresnel_workspace_bytes", "prt_frame_fresnel",
     "prt_frame_fresnel_coated_workspace_bytes", "prt_frame_fresnel_coated",
+    "prt_frame_sensitivity_workspace_bytes", "prt_frame_sensitivity",
 )
 
 

@@ -1147,6 +1147,138 @@ class DeviceFrame:
         return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless),
                        coatings=dict(coatings or {}))
 
+    # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
+    def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
+                    rays_per_source=None, n_groups=None):
+        """d(landing point)/d(parameter) at ``surface`` for rigid motions of parts, from this one trace: a
+        ``Sensitivity``.  ``parameters``: a ``Motion`` or up to 16 of them; ``system``: the components the frame was
+        traced through (or their ``SceneSnapshot``), whose snapshot -- the one the scene compiler takes -- tells the
+        pass the kind, parameters and transform of the primitive behind every ``surface`` id.
+
+        A tangent (d position, d direction) per ray and parameter is pushed through the interfaces the ray's rows
+        describe, joined by ray id on the device (``prt_frame_sensitivity``; include/prt.h states the formulas): one
+        HIP launch per generation, no re-trace.  The rows selected are those that end on ``surface`` (an id or an
+        object with ``get_id()``), of every generation or of ``generation`` (a number or "last").  Per group (``id //
+        rays_per_source``, as in ``wavefront``) and with ``weights`` (a column, or None for 1) the pass also sums what
+        the gradient of the spot size and a least-squares step need.  ``reference``: "centroid", a point or an
+        (n_groups, 3) array: what the mean square radius is taken about.
+
+        A ray that meets a surface that is not in ``system``, a row that is not finite, or an interface whose rows fit
+        neither Snell's law nor a reflection (a caller-shaded material) is NaN from there on and is counted
+        (``n_unknown``, ``n_invalid``, ``n_unfit``); the sums leave such rows out.
+
+        Out of scope: moving a source; shape and index parameters; derivatives of anything but the landing point and
+        its moments (the optical path, for one); rays whose path changes under the motion, such as those at the edge
+        of an aperture -- the result is the derivative at fixed path, as in every differential ray trace.
+        Needs the whole frame of a trace, like ``optical_path``."""
+        import torch
+
+        from . import engine
+        from .scene import PRIM_DTYPE, SceneSnapshot
+
+        motions = [parameters] if isinstance(parameters, Motion) else list(parameters)
+        if not motions or not all(isinstance(m, Motion) for m in motions):
+            raise ValueError("sensitivity: parameters is a Motion or a list of them")
+        if len(motions) > 16:
+            raise ValueError(f"sensitivity: at most 16 parameters a call (got {len(motions)})")
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        if isinstance(reference, str) and reference != "centroid":
+            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        if surface is None:
+            raise ValueError("sensitivity: surface is an id or an object with get_id()")
+        surface_id = float(_surface_id(surface))
+        snapshot = system if hasattr(system, "prims") else SceneSnapshot(system)
+        prims = np.sort(np.asarray(snapshot.prims, dtype=PRIM_DTYPE), order="surface_id")
+        if len(prims) == 0:
+            raise ValueError("sensitivity: system has no surfaces")
+        if len(np.unique(prims["surface_id"])) != len(prims):
+            raise ValueError("sensitivity: a surface id repeats in system")
+        known = set(int(v) for v in prims["surface_id"])
+        for k, motion in enumerate(motions):
+            missing = sorted(set(motion.surface_ids) - known)
+            if missing:
+                raise ValueError(f"sensitivity: parameter {k} moves surfaces that are not in system: {missing}")
+        try:
+            self._need_whole("sensitivity", columns=_PATH_COLUMNS + ((weights,) if weights else ()))
+        except KeyError as error:
+            raise ValueError(f"sensitivity: {error.args[0]}") from None
+        rows = self._contiguous_rows()
+        dev = rows.device
+        n_rows = rows.shape[1]
+        id0, n_ids, top = self._id_range("sensitivity", rows)
+        if rays_per_source:
+            if n_groups is None:
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        n_groups = int(n_groups)
+        if not 1 <= n_groups <= 65535:
+            raise ValueError("sensitivity: 1 to 65535 groups")
+        K = len(motions)
+        # the selection, in the order (group, generation, id): what makes the sums independent of the rows' order
+        # (plumbing with a price: the id range above, group_first and the pivots below are each read back to the host
+        # and wait for the stream, before a call that synchronises itself: part of the call's fixed cost, see
+        # profiles/sensitivity/README.md)
+        counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        mask = rows[_INDEX["surface"]] == surface_id
+        if generation is not None:
+            mask = mask & (rows[_INDEX["generation"]] == float(generation))
+        ids = rows[_INDEX["id"]]
+        group = torch.zeros_like(ids, dtype=torch.int64)
+        if rays_per_source:
+            group = torch.floor(ids / float(rays_per_source)).to(torch.int64)
+        mask = mask & (group >= 0) & (group < n_groups)
+        picked = torch.nonzero(mask).reshape(-1)
+        key = ((group[picked] * max(len(counts), 1) + rows[_INDEX["generation"]][picked].to(torch.int64)) * n_ids
+               + (ids[picked] - id0).to(torch.int64))
+        order = torch.argsort(key)
+        selected = picked[order].contiguous()
+        n_selected = int(selected.shape[0])
+        row_slot = torch.full((max(n_rows, 1),), -1, dtype=torch.int64, device=dev)
+        row_slot[selected] = torch.arange(n_selected, dtype=torch.int64, device=dev)
+        group_first = torch.searchsorted(group[selected].contiguous(),
+                                         torch.arange(n_groups + 1, dtype=torch.int64, device=dev))
+        group_first = np.ascontiguousarray(group_first.cpu().numpy(), dtype=np.int64)
+        centred = isinstance(reference, str)
+        if centred:  # (the sums are taken about a point of the group, its first row's; the centroid follows from them)
+            pivots = np.zeros((n_groups, 3))
+            some = np.flatnonzero(np.diff(group_first) > 0)
+            if len(some):
+                first_rows = selected[torch.as_tensor(group_first[some], device=dev)]
+                pivots[some] = rows[_INDEX["x1"]:_INDEX["z1"] + 1][:, first_rows].T.cpu().numpy()
+            pivots[~np.isfinite(pivots)] = 0.0
+        else:
+            pivots = np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float)
+            if pivots.shape == (3,):
+                pivots = np.broadcast_to(pivots, (n_groups, 3))
+            if pivots.shape != (n_groups, 3) or not np.all(np.isfinite(pivots)):
+                raise ValueError(f"reference: \"centroid\", a finite point or an ({n_groups}, 3) array")
+        pivots = np.ascontiguousarray(pivots, dtype=np.float64)
+        twists = np.ascontiguousarray([m.twist for m in motions], dtype=np.float64)
+        id_lists = [sorted(m.surface_ids) for m in motions]
+        parameter_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in id_lists])]), dtype=np.int32)
+        parameter_ids = np.ascontiguousarray([v for ids_ in id_lists for v in ids_] or [0], dtype=np.int64)
+        entries = 6 + 4 * K + K * (K + 1) // 2
+        lib = engine.library()
+        max_group_rows = int(np.diff(group_first).max())
+        work = torch.empty(int(engine._check(lib.prt_frame_sensitivity_workspace_bytes(n_ids, len(prims), K, n_groups,
+                                                                                       max_group_rows))),
+                           dtype=torch.uint8, device=dev)
+        jacobian = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
+        sums = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
+        record = np.zeros(4, dtype=np.int64)
+        engine._check(lib.prt_frame_sensitivity(
+            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
+            len(counts), id0, n_ids, prims.ctypes.data, len(prims), twists.ctypes.data, parameter_ids.ctypes.data,
+            parameter_first.ctypes.data, K, row_slot.data_ptr(), selected.data_ptr() if n_selected else None, n_selected,
+            group_first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], pivots.ctypes.data,
+            jacobian.data_ptr() if n_selected else None, sums.data_ptr(), record.ctypes.data, work.data_ptr(),
+            engine._stream_ptr(torch, dev)))
+        return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions)
+
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
         notebook writes it (cells 12, 15): ``x0 - x_tilt * y0 / y_tilt``."""
@@ -1817,6 +1949,123 @@ class Fresnel:
         launched = original.energy_through[:, original.depth == 0].sum(axis=1)
         with np.errstate(invalid="ignore", divide="ignore"):
             return arrived / launched
+
+
+class Motion:
+    """One parameter of ``DeviceFrame.sensitivity``: a rigid motion of a part, per unit of the parameter.  ``part``: a
+    surface id, an object with ``get_id()`` or a component (every leaf surface of it moves: ``surface_ids``).
+    ``translate``: the velocity, in world length per unit parameter; ``rotate``: an axis scaled to radians per unit
+    parameter (right-handed), about ``pivot`` (default: the part's position; a bare id has none, (0, 0, 0) then).  A point
+    x of the part moves with u = translate + rotate x (x - pivot).  At most 64 surface ids."""
+
+    def __init__(self, part, translate=(0.0, 0.0, 0.0), rotate=(0.0, 0.0, 0.0), pivot=None):
+        if hasattr(part, "surface_ids"):
+            ids = [int(sid) for sid, _ in part.surface_ids]
+        elif hasattr(part, "get_id"):
+            ids = [int(part.get_id())]
+        else:
+            try:
+                ids = [int(part)]
+                if ids[0] != part:
+                    raise TypeError
+            except (TypeError, ValueError):
+                raise ValueError(f"Motion: part is an id, an object with get_id() or a component (got {part!r})") from None
+        if len(set(ids)) > 64:
+            raise ValueError(f"Motion: at most 64 surface ids a parameter (got {len(set(ids))})")
+        if pivot is None:
+            pivot = (0.0, 0.0, 0.0)
+            if hasattr(part, "get_position"):
+                pivot = np.asarray(part.get_position(), dtype=float).reshape(-1)[:3]
+        vectors = []
+        for name, value in (("translate", translate), ("rotate", rotate), ("pivot", pivot)):
+            try:
+                vector = np.asarray(value, dtype=float).reshape(-1)
+            except (TypeError, ValueError):
+                vector = np.zeros(0)
+            if vector.shape != (3,) or not np.all(np.isfinite(vector)):
+                raise ValueError(f"Motion: {name} is three finite numbers (got {value!r})")
+            vectors.append(vector)
+        self.surface_ids = tuple(sorted(set(ids)))
+        self.translate, self.rotate, self.pivot = vectors
+        self.twist = np.concatenate(vectors)
+
+    def __repr__(self):
+        return (f"Motion(surfaces={self.surface_ids}, translate={tuple(self.translate)}, rotate={tuple(self.rotate)}, "
+                f"pivot={tuple(self.pivot)})")
+
+
+class Sensitivity:
+    """What ``DeviceFrame.sensitivity`` found.  ``jacobian``: device (K, 3, n_selected) float64, d(x1, y1, z1)/dp_k of the
+    selected rows, which ``rows()`` names (frame row numbers, ordered by group, generation and id); NaN for a ray that
+    could not be followed.  Per group, from the device's sums (``sums``, the layout of include/prt.h): ``weight``,
+    ``centroid``, ``mean_square`` (radius about the centroid, or about the fixed ``reference``), ``centroid_gradient``
+    (groups, K, 3), ``mean_square_gradient`` and ``rms_radius_gradient`` (groups, K), ``normal_matrix`` (groups, K, K) and
+    ``rhs`` (groups, K) of the Gauss-Newton step that ``step()`` solves.  A group without rows has NaN there.
+    ``n_unknown`` / ``n_invalid`` / ``n_unfit``: rays lost to a surface that ``system`` does not hold, to a row that is
+    not finite, to an interface whose rows fit no rule; ``n_reflections``: reflections differentiated."""
+
+    def __init__(self, jacobian, selected, sums, pivots, centred, record, parameters):
+        self.jacobian, self._selected, self.sums, self.pivots, self.centred = jacobian, selected, sums, pivots, centred
+        self.parameters = tuple(parameters)
+        self.n_unknown, self.n_invalid, self.n_unfit, self.n_reflections = (int(v) for v in record)
+        K = self.n_parameters = len(self.parameters)
+        wide = np.asarray(sums, dtype=np.longdouble)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            self.count = np.asarray(sums[:, 0], dtype=np.int64)
+            sw = np.where(wide[:, 1] > 0, wide[:, 1], np.nan)
+            offset = wide[:, 2:5] / sw[:, None] - pivots  # (centroid - pivot)
+            sq = wide[:, 5] / sw
+            sd = wide[:, 6:6 + 3 * K].reshape(-1, K, 3)
+            sxd = wide[:, 6 + 3 * K:6 + 4 * K]
+            lower = np.zeros((len(wide), K, K), dtype=np.longdouble)
+            tri = np.tril_indices(K)
+            lower[:, tri[0], tri[1]] = wide[:, 6 + 4 * K:]
+            moments = lower + np.transpose(np.tril(lower, -1), (0, 2, 1))
+            if centred:
+                sq = sq - np.sum(offset * offset, axis=1)
+                sxd = sxd - np.einsum("gc,gkc->gk", offset, sd)
+                moments = moments - np.einsum("gjc,gkc->gjk", sd, sd) / sw[:, None, None]
+            self.weight = np.asarray(sw, dtype=float)
+            self.centroid = np.asarray(offset + pivots, dtype=float)
+            self.mean_square = np.asarray(sq, dtype=float)
+            self.centroid_gradient = np.asarray(sd / sw[:, None, None], dtype=float)
+            self.mean_square_gradient = np.asarray(2 * sxd / sw[:, None], dtype=float)
+            self.rms_radius_gradient = self.mean_square_gradient / (2 * np.sqrt(self.mean_square))[:, None]
+            self.normal_matrix = np.asarray(moments / sw[:, None, None], dtype=float)
+            self.rhs = -self.mean_square_gradient / 2
+
+    def rows(self):
+        """The frame rows of the selection, in the order of ``jacobian``'s last axis: a device int64 tensor."""
+        return self._selected
+
+    def step(self, damping=0.0):
+        """Per group the change of the parameters that minimises the mean square radius to first order (Gauss-Newton
+        on the landing points): the solution of (N + damping diag(N)) dp = rhs through ``solve_normal_equations``
+        (the minimum-norm one where the rays cannot tell the parameters apart).  (groups, K); NaN without rows."""
+        if not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("damping: a number >= 0")
+        K = self.n_parameters
+        upper = np.triu_indices(K)
+        packed = np.zeros((len(self.sums), len(upper[0]) + K + 3))
+        for g in range(len(packed)):
+            if not np.all(np.isfinite(self.normal_matrix[g])) or not np.all(np.isfinite(self.rhs[g])):
+                continue
+            a = self.normal_matrix[g] + damping * np.diag(np.diag(self.normal_matrix[g]))
+            packed[g, :len(upper[0])] = a[upper]
+            packed[g, len(upper[0]):len(upper[0]) + K] = self.rhs[g]
+            packed[g, -3] = self.weight[g]
+        return solve_normal_equations(packed, K)[0]
+
+    def to_pandas(self):
+        """One line per selected row: ``row``, then ``dx_k``, ``dy_k``, ``dz_k`` per parameter k."""
+        from . import engine
+
+        data = {"row": engine.to_host(self._selected).copy()}
+        jac = engine.to_host(self.jacobian)
+        for k in range(self.n_parameters):
+            for c, name in enumerate("xyz"):
+                data[f"d{name}_{k}"] = jac[k, c].copy()
+        return pd.DataFrame(data)
 
 
 def _coating_stacks(coatings, ids_lossless):
