@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -1046,8 +1046,9 @@ int prt_frame_fresnel_coated(int device, const double* rows, int64_t ld, const i
  * by id, are its whole path, `surface` names the primitive each segment ended on, and the surface table below says what
  * that primitive is.  A tangent (do, dd) per ray and parameter is pushed through the recorded interfaces.  The result is
  * the derivative AT FIXED PATH, as in every differential ray trace: a ray whose sequence of surfaces changes under the
- * motion (the edge of an aperture) is outside it.  Sources do not move; shape and index parameters and derivatives of
- * anything but the landing point and its moments (the optical path, for one) are not computed.
+ * motion (the edge of an aperture) is outside it.  Sources do not move; derivatives of anything but the landing point and
+ * its moments (the optical path, for one) are not computed.  Shape and index parameters: prt_frame_design_sensitivity,
+ * below.
  *
  * Definitions.
  * Frame: whole and generation-major, ids as prt_frame_optical_path wants them (a repeated id, an id out of range, a row
@@ -1105,6 +1106,52 @@ int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int6
                           int n_parameters, const int64_t* row_slot, const int64_t* selected, int64_t n_selected,
                           const int64_t* group_first, int n_groups, int weight_column, const double* pivots,
                           double* jacobian_out, double* sums_out, int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Sensitivities to shape and index parameters: the design form of the pass above -----------------------------------
+ * The same pass, the same notation, for parameters that deform a surface or change the index of a glass: what a lens
+ * designer varies (radii, thicknesses, indices).  Every shape parameter of the five primitives is an affine deformation
+ * of the primitive in its own frame (sphere radius: uniform scaling about the centre; cylinder radius: scaling of x and y;
+ * paraboloid focus f: scaling of x and y at the rate 1 / (2 f); cylinder height, cuboid side: scaling along one axis; lens
+ * thickness: translation of one face), so parameter k gets, beside its twist, a 3x3 matrix S in world coordinates
+ * (linear, K x 9, row-major) and, for the index, a rate (index_rates, K) and a second list of at most 64 surface ids
+ * (index_ids [index_first[k], index_first[k + 1])).
+ * Velocity of a moved surface under parameter k: u = v + w x (x - c) + S (x - c).  S = 0 is the rigid motion above.
+ * Normal of a material point of a moved surface: dn_moved = w x n - (I - n n^T) S^T n (the normal transforms with the
+ *   inverse transpose of I + eps (W + S)); dn = dn_moved + W (dx - u).  The curvature term keeps its form: the change of
+ *   W itself is of second order.  The landing dt = n.(u - do - t dd) / (n.d) keeps its form with the general u.
+ * Index: each ray carries dnu, d(index of its current segment)/dp_k, 0 in generation 0.  At a refraction, with ni, nt,
+ *   mu = ni / nt, ci, ct and gamma as above:
+ *     dnt = index_rates[k] if the ray ENTERS a surface that index parameter k names, else 0 (a ray that leaves goes into
+ *       the ambient index, which is constant).  The ray enters where the trace's own world normal (normal_scale
+ *       included) did not have to be turned against the ray.
+ *     dmu = (dnu - mu dnt) / nt,  dct = (mu^2 ci dci - mu (1 - ci^2) dmu) / ct,  dgamma = ci dmu + mu dci - dct,
+ *     dd' = dmu d + mu dd + dgamma n + gamma dn;  after the refraction dnu' = dnt.
+ *   A reflection (total internal reflection included) and an undeviated interface keep dnu.
+ *   The index behind the named surfaces grows by the rate at every wavelength; rates that depend on the wavelength are
+ *   out of scope.  Known limit: an interface with ni == nt to the bit is differentiated as none (or as a reflection), as
+ *   above, whatever the index parameter says.
+ * Order of the arithmetic: the terms of S and of the index are added behind a per-parameter bit (S not zero; an index
+ *   list that is not empty), after the rigid terms, which are computed as prt_frame_sensitivity computes them.  So a
+ *   parameter with S = 0 and no index list gets the bits it gets from prt_frame_sensitivity, and every parameter the bits
+ *   it gets alone.
+ * Still out of scope: moving a source, derivatives of the optical path (the OPD), rays whose path changes.
+ *
+ * prt_frame_design_sensitivity: the arguments of prt_frame_sensitivity with linear, index_rates, index_ids and index_first
+ * after parameter_first; outputs, selection, sums, counters, caps and guarantees as there.  Every entry of linear and
+ * index_rates must be finite, K <= 16, at most 64 ids in either list of a parameter, every id in the table: PRT_ERR_ARG
+ * with a message otherwise, before a device is touched.  workspace:
+ * prt_frame_design_sensitivity_workspace_bytes(same arguments as above): the state is seven planes, 56 K bytes a ray
+ * (the seventh, dnu, is read and written for index parameters alone). */
+int64_t prt_frame_design_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                                                     int64_t max_group_rows);
+int prt_frame_design_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                                 int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
+                                 const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
+                                 const double* linear, const double* index_rates, const int64_t* index_ids,
+                                 const int32_t* index_first, int n_parameters, const int64_t* row_slot,
+                                 const int64_t* selected, int64_t n_selected, const int64_t* group_first, int n_groups,
+                                 int weight_column, const double* pivots, double* jacobian_out, double* sums_out,
+                                 int64_t* record_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

@@ -11,8 +11,13 @@
 //                   the new direction and lands it on its own surface.  Everything that does not depend on the parameter
 //                   (both normals, the curvature operator of the previous surface, the interface's kind) is worked out
 //                   once, in registers; the loop over the parameters runs inside the thread with its state in memory, so
-//                   the register count does not grow with K.
-//   k_sens_step     one launch per generation, in generation order on one stream: sens_row, then the counters
+//                   the register count does not grow with K.  sens_row<true> is the design form (shape and index
+//                   parameters): per parameter a 3x3 matrix S in the velocity u = v + w x (x - c) + S (x - c) and an index
+//                   rate, each behind a bit, and a seventh plane of state, d(index of the ray's segment).  Its terms are
+//                   added after the rigid ones, which are computed as in sens_row<false>: a parameter without the bits
+//                   gets the bits of sens_row<false>.
+//   k_sens_step     one launch per generation, in generation order on one stream: sens_row<false>, then the counters
+//   k_sens_design_step  the same launch for sens_row<true>
 //   k_sens_partials the group sums of the selected rows as per-workgroup partials, written in workgroup order
 //   k_sens_fold     the partials of a group added in a fixed order: one wave per (group, entry)
 // n, and the decision "wall or cap", come from the functions the trace uses: world_normal_len and object_normal of
@@ -42,10 +47,13 @@ struct SensSurface {
   double surface_id;
   int32_t type, normal_scale;
   uint32_t moved_by;
-  int32_t pad;
+  uint32_t index_by;  // bit k: index parameter k names the surface (read by the design form alone)
 };
 struct SensTwist { double v[3], w[3], c[3]; };
 struct SensArgs { SensTwist twist[SENS_MAX_PARAMETERS]; int n_parameters, n_surfaces; };
+// the design form's own arguments: S (row-major, world) and the index rate per parameter; bit k of `linear` / `index`: the
+// parameter has an S that is not zero / names surfaces whose index it changes
+struct SensDesign { double S[SENS_MAX_PARAMETERS][9]; double rate[SENS_MAX_PARAMETERS]; uint32_t linear, index; };
 struct SensWords { u64 count[SENS_COUNTERS]; int status; };  // unknown, invalid, unfit, reflections
 struct SensVec { double x, y, z; };
 
@@ -123,15 +131,25 @@ __device__ __forceinline__ SensVec sens_velocity(const SensTwist& tw, bool moved
   return {tw.v[0] + t.x, tw.v[1] + t.y, tw.v[2] + t.z};
 }
 
+// S (x - c)
+__device__ __forceinline__ SensVec sens_linear(const double* __restrict__ S, const SensTwist& tw, const SensVec& x) {
+  const SensVec r = {x.x - tw.c[0], x.y - tw.c[1], x.z - tw.c[2]};
+  return {(S[0] * r.x + S[1] * r.y) + S[2] * r.z, (S[3] * r.x + S[4] * r.y) + S[5] * r.z,
+          (S[6] * r.x + S[7] * r.y) + S[8] * r.z};
+}
+
 enum { SENS_NONE = 0, SENS_REFRACT = 1, SENS_REFLECT = 2 };
 
-// row j of `generation`; flag: what the row adds to the counters
+// row j of `generation`; flag: what the row adds to the counters.  kDesign: `design` is read and the state has seven planes.
+template <bool kDesign>
 __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t j,
                                          int generation, double id0, int64_t n_ids, const SensArgs& args,
                                          const SensSurface* __restrict__ table, double* __restrict__ state,
                                          int64_t* __restrict__ last_row, int* __restrict__ stamp, int* status,
                                          const int64_t* __restrict__ row_slot, int64_t n_selected,
-                                         double* __restrict__ jacobian, bool (&flag)[SENS_COUNTERS]) {
+                                         double* __restrict__ jacobian, bool (&flag)[SENS_COUNTERS],
+                                         const SensDesign* design) {
+  constexpr int kPlanes = kDesign ? 7 : 6;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int K = args.n_parameters;
   bool unknown = false, invalid = false, unfit = false, reflection = false;
@@ -179,7 +197,9 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
     SensHit there = {};
     double mu = 1.0, ci = 0.0, ct = 0.0, gamma = 0.0;
     double a0[3] = {0, 0, 0}, a1[3] = {0, 0, 0}, a2[3] = {0, 0, 0};
-    uint32_t moved_there = 0u;
+    uint32_t moved_there = 0u, index_there = 0u;
+    double nt_there = 1.0;
+    bool entering = false;
     if (generation > 0 && !was_dead && !invalid && !unknown) {
       xp = sv_col(rows, ld, PRT_COL_X1, p);
       const SensVec rawp = sv_col(rows, ld, PRT_COL_XTILT, p);
@@ -193,6 +213,11 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
         const SensSurface* __restrict__ sp = table + ep;
         there = sens_hit(sp, xp, dp);
         moved_there = sp->moved_by;
+        if constexpr (kDesign) {
+          index_there = sp->index_by;
+          nt_there = nt;
+          entering = there.sign == (double)sp->normal_scale;  // (the trace's normal was not turned: refract4's !leaving)
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) { a0[c] = sp->minv[c]; a1[c] = sp->minv[4 + c]; a2[c] = sp->minv[8 + c]; }
         const SensVec turn = sv_sub(dp, d);
@@ -228,15 +253,28 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
       for (int k = 0; k < K; ++k) {
         const SensTwist& tw = args.twist[k];
         SensVec dx = {0.0, 0.0, 0.0}, dd = {0.0, 0.0, 0.0}, start = {0.0, 0.0, 0.0};
+        bool lin = false, idx = false;
+        double dnu = 0.0;
+        if constexpr (kDesign) {
+          lin = (design->linear >> k) & 1u;
+          idx = (design->index >> k) & 1u;
+        }
         if (generation > 0) {
-          double* __restrict__ s = state + (int64_t)k * 6 * n_ids + i;
+          double* __restrict__ s = state + (int64_t)k * kPlanes * n_ids + i;
           dx = {s[0], s[n_ids], s[2 * n_ids]};
           dd = {s[3 * n_ids], s[4 * n_ids], s[5 * n_ids]};
+          if constexpr (kDesign) {
+            if (idx) dnu = s[6 * n_ids];
+          }
           // dn = w x n (a moved surface) + W (dx - u)
           const bool moved = (moved_there >> k) & 1u;
           SensVec dn = {0.0, 0.0, 0.0};
           if (there.h) {
-            const SensVec y = sv_sub(dx, sens_velocity(tw, moved, xp));
+            SensVec up = sens_velocity(tw, moved, xp);
+            if constexpr (kDesign) {
+              if (moved && lin) up = sv_add(up, sens_linear(design->S[k], tw, xp));
+            }
+            const SensVec y = sv_sub(dx, up);
             const double z0 = (there.h & 1) ? (a0[0] * y.x + a0[1] * y.y) + a0[2] * y.z : 0.0;
             const double z1 = (there.h & 2) ? (a1[0] * y.x + a1[1] * y.y) + a1[2] * y.z : 0.0;
             const double z2 = (there.h & 4) ? (a2[0] * y.x + a2[1] * y.y) + a2[2] * y.z : 0.0;
@@ -247,11 +285,30 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
             dn = sv_scale(there.sign, sv_sub(m, sv_scale(along, there.n)));
           }
           if (moved) dn = sv_add(sv_cross({tw.w[0], tw.w[1], tw.w[2]}, there.n), dn);
+          if constexpr (kDesign) {
+            if (moved && lin) {  // - (I - n n^T) S^T n: the normal of a material point of the deformed surface
+              const double* __restrict__ S = design->S[k];
+              const SensVec& n = there.n;
+              const SensVec q = {(S[0] * n.x + S[3] * n.y) + S[6] * n.z, (S[1] * n.x + S[4] * n.y) + S[7] * n.z,
+                                 (S[2] * n.x + S[5] * n.y) + S[8] * n.z};
+              dn = sv_sub(dn, sv_sub(q, sv_scale(sv_dot(n, q), n)));
+            }
+          }
           if (kind == SENS_REFRACT) {
             const double dci = -(sv_dot(dn, dp) + sv_dot(there.n, dd));
             const double dct = ((mu * mu) * ci) * dci / ct;
             const double dgamma = mu * dci - dct;
             dd = sv_add(sv_add(sv_scale(mu, dd), sv_scale(dgamma, there.n)), sv_scale(gamma, dn));
+            if constexpr (kDesign) {
+              if (idx) {  // the terms of dmu, after those of the geometry: dct and dgamma are linear in (dci, dmu)
+                const double dnt = (entering && ((index_there >> k) & 1u)) ? design->rate[k] : 0.0;
+                const double dmu = (dnu - mu * dnt) / nt_there;
+                const double dct_mu = (mu * (1.0 - ci * ci)) * dmu / ct;  // dct = (mu^2 ci dci) / ct - dct_mu
+                const double dgamma_mu = ci * dmu + dct_mu;
+                dd = sv_add(dd, sv_add(sv_scale(dmu, dp), sv_scale(dgamma_mu, there.n)));
+                dnu = dnt;
+              }
+            }
           } else if (kind == SENS_REFLECT) {
             const double turn = sv_dot(dd, there.n) + sv_dot(dp, dn);
             const SensVec back = sv_add(sv_scale(turn, there.n), sv_scale(there.nd, dn));
@@ -260,13 +317,19 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
           start = sv_add(dx, sv_scale(PRT_SENS_OFFSET, dd));
         }
         // the landing: dt = n.(u - do - t dd) / (n.d), dx = do + t dd + d dt
-        const SensVec u = sens_velocity(tw, (moved_here >> k) & 1u, x);
+        SensVec u = sens_velocity(tw, (moved_here >> k) & 1u, x);
+        if constexpr (kDesign) {
+          if (((moved_here >> k) & 1u) && lin) u = sv_add(u, sens_linear(design->S[k], tw, x));
+        }
         const SensVec reach = sv_add(start, sv_scale(t, dd));
         const double dt = sv_dot(here.n, sv_sub(u, reach)) / here.nd;
         dx = sv_add(reach, sv_scale(dt, d));
-        double* __restrict__ s = state + (int64_t)k * 6 * n_ids + i;
+        double* __restrict__ s = state + (int64_t)k * kPlanes * n_ids + i;
         s[0] = dx.x; s[n_ids] = dx.y; s[2 * n_ids] = dx.z;
         s[3 * n_ids] = dd.x; s[4 * n_ids] = dd.y; s[5 * n_ids] = dd.z;
+        if constexpr (kDesign) {
+          if (idx) s[6 * n_ids] = dnu;  // (read by index parameters alone)
+        }
         if (slot >= 0) {
           double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
           out[0] = dx.x; out[n_selected] = dx.y; out[2 * n_selected] = dx.z;
@@ -295,8 +358,22 @@ k_sens_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t
   const int64_t j = start + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
   bool flag[SENS_COUNTERS] = {};
   if (j < start + count)
-    sens_row(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status, row_slot,
-             n_selected, jacobian, flag);
+    sens_row<false>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status,
+                    row_slot, n_selected, jacobian, flag, nullptr);
+  fresnel_count(flag, words->count);
+}
+
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_design_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t start, int64_t count,
+                   int generation, double id0, int64_t n_ids, SensArgs args, SensDesign design,
+                   const SensSurface* __restrict__ table, double* __restrict__ state, int64_t* __restrict__ last_row,
+                   int* __restrict__ stamp, SensWords* __restrict__ words, const int64_t* __restrict__ row_slot,
+                   int64_t n_selected, double* __restrict__ jacobian) {
+  const int64_t j = start + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
+  bool flag[SENS_COUNTERS] = {};
+  if (j < start + count)
+    sens_row<true>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status,
+                   row_slot, n_selected, jacobian, flag, &design);
   fresnel_count(flag, words->count);
 }
 
@@ -391,14 +468,14 @@ static bool sens_sizes_ok(int64_t n_ids, int n_surfaces, int n_parameters, int n
 }
 
 static SensWork sens_carve(void* workspace, int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
-                           int64_t max_group_rows, char** end) {
+                           int64_t max_group_rows, char** end, int planes = 6) {
   SensWork w;
   w.words = (SensWords*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
   w.table = (SensSurface*)((char*)w.words + 64);
   w.first = (int64_t*)(w.table + n_surfaces);
   w.pivots = (double*)(w.first + n_groups + 1);
   w.state = w.pivots + 3 * (int64_t)n_groups;
-  w.last_row = (int64_t*)(w.state + 6 * (int64_t)n_parameters * n_ids);
+  w.last_row = (int64_t*)(w.state + planes * (int64_t)n_parameters * n_ids);
   w.partials = (double*)(w.last_row + n_ids);
   w.stamp = (int*)(w.partials + (int64_t)n_groups * sens_chunks(max_group_rows) * sens_entries(n_parameters));
   *end = (char*)(w.stamp + n_ids);
@@ -414,18 +491,29 @@ extern "C" int64_t prt_frame_sensitivity_workspace_bytes(int64_t n_ids, int n_su
   return (int64_t)(uintptr_t)end + 64;
 }
 
-extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
-                                     int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces,
-                                     int n_surfaces, const double* twists, const int64_t* parameter_ids,
-                                     const int32_t* parameter_first, int n_parameters, const int64_t* row_slot,
-                                     const int64_t* selected, int64_t n_selected, const int64_t* group_first,
-                                     int n_groups, int weight_column, const double* pivots, double* jacobian_out,
-                                     double* sums_out, int64_t* record_out, void* workspace, void* stream) {
+extern "C" int64_t prt_frame_design_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters,
+                                                                int n_groups, int64_t max_group_rows) {
+  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows)) return PRT_ERR_ARG;
+  char* end;
+  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end, 7);
+  (void)w;
+  return (int64_t)(uintptr_t)end + 64;
+}
+
+// both entry points: `design` chooses the form; linear, index_rates, index_ids and index_first are read by the design form
+static int sens_run(bool design, int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                    int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
+                    const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
+                    const double* linear, const double* index_rates, const int64_t* index_ids,
+                    const int32_t* index_first, int n_parameters, const int64_t* row_slot, const int64_t* selected,
+                    int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                    const double* pivots, double* jacobian_out, double* sums_out, int64_t* record_out, void* workspace,
+                    void* stream) {
   const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld, kSensBlock, "sensitivity");
   if (n_rows < 0) return (int)n_rows;
   if (!record_out || !workspace || !sums_out || !surfaces || !twists || !parameter_first || !group_first || !pivots ||
       n_selected < 0 || n_selected > n_rows || (n_rows && (!rows || !row_slot)) ||
-      (n_selected && (!selected || !jacobian_out)))
+      (n_selected && (!selected || !jacobian_out)) || (design && (!linear || !index_rates || !index_first)))
     return fail(PRT_ERR_ARG, "bad buffers");
   int rc = join_ids(id0, n_ids);
   if (rc) return rc;
@@ -486,13 +574,42 @@ extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld,
       table[lo].moved_by |= 1u << k;
     }
   }
+  SensDesign shape;
+  std::memset(&shape, 0, sizeof(shape));
+  if (design) {
+    if (index_first[0] != 0) return fail(PRT_ERR_ARG, "design sensitivity: index_first starts at 0");
+    for (int k = 0; k < n_parameters; ++k) {
+      for (int c = 0; c < 9; ++c) {
+        const double value = linear[9 * k + c];
+        if (!(std::fabs(value) < PRT_INF)) return fail(PRT_ERR_ARG, "design sensitivity: linear is not finite");
+        shape.S[k][c] = value;
+        if (value != 0.0) shape.linear |= 1u << k;
+      }
+      if (!(std::fabs(index_rates[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "design sensitivity: an index rate is not finite");
+      shape.rate[k] = index_rates[k];
+      const int from = index_first[k], to = index_first[k + 1];
+      if (to < from || to - from > SENS_MAX_IDS || (to > from && !index_ids))
+        return fail(PRT_ERR_ARG, "design sensitivity: at most 64 surface ids an index parameter");
+      for (int at = from; at < to; ++at) {
+        int lo = 0, hi = n_surfaces;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (surfaces[mid].surface_id < index_ids[at]) lo = mid + 1; else hi = mid;
+        }
+        if (lo == n_surfaces || surfaces[lo].surface_id != index_ids[at])
+          return fail(PRT_ERR_ARG, "design sensitivity: an index parameter names a surface that is not in the table");
+        table[lo].index_by |= 1u << k;
+        shape.index |= 1u << k;
+      }
+    }
+  }
   if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows))
     return fail(PRT_ERR_ARG, "sensitivity: too many rows in a group");
   for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = 0;
   rc = ops_device(device);
   if (rc) return rc;
   char* end;
-  const SensWork w = sens_carve(workspace, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end);
+  const SensWork w = sens_carve(workspace, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end, design ? 7 : 6);
   hipStream_t st = (hipStream_t)stream;
   const int entries = sens_entries(n_parameters);
   HIP_TRY(hipMemsetAsync(w.words, 0, 64, st));
@@ -503,10 +620,13 @@ extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld,
   int64_t start = 0;
   for (int g = 0; g < n_generations; ++g) {
     const int64_t count = rows_per_generation[g];
-    if (count)
-      hipLaunchKernelGGL(k_sens_step, dim3((unsigned)((count + kSensBlock - 1) / kSensBlock)), dim3(kSensBlock), 0, st,
-                         rows, ld, n_rows, start, count, g, id0, n_ids, args, w.table, w.state, w.last_row, w.stamp,
-                         w.words, row_slot, n_selected, jacobian_out);
+    const dim3 grid((unsigned)((count + kSensBlock - 1) / kSensBlock));
+    if (count && design)
+      hipLaunchKernelGGL(k_sens_design_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
+                         args, shape, w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected, jacobian_out);
+    else if (count)
+      hipLaunchKernelGGL(k_sens_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids, args,
+                         w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected, jacobian_out);
     start += count;
   }
   const int chunks = (int)sens_chunks(max_group_rows);
@@ -526,4 +646,32 @@ extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld,
     return fail(PRT_ERR_ARG, "sensitivity: row_slot or selected points outside the selection or the frame");
   for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = (int64_t)host_words.count[k];
   return PRT_OK;
+}
+
+extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                                     int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces,
+                                     int n_surfaces, const double* twists, const int64_t* parameter_ids,
+                                     const int32_t* parameter_first, int n_parameters, const int64_t* row_slot,
+                                     const int64_t* selected, int64_t n_selected, const int64_t* group_first,
+                                     int n_groups, int weight_column, const double* pivots, double* jacobian_out,
+                                     double* sums_out, int64_t* record_out, void* workspace, void* stream) {
+  return sens_run(false, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                  parameter_ids, parameter_first, nullptr, nullptr, nullptr, nullptr, n_parameters, row_slot, selected,
+                  n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out, workspace,
+                  stream);
+}
+
+extern "C" int prt_frame_design_sensitivity(int device, const double* rows, int64_t ld,
+                                            const int64_t* rows_per_generation, int n_generations, double id0,
+                                            int64_t n_ids, const prt_prim* surfaces, int n_surfaces, const double* twists,
+                                            const int64_t* parameter_ids, const int32_t* parameter_first,
+                                            const double* linear, const double* index_rates, const int64_t* index_ids,
+                                            const int32_t* index_first, int n_parameters, const int64_t* row_slot,
+                                            const int64_t* selected, int64_t n_selected, const int64_t* group_first,
+                                            int n_groups, int weight_column, const double* pivots, double* jacobian_out,
+                                            double* sums_out, int64_t* record_out, void* workspace, void* stream) {
+  return sens_run(true, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                  parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
+                  selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
+                  workspace, stream);
 }

@@ -188,6 +188,10 @@ def _declare(lib):
         "prt_frame_sensitivity_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_i64]),
         "prt_frame_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p, c_int,
                                           c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_design_sensitivity_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_i64]),
+        "prt_frame_design_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -217,6 +221,7 @@ EXPORTED_SYMBOLS = (
     "prt_frame_fresnel_workspace_bytes", "prt_frame_fresnel",
     "prt_frame_fresnel_coated_workspace_bytes", "prt_frame_fresnel_coated",
     "prt_frame_sensitivity_workspace_bytes", "prt_frame_sensitivity",
+    "prt_frame_design_sensitivity_workspace_bytes", "prt_frame_design_sensitivity",
 )
 
 

@@ -1150,8 +1150,11 @@ class DeviceFrame:
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
                     rays_per_source=None, n_groups=None):
-        """d(landing point)/d(parameter) at ``surface`` for rigid motions of parts, from this one trace: a
-        ``Sensitivity``.  ``parameters``: a ``Motion`` or up to 16 of them; ``system``: the components the frame was
+        """d(landing point)/d(parameter) at ``surface`` for motions, shape changes and index changes of parts, from
+        this one trace: a ``Sensitivity``.  ``parameters``: up to 16 of ``Motion`` (a rigid motion), ``Deformation`` (an
+        affine deformation: radii, a paraboloid's focus, heights, sides and thicknesses) and ``IndexChange`` (the index of
+        a glass), in any mix; a call of Motions alone runs ``prt_frame_sensitivity`` as it always did, any other
+        ``prt_frame_design_sensitivity``, in which a Motion has the same bits.  ``system``: the components the frame was
         traced through (or their ``SceneSnapshot``), whose snapshot -- the one the scene compiler takes -- tells the
         pass the kind, parameters and transform of the primitive behind every ``surface`` id.
 
@@ -1167,18 +1170,22 @@ class DeviceFrame:
         neither Snell's law nor a reflection (a caller-shaded material) is NaN from there on and is counted
         (``n_unknown``, ``n_invalid``, ``n_unfit``); the sums leave such rows out.
 
-        Out of scope: moving a source; shape and index parameters; derivatives of anything but the landing point and
-        its moments (the optical path, for one); rays whose path changes under the motion, such as those at the edge
-        of an aperture -- the result is the derivative at fixed path, as in every differential ray trace.
+        Out of scope: moving a source; index rates that depend on the wavelength; derivatives of anything but the
+        landing point and its moments (the optical path and the OPD, for one); rays whose path changes under the
+        parameter, such as those at the edge of an aperture -- the result is the derivative at fixed path, as in every
+        differential ray trace.  A known limit: an interface whose two indices are equal to the bit is differentiated
+        as no interface at all, whatever an ``IndexChange`` says of it.
         Needs the whole frame of a trace, like ``optical_path``."""
         import torch
 
         from . import engine
         from .scene import PRIM_DTYPE, SceneSnapshot
 
-        motions = [parameters] if isinstance(parameters, Motion) else list(parameters)
-        if not motions or not all(isinstance(m, Motion) for m in motions):
-            raise ValueError("sensitivity: parameters is a Motion or a list of them")
+        kinds = (Motion, Deformation, IndexChange)
+        motions = [parameters] if isinstance(parameters, kinds) else list(parameters)
+        if not motions or not all(isinstance(m, kinds) for m in motions):
+            raise ValueError("sensitivity: parameters is a Motion, a Deformation or an IndexChange, or a list of them")
+        design = not all(isinstance(m, Motion) for m in motions)
         if len(motions) > 16:
             raise ValueError(f"sensitivity: at most 16 parameters a call (got {len(motions)})")
         if weights is not None and weights not in _INDEX:
@@ -1257,26 +1264,38 @@ class DeviceFrame:
             if pivots.shape != (n_groups, 3) or not np.all(np.isfinite(pivots)):
                 raise ValueError(f"reference: \"centroid\", a finite point or an ({n_groups}, 3) array")
         pivots = np.ascontiguousarray(pivots, dtype=np.float64)
-        twists = np.ascontiguousarray([m.twist for m in motions], dtype=np.float64)
-        id_lists = [sorted(m.surface_ids) for m in motions]
+        index = [isinstance(m, IndexChange) for m in motions]
+        twists = np.ascontiguousarray([np.zeros(9) if i else m.twist for m, i in zip(motions, index)], dtype=np.float64)
+        id_lists = [[] if i else sorted(m.surface_ids) for m, i in zip(motions, index)]
         parameter_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in id_lists])]), dtype=np.int32)
         parameter_ids = np.ascontiguousarray([v for ids_ in id_lists for v in ids_] or [0], dtype=np.int64)
         entries = 6 + 4 * K + K * (K + 1) // 2
         lib = engine.library()
         max_group_rows = int(np.diff(group_first).max())
-        work = torch.empty(int(engine._check(lib.prt_frame_sensitivity_workspace_bytes(n_ids, len(prims), K, n_groups,
-                                                                                       max_group_rows))),
+        bytes_of = lib.prt_frame_design_sensitivity_workspace_bytes if design else lib.prt_frame_sensitivity_workspace_bytes
+        work = torch.empty(int(engine._check(bytes_of(n_ids, len(prims), K, n_groups, max_group_rows))),
                            dtype=torch.uint8, device=dev)
         jacobian = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
         sums = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
         record = np.zeros(4, dtype=np.int64)
-        engine._check(lib.prt_frame_sensitivity(
-            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
-            len(counts), id0, n_ids, prims.ctypes.data, len(prims), twists.ctypes.data, parameter_ids.ctypes.data,
-            parameter_first.ctypes.data, K, row_slot.data_ptr(), selected.data_ptr() if n_selected else None, n_selected,
-            group_first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], pivots.ctypes.data,
-            jacobian.data_ptr() if n_selected else None, sums.data_ptr(), record.ctypes.data, work.data_ptr(),
-            engine._stream_ptr(torch, dev)))
+        head = (dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
+                len(counts), id0, n_ids, prims.ctypes.data, len(prims), twists.ctypes.data, parameter_ids.ctypes.data,
+                parameter_first.ctypes.data)
+        tail = (K, row_slot.data_ptr(), selected.data_ptr() if n_selected else None, n_selected,
+                group_first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], pivots.ctypes.data,
+                jacobian.data_ptr() if n_selected else None, sums.data_ptr(), record.ctypes.data, work.data_ptr(),
+                engine._stream_ptr(torch, dev))
+        if design:  # (a call of Motions alone takes the entry point, the kernel and the workspace it always took)
+            linear = np.ascontiguousarray([m.linear.reshape(-1) if isinstance(m, Deformation) else np.zeros(9)
+                                           for m in motions], dtype=np.float64)
+            rates = np.ascontiguousarray([m.rate if i else 0.0 for m, i in zip(motions, index)], dtype=np.float64)
+            index_lists = [sorted(m.surface_ids) if i else [] for m, i in zip(motions, index)]
+            index_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in index_lists])]), dtype=np.int32)
+            index_ids = np.ascontiguousarray([v for ids_ in index_lists for v in ids_] or [0], dtype=np.int64)
+            engine._check(lib.prt_frame_design_sensitivity(*head, linear.ctypes.data, rates.ctypes.data,
+                                                           index_ids.ctypes.data, index_first.ctypes.data, *tail))
+        else:
+            engine._check(lib.prt_frame_sensitivity(*head, *tail))
         return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions)
 
     def axis_intercept(self):
@@ -1992,6 +2011,200 @@ class Motion:
     def __repr__(self):
         return (f"Motion(surfaces={self.surface_ids}, translate={tuple(self.translate)}, rotate={tuple(self.rotate)}, "
                 f"pivot={tuple(self.pivot)})")
+
+
+def _expm(generator):
+    """exp of a small square matrix: scaling and squaring around a Taylor series (the 4x4 generators of ``Deformation``)."""
+    g = np.asarray(generator, dtype=float)
+    squarings = max(0, int(np.ceil(np.log2(max(np.linalg.norm(g, 1), 1e-300)))) + 4)
+    g = g / 2.0 ** squarings
+    out, term = np.eye(len(g)), np.eye(len(g))
+    for k in range(1, 20):
+        term = term @ g / k
+        out = out + term
+    for _ in range(squarings):
+        out = out @ out
+    return out
+
+
+class Deformation:
+    """One parameter of ``DeviceFrame.sensitivity``, the general one: an affine deformation of a part, per unit of the
+    parameter.  A point x of the part moves with u = translate + rotate x (x - pivot) + linear (x - pivot); ``linear`` is
+    any 3x3 matrix in world coordinates (None: 0, a rigid motion, what a ``Motion`` is).  ``part`` and ``pivot`` are
+    ``Motion``'s.  Every shape parameter of the five primitives is such a deformation, and the constructors say which:
+
+    ``Deformation.radius(surface, keep=None)``     the radius of a sphere or cylinder leaf, in the primitive's own frame:
+                                                   linear = A^-1 diag(1/R) A (A the 3x3 of the leaf's world-to-object
+                                                   matrix, R its radius; a cylinder's axis is not scaled);
+    ``Deformation.focus(paraboloid, keep=None)``   the focus f of a paraboloid leaf: x and y scaled at the rate 1/(2f);
+    ``Deformation.stretch(part, axis, about=None)`` a scaling along a world axis (cylinder heights, cuboid sides, the
+                                                   thickness of a slab): linear = e e^T, the parameter is the relative
+                                                   elongation, so a slab of thickness t grows by t per unit.
+
+    ``keep`` is a world point that stays where it is (the pivot): a lens vertex, so that the thickness does not change with
+    the radius; by default the primitive's own origin (a sphere's centre, a paraboloid's vertex).  The leaves of a
+    component are in ``component.surface_ids``, as (id, surface) pairs, left child first: a ``biconvex_lens`` gives the
+    front sphere (the face towards -x, vertex at position - thickness / 2 along the axis), the back sphere and the
+    aperture stock, in that order; the thickness of a lens is ``Deformation(back, translate=axis)``.
+
+    ``matrix(amount)`` is the finite 4x4 world transform whose derivative at 0 is u: for a radius the exact scaling by
+    (R + amount) / R about ``keep`` (for a focus by sqrt((f + amount) / f) in x and y), for a stretch the scaling by
+    1 + amount along the axis, otherwise the matrix exponential of amount times the generator of u.  ``apply(amount)``
+    transforms the part with it (the primitive keeps its own parameters: its transform carries the change, and a later
+    ``radius`` is again measured in the primitive's own frame).  A Deformation describes the part as it stood when it was
+    made: after a step, make the next iteration's anew."""
+
+    def __init__(self, part, translate=(0.0, 0.0, 0.0), rotate=(0.0, 0.0, 0.0), linear=None, pivot=None):
+        try:
+            rigid = Motion(part, translate, rotate, pivot)
+        except ValueError as error:
+            raise ValueError(str(error).replace("Motion:", "Deformation:", 1)) from None
+        if linear is None:
+            linear = np.zeros((3, 3))
+        try:
+            linear = np.array(linear, dtype=float)
+        except (TypeError, ValueError):
+            linear = np.zeros(0)
+        if linear.shape != (3, 3) or not np.all(np.isfinite(linear)):
+            raise ValueError("Deformation: linear is a 3x3 matrix of finite numbers")
+        self.part = part
+        self.surface_ids = rigid.surface_ids
+        self.translate, self.rotate, self.pivot, self.twist = rigid.translate, rigid.rotate, rigid.pivot, rigid.twist
+        self.linear = linear
+        self._finite = None
+
+    @staticmethod
+    def _leaf(surface, kinds, what):
+        from .g3d import shapes
+
+        kind = getattr(getattr(surface, "primitive", None), "kind", None)
+        names = {shapes.SPHERE: "sphere", shapes.CYLINDER: "cylinder", shapes.PARABOLOID: "paraboloid"}
+        if kind not in kinds:
+            raise ValueError(f"Deformation.{what}: a leaf surface that is a {' or a '.join(names[k] for k in kinds)} "
+                             f"(got {surface!r})")
+        a = np.asarray(surface.get_object_transform(), dtype=float)[:3, :3]
+        return kind, a, np.linalg.inv(a), float(surface.primitive.params[0])
+
+    @classmethod
+    def _scaling(cls, surface, keep, rate, factor):
+        """The deformation whose own-frame scaling has the diagonal rate ``rate`` and the finite diagonal ``factor(amount)``."""
+        a = np.asarray(surface.get_object_transform(), dtype=float)[:3, :3]
+        back = np.linalg.inv(a)
+        if keep is None:
+            keep = np.asarray(surface.get_position(), dtype=float).reshape(-1)[:3]
+        out = cls(surface, linear=back @ np.diag(rate) @ a, pivot=keep)
+
+        def finite(amount):
+            m = np.eye(4)
+            m[:3, :3] = back @ np.diag(factor(amount)) @ a
+            m[:3, 3] = out.pivot - m[:3, :3] @ out.pivot
+            return m
+
+        out._finite = finite
+        return out
+
+    @classmethod
+    def radius(cls, surface, keep=None):
+        from .g3d import shapes
+
+        kind, _, _, r = cls._leaf(surface, (shapes.SPHERE, shapes.CYLINDER), "radius")
+        z = 1.0 if kind == shapes.SPHERE else 0.0
+
+        def factor(amount):
+            s = (r + amount) / r
+            if not s > 0:
+                raise ValueError(f"Deformation.radius: the radius {r} cannot change by {amount}")
+            return (s, s, s if z else 1.0)
+
+        return cls._scaling(surface, keep, (1 / r, 1 / r, z / r), factor)
+
+    @classmethod
+    def focus(cls, paraboloid, keep=None):
+        from .g3d import shapes
+
+        _, _, _, f = cls._leaf(paraboloid, (shapes.PARABOLOID,), "focus")
+
+        def factor(amount):
+            if not (f + amount) / f > 0:
+                raise ValueError(f"Deformation.focus: the focus {f} cannot change by {amount}")
+            s = np.sqrt((f + amount) / f)
+            return (s, s, 1.0)
+
+        return cls._scaling(paraboloid, keep, (1 / (2 * f), 1 / (2 * f), 0.0), factor)
+
+    @classmethod
+    def stretch(cls, part, axis, about=None):
+        try:
+            e = np.asarray(axis, dtype=float).reshape(-1)
+        except (TypeError, ValueError):
+            e = np.zeros(0)
+        if e.shape != (3,) or not np.all(np.isfinite(e)) or not np.linalg.norm(e) > 0:
+            raise ValueError(f"Deformation.stretch: axis is three finite numbers, not all zero (got {axis!r})")
+        e = e / np.linalg.norm(e)
+        out = cls(part, linear=np.outer(e, e), pivot=about)
+
+        def finite(amount):
+            if not 1 + amount > 0:
+                raise ValueError(f"Deformation.stretch: a length cannot change by the factor {1 + amount}")
+            m = np.eye(4)
+            m[:3, :3] += amount * np.outer(e, e)
+            m[:3, 3] = out.pivot - m[:3, :3] @ out.pivot
+            return m
+
+        out._finite = finite
+        return out
+
+    def generator(self):
+        """The 4x4 matrix G with u(x) = G (x, 1)."""
+        w = self.rotate
+        g = np.zeros((4, 4))
+        g[:3, :3] = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) + self.linear
+        g[:3, 3] = self.translate - g[:3, :3] @ self.pivot
+        return g
+
+    def matrix(self, amount):
+        amount = float(amount)
+        if not np.isfinite(amount):
+            raise ValueError("Deformation: amount is a finite number")
+        return self._finite(amount) if self._finite is not None else _expm(amount * self.generator())
+
+    def apply(self, amount):
+        if not hasattr(self.part, "transform"):
+            raise ValueError("Deformation.apply: the part was given as a bare id, there is nothing to transform")
+        self.part.transform(self.matrix(amount))
+        return self
+
+    def __repr__(self):
+        return (f"Deformation(surfaces={self.surface_ids}, translate={tuple(self.translate)}, rotate={tuple(self.rotate)}, "
+                f"linear={self.linear.tolist()}, pivot={tuple(self.pivot)})")
+
+
+class IndexChange:
+    """One parameter of ``DeviceFrame.sensitivity``: the refractive index of the medium behind every leaf surface of
+    ``part`` grows by ``rate`` per unit of the parameter, at every wavelength (rates that depend on the wavelength are out
+    of scope).  ``part``: an object with ``get_id()`` or a component, with a glass on at least one leaf."""
+
+    def __init__(self, part, rate=1.0):
+        from . import materials as matl
+
+        if not hasattr(part, "surface_ids"):
+            raise ValueError(f"IndexChange: part is a surface or a component (got {part!r})")
+        leaves = list(part.surface_ids)
+        if not any(isinstance(getattr(surface, "material", None), matl.Glass) for _, surface in leaves):
+            raise ValueError("IndexChange: the part has no glass")
+        if len({int(sid) for sid, _ in leaves}) > 64:
+            raise ValueError(f"IndexChange: at most 64 surface ids a parameter (got {len(leaves)})")
+        try:
+            rate = float(rate)
+        except (TypeError, ValueError):
+            rate = np.nan
+        if not np.isfinite(rate):
+            raise ValueError("IndexChange: rate is a finite number")
+        self.part, self.rate = part, rate
+        self.surface_ids = tuple(sorted({int(sid) for sid, _ in leaves}))
+
+    def __repr__(self):
+        return f"IndexChange(surfaces={self.surface_ids}, rate={self.rate})"
 
 
 class Sensitivity:
