@@ -154,7 +154,10 @@ typedef struct prt_scene_options {
                                 the interval form (an intersection of the leaves' [enter, exit] intervals) */
   int32_t no_clearance;      /* 1: the cylinder that cuts a lens chain to its aperture is evaluated for every wave (0: not for a
                                 wave all of whose chords run inside it by a margin: a convexity argument) */
-  int32_t reserved[4];
+  int32_t no_plane_bound;    /* 1: a bare plane of a trace program (a detector, a baffle) evaluates its two slabs for every wave (0: only
+                                for a wave in which some lane's crossing t is positive and beats its nearest hit so far: the slabs
+                                can only remove that t) */
+  int32_t reserved[3];
 } prt_scene_options;
 
 /* Build a scene from a snapshot.  roots[] lists the node index of every top-level component
@@ -1205,6 +1208,9 @@ int prt_trace_stats(const prt_scene* scene, double* out8);
  * remaining 80 B each way).  Any other wave hands the rows on as they are, so every ray set is served.  A ray whose
  * genuine id carries that tag would be misread: it raises the same repeat with all 13 rows. */
 int prt_trace_telemetry(const prt_scene* scene, int64_t* out12);
+/* one more counter of the traces run with PRT_TRACE_COUNT_PATHS, per WAVE: out1 = { waves that did not finish a bare
+ * plane leaf because no lane's crossing could win (prt_scene_options.no_plane_bound) } */
+int prt_trace_shortcut_counts(const prt_scene* scene, int64_t* out1);
 
 /* ---- renderers (second consumer of the intersect path) ----------
  * tinygfx/g3d/renderers.py: an OrthographicCamera grid (world_objects.py:499-537) is pushed

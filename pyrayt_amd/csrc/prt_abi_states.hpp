@@ -208,7 +208,7 @@ __global__ void k_ctrl_init(TraceCtrl* ctrl, int64_t n, int64_t rows_cap) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
     ctrl->n_cur = n; ctrl->n_live = 0; ctrl->n_carry = 0; ctrl->row_base = 0;
     ctrl->rows_cap = rows_cap; ctrl->error = 0; ctrl->pad = 0;
-    for (int k = 0; k < 4; ++k) ctrl->paths[k] = 0;
+    for (int k = 0; k < 6; ++k) ctrl->paths[k] = 0;
   }
 }
 

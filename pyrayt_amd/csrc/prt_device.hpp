@@ -69,7 +69,7 @@ struct DevInstr {
   int32_t a5;     //                   CSG: right base
   int32_t a6;     //                   CSG: right length
   int32_t a7;     //                   CSG: out base
-  int32_t pad[2]; // CSG: [0] root node of a component, [1] cull box implied (see csg_node); LEAF: [0] == 1 skippable right leaf, == 2 a whole component
+  int32_t pad[2]; // CSG: [0] root node of a component, [1] cull box implied (see csg_node); LEAF: [0] == 1 skippable right leaf, == 2 a whole component, [1] a bare plane of a trace program that computes t first (plane_leaf_candidate)
   int32_t type;   // LEAF: PRIM_*
   double data[18];// LEAF: params[0..5], M^-1 rows 0..2 [6..17]   CSG: cull box [0..5]
 };
@@ -155,6 +155,11 @@ __device__ __forceinline__ void count_paths(unsigned long long* paths, int k, bo
   const unsigned long long m = __ballot(flag);
   if (m != 0ull && (int)(threadIdx.x & 63) == __ffsll((long long)__ballot(true)) - 1)
     atomicAdd(&paths[k], (unsigned long long)__popcll(m));
+}
+// ... and one per WAVE that takes a wave-level shortcut (slot 4: plane_leaf_candidate)
+__device__ __forceinline__ void count_wave(unsigned long long* paths, int k) {
+  if (paths == nullptr) return;
+  if ((int)(threadIdx.x & 63) == __ffsll((long long)__ballot(true)) - 1) atomicAdd(&paths[k], 1ull);
 }
 
 // a sorted pair of hit parameters with the primitive that produced it
@@ -379,6 +384,42 @@ __device__ __forceinline__ void surface_pair(int type, const double* __restrict_
   const double dy = row_dot(m, 1, r.dx, r.dy, r.dz, r.dw);
   const double dz = row_dot(m, 2, r.dx, r.dy, r.dz, r.dw);
   object_pair(type, q, ox, oy, oz, dx, dy, dz, t0, t1);
+}
+
+// ---- a bare PLANE as a whole component of a trace program (a detector, a baffle, a stop) ----------
+// primitive_pair's PLANE reports (t, t) or (inf, inf): its two slabs -- four of its five divisions -- can only
+// turn t into +inf, they are never a candidate themselves.  So t comes first, from the two rows it needs and
+// exactly as primitive_pair forms it; a lane whose t is not positive and finite, or does not beat its nearest
+// hit so far, is left alone by this leaf whatever the slabs say, and a wave without any other lane does not
+// finish the leaf.  An identity on the leaf's own numbers, not a geometric argument: it holds for every ray
+// (no well_formed gate) and every visiting order (beats() is the rule the candidate meets anyway).  The
+// renderers may offer a non-positive entry and keep the full leaf.  Scene option `no_plane_bound`.
+__device__ __forceinline__ void plane_leaf_candidate(const double* __restrict__ q, const double* __restrict__ m,
+                                                     const Ray8& r, int p, double& best_t, int& best_prim) {
+  const double oz = row_dot(m, 2, r.ox, r.oy, r.oz, r.ow);
+  const double dz = row_dot(m, 2, r.dx, r.dy, r.dz, r.dw);
+  const bool skew = near0(dz);
+  double t = -oz / (dz + (skew ? 1.0 : 0.0));
+  if (skew) t = PRT_INF;
+  const bool can = t > 0 && t < PRT_INF && beats(r, t, p, best_t, best_prim);  // (a NaN cannot)
+  if (__ballot(can) == 0ull) {
+    count_wave(r.paths, 4);
+    return;
+  }
+  const double ox = row_dot(m, 0, r.ox, r.oy, r.oz, r.ow);
+  const double oy = row_dot(m, 1, r.ox, r.oy, r.oz, r.ow);
+  const double dx = row_dot(m, 0, r.dx, r.dy, r.dz, r.dw);
+  const double dy = row_dot(m, 1, r.dx, r.dy, r.dz, r.dw);
+  const double hw = q[0] / 2, hl = q[1] / 2;
+  double lx, hx, ly, hy;
+  axis_slab(ox, dx, hw, -hw, fabs(ox) <= hw, lx, hx);
+  axis_slab(oy, dy, hl, -hl, fabs(oy) <= hl, ly, hy);
+  const double enter = dmax(lx, ly), leave = dmin(hx, hy);
+  if (!(t >= enter && t <= leave)) t = PRT_INF;
+  if (t > 0 && t < PRT_INF && beats(r, t, p, best_t, best_prim)) {
+    best_t = t;
+    best_prim = p;
+  }
 }
 
 // ---- primitive.normal in object space (primitives.py Sphere :273-296, Paraboloid :401-419,
@@ -1228,6 +1269,11 @@ __device__ __forceinline__ void run_step(const DevInstr* in, const Ray8& ray, co
         rb.t0 = PRT_INF; rb.t1 = PRT_INF; rb.prim = p;
         return;
       }
+    }
+    if (!RENDER && in->pad[0] == 2 && in->pad[1] != 0 && in->type == PRIM_PLANE) {  // (uniform)
+      // a bare plane: its slabs only where some lane's t can win (plane_leaf_candidate)
+      plane_leaf_candidate(in->data, in->data + 6, ray, p, best_t, best_prim);
+      return;
     }
     surface_pair(in->type, in->data, in->data + 6, ray, t0, t1);
     const int dst = in->a1;

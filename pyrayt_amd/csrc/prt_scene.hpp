@@ -158,7 +158,7 @@ struct prt_scene {
   long sparse_keep_launches = 0;  // ... of which kept their absorbed rays to stay dense (hint mode 4)
   // PRT_TRACE_COUNT_PATHS: traces counted, rays that were not well formed, CSG node evaluations under an
   // implied cull box that had survivors, ... of which took upstream's exact box test
-  long long path_counts[4] = {0, 0, 0, 0};
+  long long path_counts[5] = {0, 0, 0, 0, 0};  // ([4]: prt_trace_shortcut_counts)
   int hint_holdoff = 0;         // traces still to run without hints after a miss (doubles with every miss in a row)
   std::vector<char> missed_mode;            // the hint modes of an attempt that missed, until its repeat has been looked at
   std::vector<int> hint_rest, hint_rest_span;  // per generation: traces for which its dense hint is not offered / the span of its last rest
@@ -549,6 +549,8 @@ static Operand compile_component(const prt_scene* s, int root_node, std::vector<
     res = c.emit(root_node, 0);
   if (root_rule != ROOT_NONE && s->nodes[root_node].op == PRT_NODE_LEAF) {
     code.back().pad[0] = 2;  // a bare surface: the leaf step itself yields the component's candidate
+    // a bare plane of a trace program finishes its slabs only for a wave in which its t can win (plane_leaf_candidate)
+    if (root_rule == ROOT_TRACE && code.back().type == PRIM_PLANE && !s->options.no_plane_bound) code.back().pad[1] = 1;
   } else if (root_rule == ROOT_TRACE && code.size() > from && code.back().kind == I_CSG) {
     code.back().pad[0] = 1;  // the node reduces straight to its nearest positive survivor
   } else if (root_rule != ROOT_NONE) {

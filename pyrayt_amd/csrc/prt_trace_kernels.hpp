@@ -29,7 +29,8 @@ struct TraceCtrl {
   int64_t rows_cap;
   int32_t error;      // PRT_ERR_* raised on the device
   int32_t pad;
-  unsigned long long paths[4];  // PRT_TRACE_COUNT_PATHS: [1] rays not well formed, [2] implied-box nodes with survivors, [3] ... tested exactly
+  unsigned long long paths[6];  // PRT_TRACE_COUNT_PATHS: [1] rays not well formed, [2] implied-box nodes with survivors, [3] ... tested exactly,
+                                // [4] waves that did not finish a bare plane leaf, [5] spare
 };
 
 // dead-ray rule of _pyrayt.py:415-420: absorbed (|d| ~ 0 before the interaction) or no hit;

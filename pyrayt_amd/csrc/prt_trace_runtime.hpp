@@ -119,6 +119,7 @@ static int64_t trace_unfused(prt_scene* s, DeviceCopy* c, TraceTicket* t, int64_
     hipLaunchKernelGGL(k_advance, dim3(1), dim3(1), 0, st, ctrl, gen_rows, g);
     HIP_TRY(hipEventRecord(t->ev1, st));
     // the host needs the new ray count to size the next launch
+    static_assert(sizeof(TraceCtrl) <= 12 * sizeof(int64_t), "the control block ends in front of the row count's slot");
     HIP_TRY(hipMemcpyAsync(t->host_pinned, ctrl, sizeof(TraceCtrl), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(t->host_pinned + 12, gen_rows + g, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -143,7 +144,7 @@ static int64_t trace_unfused(prt_scene* s, DeviceCopy* c, TraceTicket* t, int64_
   if (count_paths) {  // (the control block of the last generation is on the host: the counters are cumulative)
     const TraceCtrl* h = (const TraceCtrl*)t->host_pinned;
     s->path_counts[0] += 1;
-    for (int k = 1; k < 4; ++k) s->path_counts[k] += (long long)h->paths[k];
+    for (int k = 1; k < 5; ++k) s->path_counts[k] += (long long)h->paths[k];
   }
   return total_rows;
 }
@@ -941,6 +942,12 @@ extern "C" int prt_trace_telemetry(const prt_scene* s, int64_t* out12) {
   out8[2] = s->dense_launches;
   out8[3] = s->full_rows_fallbacks;
   for (int k = 0; k < 4; ++k) out8[4 + k] = s->path_counts[k];
+  return PRT_OK;
+}
+
+extern "C" int prt_trace_shortcut_counts(const prt_scene* s, int64_t* out1) {
+  if (!s || !out1) return fail(PRT_ERR_ARG, "null argument");
+  out1[0] = s->path_counts[4];
   return PRT_OK;
 }
 

@@ -44,7 +44,8 @@ TRACE_TICKETS = 4
 OPTIONS_DTYPE = np.dtype(
     [("struct_size", "<i4"), ("no_chain", "<i4"), ("no_cull", "<i4"), ("cull_min", "<i4"), ("no_groups", "<i4"),
      ("no_implied", "<i4"), ("hit_lanes", "<i4"), ("hit_staged", "<i4"), ("list_order_groups", "<i4"),
-     ("one_direction", "<i4"), ("no_intervals", "<i4"), ("no_clearance", "<i4"), ("reserved", "<i4", (4,))])
+     ("one_direction", "<i4"), ("no_intervals", "<i4"), ("no_clearance", "<i4"), ("no_plane_bound", "<i4"),
+     ("reserved", "<i4", (3,))])
 assert OPTIONS_DTYPE.itemsize == 64
 OPTION_NAMES = tuple(name for name in OPTIONS_DTYPE.names if name not in ("struct_size", "reserved"))
 DEFAULT_OPTIONS = {}
@@ -123,6 +124,7 @@ def _declare(lib):
         "prt_trace_set_plan": (c_int, [c_p, c_int, c_int, c_p]),
         "prt_trace_stats": (c_int, [c_p, c_p]),
         "prt_trace_telemetry": (c_int, [c_p, c_p]),
+        "prt_trace_shortcut_counts": (c_int, [c_p, c_p]),
         "prt_generate_rays": (c_int, [c_int, c_p, c_i64, c_i64, c_i64, c_i64, c_p, c_i64, c_i64, c_p]),
         "prt_camera_rays": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p]),
         "prt_render_hits": (c_int, [c_p, c_int, c_p, c_i64, c_i64, c_p, c_p, c_p]),
@@ -205,7 +207,7 @@ EXPORTED_SYMBOLS = (
     "prt_scene_component_rows", "prt_scene_info", "prt_intersect", "prt_propagate", "prt_world_normals",
     "prt_material_trace", "prt_interact_workspace_bytes", "prt_interact", "prt_scene_set_index_tables",
     "prt_gather_hits", "prt_scatter_shaded", "prt_unique_workspace_bytes", "prt_unique_values",
-    "prt_trace_workspace_bytes", "prt_trace", "prt_trace_begin", "prt_trace_end", "prt_trace_batch", "prt_trace_batch_busy", "prt_trace_set_plan", "prt_trace_stats", "prt_trace_telemetry", "prt_generate_rays",
+    "prt_trace_workspace_bytes", "prt_trace", "prt_trace_begin", "prt_trace_end", "prt_trace_batch", "prt_trace_batch_busy", "prt_trace_set_plan", "prt_trace_stats", "prt_trace_telemetry", "prt_trace_shortcut_counts", "prt_generate_rays",
     "prt_camera_rays", "prt_render_hits", "prt_gooch_shade", "prt_gooch_mix", "prt_render",
     "prt_edge_workspace_bytes", "prt_edge_canvas", "prt_reflect", "prt_refract", "prt_binomial_root",
     "prt_smallest_positive_root", "prt_dot", "prt_array_csg", "prt_primitive_intersect",
@@ -847,7 +849,11 @@ class DeviceScene:
         keys = ("lookback_fallbacks", "speculation_misses", "dense_launches", "full_rows_fallbacks",
                 "counted_traces", "rays_not_well_formed", "implied_box_nodes", "exact_box_tests",
                 "plan_launches", "plan_misses", "sparse_keep_launches", "plan_dense_launches")
-        return dict(zip(keys, (int(v) for v in out)))
+        told = dict(zip(keys, (int(v) for v in out)))
+        more = (ctypes.c_int64 * 1)()
+        _check(library().prt_trace_shortcut_counts(self.handle, more))
+        told["plane_leaves_not_finished"] = int(more[0])
+        return told
 
     # --- per-state entry points -----------------------------------------------------------------
     def propagate(self, rays):
