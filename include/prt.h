@@ -1049,9 +1049,9 @@ int prt_frame_fresnel_coated(int device, const double* rows, int64_t ld, const i
  * by id, are its whole path, `surface` names the primitive each segment ended on, and the surface table below says what
  * that primitive is.  A tangent (do, dd) per ray and parameter is pushed through the recorded interfaces.  The result is
  * the derivative AT FIXED PATH, as in every differential ray trace: a ray whose sequence of surfaces changes under the
- * motion (the edge of an aperture) is outside it.  Sources do not move; derivatives of anything but the landing point and
- * its moments (the optical path, for one) are not computed.  Shape and index parameters: prt_frame_design_sensitivity,
- * below.
+ * motion (the edge of an aperture) is outside it.  Sources do not move.  Shape and index parameters:
+ * prt_frame_design_sensitivity, below; the optical path, the OPD and its Zernike terms: prt_frame_opd_sensitivity, below
+ * that.
  *
  * Definitions.
  * Frame: whole and generation-major, ids as prt_frame_optical_path wants them (a repeated id, an id out of range, a row
@@ -1137,7 +1137,8 @@ int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int6
  *   list that is not empty), after the rigid terms, which are computed as prt_frame_sensitivity computes them.  So a
  *   parameter with S = 0 and no index list gets the bits it gets from prt_frame_sensitivity, and every parameter the bits
  *   it gets alone.
- * Still out of scope: moving a source, derivatives of the optical path (the OPD), rays whose path changes.
+ * Still out of scope: moving a source, rays whose path changes.  The optical path and the OPD: prt_frame_opd_sensitivity,
+ * below.
  *
  * prt_frame_design_sensitivity: the arguments of prt_frame_sensitivity with linear, index_rates, index_ids and index_first
  * after parameter_first; outputs, selection, sums, counters, caps and guarantees as there.  Every entry of linear and
@@ -1155,6 +1156,60 @@ int prt_frame_design_sensitivity(int device, const double* rows, int64_t ld, con
                                  const int64_t* selected, int64_t n_selected, const int64_t* group_first, int n_groups,
                                  int weight_column, const double* pivots, double* jacobian_out, double* sums_out,
                                  int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Wavefront sensitivities: d(OPD) and the Zernike right-hand sides per parameter ------------------------------------
+ * The design form above with one more plane of state per ray and parameter, dL: the derivative of the row's cumulative
+ * optical path as prt_frame_optical_path defines it (index * |x - o|, the 1e-6 relaunch offset part of o).  With the
+ * notation above, len = |x - o|, n the index of the row's segment and dnu its derivative, start = do (0 in generation 0):
+ *     dL = dL_prev + dnu len + n d.(dx - start),   dL_prev = 0 in generation 0.
+ * (d(n len) = dnu len + n d.(dx - do): the segment's unit vector is d.)
+ * At a selected row the reference sphere of a wavefront pass is HELD FIXED: per group P, R, the pivot and the pupil
+ * radius (wavefront_groups HOST (n_groups, 6), as prt_frame_wavefront's group records have them in [0..5]), and the basis
+ * (axes HOST 9 doubles: a, e1, e2).  Q = x is the landing point, u = d, s the larger root of |Q - s u - P| = R and
+ * E = Q - s u, as prt_frame_wavefront computes them; OPD = (L - n s) - pivot, L the row's cumulative optical path (opl
+ * DEVICE n_rows, from prt_frame_optical_path).  Per parameter:
+ *   dfield = dL - s dnu - n (u.dx)          the wavefront change at a FIXED pupil point (Hopkins and Tiziani 1966): to first
+ *                                           order the OPD along the ray through E is stationary in E (Fermat), so ds drops out
+ *   dE     = dx - ds u - s dd,  ds = (E - P).(dx - s dd) / ((E - P).u)      the motion of the ray's point on the sphere
+ *   dpupil = (dE.e1, dE.e2) / pupil radius
+ *   dopd   = dfield + n (u.dE)              the derivative of this ray's own OPD, following the ray (= dL - s dnu - n ds, as
+ *                                           u.dd = 0)
+ * A reference that follows the group's centroid P(p) is not computed here: it is dfield - n (u.dP_k), linear in the three
+ * columns n u_c, whose Zernike right-hand sides are among the sums.
+ * A ray that misses the sphere, or that the pass cannot follow, is NaN in dfield, dopd and dpupil (and in opd_out and
+ * pupil_out), and is left out of the sums below; the counters are those of prt_frame_sensitivity.
+ * Order of the arithmetic: the terms of dL and of the sphere come after those of the design form, behind a compile-time
+ * flag: jacobian_out and sums_out have the bits of prt_frame_design_sensitivity (for parameters with S = 0 and no index
+ * list: of prt_frame_sensitivity).
+ * Wavefront sums, per group, F = 5 + J (K + 3) + 4 K + K (K + 1) / 2 doubles (opd_sums_out DEVICE (n_groups, F)), over the
+ * selected rows that are finite in w, x, dx, OPD, the pupil point, dfield and dopd; Z the J <= 36 Noll terms of
+ * prt_frame_wavefront at the row's nominal pupil point:
+ *   count, rows followed that miss the sphere, sum w, sum w OPD, sum w OPD^2 (OPD about the pivot);
+ *   Z^T W y, column-major (column c at [5 + c J, 5 + (c + 1) J)), for y = dfield_k (K columns), then n u_c (3 columns);
+ *   sum w dopd_k, sum w OPD dopd_k, sum w dfield_k, sum w OPD dfield_k (K each);
+ *   sum w dfield_j dfield_k for k <= j (row-major lower triangle).
+ *   Each workgroup writes the partial sums of its 256 outputs, each entry owned by one thread that walks the rows in
+ *   order; the partials are added as those of prt_frame_sensitivity are.  Same bits on every run.
+ *
+ * prt_frame_opd_sensitivity: the arguments of prt_frame_design_sensitivity up to pivots; then opl, wavefront_groups, axes,
+ * n_terms (J); then out, overwritten: jacobian_out, sums_out (as there), dfield_out, dopd_out DEVICE (K, n_selected),
+ * dpupil_out DEVICE (K, 2, n_selected), opd_out DEVICE n_selected (about the pivot, piston not removed), pupil_out DEVICE
+ * (n_selected, 2) (normalised), opd_sums_out, record_out.  A group with rows must have a pupil radius > 0; J in [1, 36];
+ * otherwise the refusals of prt_frame_design_sensitivity.  workspace:
+ * prt_frame_opd_sensitivity_workspace_bytes(the arguments of the others, then J): eight planes, 64 K bytes a ray, the group
+ * records and the partials of the wavefront sums. */
+int64_t prt_frame_opd_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                                                  int64_t max_group_rows, int n_terms);
+int prt_frame_opd_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                              int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
+                              const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
+                              const double* linear, const double* index_rates, const int64_t* index_ids,
+                              const int32_t* index_first, int n_parameters, const int64_t* row_slot,
+                              const int64_t* selected, int64_t n_selected, const int64_t* group_first, int n_groups,
+                              int weight_column, const double* pivots, const double* opl, const double* wavefront_groups,
+                              const double* axes, int n_terms, double* jacobian_out, double* sums_out, double* dfield_out,
+                              double* dopd_out, double* dpupil_out, double* opd_out, double* pupil_out,
+                              double* opd_sums_out, int64_t* record_out, void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

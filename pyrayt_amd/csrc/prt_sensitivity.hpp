@@ -18,7 +18,12 @@
 //                   gets the bits of sens_row<false>.
 //   k_sens_step     one launch per generation, in generation order on one stream: sens_row<false>, then the counters
 //   k_sens_design_step  the same launch for sens_row<true>
+//   k_sens_opd_step the design form plus an eighth plane, dL = d(cumulative optical path): sens_row<true, true>.  At a
+//                   selected row it also writes the wavefront change per parameter (dfield, dopd, dpupil) against the fixed
+//                   reference sphere of a wavefront pass, and the row's own OPD and pupil point
 //   k_sens_partials the group sums of the selected rows as per-workgroup partials, written in workgroup order
+//   k_sens_opd_partials  the wavefront sums (Z^T W y for K + 3 right-hand sides, the moments of dopd and dfield) as
+//                   per-workgroup partials: a 64-row tile of factors in LDS, every entry a product of two of its columns
 //   k_sens_fold     the partials of a group added in a fixed order: one wave per (group, entry)
 // n, and the decision "wall or cap", come from the functions the trace uses: world_normal_len and object_normal of
 // prt_device.hpp.  No two lanes touch one ray's state, there are no floating-point atomics; the sums run over the
@@ -56,6 +61,17 @@ struct SensArgs { SensTwist twist[SENS_MAX_PARAMETERS]; int n_parameters, n_surf
 struct SensDesign { double S[SENS_MAX_PARAMETERS][9]; double rate[SENS_MAX_PARAMETERS]; uint32_t linear, index; };
 struct SensWords { u64 count[SENS_COUNTERS]; int status; };  // unknown, invalid, unfit, reflections
 struct SensVec { double x, y, z; };
+// the wavefront form's own arguments: the rows' cumulative optical path, per group (P (3), R, pivot, pupil radius), the
+// device copy of group_first, the pupil basis, and the outputs in selection order
+enum { SENS_OPD_GROUP = 6 };
+struct SensOpd {
+  const double* opl;
+  const double* groups;
+  const int64_t* first;
+  int n_groups;
+  double e1[3], e2[3];
+  double *dfield, *dopd, *dpupil, *opd, *pupil;
+};
 
 __device__ __forceinline__ double sv_dot(const SensVec& a, const SensVec& b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ SensVec sv_cross(const SensVec& a, const SensVec& b) {
@@ -141,15 +157,16 @@ __device__ __forceinline__ SensVec sens_linear(const double* __restrict__ S, con
 enum { SENS_NONE = 0, SENS_REFRACT = 1, SENS_REFLECT = 2 };
 
 // row j of `generation`; flag: what the row adds to the counters.  kDesign: `design` is read and the state has seven planes.
-template <bool kDesign>
+// kOpd (with kDesign): `wave` is read and the state has an eighth plane, dL; its terms come after everything else.
+template <bool kDesign, bool kOpd = false>
 __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t j,
                                          int generation, double id0, int64_t n_ids, const SensArgs& args,
                                          const SensSurface* __restrict__ table, double* __restrict__ state,
                                          int64_t* __restrict__ last_row, int* __restrict__ stamp, int* status,
                                          const int64_t* __restrict__ row_slot, int64_t n_selected,
                                          double* __restrict__ jacobian, bool (&flag)[SENS_COUNTERS],
-                                         const SensDesign* design) {
-  constexpr int kPlanes = kDesign ? 7 : 6;
+                                         const SensDesign* design, const SensOpd* wave = nullptr) {
+  constexpr int kPlanes = kOpd ? 8 : kDesign ? 7 : 6;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int K = args.n_parameters;
   bool unknown = false, invalid = false, unfit = false, reflection = false;
@@ -248,6 +265,36 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
       }
     }
     dead = was_dead || invalid || unknown || unfit;
+    // the wavefront form: the segment as prt_frame_optical_path has it, and at a selected row E, s, the OPD and the pupil
+    // point as k_frame_wavefront_pupil has them, against the group's fixed sphere
+    double seg = 0.0, nidx = 1.0, s_ext = 0.0, ep_d = 1.0, pupil_r = 1.0;
+    SensVec ep = {0.0, 0.0, 0.0};
+    bool hit = false;
+    if constexpr (kOpd) {
+      seg = sqrt(sv_dot(run, run));
+      nidx = rows[PRT_COL_INDEX * ld + j];
+      if (slot >= 0) {
+        int lo = 0, hi = wave->n_groups;  // the last group q with first[q] <= slot
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (wave->first[mid] <= slot) lo = mid; else hi = mid;
+        }
+        const double* __restrict__ g = wave->groups + (int64_t)lo * SENS_OPD_GROUP;
+        double e[3], opd = nan, p1 = nan, p2 = nan;
+        pupil_r = g[5];
+        if (!dead && wf_extend(rows, ld, j, g, g[3], s_ext, e)) {
+          opd = (wave->opl[j] - nidx * s_ext) - g[4];
+          ep = {e[0] - g[0], e[1] - g[1], e[2] - g[2]};
+          p1 = ((ep.x * wave->e1[0] + ep.y * wave->e1[1]) + ep.z * wave->e1[2]) / pupil_r;
+          p2 = ((ep.x * wave->e2[0] + ep.y * wave->e2[1]) + ep.z * wave->e2[2]) / pupil_r;
+          ep_d = sv_dot(ep, d);
+          hit = is_finite(opd) && is_finite(p1) && is_finite(p2);
+        }
+        wave->opd[slot] = hit ? opd : nan;
+        wave->pupil[2 * slot] = hit ? p1 : nan;
+        wave->pupil[2 * slot + 1] = hit ? p2 : nan;
+      }
+    }
     if (!dead) {
 #pragma unroll 1
       for (int k = 0; k < K; ++k) {
@@ -334,6 +381,27 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
           double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
           out[0] = dx.x; out[n_selected] = dx.y; out[2 * n_selected] = dx.z;
         }
+        if constexpr (kOpd) {  // dL = dL_prev + dnu len + n d.(dx - start); then the wavefront change at the fixed sphere
+          const double before = generation > 0 ? s[7 * n_ids] : 0.0;
+          const double dL = (before + dnu * seg) + nidx * sv_dot(d, sv_sub(dx, start));
+          s[7 * n_ids] = dL;
+          if (slot >= 0) {
+            double dfield = nan, dopd = nan, dp1 = nan, dp2 = nan;
+            if (hit) {
+              dfield = (dL - s_ext * dnu) - nidx * sv_dot(d, dx);
+              const SensVec y = sv_sub(dx, sv_scale(s_ext, dd));
+              const double ds = sv_dot(ep, y) / ep_d;
+              const SensVec dE = sv_sub(y, sv_scale(ds, d));
+              dp1 = ((dE.x * wave->e1[0] + dE.y * wave->e1[1]) + dE.z * wave->e1[2]) / pupil_r;
+              dp2 = ((dE.x * wave->e2[0] + dE.y * wave->e2[1]) + dE.z * wave->e2[2]) / pupil_r;
+              dopd = dfield + nidx * sv_dot(d, dE);
+            }
+            wave->dfield[(int64_t)k * n_selected + slot] = dfield;
+            wave->dopd[(int64_t)k * n_selected + slot] = dopd;
+            wave->dpupil[(int64_t)(2 * k) * n_selected + slot] = dp1;
+            wave->dpupil[(int64_t)(2 * k + 1) * n_selected + slot] = dp2;
+          }
+        }
       }
     }
     // a ray is counted once: it is NaN from there on
@@ -345,7 +413,18 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
     for (int k = 0; k < K; ++k) {
       double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
       out[0] = nan; out[n_selected] = nan; out[2 * n_selected] = nan;
+      if constexpr (kOpd) {
+        wave->dfield[(int64_t)k * n_selected + slot] = nan;
+        wave->dopd[(int64_t)k * n_selected + slot] = nan;
+        wave->dpupil[(int64_t)(2 * k) * n_selected + slot] = nan;
+        wave->dpupil[(int64_t)(2 * k + 1) * n_selected + slot] = nan;
+      }
     }
+  if constexpr (kOpd) {
+    if (dead && !joined && slot >= 0) {  // (a row the join refused never reached the block above)
+      wave->opd[slot] = nan; wave->pupil[2 * slot] = nan; wave->pupil[2 * slot + 1] = nan;
+    }
+  }
   if (i >= 0) last_row[i] = dead ? -1 - j : j;  // (also for a row the status word refuses: the next launch reads this one's)
   flag[0] = unknown; flag[1] = invalid; flag[2] = unfit; flag[3] = reflection;
 }
@@ -374,6 +453,20 @@ k_sens_design_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, 
   if (j < start + count)
     sens_row<true>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status,
                    row_slot, n_selected, jacobian, flag, &design);
+  fresnel_count(flag, words->count);
+}
+
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_opd_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t start, int64_t count, int generation,
+                double id0, int64_t n_ids, SensArgs args, SensDesign design, SensOpd wave,
+                const SensSurface* __restrict__ table, double* __restrict__ state, int64_t* __restrict__ last_row,
+                int* __restrict__ stamp, SensWords* __restrict__ words, const int64_t* __restrict__ row_slot,
+                int64_t n_selected, double* __restrict__ jacobian) {
+  const int64_t j = start + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
+  bool flag[SENS_COUNTERS] = {};
+  if (j < start + count)
+    sens_row<true, true>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status,
+                         row_slot, n_selected, jacobian, flag, &design, &wave);
   fresnel_count(flag, words->count);
 }
 
@@ -456,10 +549,163 @@ k_sens_fold(const double* __restrict__ partials, int chunks, int entries, int n_
   if (threadIdx.x == 0) sums[at] = sum;
 }
 
+// ---- the wavefront sums ----------------------------------------------------------------------------------------------------
+// entries of a group, K parameters and J Zernike terms, over the selected rows that are finite throughout and met the sphere:
+// count, rows that missed the sphere, sum w, sum w OPD, sum w OPD^2 (OPD about the pivot); Z^T W y, column-major, for the
+// K + 3 columns y = dfield_k and n u_c (J (K + 3)); sum w dopd_k, sum w OPD dopd_k, sum w dfield_k, sum w OPD dfield_k (K each);
+// sum w dfield_j dfield_k for k <= j (row-major lower triangle).
+// Every entry is a sum over rows of L[l] * R[r], two columns of a tile that a workgroup keeps in LDS for 64 rows at a time:
+//   L: Z_1..Z_J, 1, OPD, dfield_k (J + 2 + K)      R: w dfield_k, w n u_c, w dopd_k, w, w OPD, live, missed (2 K + 7)
+// A thread owns up to four entries and walks the tile's rows in order, four independent chains; the basis is evaluated
+// once a row, by the wave whose rows are staged.  (k_frame_zernike owns one entry a thread over thousands of rows in few
+// workgroups; here a workgroup has 256 rows and the grid has one workgroup per 256 rows, so the chains are short and many.)
+enum { SENS_OPD_FIXED = 5, SENS_OPD_TILE = 64 };
+static int sens_opd_entries(int K, int J) { return SENS_OPD_FIXED + J * (K + 3) + 4 * K + K * (K + 1) / 2; }
+enum { SENS_OPD_MAX_ENTRIES = SENS_OPD_FIXED + WF_MAX_TERMS * (SENS_MAX_PARAMETERS + 3) + 4 * SENS_MAX_PARAMETERS +
+                              SENS_MAX_PARAMETERS * (SENS_MAX_PARAMETERS + 1) / 2 };
+static const int kOpdEntriesPerThread = (SENS_OPD_MAX_ENTRIES + kSensBlock - 1) / kSensBlock;
+__host__ __device__ constexpr int sens_opd_stride(int K, int J) { return (J + 3 * K + 9) | 1; }
+
+// the columns (l of L, r of R) of entry e
+__device__ __forceinline__ void sens_opd_entry(int e, int K, int J, int& l, int& r) {
+  const int one = J, opd = J + 1, w = 2 * K + 3, w_opd = 2 * K + 4;
+  if (e < SENS_OPD_FIXED) {
+    l = e == 4 ? opd : one;
+    r = e == 0 ? 2 * K + 5 : e == 1 ? 2 * K + 6 : e == 2 ? w : w_opd;
+    return;
+  }
+  e -= SENS_OPD_FIXED;
+  if (e < J * (K + 3)) { l = e % J; r = e / J; return; }
+  e -= J * (K + 3);
+  if (e < 4 * K) {
+    const int which = e / K, k = e % K;  // dopd, OPD dopd, dfield, OPD dfield
+    l = (which & 1) ? opd : one;
+    r = which < 2 ? K + 3 + k : k;
+    return;
+  }
+  e -= 4 * K;
+  int row = 0;
+  while ((row + 1) * (row + 2) / 2 <= e) ++row;
+  l = J + 2 + row;
+  r = e - row * (row + 1) / 2;
+}
+
+// workgroup (chunk, group): slots [first[group] + 256 chunk, ...) of the group; its partial sums to
+// partials[(group * chunks + chunk) * entries + e]
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_opd_partials(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const int64_t* __restrict__ selected,
+                    int64_t n_selected, const int64_t* __restrict__ first, int K, int J, int weight_column,
+                    const double* __restrict__ jacobian, const double* __restrict__ opd, const double* __restrict__ pupil,
+                    const double* __restrict__ dfield, const double* __restrict__ dopd, double* __restrict__ partials,
+                    int* status) {
+  extern __shared__ double opd_tile[];  // [SENS_OPD_TILE][stride]: L then R of each row
+  const int group = blockIdx.y, entries = SENS_OPD_FIXED + J * (K + 3) + 4 * K + K * (K + 1) / 2;
+  const int stride = sens_opd_stride(K, J), n_left = J + 2 + K;
+  const int64_t begin = first[group] + (int64_t)blockIdx.x * kSensBlock;
+  const int64_t end = first[group + 1] < n_selected ? first[group + 1] : n_selected;
+  double* __restrict__ out = partials + ((int64_t)group * gridDim.x + blockIdx.x) * entries;
+  int el[kOpdEntriesPerThread], er[kOpdEntriesPerThread];
+  double acc[kOpdEntriesPerThread];
+#pragma unroll
+  for (int q = 0; q < kOpdEntriesPerThread; ++q) {
+    const int e = threadIdx.x + q * kSensBlock;
+    el[q] = er[q] = -1;
+    if (e < entries) sens_opd_entry(e, K, J, el[q], er[q]);
+    acc[q] = 0.0;
+  }
+  for (int sub = 0; sub < kSensWaves; ++sub) {
+    const int64_t base = begin + (int64_t)sub * SENS_OPD_TILE;
+    if (base >= end) break;  // (the same for every thread of the workgroup)
+    const int here = (int)(end - base < SENS_OPD_TILE ? end - base : SENS_OPD_TILE);
+    if ((int)(threadIdx.x >> 6) == sub) {
+      const int lane = threadIdx.x & 63;
+      double* __restrict__ L = opd_tile + lane * stride;
+      double* __restrict__ R = L + n_left;
+      const int64_t s = base + lane;
+      bool live = false, missed = false;
+      double w = 0.0, v = 0.0, nu[3] = {0.0, 0.0, 0.0};
+      double z[WF_MAX_TERMS];
+#pragma unroll
+      for (int k = 0; k < WF_MAX_TERMS; ++k) z[k] = 0.0;
+      if (lane < here) {
+        const int64_t r = selected[s];
+        if (r < 0 || r >= n_rows) {
+          atomicOr(status, SENS_BAD_SELECTION);
+        } else {
+          w = weight_column < 0 ? 1.0 : rows[weight_column * ld + r];
+          bool followed = is_finite(w) && sv_finite(sv_col(rows, ld, PRT_COL_X1, r));
+          for (int c = 0; c < 3 * K; ++c) followed = followed && is_finite(jacobian[(int64_t)c * n_selected + s]);
+          v = opd[s];
+          const double px = pupil[2 * s], py = pupil[2 * s + 1];
+          live = followed && is_finite(v) && is_finite(px) && is_finite(py);
+          missed = followed && !live;
+          for (int k = 0; k < K; ++k)
+            live = live && is_finite(dfield[(int64_t)k * n_selected + s]) && is_finite(dopd[(int64_t)k * n_selected + s]);
+          if (live) {
+            wf_zernike(px, py, z);
+            const double n = rows[PRT_COL_INDEX * ld + r];
+            const SensVec u = sv_col(rows, ld, PRT_COL_XTILT, r);
+            nu[0] = n * u.x; nu[1] = n * u.y; nu[2] = n * u.z;
+            live = is_finite(nu[0]) && is_finite(nu[1]) && is_finite(nu[2]);
+          }
+        }
+      }
+      if (!live) { w = 0.0; v = 0.0; }
+#pragma unroll
+      for (int k = 0; k < WF_MAX_TERMS; ++k)
+        if (k < J) L[k] = live ? z[k] : 0.0;
+      L[J] = 1.0;
+      L[J + 1] = v;
+      for (int k = 0; k < K; ++k) {
+        const double f = live ? dfield[(int64_t)k * n_selected + s] : 0.0;
+        const double o = live ? dopd[(int64_t)k * n_selected + s] : 0.0;
+        L[J + 2 + k] = f;
+        R[k] = w * f;
+        R[K + 3 + k] = w * o;
+      }
+      for (int c = 0; c < 3; ++c) R[K + c] = live ? w * nu[c] : 0.0;
+      R[2 * K + 3] = w;
+      R[2 * K + 4] = w * v;
+      R[2 * K + 5] = live ? 1.0 : 0.0;
+      R[2 * K + 6] = missed ? 1.0 : 0.0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < kOpdEntriesPerThread; ++q) {
+      if (el[q] < 0) continue;
+      const double* __restrict__ a = opd_tile + el[q];
+      const double* __restrict__ b = opd_tile + n_left + er[q];
+      double c = acc[q];
+      for (int k = 0; k < here; ++k) c += a[k * stride] * b[k * stride];
+      acc[q] = c;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < kOpdEntriesPerThread; ++q)
+    if (el[q] >= 0) out[threadIdx.x + q * kSensBlock] = acc[q];
+}
+
 // ---- entry points ----------------------------------------------------------------------------------------------------------
 struct SensWork { SensWords* words; SensSurface* table; int64_t* first; double* pivots; double* state; int64_t* last_row; int* stamp; double* partials; };
+// what the wavefront form has behind the others' workspace: the group records and the partials of its own sums
+struct SensOpdWork { double* groups; double* partials; };
+// the wavefront form's arguments on the host: opl DEVICE n_rows; groups HOST (n_groups, 6); axes HOST 9; the outputs DEVICE
+struct SensOpdCall {
+  const double* opl; const double* groups; const double* axes; int n_terms;
+  double *dfield, *dopd, *dpupil, *opd, *pupil, *sums;
+};
+
 
 static int64_t sens_chunks(int64_t max_group_rows) { return (max_group_rows + kSensBlock - 1) / kSensBlock; }
+
+static SensOpdWork sens_opd_carve(char* after, int n_parameters, int n_groups, int64_t max_group_rows, int n_terms, char** end) {
+  SensOpdWork w;
+  w.groups = (double*)(((uintptr_t)after + 7) & ~(uintptr_t)7);
+  w.partials = w.groups + (int64_t)n_groups * SENS_OPD_GROUP;
+  *end = (char*)(w.partials + (int64_t)n_groups * sens_chunks(max_group_rows) * sens_opd_entries(n_parameters, n_terms));
+  return w;
+}
 
 static bool sens_sizes_ok(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups, int64_t max_group_rows) {
   return join_n_ids_ok(n_ids) && n_surfaces >= 1 && n_surfaces <= (1 << 20) && n_parameters >= 1 &&
@@ -500,7 +746,19 @@ extern "C" int64_t prt_frame_design_sensitivity_workspace_bytes(int64_t n_ids, i
   return (int64_t)(uintptr_t)end + 64;
 }
 
-// both entry points: `design` chooses the form; linear, index_rates, index_ids and index_first are read by the design form
+extern "C" int64_t prt_frame_opd_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                                                             int64_t max_group_rows, int n_terms) {
+  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows) || n_terms < 1 || n_terms > WF_MAX_TERMS)
+    return PRT_ERR_ARG;
+  char *mid, *end;
+  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &mid, 8);
+  (void)w;
+  const SensOpdWork o = sens_opd_carve(mid, n_parameters, n_groups, max_group_rows, n_terms, &end);
+  (void)o;
+  return (int64_t)(uintptr_t)end + 64;
+}
+
+// the entry points: `design` chooses the form, `wave` (not null: with design) the wavefront form; linear, index_rates, index_ids and index_first are read by the design form
 static int sens_run(bool design, int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
                     int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
                     const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
@@ -508,13 +766,21 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
                     const int32_t* index_first, int n_parameters, const int64_t* row_slot, const int64_t* selected,
                     int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
                     const double* pivots, double* jacobian_out, double* sums_out, int64_t* record_out, void* workspace,
-                    void* stream) {
+                    void* stream, const SensOpdCall* wave = nullptr) {
   const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld, kSensBlock, "sensitivity");
   if (n_rows < 0) return (int)n_rows;
   if (!record_out || !workspace || !sums_out || !surfaces || !twists || !parameter_first || !group_first || !pivots ||
       n_selected < 0 || n_selected > n_rows || (n_rows && (!rows || !row_slot)) ||
       (n_selected && (!selected || !jacobian_out)) || (design && (!linear || !index_rates || !index_first)))
     return fail(PRT_ERR_ARG, "bad buffers");
+  if (wave) {
+    if (!wave->groups || !wave->axes || !wave->sums || (n_rows && !wave->opl) ||
+        (n_selected && (!wave->dfield || !wave->dopd || !wave->dpupil || !wave->opd || !wave->pupil)))
+      return fail(PRT_ERR_ARG, "bad buffers");
+    if (wave->n_terms < 1 || wave->n_terms > WF_MAX_TERMS) return fail(PRT_ERR_ARG, "opd sensitivity: 1 to 36 Zernike terms");
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(wave->axes[k])) return fail(PRT_ERR_ARG, "opd sensitivity: axes finite");
+  }
   int rc = join_ids(id0, n_ids);
   if (rc) return rc;
   if (n_parameters < 1 || n_parameters > SENS_MAX_PARAMETERS)
@@ -531,6 +797,10 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
   }
   for (int k = 0; k < 3 * n_groups; ++k)
     if (!(std::fabs(pivots[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: pivots finite");
+  if (wave)  // (a group without rows has a NaN record and no row reads it; a pupil radius must divide)
+    for (int g = 0; g < n_groups; ++g)
+      if (group_first[g + 1] > group_first[g] && !(wave->groups[SENS_OPD_GROUP * g + 5] > 0.0 && wave->groups[SENS_OPD_GROUP * g + 5] < PRT_INF))
+        return fail(PRT_ERR_ARG, "opd sensitivity: a group's pupil radius is not a positive number");
   std::vector<SensSurface> table((size_t)n_surfaces);
   for (int s = 0; s < n_surfaces; ++s) {
     const prt_prim& pr = surfaces[s];
@@ -609,9 +879,22 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
   rc = ops_device(device);
   if (rc) return rc;
   char* end;
-  const SensWork w = sens_carve(workspace, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end, design ? 7 : 6);
+  const SensWork w = sens_carve(workspace, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end,
+                                wave ? 8 : design ? 7 : 6);
   hipStream_t st = (hipStream_t)stream;
   const int entries = sens_entries(n_parameters);
+  SensOpd field;
+  SensOpdWork ow = {nullptr, nullptr};
+  std::memset(&field, 0, sizeof(field));
+  if (wave) {
+    char* opd_end;
+    ow = sens_opd_carve(end, n_parameters, n_groups, max_group_rows, wave->n_terms, &opd_end);
+    HIP_TRY(hipMemcpyAsync(ow.groups, wave->groups, (size_t)n_groups * SENS_OPD_GROUP * sizeof(double), hipMemcpyHostToDevice, st));
+    field.opl = wave->opl; field.groups = ow.groups; field.first = w.first; field.n_groups = n_groups;
+    for (int k = 0; k < 3; ++k) { field.e1[k] = wave->axes[3 + k]; field.e2[k] = wave->axes[6 + k]; }
+    field.dfield = wave->dfield; field.dopd = wave->dopd; field.dpupil = wave->dpupil; field.opd = wave->opd;
+    field.pupil = wave->pupil;
+  }
   HIP_TRY(hipMemsetAsync(w.words, 0, 64, st));
   HIP_TRY(hipMemsetAsync(w.stamp, 0, (size_t)n_ids * sizeof(int), st));
   HIP_TRY(hipMemcpyAsync(w.table, table.data(), table.size() * sizeof(SensSurface), hipMemcpyHostToDevice, st));
@@ -621,7 +904,11 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
   for (int g = 0; g < n_generations; ++g) {
     const int64_t count = rows_per_generation[g];
     const dim3 grid((unsigned)((count + kSensBlock - 1) / kSensBlock));
-    if (count && design)
+    if (count && wave)
+      hipLaunchKernelGGL(k_sens_opd_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
+                         args, shape, field, w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected,
+                         jacobian_out);
+    else if (count && design)
       hipLaunchKernelGGL(k_sens_design_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
                          args, shape, w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected, jacobian_out);
     else if (count)
@@ -636,6 +923,16 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
                        w.partials, &w.words->status);
   hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)n_groups * entries)), dim3(64), 0, st, w.partials, chunks,
                      entries, n_groups, sums_out);
+  if (wave) {
+    const int opd_entries = sens_opd_entries(n_parameters, wave->n_terms);
+    const size_t lds = (size_t)SENS_OPD_TILE * sens_opd_stride(n_parameters, wave->n_terms) * sizeof(double);
+    if (chunks)
+      hipLaunchKernelGGL(k_sens_opd_partials, dim3((unsigned)chunks, (unsigned)n_groups), dim3(kSensBlock), lds, st, rows,
+                         ld, n_rows, selected, n_selected, w.first, n_parameters, wave->n_terms, weight_column,
+                         jacobian_out, wave->opd, wave->pupil, wave->dfield, wave->dopd, ow.partials, &w.words->status);
+    hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)n_groups * opd_entries)), dim3(64), 0, st, ow.partials, chunks,
+                       opd_entries, n_groups, wave->sums);
+  }
   SensWords host_words;
   HIP_TRY(hipMemcpyAsync(&host_words, w.words, sizeof(SensWords), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -674,4 +971,23 @@ extern "C" int prt_frame_design_sensitivity(int device, const double* rows, int6
                   parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
                   selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
                   workspace, stream);
+}
+
+extern "C" int prt_frame_opd_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                                         int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces,
+                                         int n_surfaces, const double* twists, const int64_t* parameter_ids,
+                                         const int32_t* parameter_first, const double* linear, const double* index_rates,
+                                         const int64_t* index_ids, const int32_t* index_first, int n_parameters,
+                                         const int64_t* row_slot, const int64_t* selected, int64_t n_selected,
+                                         const int64_t* group_first, int n_groups, int weight_column, const double* pivots,
+                                         const double* opl, const double* wavefront_groups, const double* axes, int n_terms,
+                                         double* jacobian_out, double* sums_out, double* dfield_out, double* dopd_out,
+                                         double* dpupil_out, double* opd_out, double* pupil_out, double* opd_sums_out,
+                                         int64_t* record_out, void* workspace, void* stream) {
+  const SensOpdCall wave = {opl, wavefront_groups, axes, n_terms, dfield_out, dopd_out, dpupil_out, opd_out, pupil_out,
+                            opd_sums_out};
+  return sens_run(true, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                  parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
+                  selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
+                  workspace, stream, &wave);
 }

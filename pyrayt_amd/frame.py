@@ -550,6 +550,9 @@ class DeviceFrame:
         normal_host = engine.to_host(normal).copy()
         n_selected = int(record_host[:, 6].sum())
         wave = Wavefront(opd[:n_selected], pupil[:n_selected], record_host, normal_host, terms)
+        # (what sensitivity(wavefront=) holds a Wavefront to: the frame, the selection, the weights and the pupil's basis)
+        wave._made_of = dict(frame=self, surface=surface_id, generation=None if generation is None else int(generation),
+                             rays_per_source=float(rays_per_source or 0), n_groups=n_groups, weights=weights, axes=axes)
         return wave, rows, surface_id, n_groups, record
 
     # --- diffraction PSF and Strehl ratio (no counterpart upstream) ---------------------------------------------------
@@ -1149,7 +1152,7 @@ class DeviceFrame:
 
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
-                    rays_per_source=None, n_groups=None):
+                    rays_per_source=None, n_groups=None, wavefront=None):
         """d(landing point)/d(parameter) at ``surface`` for motions, shape changes and index changes of parts, from
         this one trace: a ``Sensitivity``.  ``parameters``: up to 16 of ``Motion`` (a rigid motion), ``Deformation`` (an
         affine deformation: radii, a paraboloid's focus, heights, sides and thicknesses) and ``IndexChange`` (the index of
@@ -1170,8 +1173,15 @@ class DeviceFrame:
         neither Snell's law nor a reflection (a caller-shaded material) is NaN from there on and is counted
         (``n_unknown``, ``n_invalid``, ``n_unfit``); the sums leave such rows out.
 
-        Out of scope: moving a source; index rates that depend on the wavelength; derivatives of anything but the
-        landing point and its moments (the optical path and the OPD, for one); rays whose path changes under the
+        ``wavefront``: a ``Wavefront`` of this frame at the same ``surface``, ``generation``, groups and ``weights``
+        (``ValueError`` for any other), or True for ``self.wavefront(surface, ...)`` with its defaults and these.  The
+        call then runs ``prt_frame_opd_sensitivity``: the same pass with the derivative of the optical path carried along,
+        and the ``Sensitivity`` also has the wavefront change per parameter against that Wavefront's reference sphere,
+        HELD FIXED (``dfield``, ``dopd``, ``dpupil``, ``dzernike()``, ``rms_opd_gradient``, ``step(merit="wavefront")``);
+        ``jacobian`` and the landing-point sums keep their bits.  Without it nothing changes.
+
+        Out of scope: moving a source; index rates that depend on the wavelength; a reference radius that changes with
+        the parameter; rays whose path changes under the
         parameter, such as those at the edge of an aperture -- the result is the derivative at fixed path, as in every
         differential ray trace.  A known limit: an interface whose two indices are equal to the bit is differentiated
         as no interface at all, whatever an ``IndexChange`` says of it.
@@ -1195,6 +1205,8 @@ class DeviceFrame:
         if surface is None:
             raise ValueError("sensitivity: surface is an id or an object with get_id()")
         surface_id = float(_surface_id(surface))
+        if wavefront is not None and wavefront is not True and not isinstance(wavefront, Wavefront):
+            raise ValueError("wavefront: a Wavefront of this frame, True or None")
         snapshot = system if hasattr(system, "prims") else SceneSnapshot(system)
         prims = np.sort(np.asarray(snapshot.prims, dtype=PRIM_DTYPE), order="surface_id")
         if len(prims) == 0:
@@ -1230,6 +1242,19 @@ class DeviceFrame:
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
         if generation == "last":
             generation = self.last_generation_number() or 0
+        if wavefront is True:
+            wavefront = self.wavefront(surface_id, weights=weights, generation=generation,
+                                       rays_per_source=rays_per_source, n_groups=n_groups)
+        if wavefront is not None:
+            made = getattr(wavefront, "_made_of", None)
+            mine = dict(frame=self, surface=surface_id, generation=None if generation is None else int(generation),
+                        rays_per_source=float(rays_per_source or 0), n_groups=n_groups, weights=weights)
+            if made is None:
+                raise ValueError("sensitivity: wavefront was not made by this frame's wavefront()")
+            for name, value in mine.items():
+                if (made[name] is not value) if name == "frame" else (made[name] != value):
+                    raise ValueError(f"sensitivity: wavefront is of another {name} ({made[name]!r}, this call: {value!r}): "
+                                     "it must be this frame's, at the same surface, generation, groups and weights")
         mask = rows[_INDEX["surface"]] == surface_id
         if generation is not None:
             mask = mask & (rows[_INDEX["generation"]] == float(generation))
@@ -1273,7 +1298,8 @@ class DeviceFrame:
         lib = engine.library()
         max_group_rows = int(np.diff(group_first).max())
         bytes_of = lib.prt_frame_design_sensitivity_workspace_bytes if design else lib.prt_frame_sensitivity_workspace_bytes
-        work = torch.empty(int(engine._check(bytes_of(n_ids, len(prims), K, n_groups, max_group_rows))),
+        work = torch.empty(0 if wavefront is not None  # (the wavefront form sizes its own, below)
+                           else int(engine._check(bytes_of(n_ids, len(prims), K, n_groups, max_group_rows))),
                            dtype=torch.uint8, device=dev)
         jacobian = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
         sums = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
@@ -1285,13 +1311,38 @@ class DeviceFrame:
                 group_first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], pivots.ctypes.data,
                 jacobian.data_ptr() if n_selected else None, sums.data_ptr(), record.ctypes.data, work.data_ptr(),
                 engine._stream_ptr(torch, dev))
-        if design:  # (a call of Motions alone takes the entry point, the kernel and the workspace it always took)
+        if design or wavefront is not None:  # (a call of Motions alone takes the entry point, the kernel and the workspace it always took)
             linear = np.ascontiguousarray([m.linear.reshape(-1) if isinstance(m, Deformation) else np.zeros(9)
                                            for m in motions], dtype=np.float64)
             rates = np.ascontiguousarray([m.rate if i else 0.0 for m, i in zip(motions, index)], dtype=np.float64)
             index_lists = [sorted(m.surface_ids) if i else [] for m, i in zip(motions, index)]
             index_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in index_lists])]), dtype=np.int32)
             index_ids = np.ascontiguousarray([v for ids_ in index_lists for v in ids_] or [0], dtype=np.int64)
+        if wavefront is not None:
+            J = wavefront.terms
+            opl = self._optical_path()
+            groups = np.ascontiguousarray(np.column_stack([wavefront.reference, wavefront.radius, wavefront.pivot,
+                                                           wavefront.pupil_radius]), dtype=np.float64)
+            axes = np.ascontiguousarray(made["axes"], dtype=np.float64)
+            wide = 5 + J * (K + 3) + 4 * K + K * (K + 1) // 2
+            out = dict(dfield=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
+                       dopd=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
+                       dpupil=torch.empty((K, 2, n_selected), dtype=torch.float64, device=dev),
+                       opd=torch.empty(n_selected, dtype=torch.float64, device=dev),
+                       pupil=torch.empty((n_selected, 2), dtype=torch.float64, device=dev),
+                       sums=torch.empty((n_groups, wide), dtype=torch.float64, device=dev))
+            work = torch.empty(int(engine._check(lib.prt_frame_opd_sensitivity_workspace_bytes(
+                n_ids, len(prims), K, n_groups, max_group_rows, J))), dtype=torch.uint8, device=dev)
+            ptr = {name: (t.data_ptr() if t.numel() else None) for name, t in out.items()}
+            engine._check(lib.prt_frame_opd_sensitivity(
+                *head, linear.ctypes.data, rates.ctypes.data, index_ids.ctypes.data, index_first.ctypes.data, *tail[:8],
+                opl.data_ptr() if n_rows else None, groups.ctypes.data, axes.ctypes.data, J, tail[8], tail[9],
+                ptr["dfield"], ptr["dopd"], ptr["dpupil"], ptr["opd"], ptr["pupil"], out["sums"].data_ptr(), tail[10],
+                work.data_ptr(), tail[12]))
+            out["sums"] = engine.to_host(out["sums"]).copy()
+            return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
+                               wave=dict(out, wavefront=wavefront))
+        if design:
             engine._check(lib.prt_frame_design_sensitivity(*head, linear.ctypes.data, rates.ctypes.data,
                                                            index_ids.ctypes.data, index_first.ctypes.data, *tail))
         else:
@@ -2215,9 +2266,18 @@ class Sensitivity:
     (groups, K, 3), ``mean_square_gradient`` and ``rms_radius_gradient`` (groups, K), ``normal_matrix`` (groups, K, K) and
     ``rhs`` (groups, K) of the Gauss-Newton step that ``step()`` solves.  A group without rows has NaN there.
     ``n_unknown`` / ``n_invalid`` / ``n_unfit``: rays lost to a surface that ``system`` does not hold, to a row that is
-    not finite, to an interface whose rows fit no rule; ``n_reflections``: reflections differentiated."""
+    not finite, to an interface whose rows fit no rule; ``n_reflections``: reflections differentiated.
 
-    def __init__(self, jacobian, selected, sums, pivots, centred, record, parameters):
+    With ``sensitivity(wavefront=)`` also, against that ``Wavefront``'s reference sphere held fixed (device tensors in the
+    order of ``rows()``, NaN for a ray that misses the sphere or could not be followed): ``dfield`` (K, n_selected), the
+    change of the wavefront at a fixed pupil point; ``dopd`` (K, n_selected), the derivative of the ray's own OPD, following
+    the ray; ``dpupil`` (K, 2, n_selected), the motion of its normalised pupil point; ``opd`` and ``pupil``, the row's OPD
+    about the pivot and its pupil point as the pass evaluated them.  Per group: ``opd_sums`` (the layout of include/prt.h),
+    ``n_missed``, ``dzernike()``, ``wavefront_variance_gradient`` and ``rms_opd_gradient`` (groups, K): the exact
+    derivatives of the sample statistic that ``Wavefront.rms`` reports (from ``dopd``, piston removed), over the rays
+    that were followed.  ``wavefront`` is the Wavefront; None, and none of these, without the argument."""
+
+    def __init__(self, jacobian, selected, sums, pivots, centred, record, parameters, wave=None):
         self.jacobian, self._selected, self.sums, self.pivots, self.centred = jacobian, selected, sums, pivots, centred
         self.parameters = tuple(parameters)
         self.n_unknown, self.n_invalid, self.n_unfit, self.n_reflections = (int(v) for v in record)
@@ -2246,27 +2306,101 @@ class Sensitivity:
             self.rms_radius_gradient = self.mean_square_gradient / (2 * np.sqrt(self.mean_square))[:, None]
             self.normal_matrix = np.asarray(moments / sw[:, None, None], dtype=float)
             self.rhs = -self.mean_square_gradient / 2
+        self.wavefront = None
+        if wave is not None:
+            self._wave(wave)
+
+    def _wave(self, wave):
+        """The per-group wavefront results from the device's sums, in longdouble as the others are."""
+        self.wavefront = wave["wavefront"]
+        self.dfield, self.dopd, self.dpupil, self.opd, self.pupil = (wave[k] for k in ("dfield", "dopd", "dpupil", "opd", "pupil"))
+        self.opd_sums = wave["sums"]
+        K, J = self.n_parameters, self.wavefront.terms
+        wide = np.asarray(self.opd_sums, dtype=np.longdouble)
+        self.n_missed = np.asarray(self.opd_sums[:, 1], dtype=np.int64)
+        at = 5 + J * (K + 3)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sw = np.where(wide[:, 2] > 0, wide[:, 2], np.nan)[:, None]
+            mean = wide[:, 3:4] / sw
+            variance = wide[:, 4:5] / sw - mean * mean
+            self._z_rhs = np.asarray(wide[:, 5:at].reshape(-1, K + 3, J), dtype=float)  # (columns dfield_k, then n u_c)
+            dopd, opd_dopd, dfield, opd_dfield = (wide[:, at + q * K:at + (q + 1) * K] / sw for q in range(4))
+            lower = np.zeros((len(wide), K, K), dtype=np.longdouble)
+            tri = np.tril_indices(K)
+            lower[:, tri[0], tri[1]] = wide[:, at + 4 * K:]
+            moments = (lower + np.transpose(np.tril(lower, -1), (0, 2, 1))) / sw[:, :, None]
+            self.wavefront_variance = np.asarray(variance[:, 0], dtype=float)
+            self.wavefront_variance_gradient = np.asarray(2 * (opd_dopd - mean * dopd), dtype=float)
+            self.rms_opd_gradient = self.wavefront_variance_gradient / (2 * np.sqrt(self.wavefront_variance))[:, None]
+            # Gauss-Newton on the piston-removed OPD, dfield the Jacobian: both centred on their weighted means
+            self._wave_weight = np.asarray(sw[:, 0], dtype=float)
+            self.wavefront_normal_matrix = np.asarray(moments - dfield[:, :, None] * dfield[:, None, :], dtype=float)
+            self.wavefront_rhs = np.asarray(-(opd_dfield - mean * dfield), dtype=float)
+
+    def _need_wave(self, what):
+        if self.wavefront is None:
+            raise ValueError(f"{what}: this Sensitivity was made without sensitivity(wavefront=)")
+
+    def dzernike(self, reference="fixed"):
+        """(groups, K, J): per parameter the Zernike expansion of the wavefront change ``dfield_k``, the least-squares fit
+        through ``solve_normal_equations`` with the Wavefront's own ``Z^T W Z`` at the rows' nominal pupil points.
+        ``reference="fixed"``: the reference sphere stays where it is.  ``"centroid"``: its centre follows the group's
+        centroid, ``dfield_k - n (u.dP_k)`` with ``dP_k`` this object's ``centroid_gradient`` (the weighted centroid of the
+        rays that were followed: the Wavefront's own "centroid" where the weights are equal); R stays.
+
+        This is the expansion of the wavefront CHANGE.  It equals the derivative of the fitted coefficients
+        ``Wavefront.zernike`` exactly where the residual of that fit is zero; elsewhere it leaves out the terms that come
+        from the sample points moving in the pupil (``dZ/dp`` at ``dpupil``, times the residual), which vanish as the
+        sampling of the pupil gets dense.  Rays that were not followed have no part in the right-hand sides while they
+        have one in ``Z^T W Z``."""
+        self._need_wave("dzernike")
+        if reference not in ("fixed", "centroid"):
+            raise ValueError('reference: "fixed" or "centroid"')
+        K, J = self.n_parameters, self.wavefront.terms
+        rhs = self._z_rhs[:, :K, :]
+        if reference == "centroid":
+            rhs = rhs - np.einsum("gkc,gcj->gkj", self.centroid_gradient, self._z_rhs[:, K:, :])
+        tri = J * (J + 1) // 2
+        out = np.full((len(rhs), K, J), np.nan)
+        for k in range(K):
+            packed = np.array(self.wavefront.normal, dtype=float)
+            usable = np.all(np.isfinite(rhs[:, k, :]), axis=1)
+            packed[:, tri:tri + J] = np.where(usable[:, None], rhs[:, k, :], 0.0)
+            packed[~usable, -3] = 0.0
+            out[:, k, :] = solve_normal_equations(packed, J)[0]
+        return out
 
     def rows(self):
         """The frame rows of the selection, in the order of ``jacobian``'s last axis: a device int64 tensor."""
         return self._selected
 
-    def step(self, damping=0.0):
+    def step(self, damping=0.0, merit="spot"):
         """Per group the change of the parameters that minimises the mean square radius to first order (Gauss-Newton
         on the landing points): the solution of (N + damping diag(N)) dp = rhs through ``solve_normal_equations``
-        (the minimum-norm one where the rays cannot tell the parameters apart).  (groups, K); NaN without rows."""
+        (the minimum-norm one where the rays cannot tell the parameters apart).  (groups, K); NaN without rows.
+        ``merit="wavefront"`` (with ``sensitivity(wavefront=)``): Gauss-Newton on the piston-removed OPD with ``dfield``
+        as the Jacobian, which minimises the wavefront variance to first order."""
         if not (np.isfinite(damping) and damping >= 0):
             raise ValueError("damping: a number >= 0")
+        if merit not in ("spot", "wavefront"):
+            raise ValueError('merit: "spot" or "wavefront"')
+        K = self.n_parameters
+        if merit == "wavefront":
+            self._need_wave('step(merit="wavefront")')
+            return self._solve(self.wavefront_normal_matrix, self.wavefront_rhs, self._wave_weight, damping)
+        return self._solve(self.normal_matrix, self.rhs, self.weight, damping)
+
+    def _solve(self, normal_matrix, rhs, weight, damping):
         K = self.n_parameters
         upper = np.triu_indices(K)
         packed = np.zeros((len(self.sums), len(upper[0]) + K + 3))
         for g in range(len(packed)):
-            if not np.all(np.isfinite(self.normal_matrix[g])) or not np.all(np.isfinite(self.rhs[g])):
+            if not np.all(np.isfinite(normal_matrix[g])) or not np.all(np.isfinite(rhs[g])):
                 continue
-            a = self.normal_matrix[g] + damping * np.diag(np.diag(self.normal_matrix[g]))
+            a = normal_matrix[g] + damping * np.diag(np.diag(normal_matrix[g]))
             packed[g, :len(upper[0])] = a[upper]
-            packed[g, len(upper[0]):len(upper[0]) + K] = self.rhs[g]
-            packed[g, -3] = self.weight[g]
+            packed[g, len(upper[0]):len(upper[0]) + K] = rhs[g]
+            packed[g, -3] = weight[g]
         return solve_normal_equations(packed, K)[0]
 
     def to_pandas(self):
