@@ -1049,9 +1049,9 @@ int prt_frame_fresnel_coated(int device, const double* rows, int64_t ld, const i
  * by id, are its whole path, `surface` names the primitive each segment ended on, and the surface table below says what
  * that primitive is.  A tangent (do, dd) per ray and parameter is pushed through the recorded interfaces.  The result is
  * the derivative AT FIXED PATH, as in every differential ray trace: a ray whose sequence of surfaces changes under the
- * motion (the edge of an aperture) is outside it.  Sources do not move.  Shape and index parameters:
+ * motion (the edge of an aperture) is outside it.  Sources do not move here.  Shape and index parameters:
  * prt_frame_design_sensitivity, below; the optical path, the OPD and its Zernike terms: prt_frame_opd_sensitivity, below
- * that.
+ * that; motions of the rays' launch and changes of their wavelength: prt_frame_launch_sensitivity, below that.
  *
  * Definitions.
  * Frame: whole and generation-major, ids as prt_frame_optical_path wants them (a repeated id, an id out of range, a row
@@ -1130,15 +1130,15 @@ int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int6
  *     dmu = (dnu - mu dnt) / nt,  dct = (mu^2 ci dci - mu (1 - ci^2) dmu) / ct,  dgamma = ci dmu + mu dci - dct,
  *     dd' = dmu d + mu dd + dgamma n + gamma dn;  after the refraction dnu' = dnt.
  *   A reflection (total internal reflection included) and an undeviated interface keep dnu.
- *   The index behind the named surfaces grows by the rate at every wavelength; rates that depend on the wavelength are
- *   out of scope.  Known limit: an interface with ni == nt to the bit is differentiated as none (or as a reflection), as
+ *   The index behind the named surfaces grows by the rate at every wavelength (the index following the wavelength by the
+ *   glass's dispersion: prt_frame_launch_sensitivity).  Known limit: an interface with ni == nt to the bit is differentiated as none (or as a reflection), as
  *   above, whatever the index parameter says.
  * Order of the arithmetic: the terms of S and of the index are added behind a per-parameter bit (S not zero; an index
  *   list that is not empty), after the rigid terms, which are computed as prt_frame_sensitivity computes them.  So a
  *   parameter with S = 0 and no index list gets the bits it gets from prt_frame_sensitivity, and every parameter the bits
  *   it gets alone.
- * Still out of scope: moving a source, rays whose path changes.  The optical path and the OPD: prt_frame_opd_sensitivity,
- * below.
+ * Still out of scope: rays whose path changes.  The optical path and the OPD: prt_frame_opd_sensitivity, below; moving
+ * a source: prt_frame_launch_sensitivity, below that.
  *
  * prt_frame_design_sensitivity: the arguments of prt_frame_sensitivity with linear, index_rates, index_ids and index_first
  * after parameter_first; outputs, selection, sums, counters, caps and guarantees as there.  Every entry of linear and
@@ -1210,6 +1210,57 @@ int prt_frame_opd_sensitivity(int device, const double* rows, int64_t ld, const 
                               const double* axes, int n_terms, double* jacobian_out, double* sums_out, double* dfield_out,
                               double* dopd_out, double* dpupil_out, double* opd_out, double* pupil_out,
                               double* opd_sums_out, int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Launch and wavelength sensitivities: the ray itself as the parameter ---------------------------------------------
+ * The design form (or, with opl, the wavefront form) above with two more kinds of parameter, which close the differential
+ * ray tracer: a rigid motion of the rays' launch, and a change of their wavelength.  Both name rays, not surfaces: per
+ * parameter k an id range [lo, hi) (launch_ranges HOST (K, 2) doubles, compared with the row's id column as doubles;
+ * -inf and +inf are allowed, lo <= hi), flags (launch_flags HOST K int32: bit 0 "seeds the launch", bit 1 "changes the
+ * wavelength"; 0 for a parameter of the other kinds) and a wavelength rate (wavelength_rates HOST K, micrometres per unit
+ * parameter, finite).  A parameter with a flag has an empty list of surface ids; its twist (v, w, c) is the launch twist.
+ * Seed: in generation 0, for a parameter with bit 0 whose range holds the ray's id, with o the row's start and d its unit
+ *   direction:  do = v + w x (o - c),  dd = w x d  (v + (w x (o - c)), the cross products as everywhere above).  For every
+ *   other ray and parameter do = dd = 0 as before.  The landing that follows, and dL = dnu len + n d.(dx - do), are the
+ *   forms above with this do: d(n |x - o|) = dnu len + n d.(dx - do).
+ * Dispersion: materials HOST n_materials prt_material records, what prt_prim.material of the surface table indexes (here
+ *   it IS read).  At a refraction in which the ray ENTERS (as above) a surface whose material is PRT_MAT_SELLMEIER, with
+ *   wl the wavelength column of the ray's row in the glass, w2 = wl * wl, t_i = w2 - c_i:
+ *     n2   = ((1 + (b1 w2) / t1) + (b2 w2) / t2) + (b3 w2) / t3                       (the trace's own index, squared)
+ *     down = (((b1 c1) wl) / (t1 t1) + ((b2 c2) wl) / (t2 t2)) + ((b3 c3) wl) / (t3 t3)
+ *     dn/dlambda = -down / sqrt(n2)                     (= (sum_i -b_i c_i wl / (wl^2 - c_i)^2) / n, per micrometre)
+ *   evaluated once a row; for a parameter with bit 1 whose range holds the ray, dnt = wavelength_rates[k] * dn/dlambda
+ *   in the dmu terms above, and dnu' = dnt.  On leaving dnt = 0, as for an index parameter; a surface whose material is
+ *   NONE, ABSORBER, MIRROR or CONST_INDEX has no dispersion (dnt = 0).  With a bit 1 anywhere in the call a surface of
+ *   any other kind (TABLE, HOST: their index is host code) is refused, PRT_ERR_ARG.
+ *   Known limit: dnu is 0 in generation 0, so a ray launched inside a glass keeps dnu = 0 on its first segment.
+ * slopes_out DEVICE (K, 3, n_selected): dd of the selected row's segment per parameter, NaN where jacobian_out is NaN.
+ * Order of the arithmetic: the seed and the dispersion sit behind their bits and the ray's range, after everything else: a
+ *   parameter without flags has the bits it has through prt_frame_design_sensitivity (with S = 0 and no index list: through
+ *   prt_frame_sensitivity), jacobian_out and sums_out are the same bits with and without opl, and every parameter has the
+ *   bits it has alone.  A ray outside a launch parameter's range has +0.0 in that parameter's jacobian and slopes.
+ *
+ * prt_frame_launch_sensitivity: the arguments of prt_frame_opd_sensitivity up to n_terms; then launch_ranges, launch_flags,
+ * wavelength_rates, materials, n_materials; then out, overwritten: jacobian_out, sums_out, slopes_out, and the wavefront
+ * outputs and record_out as there.  opl == NULL selects the form without the wavefront: wavefront_groups, axes, n_terms and
+ * the six wavefront outputs are not read or written, the state is seven planes.  The frame needs its wavelength column
+ * where a parameter has bit 1.  workspace: prt_frame_launch_sensitivity_workspace_bytes(the arguments of
+ * prt_frame_opd_sensitivity_workspace_bytes; n_terms = 0 for the form without the wavefront): what that form needs and 56
+ * bytes a surface for the dispersion table.  Caps, refusals and guarantees as above. */
+int64_t prt_frame_launch_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
+                                                     int64_t max_group_rows, int n_terms);
+int prt_frame_launch_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                                 int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
+                                 const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
+                                 const double* linear, const double* index_rates, const int64_t* index_ids,
+                                 const int32_t* index_first, int n_parameters, const int64_t* row_slot,
+                                 const int64_t* selected, int64_t n_selected, const int64_t* group_first, int n_groups,
+                                 int weight_column, const double* pivots, const double* opl,
+                                 const double* wavefront_groups, const double* axes, int n_terms,
+                                 const double* launch_ranges, const int32_t* launch_flags, const double* wavelength_rates,
+                                 const prt_material* materials, int n_materials, double* jacobian_out, double* sums_out,
+                                 double* slopes_out, double* dfield_out, double* dopd_out, double* dpupil_out,
+                                 double* opd_out, double* pupil_out, double* opd_sums_out, int64_t* record_out,
+                                 void* workspace, void* stream);
 
 /* statistics of the trace of this scene that ended last (prt_trace / prt_trace_end; for bench.py's roofline):
  * out[0] = generations that found rays, out[1] = sum over generations of rays alive at entry,

@@ -21,6 +21,11 @@
 //   k_sens_opd_step the design form plus an eighth plane, dL = d(cumulative optical path): sens_row<true, true>.  At a
 //                   selected row it also writes the wavefront change per parameter (dfield, dopd, dpupil) against the fixed
 //                   reference sphere of a wavefront pass, and the row's own OPD and pupil point
+//   k_sens_launch_step, k_sens_launch_opd_step  the design and the wavefront form with the ray itself as a parameter:
+//                   sens_row<true, false, true> and sens_row<true, true, true>.  A parameter may name rays (an id range) instead
+//                   of surfaces: it seeds the tangent in generation 0 (a rigid motion of the launch) or feeds dnu from the
+//                   dispersion of the Sellmeier glass the ray enters (a change of the wavelength); the step also writes dd of
+//                   the selected rows (the slopes)
 //   k_sens_partials the group sums of the selected rows as per-workgroup partials, written in workgroup order
 //   k_sens_opd_partials  the wavefront sums (Z^T W y for K + 3 right-hand sides, the moments of dopd and dfield) as
 //                   per-workgroup partials: a 64-row tile of factors in LDS, every entry a product of two of its columns
@@ -59,6 +64,11 @@ struct SensArgs { SensTwist twist[SENS_MAX_PARAMETERS]; int n_parameters, n_surf
 // the design form's own arguments: S (row-major, world) and the index rate per parameter; bit k of `linear` / `index`: the
 // parameter has an S that is not zero / names surfaces whose index it changes
 struct SensDesign { double S[SENS_MAX_PARAMETERS][9]; double rate[SENS_MAX_PARAMETERS]; uint32_t linear, index; };
+// the launch form's own arguments: per parameter the ray ids [lo, hi) it names, as doubles, and the wavelength rate; bit k of
+// `seeds` / `colour`: the parameter moves the launch of those rays (by its twist) / changes their wavelength
+struct SensLaunch { double lo[SENS_MAX_PARAMETERS], hi[SENS_MAX_PARAMETERS], rate[SENS_MAX_PARAMETERS]; uint32_t seeds, colour; };
+// the dispersion table: entry e is the material behind entry e of the surface table (SensSurface keeps its 200 bytes)
+struct SensGlass { double coef[6]; int32_t kind, reserved; };
 struct SensWords { u64 count[SENS_COUNTERS]; int status; };  // unknown, invalid, unfit, reflections
 struct SensVec { double x, y, z; };
 // the wavefront form's own arguments: the rows' cumulative optical path, per group (P (3), R, pivot, pupil radius), the
@@ -158,14 +168,19 @@ enum { SENS_NONE = 0, SENS_REFRACT = 1, SENS_REFLECT = 2 };
 
 // row j of `generation`; flag: what the row adds to the counters.  kDesign: `design` is read and the state has seven planes.
 // kOpd (with kDesign): `wave` is read and the state has an eighth plane, dL; its terms come after everything else.
-template <bool kDesign, bool kOpd = false>
+// kLaunch (with kDesign): `launch` and `glass` are read: a parameter may seed the tangent in generation 0 and may feed dnu
+// from the dispersion of the glass the ray enters; dd of the selected rows goes to `slopes`.  Its terms sit behind the
+// parameter's bits and the ray's id range, after everything else.
+template <bool kDesign, bool kOpd = false, bool kLaunch = false>
 __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t j,
                                          int generation, double id0, int64_t n_ids, const SensArgs& args,
                                          const SensSurface* __restrict__ table, double* __restrict__ state,
                                          int64_t* __restrict__ last_row, int* __restrict__ stamp, int* status,
                                          const int64_t* __restrict__ row_slot, int64_t n_selected,
                                          double* __restrict__ jacobian, bool (&flag)[SENS_COUNTERS],
-                                         const SensDesign* design, const SensOpd* wave = nullptr) {
+                                         const SensDesign* design, const SensOpd* wave = nullptr,
+                                         const SensLaunch* launch = nullptr, const SensGlass* __restrict__ glass = nullptr,
+                                         double* __restrict__ slopes = nullptr) {
   constexpr int kPlanes = kOpd ? 8 : kDesign ? 7 : 6;
   const double nan = __longlong_as_double(0x7ff8000000000000ll);
   const int K = args.n_parameters;
@@ -217,6 +232,8 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
     uint32_t moved_there = 0u, index_there = 0u;
     double nt_there = 1.0;
     bool entering = false;
+    double rid = 0.0, dndl = 0.0;  // (the launch form: the ray's id as the frame has it; dn/dlambda of the glass it enters)
+    if constexpr (kLaunch) rid = rows[PRT_COL_ID * ld + j];
     if (generation > 0 && !was_dead && !invalid && !unknown) {
       xp = sv_col(rows, ld, PRT_COL_X1, p);
       const SensVec rawp = sv_col(rows, ld, PRT_COL_XTILT, p);
@@ -262,6 +279,17 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
         const SensVec miss = sv_sub(want, d);
         unfit = !invalid && (unfit || !(sv_dot(miss, miss) <= PRT_SENS_EPS_DIR));
         reflection = reflection && !unfit && !invalid;
+        if constexpr (kLaunch) {  // Sellmeier: n^2 = 1 + sum b w^2 / (w^2 - c), dn/dlambda = -(sum b c w / (w^2 - c)^2) / n
+          if (kind == SENS_REFRACT && entering && launch->colour && glass[ep].kind == MAT_SELLMEIER) {
+            const double* __restrict__ q = glass[ep].coef;
+            const double wl = rows[PRT_COL_WAVELENGTH * ld + j], w2 = wl * wl;
+            const double t0 = w2 - q[3], t1 = w2 - q[4], t2 = w2 - q[5];
+            const double n2 = ((1 + (q[0] * w2) / t0) + (q[1] * w2) / t1) + (q[2] * w2) / t2;
+            const double down = (((q[0] * q[3]) * wl) / (t0 * t0) + ((q[1] * q[4]) * wl) / (t1 * t1)) +
+                                ((q[2] * q[5]) * wl) / (t2 * t2);
+            dndl = -down / sqrt(n2);
+          }
+        }
       }
     }
     dead = was_dead || invalid || unknown || unfit;
@@ -306,6 +334,12 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
           lin = (design->linear >> k) & 1u;
           idx = (design->index >> k) & 1u;
         }
+        bool seeded = false, coloured = false;
+        if constexpr (kLaunch) {
+          const bool named = rid >= launch->lo[k] && rid < launch->hi[k];
+          seeded = named && ((launch->seeds >> k) & 1u);
+          coloured = named && ((launch->colour >> k) & 1u);
+        }
         if (generation > 0) {
           double* __restrict__ s = state + (int64_t)k * kPlanes * n_ids + i;
           dx = {s[0], s[n_ids], s[2 * n_ids]};
@@ -348,7 +382,10 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
             dd = sv_add(sv_add(sv_scale(mu, dd), sv_scale(dgamma, there.n)), sv_scale(gamma, dn));
             if constexpr (kDesign) {
               if (idx) {  // the terms of dmu, after those of the geometry: dct and dgamma are linear in (dci, dmu)
-                const double dnt = (entering && ((index_there >> k) & 1u)) ? design->rate[k] : 0.0;
+                double dnt = (entering && ((index_there >> k) & 1u)) ? design->rate[k] : 0.0;
+                if constexpr (kLaunch) {
+                  if (coloured) dnt = entering ? launch->rate[k] * dndl : 0.0;
+                }
                 const double dmu = (dnu - mu * dnt) / nt_there;
                 const double dct_mu = (mu * (1.0 - ci * ci)) * dmu / ct;  // dct = (mu^2 ci dci) / ct - dct_mu
                 const double dgamma_mu = ci * dmu + dct_mu;
@@ -362,6 +399,12 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
             dd = sv_sub(dd, sv_scale(2.0, back));
           }
           start = sv_add(dx, sv_scale(PRT_SENS_OFFSET, dd));
+        }
+        if constexpr (kLaunch) {  // the seed: the launch point moves with v + w x (o - c), the direction with w x d
+          if (generation == 0 && seeded) {
+            start = sens_velocity(tw, true, o);
+            dd = sv_cross({tw.w[0], tw.w[1], tw.w[2]}, d);
+          }
         }
         // the landing: dt = n.(u - do - t dd) / (n.d), dx = do + t dd + d dt
         SensVec u = sens_velocity(tw, (moved_here >> k) & 1u, x);
@@ -380,6 +423,10 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
         if (slot >= 0) {
           double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
           out[0] = dx.x; out[n_selected] = dx.y; out[2 * n_selected] = dx.z;
+          if constexpr (kLaunch) {
+            double* __restrict__ slope = slopes + (int64_t)k * 3 * n_selected + slot;
+            slope[0] = dd.x; slope[n_selected] = dd.y; slope[2 * n_selected] = dd.z;
+          }
         }
         if constexpr (kOpd) {  // dL = dL_prev + dnu len + n d.(dx - start); then the wavefront change at the fixed sphere
           const double before = generation > 0 ? s[7 * n_ids] : 0.0;
@@ -413,6 +460,10 @@ __device__ __forceinline__ void sens_row(const double* __restrict__ rows, int64_
     for (int k = 0; k < K; ++k) {
       double* __restrict__ out = jacobian + (int64_t)k * 3 * n_selected + slot;
       out[0] = nan; out[n_selected] = nan; out[2 * n_selected] = nan;
+      if constexpr (kLaunch) {
+        double* __restrict__ slope = slopes + (int64_t)k * 3 * n_selected + slot;
+        slope[0] = nan; slope[n_selected] = nan; slope[2 * n_selected] = nan;
+      }
       if constexpr (kOpd) {
         wave->dfield[(int64_t)k * n_selected + slot] = nan;
         wave->dopd[(int64_t)k * n_selected + slot] = nan;
@@ -467,6 +518,38 @@ k_sens_opd_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int
   if (j < start + count)
     sens_row<true, true>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp, &words->status,
                          row_slot, n_selected, jacobian, flag, &design, &wave);
+  fresnel_count(flag, words->count);
+}
+
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_launch_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t start, int64_t count,
+                   int generation, double id0, int64_t n_ids, SensArgs args, SensDesign design, SensLaunch launch,
+                   const SensSurface* __restrict__ table, const SensGlass* __restrict__ glass, double* __restrict__ state,
+                   int64_t* __restrict__ last_row, int* __restrict__ stamp, SensWords* __restrict__ words,
+                   const int64_t* __restrict__ row_slot, int64_t n_selected, double* __restrict__ jacobian,
+                   double* __restrict__ slopes) {
+  const int64_t j = start + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
+  bool flag[SENS_COUNTERS] = {};
+  if (j < start + count)
+    sens_row<true, false, true>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp,
+                                &words->status, row_slot, n_selected, jacobian, flag, &design, nullptr, &launch, glass,
+                                slopes);
+  fresnel_count(flag, words->count);
+}
+
+__global__ void __launch_bounds__(kSensBlock)
+k_sens_launch_opd_step(const double* __restrict__ rows, int64_t ld, int64_t n_rows, int64_t start, int64_t count,
+                       int generation, double id0, int64_t n_ids, SensArgs args, SensDesign design, SensOpd wave,
+                       SensLaunch launch, const SensSurface* __restrict__ table, const SensGlass* __restrict__ glass,
+                       double* __restrict__ state, int64_t* __restrict__ last_row, int* __restrict__ stamp,
+                       SensWords* __restrict__ words, const int64_t* __restrict__ row_slot, int64_t n_selected,
+                       double* __restrict__ jacobian, double* __restrict__ slopes) {
+  const int64_t j = start + (int64_t)blockIdx.x * kSensBlock + threadIdx.x;
+  bool flag[SENS_COUNTERS] = {};
+  if (j < start + count)
+    sens_row<true, true, true>(rows, ld, n_rows, j, generation, id0, n_ids, args, table, state, last_row, stamp,
+                               &words->status, row_slot, n_selected, jacobian, flag, &design, &wave, &launch, glass,
+                               slopes);
   fresnel_count(flag, words->count);
 }
 
@@ -695,6 +778,12 @@ struct SensOpdCall {
   const double* opl; const double* groups; const double* axes; int n_terms;
   double *dfield, *dopd, *dpupil, *opd, *pupil, *sums;
 };
+// the launch form's arguments on the host: ranges HOST (K, 2), flags HOST K (bit 0 seeds the launch, bit 1 changes the
+// wavelength), rates HOST K, materials HOST n_materials (what prt_prim.material indexes); slopes DEVICE (K, 3, n_selected)
+struct SensLaunchCall {
+  const double* ranges; const int32_t* flags; const double* rates; const prt_material* materials; int n_materials;
+  double* slopes;
+};
 
 
 static int64_t sens_chunks(int64_t max_group_rows) { return (max_group_rows + kSensBlock - 1) / kSensBlock; }
@@ -766,7 +855,7 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
                     const int32_t* index_first, int n_parameters, const int64_t* row_slot, const int64_t* selected,
                     int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
                     const double* pivots, double* jacobian_out, double* sums_out, int64_t* record_out, void* workspace,
-                    void* stream, const SensOpdCall* wave = nullptr) {
+                    void* stream, const SensOpdCall* wave = nullptr, const SensLaunchCall* launch = nullptr) {
   const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld, kSensBlock, "sensitivity");
   if (n_rows < 0) return (int)n_rows;
   if (!record_out || !workspace || !sums_out || !surfaces || !twists || !parameter_first || !group_first || !pivots ||
@@ -873,6 +962,41 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
       }
     }
   }
+  SensLaunch seed;
+  std::memset(&seed, 0, sizeof(seed));
+  std::vector<SensGlass> glasses;
+  if (launch) {
+    if (!launch->ranges || !launch->flags || !launch->rates || !launch->materials || (n_selected && !launch->slopes))
+      return fail(PRT_ERR_ARG, "bad buffers");
+    for (int k = 0; k < n_parameters; ++k) {
+      const double lo = launch->ranges[2 * k], hi = launch->ranges[2 * k + 1];
+      if (launch->flags[k] < 0 || launch->flags[k] > 3) return fail(PRT_ERR_ARG, "launch sensitivity: flags are 0 to 3");
+      if (!(lo <= hi)) return fail(PRT_ERR_ARG, "launch sensitivity: a parameter's ray ids [lo, hi) are not a range");
+      if (!(std::fabs(launch->rates[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "launch sensitivity: a wavelength rate is not finite");
+      if (launch->flags[k] && parameter_first[k + 1] != parameter_first[k])
+        return fail(PRT_ERR_ARG, "launch sensitivity: a launch parameter names no surfaces");
+      seed.lo[k] = lo; seed.hi[k] = hi; seed.rate[k] = launch->rates[k];
+      if (launch->flags[k] & 1) seed.seeds |= 1u << k;
+      if (launch->flags[k] & 2) { seed.colour |= 1u << k; shape.index |= 1u << k; }  // (the dnu plane is the parameter's)
+    }
+    glasses.resize((size_t)n_surfaces);
+    for (int s = 0; s < n_surfaces; ++s) {
+      const int m = surfaces[s].material;
+      if (m < 0 || m >= launch->n_materials) return fail(PRT_ERR_ARG, "launch sensitivity: a surface's material is not in materials");
+      const prt_material& mat = launch->materials[m];
+      std::memset(&glasses[s], 0, sizeof(SensGlass));
+      if (mat.kind == PRT_MAT_SELLMEIER) {
+        for (int c = 0; c < 6; ++c) {
+          if (!(std::fabs(mat.coef[c]) < PRT_INF)) return fail(PRT_ERR_ARG, "launch sensitivity: a Sellmeier coefficient is not finite");
+          glasses[s].coef[c] = mat.coef[c];
+        }
+      } else if (seed.colour && (mat.kind < PRT_MAT_NONE || mat.kind > PRT_MAT_CONST_INDEX)) {
+        return fail(PRT_ERR_ARG, "launch sensitivity: a wavelength parameter needs glasses whose dispersion the device has "
+                                 "(a table or host material is in the table)");
+      }
+      glasses[s].kind = mat.kind;
+    }
+  }
   if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows))
     return fail(PRT_ERR_ARG, "sensitivity: too many rows in a group");
   for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = 0;
@@ -894,6 +1018,12 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
     for (int k = 0; k < 3; ++k) { field.e1[k] = wave->axes[3 + k]; field.e2[k] = wave->axes[6 + k]; }
     field.dfield = wave->dfield; field.dopd = wave->dopd; field.dpupil = wave->dpupil; field.opd = wave->opd;
     field.pupil = wave->pupil;
+    end = opd_end;
+  }
+  SensGlass* glass_table = nullptr;  // (the launch form: behind everything the other forms carve)
+  if (launch) {
+    glass_table = (SensGlass*)(((uintptr_t)end + 7) & ~(uintptr_t)7);
+    HIP_TRY(hipMemcpyAsync(glass_table, glasses.data(), glasses.size() * sizeof(SensGlass), hipMemcpyHostToDevice, st));
   }
   HIP_TRY(hipMemsetAsync(w.words, 0, 64, st));
   HIP_TRY(hipMemsetAsync(w.stamp, 0, (size_t)n_ids * sizeof(int), st));
@@ -904,7 +1034,15 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
   for (int g = 0; g < n_generations; ++g) {
     const int64_t count = rows_per_generation[g];
     const dim3 grid((unsigned)((count + kSensBlock - 1) / kSensBlock));
-    if (count && wave)
+    if (count && launch && wave)
+      hipLaunchKernelGGL(k_sens_launch_opd_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0,
+                         n_ids, args, shape, field, seed, w.table, glass_table, w.state, w.last_row, w.stamp, w.words,
+                         row_slot, n_selected, jacobian_out, launch->slopes);
+    else if (count && launch)
+      hipLaunchKernelGGL(k_sens_launch_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
+                         args, shape, seed, w.table, glass_table, w.state, w.last_row, w.stamp, w.words, row_slot,
+                         n_selected, jacobian_out, launch->slopes);
+    else if (count && wave)
       hipLaunchKernelGGL(k_sens_opd_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
                          args, shape, field, w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected,
                          jacobian_out);
@@ -990,4 +1128,42 @@ extern "C" int prt_frame_opd_sensitivity(int device, const double* rows, int64_t
                   parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
                   selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
                   workspace, stream, &wave);
+}
+
+extern "C" int64_t prt_frame_launch_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters,
+                                                                int n_groups, int64_t max_group_rows, int n_terms) {
+  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows) || n_terms < 0 || n_terms > WF_MAX_TERMS)
+    return PRT_ERR_ARG;
+  char* end;
+  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end, n_terms ? 8 : 7);
+  (void)w;
+  if (n_terms) {
+    char* mid = end;
+    const SensOpdWork o = sens_opd_carve(mid, n_parameters, n_groups, max_group_rows, n_terms, &end);
+    (void)o;
+  }
+  return (int64_t)(((uintptr_t)end + 7) & ~(uintptr_t)7) + (int64_t)n_surfaces * (int64_t)sizeof(SensGlass) + 64;
+}
+
+extern "C" int prt_frame_launch_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                                            int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces,
+                                            int n_surfaces, const double* twists, const int64_t* parameter_ids,
+                                            const int32_t* parameter_first, const double* linear, const double* index_rates,
+                                            const int64_t* index_ids, const int32_t* index_first, int n_parameters,
+                                            const int64_t* row_slot, const int64_t* selected, int64_t n_selected,
+                                            const int64_t* group_first, int n_groups, int weight_column,
+                                            const double* pivots, const double* opl, const double* wavefront_groups,
+                                            const double* axes, int n_terms, const double* launch_ranges,
+                                            const int32_t* launch_flags, const double* wavelength_rates,
+                                            const prt_material* materials, int n_materials, double* jacobian_out,
+                                            double* sums_out, double* slopes_out, double* dfield_out, double* dopd_out,
+                                            double* dpupil_out, double* opd_out, double* pupil_out, double* opd_sums_out,
+                                            int64_t* record_out, void* workspace, void* stream) {
+  const SensOpdCall wave = {opl, wavefront_groups, axes, n_terms, dfield_out, dopd_out, dpupil_out, opd_out, pupil_out,
+                            opd_sums_out};
+  const SensLaunchCall launch = {launch_ranges, launch_flags, wavelength_rates, materials, n_materials, slopes_out};
+  return sens_run(true, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                  parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
+                  selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
+                  workspace, stream, opl ? &wave : nullptr, &launch);
 }

@@ -198,6 +198,11 @@ def _declare(lib):
         "prt_frame_opd_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p,
                                               c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p,
                                               c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_launch_sensitivity_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_i64, c_int]),
+        "prt_frame_launch_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p,
+                                                 c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p,
+                                                 c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -229,6 +234,7 @@ EXPORTED_SYMBOLS = (
     "prt_frame_sensitivity_workspace_bytes", "prt_frame_sensitivity",
     "prt_frame_design_sensitivity_workspace_bytes", "prt_frame_design_sensitivity",
     "prt_frame_opd_sensitivity_workspace_bytes", "prt_frame_opd_sensitivity",
+    "prt_frame_launch_sensitivity_workspace_bytes", "prt_frame_launch_sensitivity",
 )
 
 

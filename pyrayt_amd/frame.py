@@ -1153,11 +1153,17 @@ class DeviceFrame:
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
                     rays_per_source=None, n_groups=None, wavefront=None):
-        """d(landing point)/d(parameter) at ``surface`` for motions, shape changes and index changes of parts, from
-        this one trace: a ``Sensitivity``.  ``parameters``: up to 16 of ``Motion`` (a rigid motion), ``Deformation`` (an
-        affine deformation: radii, a paraboloid's focus, heights, sides and thicknesses) and ``IndexChange`` (the index of
-        a glass), in any mix; a call of Motions alone runs ``prt_frame_sensitivity`` as it always did, any other
-        ``prt_frame_design_sensitivity``, in which a Motion has the same bits.  ``system``: the components the frame was
+        """d(landing point)/d(parameter) at ``surface`` for motions, shape changes and index changes of parts, and for
+        motions of the rays' launch and changes of their wavelength, from this one trace: a ``Sensitivity``.
+        ``parameters``: up to 16 of ``Motion`` (a rigid motion), ``Deformation`` (an affine deformation: radii, a
+        paraboloid's focus, heights, sides and thicknesses), ``IndexChange`` (the index of a glass), ``SourceMotion`` (a
+        rigid motion of the launch of rays: field points, the ray-transfer matrix, focal lengths) and ``WavelengthChange``
+        (colour: the Sellmeier glasses' own dispersion), in any mix; a call of Motions alone runs
+        ``prt_frame_sensitivity`` as it always did, a call without the last two kinds ``prt_frame_design_sensitivity`` as
+        it always did, and a call with one of them ``prt_frame_launch_sensitivity``, in which the other kinds have the
+        same bits and which also gives ``slopes``, the derivative of the rows' directions (``focus_gradient``,
+        ``transfer``, ``effective_focal_length``).  A ``WavelengthChange`` needs the frame's ``wavelength`` column and
+        raises ``ValueError`` for a system with a table glass.  ``system``: the components the frame was
         traced through (or their ``SceneSnapshot``), whose snapshot -- the one the scene compiler takes -- tells the
         pass the kind, parameters and transform of the primitive behind every ``surface`` id.
 
@@ -1180,24 +1186,31 @@ class DeviceFrame:
         HELD FIXED (``dfield``, ``dopd``, ``dpupil``, ``dzernike()``, ``rms_opd_gradient``, ``step(merit="wavefront")``);
         ``jacobian`` and the landing-point sums keep their bits.  Without it nothing changes.
 
-        Out of scope: moving a source; index rates that depend on the wavelength; a reference radius that changes with
-        the parameter; rays whose path changes under the
+        Out of scope: a reference radius that changes with the parameter; rays whose path changes under the
         parameter, such as those at the edge of an aperture -- the result is the derivative at fixed path, as in every
-        differential ray trace.  A known limit: an interface whose two indices are equal to the bit is differentiated
-        as no interface at all, whatever an ``IndexChange`` says of it.
+        differential ray trace.  Known limits: an interface whose two indices are equal to the bit is differentiated
+        as no interface at all, whatever an ``IndexChange`` or a ``WavelengthChange`` says of it; a ray launched inside a
+        glass keeps the index of its first segment under a ``WavelengthChange``.
         Needs the whole frame of a trace, like ``optical_path``."""
         import torch
 
         from . import engine
         from .scene import PRIM_DTYPE, SceneSnapshot
 
-        kinds = (Motion, Deformation, IndexChange)
+        from . import materials as matl
+
+        kinds = (Motion, Deformation, IndexChange, SourceMotion, WavelengthChange)
         motions = [parameters] if isinstance(parameters, kinds) else list(parameters)
         if not motions or not all(isinstance(m, kinds) for m in motions):
-            raise ValueError("sensitivity: parameters is a Motion, a Deformation or an IndexChange, or a list of them")
+            raise ValueError("sensitivity: parameters is a Motion, a Deformation, an IndexChange, a SourceMotion or a "
+                             "WavelengthChange, or a list of them")
         design = not all(isinstance(m, Motion) for m in motions)
+        launch = any(isinstance(m, (SourceMotion, WavelengthChange)) for m in motions)
+        colour = any(isinstance(m, WavelengthChange) for m in motions)
         if len(motions) > 16:
             raise ValueError(f"sensitivity: at most 16 parameters a call (got {len(motions)})")
+        if launch:
+            motions = [m.resolved(rays_per_source) if isinstance(m, SourceMotion) else m for m in motions]
         if weights is not None and weights not in _INDEX:
             raise ValueError(f"weights: None or a column name (got {weights!r})")
         if isinstance(reference, str) and reference != "centroid":
@@ -1218,8 +1231,12 @@ class DeviceFrame:
             missing = sorted(set(motion.surface_ids) - known)
             if missing:
                 raise ValueError(f"sensitivity: parameter {k} moves surfaces that are not in system: {missing}")
+        if colour and any(int(kind) == matl.TABLE for kind in np.asarray(snapshot.materials)["kind"][prims["material"]]):
+            raise ValueError("sensitivity: a WavelengthChange needs the dispersion of every glass in system, and a table "
+                             "glass's index_at is host code without a derivative")
         try:
-            self._need_whole("sensitivity", columns=_PATH_COLUMNS + ((weights,) if weights else ()))
+            self._need_whole("sensitivity", columns=_PATH_COLUMNS + (("wavelength",) if colour else ())
+                             + ((weights,) if weights else ()))
         except KeyError as error:
             raise ValueError(f"sensitivity: {error.args[0]}") from None
         rows = self._contiguous_rows()
@@ -1289,7 +1306,7 @@ class DeviceFrame:
             if pivots.shape != (n_groups, 3) or not np.all(np.isfinite(pivots)):
                 raise ValueError(f"reference: \"centroid\", a finite point or an ({n_groups}, 3) array")
         pivots = np.ascontiguousarray(pivots, dtype=np.float64)
-        index = [isinstance(m, IndexChange) for m in motions]
+        index = [isinstance(m, (IndexChange, WavelengthChange)) for m in motions]
         twists = np.ascontiguousarray([np.zeros(9) if i else m.twist for m, i in zip(motions, index)], dtype=np.float64)
         id_lists = [[] if i else sorted(m.surface_ids) for m, i in zip(motions, index)]
         parameter_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in id_lists])]), dtype=np.int32)
@@ -1314,10 +1331,50 @@ class DeviceFrame:
         if design or wavefront is not None:  # (a call of Motions alone takes the entry point, the kernel and the workspace it always took)
             linear = np.ascontiguousarray([m.linear.reshape(-1) if isinstance(m, Deformation) else np.zeros(9)
                                            for m in motions], dtype=np.float64)
-            rates = np.ascontiguousarray([m.rate if i else 0.0 for m, i in zip(motions, index)], dtype=np.float64)
-            index_lists = [sorted(m.surface_ids) if i else [] for m, i in zip(motions, index)]
+            named = [isinstance(m, IndexChange) for m in motions]
+            rates = np.ascontiguousarray([m.rate if i else 0.0 for m, i in zip(motions, named)], dtype=np.float64)
+            index_lists = [sorted(m.surface_ids) if i else [] for m, i in zip(motions, named)]
             index_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in index_lists])]), dtype=np.int32)
             index_ids = np.ascontiguousarray([v for ids_ in index_lists for v in ids_] or [0], dtype=np.int64)
+        if launch:  # (the launch form: the design or wavefront form's arguments, the rays each parameter names, the glasses)
+            ranges = np.ascontiguousarray([m.id_range if isinstance(m, (SourceMotion, WavelengthChange))
+                                           else (0.0, 0.0) for m in motions], dtype=np.float64)
+            flags = np.ascontiguousarray([1 if isinstance(m, SourceMotion) else 2 if isinstance(m, WavelengthChange)
+                                          else 0 for m in motions], dtype=np.int32)
+            colour_rates = np.ascontiguousarray([m.rate if isinstance(m, WavelengthChange) else 0.0 for m in motions],
+                                                dtype=np.float64)
+            mats = np.ascontiguousarray(snapshot.materials)
+            slopes = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
+            J, out, ptr, wave_args = 0, None, dict.fromkeys(("dfield", "dopd", "dpupil", "opd", "pupil", "sums")), (None,) * 3
+            if wavefront is not None:
+                J = wavefront.terms
+                groups = np.ascontiguousarray(np.column_stack([wavefront.reference, wavefront.radius, wavefront.pivot,
+                                                               wavefront.pupil_radius]), dtype=np.float64)
+                axes = np.ascontiguousarray(made["axes"], dtype=np.float64)
+                wide = 5 + J * (K + 3) + 4 * K + K * (K + 1) // 2
+                out = dict(dfield=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
+                           dopd=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
+                           dpupil=torch.empty((K, 2, n_selected), dtype=torch.float64, device=dev),
+                           opd=torch.empty(n_selected, dtype=torch.float64, device=dev),
+                           pupil=torch.empty((n_selected, 2), dtype=torch.float64, device=dev),
+                           sums=torch.empty((n_groups, wide), dtype=torch.float64, device=dev))
+                ptr = {name: (t.data_ptr() if t.numel() else None) for name, t in out.items()}
+                if not n_rows:  # (the entry point reads opl == NULL as "no wavefront": there is no path to point at)
+                    raise ValueError("sensitivity: wavefront= with a SourceMotion or a WavelengthChange needs a frame with rows")
+                opl = self._optical_path()
+                wave_args = (opl.data_ptr(), groups.ctypes.data, axes.ctypes.data)
+            work = torch.empty(int(engine._check(lib.prt_frame_launch_sensitivity_workspace_bytes(
+                n_ids, len(prims), K, n_groups, max_group_rows, J))), dtype=torch.uint8, device=dev)
+            engine._check(lib.prt_frame_launch_sensitivity(
+                *head, linear.ctypes.data, rates.ctypes.data, index_ids.ctypes.data, index_first.ctypes.data, *tail[:8],
+                *wave_args, J, ranges.ctypes.data, flags.ctypes.data, colour_rates.ctypes.data, mats.ctypes.data, len(mats),
+                tail[8], tail[9], slopes.data_ptr() if n_selected else None, ptr["dfield"], ptr["dopd"], ptr["dpupil"],
+                ptr["opd"], ptr["pupil"], ptr["sums"], tail[10], work.data_ptr(), tail[12]))
+            if out is not None:
+                out["sums"] = engine.to_host(out["sums"]).copy()
+                out["wavefront"] = wavefront
+            return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
+                               wave=out, launch=dict(slopes=slopes, rows=rows, weights=weights, group_first=group_first))
         if wavefront is not None:
             J = wavefront.terms
             opl = self._optical_path()
@@ -2232,8 +2289,8 @@ class Deformation:
 
 class IndexChange:
     """One parameter of ``DeviceFrame.sensitivity``: the refractive index of the medium behind every leaf surface of
-    ``part`` grows by ``rate`` per unit of the parameter, at every wavelength (rates that depend on the wavelength are out
-    of scope).  ``part``: an object with ``get_id()`` or a component, with a glass on at least one leaf."""
+    ``part`` grows by ``rate`` per unit of the parameter, at every wavelength (the index following the wavelength by the
+    glass's own dispersion is ``WavelengthChange``).  ``part``: an object with ``get_id()`` or a component, with a glass on at least one leaf."""
 
     def __init__(self, part, rate=1.0):
         from . import materials as matl
@@ -2258,6 +2315,112 @@ class IndexChange:
         return f"IndexChange(surfaces={self.surface_ids}, rate={self.rate})"
 
 
+def _ray_range(rays, what):
+    """``rays`` of a SourceMotion or WavelengthChange as the id range [lo, hi) in floats: None is every ray."""
+    if rays is None:
+        return (-np.inf, np.inf)
+    try:
+        first, count = rays
+        if first != int(first) or count != int(count) or isinstance(first, bool) or isinstance(count, bool):
+            raise TypeError
+        first, count = int(first), int(count)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"{what}: rays is None or (first_id, count), two integers (got {rays!r})") from None
+    if first < 0 or count < 1 or first + count > 2 ** 53:
+        raise ValueError(f"{what}: rays is None or (first_id, count) with first_id >= 0 and count >= 1 (got {rays!r})")
+    return (float(first), float(first + count))
+
+
+class SourceMotion:
+    """One parameter of ``DeviceFrame.sensitivity``: a rigid motion of the launch of rays, per unit of the parameter.  The
+    launch point o of a named ray moves with u = translate + rotate x (o - pivot), its unit direction with rotate x d
+    (``translate``, ``rotate``, ``pivot`` as in ``Motion``; the pivot defaults to (0, 0, 0)).  ``rays``: None (every ray),
+    ``(first_id, count)`` (the ids first_id .. first_id + count - 1) or ``SourceMotion.of_source(index, rays_per_source)``,
+    which is ``(index * rays_per_source, rays_per_source)``, the tracer's own id rule; without ``rays_per_source`` the
+    range is filled in by ``RayTracer.trace_sensitivity`` (its own) or by ``sensitivity(rays_per_source=)``.  It names
+    no surfaces.  With two translations and two rotations the Jacobian and the slopes are the ray-transfer matrix about
+    every real ray (``Sensitivity.transfer``)."""
+
+    surface_ids = ()
+
+    def __init__(self, rays=None, translate=(0.0, 0.0, 0.0), rotate=(0.0, 0.0, 0.0), pivot=(0.0, 0.0, 0.0)):
+        self.id_range = _ray_range(rays, "SourceMotion")
+        self.rays = None if rays is None else (int(rays[0]), int(rays[1]))
+        self.source = None
+        vectors = []
+        for name, value in (("translate", translate), ("rotate", rotate), ("pivot", pivot)):
+            try:
+                vector = np.asarray(value, dtype=float).reshape(-1)
+            except (TypeError, ValueError):
+                vector = np.zeros(0)
+            if vector.shape != (3,) or not np.all(np.isfinite(vector)):
+                raise ValueError(f"SourceMotion: {name} is three finite numbers (got {value!r})")
+            vectors.append(vector)
+        self.translate, self.rotate, self.pivot = vectors
+        self.twist = np.concatenate(vectors)
+
+    @classmethod
+    def of_source(cls, index, rays_per_source=None, **motion):
+        """The rays of source ``index``: ids [index * rays_per_source, (index + 1) * rays_per_source)."""
+        try:
+            if index != int(index) or isinstance(index, bool) or int(index) < 0:
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"SourceMotion.of_source: index is an integer >= 0 (got {index!r})") from None
+        if rays_per_source is None:
+            out = cls(None, **motion)
+            out.id_range, out.source = None, int(index)
+            return out
+        try:
+            if rays_per_source != int(rays_per_source) or isinstance(rays_per_source, bool) or int(rays_per_source) < 1:
+                raise TypeError
+        except (TypeError, ValueError):
+            raise ValueError(f"SourceMotion.of_source: rays_per_source is an integer >= 1 (got {rays_per_source!r})") from None
+        out = cls((int(index) * int(rays_per_source), int(rays_per_source)), **motion)
+        out.source = int(index)
+        return out
+
+    def resolved(self, rays_per_source):
+        """This parameter with its id range known: itself, or for ``of_source(index)`` a copy with ``rays_per_source``."""
+        if self.id_range is not None:
+            return self
+        if not rays_per_source or rays_per_source is True:
+            raise ValueError("sensitivity: SourceMotion.of_source(index) without rays_per_source needs "
+                             "sensitivity(rays_per_source=) or RayTracer.trace_sensitivity")
+        return SourceMotion.of_source(self.source, rays_per_source, translate=self.translate, rotate=self.rotate,
+                                      pivot=self.pivot)
+
+    def __repr__(self):
+        rays = f"source {self.source}" if self.id_range is None else self.rays
+        return (f"SourceMotion(rays={rays}, translate={tuple(self.translate)}, rotate={tuple(self.rotate)}, "
+                f"pivot={tuple(self.pivot)})")
+
+
+class WavelengthChange:
+    """One parameter of ``DeviceFrame.sensitivity``: the wavelength of the named rays grows by ``rate`` micrometres per unit
+    of the parameter.  The index behind every Sellmeier glass follows with that glass's own dn/dlambda at the ray's own
+    wavelength (include/prt.h states the formula); a ``BasicRefractor`` has none, its rate is 0.  A table glass's
+    ``index_at`` is host code without a derivative: ``sensitivity`` raises ``ValueError`` for a system that holds one.
+    ``rays``: as in ``SourceMotion`` (None: every ray, or ``(first_id, count)``).  Known limit: a ray launched inside a
+    glass keeps the index of its first segment."""
+
+    surface_ids = ()
+
+    def __init__(self, rays=None, rate=1.0):
+        self.id_range = _ray_range(rays, "WavelengthChange")
+        self.rays = None if rays is None else (int(rays[0]), int(rays[1]))
+        try:
+            rate = float(rate)
+        except (TypeError, ValueError):
+            rate = np.nan
+        if not np.isfinite(rate):
+            raise ValueError("WavelengthChange: rate is a finite number")
+        self.rate = rate
+
+    def __repr__(self):
+        return f"WavelengthChange(rays={self.rays}, rate={self.rate})"
+
+
 class Sensitivity:
     """What ``DeviceFrame.sensitivity`` found.  ``jacobian``: device (K, 3, n_selected) float64, d(x1, y1, z1)/dp_k of the
     selected rows, which ``rows()`` names (frame row numbers, ordered by group, generation and id); NaN for a ray that
@@ -2268,6 +2431,10 @@ class Sensitivity:
     ``n_unknown`` / ``n_invalid`` / ``n_unfit``: rays lost to a surface that ``system`` does not hold, to a row that is
     not finite, to an interface whose rows fit no rule; ``n_reflections``: reflections differentiated.
 
+    With a ``SourceMotion`` or a ``WavelengthChange`` among the parameters also ``slopes``: device (K, 3, n_selected)
+    float64, the derivative of the selected rows' unit directions, NaN where ``jacobian`` is; on top of both
+    ``focus_gradient()``, ``transfer()`` and ``effective_focal_length()``.  ``slopes`` is None otherwise.
+
     With ``sensitivity(wavefront=)`` also, against that ``Wavefront``'s reference sphere held fixed (device tensors in the
     order of ``rows()``, NaN for a ray that misses the sphere or could not be followed): ``dfield`` (K, n_selected), the
     change of the wavefront at a fixed pupil point; ``dopd`` (K, n_selected), the derivative of the ray's own OPD, following
@@ -2277,7 +2444,9 @@ class Sensitivity:
     derivatives of the sample statistic that ``Wavefront.rms`` reports (from ``dopd``, piston removed), over the rays
     that were followed.  ``wavefront`` is the Wavefront; None, and none of these, without the argument."""
 
-    def __init__(self, jacobian, selected, sums, pivots, centred, record, parameters, wave=None):
+    def __init__(self, jacobian, selected, sums, pivots, centred, record, parameters, wave=None, launch=None):
+        self.slopes = None if launch is None else launch["slopes"]
+        self._launch = launch
         self.jacobian, self._selected, self.sums, self.pivots, self.centred = jacobian, selected, sums, pivots, centred
         self.parameters = tuple(parameters)
         self.n_unknown, self.n_invalid, self.n_unfit, self.n_reflections = (int(v) for v in record)
@@ -2369,6 +2538,109 @@ class Sensitivity:
             packed[~usable, -3] = 0.0
             out[:, k, :] = solve_normal_equations(packed, J)[0]
         return out
+
+    def _need_slopes(self, what):
+        if self.slopes is None:
+            raise ValueError(f"{what}: this Sensitivity has no slopes (they come with a SourceMotion or a WavelengthChange "
+                             "among the parameters)")
+
+    def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
+        """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the
+        surface a ray is a straight line; in the plane shifted by delta along the unit axis a it is at p + delta s, p the
+        landing point and s = d / (d.a), both projected across a (the plane-shift convention of ``mtf(focus=)`` and
+        ``enclosed_energy(focus=)``).  The weighted mean square radius about the centroid is least at
+        delta = -cov(p, s) / var(s); this is d delta / d parameter, from ``jacobian`` (dp) and ``slopes`` (ds), over the
+        selected rows that are finite in both, with the call's ``weights``.  For a ``WavelengthChange`` it is the
+        chromatic focal shift per micrometre.  These are float64 torch reductions on the device: their bits are torch's
+        and are NOT covered by the fixed-order contract of the sums.  NaN for a group without rows or with one slope."""
+        import torch
+
+        self._need_slopes("focus_gradient")
+        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        try:
+            a = np.asarray(axis, dtype=float).reshape(-1)
+        except (TypeError, ValueError):
+            a = np.zeros(0)
+        if a.shape != (3,) or not np.all(np.isfinite(a)) or not np.linalg.norm(a) > 0:
+            raise ValueError(f"axis: three finite numbers, not all zero (got {axis!r})")
+        dev = self.jacobian.device
+        a = torch.as_tensor(a / np.linalg.norm(a), dtype=torch.float64, device=dev)
+        across = torch.eye(3, dtype=torch.float64, device=dev) - torch.outer(a, a)
+        sel = self._selected
+        x = rows[_INDEX["x1"]:_INDEX["z1"] + 1][:, sel]
+        d = rows[_INDEX["x_tilt"]:_INDEX["z_tilt"] + 1][:, sel]
+        d = d / torch.sqrt((d * d).sum(dim=0))
+        w = rows[_INDEX[weights]][sel] if weights else torch.ones(len(sel), dtype=torch.float64, device=dev)
+        da = a @ d
+        p, s = across @ x, across @ (d / da)
+        dp = torch.einsum("ab,kbn->kan", across, self.jacobian)
+        ds = torch.einsum("ab,kbn->kan", across, self.slopes / da - d * (torch.einsum("b,kbn->kn", a, self.slopes) / (da * da))[:, None, :])
+        keep = (torch.isfinite(w) & torch.isfinite(p).all(dim=0) & torch.isfinite(s).all(dim=0)
+                & torch.isfinite(dp).all(dim=(0, 1)) & torch.isfinite(ds).all(dim=(0, 1)))
+        out = np.full((len(first) - 1, self.n_parameters), np.nan)
+        for g in range(len(first) - 1):
+            at = slice(int(first[g]), int(first[g + 1]))
+            k = keep[at]
+            wg = w[at][k]
+            total = wg.sum()
+            if not int(k.sum()) or not float(total) > 0:
+                continue
+            pg, sg, dpg, dsg = p[:, at][:, k], s[:, at][:, k], dp[:, :, at][:, :, k], ds[:, :, at][:, :, k]
+            pc = pg - (pg * wg).sum(dim=1, keepdim=True) / total
+            sc = sg - (sg * wg).sum(dim=1, keepdim=True) / total
+            cov = (wg * (pc * sc).sum(dim=0)).sum() / total
+            var = (wg * (sc * sc).sum(dim=0)).sum() / total
+            dcov = (wg * ((dpg * sc).sum(dim=1) + (dsg * pc).sum(dim=1))).sum(dim=1) / total
+            dvar = 2 * (wg * (dsg * sc).sum(dim=1)).sum(dim=1) / total
+            if float(var) > 0:
+                out[g] = (-(dcov * var - cov * dvar) / (var * var)).cpu().numpy()
+        return out
+
+    def transfer(self, parameters_xy, parameters_uv, basis=None):
+        """The 4x4 ray-transfer matrix about every selected ray: a device (n_selected, 4, 4) float64 tensor.
+        ``parameters_xy``: the indices of two ``SourceMotion`` translations, ``parameters_uv``: of two rotations; the
+        columns are per unit of those four parameters.  The rows are (x.e1, x.e2, d.e1, d.e2) of the landing point's and
+        the direction's derivative in the transverse basis (e1, e2): ``basis``, or by default the unit vectors of the two
+        translations (the launch's own transverse basis, right for a system that does not fold the axis).  For a
+        translation by e and a rotation by 1 rad about a x e (a the axis) these are the blocks A, B / C, D of first-order
+        optics, about the real ray, not the axis.  Index arithmetic on ``jacobian`` and ``slopes``."""
+        import torch
+
+        self._need_slopes("transfer")
+        picked = []
+        for name, pair in (("parameters_xy", parameters_xy), ("parameters_uv", parameters_uv)):
+            pair = list(pair)
+            if len(pair) != 2 or not all(isinstance(k, (int, np.integer)) and 0 <= k < self.n_parameters
+                                         and isinstance(self.parameters[k], SourceMotion) for k in pair):
+                raise ValueError(f"transfer: {name} is the indices of two SourceMotions among the parameters")
+            picked += [int(k) for k in pair]
+        if basis is None:
+            basis = [self.parameters[k].translate for k in picked[:2]]
+        e = np.asarray(basis, dtype=float)
+        if e.shape != (2, 3) or not np.all(np.isfinite(e)) or not np.all(np.linalg.norm(e, axis=1) > 0):
+            raise ValueError("transfer: basis is two vectors that are not zero (by default the translations of parameters_xy)")
+        e = torch.as_tensor(e / np.linalg.norm(e, axis=1, keepdims=True), dtype=torch.float64, device=self.jacobian.device)
+        top = torch.einsum("ac,kcn->nak", e, self.jacobian[picked])
+        bottom = torch.einsum("ac,kcn->nak", e, self.slopes[picked])
+        return torch.cat([top, bottom], dim=1)
+
+    def effective_focal_length(self, parameter, axis=(1.0, 0.0, 0.0)):
+        """(groups,): the effective focal length from a collimated source along ``axis`` whose field angle is parameter
+        ``parameter``, a ``SourceMotion`` rotation: d(centroid)/d(field angle) along the direction the beam tilts in,
+        ``centroid_gradient[:, k].t / |rotate x a|`` with t the unit vector of rotate x a -- the weighted mean of the
+        block B of ``transfer`` over the group.  On a detector in the focal plane of a lens without a fold this is f
+        (the image of a beam at the angle theta is at f tan(theta)); its change over the field is the distortion."""
+        k = parameter
+        if not (isinstance(k, (int, np.integer)) and 0 <= k < self.n_parameters and isinstance(self.parameters[k], SourceMotion)):
+            raise ValueError("effective_focal_length: parameter is the index of a SourceMotion among the parameters")
+        a = np.asarray(axis, dtype=float).reshape(-1)
+        if a.shape != (3,) or not np.all(np.isfinite(a)) or not np.linalg.norm(a) > 0:
+            raise ValueError(f"axis: three finite numbers, not all zero (got {axis!r})")
+        tilt = np.cross(self.parameters[k].rotate, a / np.linalg.norm(a))
+        rate = np.linalg.norm(tilt)
+        if not rate > 0:
+            raise ValueError("effective_focal_length: the parameter does not tilt a beam along axis (rotate x axis is zero)")
+        return self.centroid_gradient[:, k] @ (tilt / rate) / rate
 
     def rows(self):
         """The frame rows of the selection, in the order of ``jacobian``'s last axis: a device int64 tensor."""
