@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -668,6 +668,62 @@ int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t n_rows, do
                   const double* group_record, int weight_column, const double* wavelengths_um, int n_wavelengths,
                   double world_unit_um, int nx, int ny, double du, double dv, const double* centre_uv,
                   double* image_out, double* strehl_out, double* record_out, void* workspace, void* stream);
+
+/* Polarised diffraction PSF of the frame: the Huygens sum above with the Fresnel pass's complex field vectors as the
+ * rays' amplitudes (no counterpart upstream).  The scalar PSF sees the Fresnel losses as apodisation only; this sum
+ * also carries the phase a coating, a metal or a total internal reflection puts on s and p, the rotation of the field
+ * across the pupil and the field's axial component.
+ *
+ * Definitions.
+ * Everything of the scalar PSF stays: the wavefront's P, R, rho, axes (e1, e2, a) and OPD; the selected rows, the
+ *   (group, wavelength) buckets and the pixel grid; d_r and the phase in cycles; the usable-ray rule.
+ * States.  A Fresnel from polarised input (polarization not None) has one state, Ea.  From unpolarised input it has
+ *   two, Ea and Eb, which add incoherently with weight 1/2 each.  The sum is coherent over the rays, so a state must be
+ *   one state of the whole beam: prt_frame_fresnel launches an unpolarised ray in a basis made from the ray's own
+ *   direction, and the caller recombines Ea and Eb per ray into states that are uniform across the beam before this
+ *   call (the pass is linear in the launch field; pyrayt_amd does it in Fresnel.uniform_states).
+ * Component amplitudes.  Ray r in state s has amplitude A_r = sqrt(w_r) E_r.  w_r is the weights column of the frame
+ *   the Fresnel was computed on.  It is not the applied frame, so T does not enter twice.  E_r is the field on the
+ *   selected row's segment.  The components are c_r = (A_r.e1, A_r.e2, A_r.a): plain dot products with the real axes,
+ *   complex in general.  A ray whose field is not finite (one past an invalid interface) is left out and counted,
+ *   like a ray without a usable weight; with two states it is left out of both when either field is not finite.
+ * Field at a pixel.  U_{l,s,k}(u, v) = (1 / lambda_l) sum_r c_{r,k} exp(2 pi i phase_r(u, v)), for k = 1, 2, 3.
+ * Per state and wavelength.  S0 = |U1|^2 + |U2|^2, S1 = |U1|^2 - |U2|^2, S2 = 2 Re(conj(U1) U2),
+ *   S3 = 2 Im(conj(U1) U2), axial = |U3|^2.  This is the convention of Fresnel.stokes.  The image of a bucket is the
+ *   mean over its states of S0 + axial.
+ * Normalisation.  Divide by the scalar PSF's own denominator, D_g = sum_l (sum_r sqrt(w_r) / lambda_l)^2.  This is the
+ *   perfect, lossless wave with parallel fields on the same rays.
+ * Two Strehl ratios.  strehl is the image at P over D_g.  It is comparable to the scalar psf() of the bare frame and
+ *   across coatings.  strehl_apodized is the image at P over D'_g = mean_s sum_l (sum_r |A_r| / lambda_l)^2, with
+ *   |A_r| the complex 3-norm.  This is the strict ratio against the same amplitudes with phases and field directions
+ *   aligned.  Both are evaluated at P with fp64 sincospi, as k_psf_strehl does, whether or not P is a pixel centre.
+ * Throughput.  throughput_g = sum_r w_r |E_r|^2 / sum_r w_r, the mean over states, over the rays summed.
+ * Accuracy: the phase path is the scalar kernel's, so |U~_k - U_k| <= eps sum_r |c_{r,k}| / lambda with the eps above;
+ *   tests/vector_psf_reference.py derives from it the bound of every Stokes plane.
+ *
+ * prt_frame_vector_psf: the arguments of prt_frame_psf, and: field (DEVICE) -- (field_planes, field_ld) float64, the
+ * block prt_frame_fresnel (field_planes = 6: Ea then Eb by component, real) or prt_frame_fresnel_coated (12: the six
+ * real parts, then the six imaginary parts) wrote, offset to the first of the n_rows rows; field_ld >= n_rows, the
+ * distance between two planes; n_states 1 (Ea alone) or 2; axes HOST 9 doubles (a, e1, e2), the ones
+ * prt_frame_wavefront was given.  n_groups * n_wavelengths * n_states may not pass 65535, and
+ * n_groups * n_wavelengths * n_states * nx * ny * 48 bytes may not pass the 256 MiB cap of the partial-sum slab.
+ * Out, DEVICE, overwritten: stokes_out (n_groups, n_wavelengths, 5, nx, ny) -- S0, S1, S2, S3 and axial, the mean
+ * over the states, over D_g; NaN for a group without rays --; strehl_out (n_groups, 4): strehl, strehl_apodized,
+ * throughput, D_g; record_out (n_groups, n_wavelengths, n_states, 6): rays used, rays left out, sum sqrt(w), sum |A|,
+ * the Strehl numerator sum_k |sum c_k exp(2 pi i OPD / lambda_w)|^2 / lambda_w^2, sum w |E|^2.  workspace:
+ * prt_frame_vector_psf_workspace_bytes(n_rows, n_groups, n_wavelengths, n_states) device bytes (-1 for arguments the
+ * call would refuse).  The sum is a grid of (pixel tile, ray slice, (group, wavelength, state) bucket) workgroups;
+ * partial sums are folded in slice order, with no floating-point atomics: every output is the same, bit for bit, on
+ * every run.  All arguments are checked before a device is touched.  Stream-ordered; the call reads one status word
+ * back and so returns when the stream has reached its end. */
+int64_t prt_frame_vector_psf_workspace_bytes(int64_t n_rows, int n_groups, int n_wavelengths, int n_states);
+int prt_frame_vector_psf(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                         double rays_per_source, int n_groups, const double* opd, const double* pupil,
+                         const double* group_record, int weight_column, const double* wavelengths_um,
+                         int n_wavelengths, double world_unit_um, int nx, int ny, double du, double dv,
+                         const double* centre_uv, const double* field, int64_t field_ld, int field_planes,
+                         int n_states, const double* axes, double* stokes_out, double* strehl_out, double* record_out,
+                         void* workspace, void* stream);
 
 /* Geometric MTF of the frame, through focus (no counterpart upstream).  It reads only each ray's end point and
  * direction at the surface, so it works on frames that hold the detector's rows alone.

@@ -168,6 +168,10 @@ def _declare(lib):
         "prt_frame_psf_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
         "prt_frame_psf": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_p, c_p, c_p, c_int, c_p, c_int, c_d,
                                   c_int, c_int, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_vector_psf_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+        "prt_frame_vector_psf": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_p, c_p, c_p, c_int, c_p, c_int,
+                                         c_d, c_int, c_int, c_d, c_d, c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p,
+                                         c_p, c_p]),
         "prt_frame_mtf_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_int]),
         "prt_frame_mtf": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_p, c_p, c_int, c_p, c_int, c_p, c_int,
                                   c_p, c_int, c_p, c_p, c_p, c_p]),
@@ -226,7 +230,8 @@ EXPORTED_SYMBOLS = (
     "prt_frame_stats", "prt_frame_stats_sharded", "prt_frame_pivots", "prt_frame_finish", "prt_frame_mean_square",
     "prt_frame_range", "prt_frame_histogram_workspace_bytes", "prt_frame_histogram",
     "prt_frame_optical_path", "prt_frame_wavefront_workspace_bytes", "prt_frame_wavefront",
-    "prt_frame_psf_workspace_bytes", "prt_frame_psf", "prt_frame_mtf_workspace_bytes", "prt_frame_mtf",
+    "prt_frame_psf_workspace_bytes", "prt_frame_psf", "prt_frame_vector_psf_workspace_bytes", "prt_frame_vector_psf",
+    "prt_frame_mtf_workspace_bytes", "prt_frame_mtf",
     "prt_frame_launch_index", "prt_frame_ray_aberrations_workspace_bytes", "prt_frame_ray_aberrations",
     "prt_frame_energy_workspace_bytes", "prt_frame_energy", "prt_frame_paths_workspace_bytes", "prt_frame_paths",
     "prt_frame_fresnel_workspace_bytes", "prt_frame_fresnel",

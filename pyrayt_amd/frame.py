@@ -558,7 +558,7 @@ class DeviceFrame:
     # --- diffraction PSF and Strehl ratio (no counterpart upstream) ---------------------------------------------------
     def psf(self, surface, *, world_unit_um, pixels=128, pixel_size=None, centre=(0.0, 0.0), weights="intensity",
             reference="centroid", radius=None, axis=None, basis=None, generation=None, rays_per_source=None,
-            n_groups=None, group=None):
+            n_groups=None, group=None, fresnel=None):
         """The diffraction image of a point at ``surface`` -- the Huygens PSF -- and its Strehl ratio, per group
         (``id // rays_per_source``).  Returns a ``PSF``.
 
@@ -577,13 +577,31 @@ class DeviceFrame:
         Sampling: each ray stands for an equal share of the pupil's area, or carries its share in ``weights``; random
         pupil samples leave a noise floor of about 1 / (number of rays) in the normalised image.  Obliquity and 1/r
         are taken as constant over the pupil (an error of order NA^2 at the rim).  Needs the whole frame of a trace,
-        like ``wavefront``; ``group=`` (sharded frames) is not supported yet."""
+        like ``wavefront``; ``group=`` (sharded frames) is not supported yet.
+
+        ``fresnel``: None, or the ``Fresnel`` of this frame with its fields (``self.fresnel(fields=True, ...)``).  The
+        sum is then the polarised one (``prt_frame_vector_psf``): every ray's amplitude is ``sqrt(w)`` times its complex
+        field vector, projected on (e1, e2, a), so the image carries the coatings' phases, the rotation of the field
+        across the pupil and its axial component besides the losses.  ``weights`` is read from this frame, not from
+        ``fresnel.apply()``: the transmittance is in the fields already.  Polarised input has one state (Ea),
+        unpolarised input two (Ea and Eb, added incoherently with weight 1/2).  The two states of
+        ``fresnel(polarization=None)`` follow each ray's own direction, which serves the per-ray transmittance but is
+        not a state of the beam; they are first turned into two states that are uniform across the beam
+        (``Fresnel.uniform_states()``; ``VectorPSF.fresnel`` is the Fresnel that was summed).  A ``Fresnel`` built by
+        hand is summed as it is.  Returns a ``VectorPSF``."""
         import torch
 
         from . import engine
 
         if group is not None:
             raise NotImplementedError("psf() of a sharded frame (group=) is not supported yet")
+        if fresnel is not None:
+            if not isinstance(fresnel, Fresnel):
+                raise ValueError(f"fresnel: None or the Fresnel of this frame (got {fresnel!r})")
+            if fresnel.frame is not self:
+                raise ValueError("psf: fresnel was computed on another frame (call this frame's fresnel(fields=True))")
+            if fresnel.field is None:
+                raise ValueError("psf: the fields were not kept (fresnel(fields=True))")
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         nx, ny = _pixel_counts(pixels)
         step = None
@@ -615,6 +633,11 @@ class DeviceFrame:
         dev = rows.device
         n_rows = rows.shape[1]
         n_w = len(wavelengths)
+        if fresnel is not None:
+            if fresnel.launch_states == "per_ray":  # (the pass's own two states: made uniform across the beam first)
+                fresnel = fresnel.uniform_states()
+            return self._vector_psf(fresnel, wave, rows, surface_id, n_groups, record, weights, generation,
+                                    rays_per_source, wavelengths, unit, (nx, ny), step, uv0, f_number)
         image = torch.empty((n_groups, n_w, nx, ny), dtype=torch.float64, device=dev)
         strehl = torch.empty(n_groups, dtype=torch.float64, device=dev)
         out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
@@ -633,6 +656,49 @@ class DeviceFrame:
             out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
         return PSF(engine.to_host(image).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(), wavelengths,
                    unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave)
+
+    def _vector_psf(self, fresnel, wave, rows, surface_id, n_groups, record, weights, generation, rays_per_source,
+                    wavelengths, unit, pixels, step, uv0, f_number):
+        """``psf(fresnel=)`` after the wavefront: the field planes as the library reads them, and the call."""
+        import torch
+
+        from . import engine
+
+        dev = rows.device
+        n_rows, n_w, (nx, ny) = rows.shape[1], len(wavelengths), pixels
+        n_states = 1 if fresnel.polarization is not None else 2
+        field = fresnel.field
+        if tuple(field.shape) != (6, len(self)):
+            raise ValueError(f"psf: fresnel.field is (6, {len(self)}) for this frame (got {tuple(field.shape)})")
+        # (6, n) real as prt_frame_fresnel wrote it, or the real parts and then the imaginary parts of a complex one
+        planes = torch.cat([field.real, field.imag]) if field.is_complex() else field
+        planes = planes.to(dev, torch.float64).contiguous()
+        start = 0
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if generation is not None:  # (the rows are that generation's slice: the planes are read from the same offset)
+            start = sum(self.rows_per_generation[:int(generation)])
+        field_ld = max(planes.shape[1], 1)
+        stokes = torch.empty((n_groups, n_w, 5, nx, ny), dtype=torch.float64, device=dev)
+        strehl = torch.empty((n_groups, 4), dtype=torch.float64, device=dev)
+        out = torch.empty((n_groups, n_w, n_states, 6), dtype=torch.float64, device=dev)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_vector_psf_workspace_bytes(n_rows, n_groups, n_w, n_states))),
+                           dtype=torch.uint8, device=dev)
+        lam = np.ascontiguousarray(wavelengths, dtype=np.float64)
+        uv0 = np.ascontiguousarray(uv0)
+        axes = np.ascontiguousarray(wave._made_of["axes"], dtype=np.float64)
+        opd = wave.opd if wave.opd.numel() else torch.empty(1, dtype=torch.float64, device=dev)
+        pupil = wave.pupil if wave.pupil.numel() else torch.empty(2, dtype=torch.float64, device=dev)
+        engine._check(lib.prt_frame_vector_psf(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
+            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
+            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), -1 if weights is None else _INDEX[weights],
+            lam.ctypes.data, n_w, unit, nx, ny, step[0], step[1], uv0.ctypes.data,
+            planes.data_ptr() + 8 * start if n_rows else None, field_ld, int(planes.shape[0]), n_states, axes.ctypes.data,
+            stokes.data_ptr(), strehl.data_ptr(), out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        return VectorPSF(engine.to_host(stokes).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(),
+                         wavelengths, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave, fresnel)
 
     def _psf_wavelengths(self, surface_id, generation):
         """The distinct wavelengths of the rows the wavefront selects (sorted), found where the rows are."""
@@ -1145,10 +1211,13 @@ class DeviceFrame:
             transmittance.data_ptr() if n_rows else None, field.data_ptr() if field is not None and n_rows else None,
             record.ctypes.data, work.data_ptr(), engine._stream_ptr(torch, dev)))
         if not is_complex:
-            return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
-        field = torch.complex(field[:6], field[6:]) if field is not None else None
-        return Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless),
-                       coatings=dict(coatings or {}))
+            out = Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
+        else:
+            field = torch.complex(field[:6], field[6:]) if field is not None else None
+            out = Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless),
+                          coatings=dict(coatings or {}))
+        out.launch_states = "per_ray" if v is None else "polarised"
+        return out
 
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
@@ -1630,6 +1699,58 @@ class PSF:
         return MTF(otf, record, nu, theta, np.zeros(1))
 
 
+class VectorPSF(PSF):
+    """What ``DeviceFrame.psf(fresnel=...)`` returns: a ``PSF`` of the polarised Huygens sum (numpy arrays).  ``image``
+    and ``image_by_wavelength`` are S0 + axial, the mean over the input states, over the scalar PSF's own denominator
+    D_g (the perfect, lossless wave with parallel fields on the same rays).  Besides what a ``PSF`` has:
+    ``stokes`` (n_groups, 4, nx, ny) and ``stokes_by_wavelength`` (n_groups, n_wavelengths, 4, nx, ny): S0..S3 of the
+    transverse field in (e1, e2), the convention of ``Fresnel.stokes``; ``axial`` (n_groups, nx, ny) and
+    ``axial_by_wavelength``: |U3|^2, the field along the axis; per group ``strehl`` (the image at P over D_g: comparable
+    with the scalar ``psf()`` of the bare frame and across coatings), ``strehl_apodized`` (the image at P over the same
+    amplitudes with phases and field directions aligned: the strict ratio), ``throughput`` (sum w |E|^2 / sum w over
+    the rays summed) and ``denominator`` (D_g); ``record`` (n_groups, n_wavelengths, n_states, 6): rays used, rays
+    left out, sum sqrt(w), sum |A|, Strehl numerator, sum w |E|^2; ``n_states`` (1: polarised input, 2: unpolarised);
+    ``fresnel``: the ``Fresnel`` whose fields were summed."""
+
+    def __init__(self, stokes, strehl, record, wavelengths, world_unit_um, pixels, pixel_size, centre, f_number,
+                 wavefront, fresnel=None):
+        super().__init__(stokes[:, :, 0] + stokes[:, :, 4], strehl[:, 0], record[:, :, 0, :], wavelengths,
+                         world_unit_um, pixels, pixel_size, centre, f_number, wavefront)
+        self.record, self.n_states, self.fresnel = record, record.shape[2], fresnel
+        self.stokes_by_wavelength, self.axial_by_wavelength = stokes[:, :, :4], stokes[:, :, 4]
+        self.stokes, self.axial = self.stokes_by_wavelength.sum(axis=1), self.axial_by_wavelength.sum(axis=1)
+        self.strehl_apodized, self.throughput, self.denominator = strehl[:, 1], strehl[:, 2], strehl[:, 3]
+
+    def degree_of_polarization(self):
+        """sqrt(S1^2 + S2^2 + S3^2) / S0 per pixel of the polychromatic image, (n_groups, nx, ny); NaN where S0 is 0."""
+        s = self.stokes
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.sqrt(s[:, 1] ** 2 + s[:, 2] ** 2 + s[:, 3] ** 2) / s[:, 0]
+
+    def analyzed(self, jones):
+        """The image behind an ideal analyser that passes the transverse state ``jones`` = (j1, j2) in (e1, e2), complex
+        in general ((1, 0): linear along e1; (1, 1j): the circular state of S3 > 0): |conj(j).U|^2 / |j|^2 =
+        (S0 + q1 S1 + q2 S2 + q3 S3) / 2 with (q1, q2, q3) the analyser's own normalised Stokes vector.  Linear in the
+        Stokes images, computed on the host; (n_groups, nx, ny).  The axial component does not pass."""
+        try:
+            j = np.asarray(jones, dtype=complex).reshape(-1)
+        except (TypeError, ValueError):
+            j = np.zeros(0, dtype=complex)
+        if j.shape != (2,) or not np.all(np.isfinite(j)) or not np.any(j != 0):
+            raise ValueError(f"jones: two finite numbers (j1, j2), not both zero (got {jones!r})")
+        norm = float(abs(j[0]) ** 2 + abs(j[1]) ** 2)
+        cross = np.conj(j[0]) * j[1]
+        q = ((abs(j[0]) ** 2 - abs(j[1]) ** 2) / norm, 2.0 * cross.real / norm, 2.0 * cross.imag / norm)
+        s = self.stokes
+        return 0.5 * (s[:, 0] + q[0] * s[:, 1] + q[1] * s[:, 2] + q[2] * s[:, 3])
+
+    def to_pandas(self):
+        """One row per group: what ``PSF.to_pandas`` gives, and strehl_apodized and throughput."""
+        frame = super().to_pandas()
+        frame["strehl_apodized"], frame["throughput"] = self.strehl_apodized, self.throughput
+        return frame
+
+
 class MTF:
     """What ``DeviceFrame.mtf`` returns (numpy arrays).  ``otf`` (n_groups, n_focus, n_azimuths, n_frequencies),
     complex; ``mtf`` = |otf| and ``ptf`` = arg otf (radians, about the group's centre); ``frequencies`` (cycles per world
@@ -2012,7 +2133,59 @@ class Fresnel:
         self.n_reflections, self.n_lossless, self.n_undeviated, self.n_invalid = (int(v) for v in record[:4])
         self.n_coated, self.n_tir = (int(v) for v in record[4:6]) if len(record) >= 6 else (0, 0)
         self.polarization, self.lossless, self.coatings = polarization, tuple(lossless), coatings
+        self.launch_states = None  # ("per_ray": the two states of fresnel(polarization=None); see uniform_states)
         self._paths = {}
+
+    def uniform_states(self, polarization=None):
+        """A ``Fresnel`` with the same transmittance whose two states are uniform across the beam, for sums that are
+        coherent over the rays (``DeviceFrame.psf(fresnel=)``).  ``fresnel(polarization=None)`` launches every ray with
+        two orthogonal fields in a transverse basis made from the ray's own direction (the world axis of its smallest
+        component), which is all the per-ray transmittance needs; across a cone that basis jumps from ray to ray, so
+        ``Ea`` alone is not one polarisation state of the beam.  The pass is linear in the launch field, so the fields
+        of any other launch state are combinations of ``Ea`` and ``Eb``: the new ``Ea`` belongs to the launch field of
+        ``polarization`` (a real world vector; None: the world axis most nearly perpendicular to the mean launch
+        direction) taken perpendicular to each ray's launch direction u0 and normalised, as ``fresnel(polarization=)``
+        launches it, and the new ``Eb`` to u0 x that.  A rotation per ray: ``|Ea|^2 + |Eb|^2`` is unchanged.  Rows of a
+        ray without a generation-0 row are NaN."""
+        import torch
+
+        if self.field is None:
+            raise ValueError("uniform_states: the fields were not kept (fresnel(fields=True))")
+        if self.polarization is not None:
+            raise ValueError("uniform_states: this Fresnel has one state (polarised input)")
+        rows, counts = self.frame.rows, self.frame.rows_per_generation
+        if not counts or sum(counts) != rows.shape[1]:
+            raise ValueError("uniform_states needs the whole frame of a trace")
+        n0 = int(counts[0])
+        ids = rows[_INDEX["id"]]
+        slot = (ids - ids.min()).long() if rows.shape[1] else ids.long()
+        table = torch.full((int(slot.max()) + 1 if rows.shape[1] else 1,), -1, dtype=torch.long, device=rows.device)
+        table[slot[:n0]] = torch.arange(n0, device=rows.device)
+        launch = table[slot]  # (per row: the generation-0 row of its ray)
+        known = launch >= 0
+        launch = launch.clamp(min=0)
+        u0 = torch.stack([rows[_INDEX[name]][launch] for name in ("x_tilt", "y_tilt", "z_tilt")])
+        u0 = u0 / torch.sqrt((u0 * u0).sum(dim=0))
+        if polarization is None:
+            mean = u0[:, known].mean(dim=1).abs()
+            g = torch.nn.functional.one_hot(torch.argmin(mean), 3).to(u0.dtype)
+        else:
+            g = torch.as_tensor(np.asarray(polarization, dtype=np.float64).reshape(-1), device=rows.device)
+            if g.shape != (3,) or not bool(torch.isfinite(g).all()) or not bool((g != 0).any()):
+                raise ValueError("uniform_states: polarization is a real world vector of three finite numbers, not all zero")
+        g1 = g[:, None] - (g[:, None] * u0).sum(dim=0) * u0
+        g1 = g1 / torch.sqrt((g1 * g1).sum(dim=0))
+        g2 = torch.linalg.cross(u0, g1, dim=0)
+        ea, eb = self.field[:3], self.field[3:6]
+        base_a, base_b = (x[:, launch].real if x.is_complex() else x[:, launch] for x in (ea, eb))
+        nan = torch.full_like(self.transmittance, float("nan"))
+        weights = [torch.where(known, (base * axis).sum(dim=0), nan) for axis in (g1, g2) for base in (base_a, base_b)]
+        field = torch.cat([weights[0] * ea + weights[1] * eb, weights[2] * ea + weights[3] * eb])
+        out = Fresnel(self.frame, self.transmittance, field, np.array([self.n_reflections, self.n_lossless,
+                      self.n_undeviated, self.n_invalid, self.n_coated, self.n_tir]), polarization=None,
+                      lossless=self.lossless, coatings=self.coatings)
+        out.launch_states = "uniform"
+        return out
 
     def stokes(self, rows=None):
         """Per row (``rows``: an index tensor or slice; None: all) the Stokes parameters S0..S3 of ``Ea`` -- the field of
