@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -767,6 +767,59 @@ int prt_frame_mtf(int device, const double* rows, int64_t ld, int64_t n_rows, do
                   double rays_per_source, int n_groups, const double* reference, const double* axes, int weight_column,
                   const double* frequencies, int n_frequencies, const double* azimuths_deg, int n_azimuths,
                   const double* focus, int n_focus, double* otf_out, double* record_out, void* workspace, void* stream);
+
+/* MTF sensitivities: d(OTF)/d(parameter) through focus, from the rows, jacobian_out and slopes_out of one
+ * prt_frame_launch_sensitivity call (below; any kinds of parameter), without a re-trace.
+ *
+ * Definitions, with those of the geometric MTF above.
+ * Rays: the selected rows of the sensitivity call, in its order (selected DEVICE n_selected int64 row numbers, ordered by
+ *   group, generation and id; group_first HOST n_groups + 1 int64: group q is [group_first[q], group_first[q + 1]), a
+ *   contiguous run, so nothing is sorted).  Weights: weight_column, or ones for -1.
+ * Rays kept: a ray is kept if the MTF would keep it (the rule "Rays left out" above; a row number outside [0, n_rows)
+ *   counts as left out too) and its 3 K entries of jacobian and its 3 K entries of slopes are all finite.  There is one
+ *   kept set for all K.  The others are counted per group: n_missed by the MTF's rule, n_unfollowed by the second.  A ray
+ *   that is left out contributes exactly nothing: it keeps its place in the order with w = 0 and zero derivatives.
+ * Staged: uh = u / |u| (slopes is duh_k, the derivative of the unit direction), s = (uh.e1, uh.e2) / (uh.a),
+ *   d = Q - C_g, p = (d.e1, d.e2) - s (d.a), x(delta) = p + delta s.  C_g is the weighted centroid of the kept rays' Q, or a
+ *   given point per group (reference); it is HELD FIXED under the parameter.
+ * Per parameter k, with dQ_k = jacobian and duh_k = slopes:
+ *   ds_k = ((duh_k.e1, duh_k.e2) - s (duh_k.a)) / (uh.a)
+ *   dp_k = (dQ_k.e1, dQ_k.e2) - s (dQ_k.a) - ds_k (d.a)
+ *   dx_k(delta) = dp_k + delta ds_k
+ * Outputs:
+ *   OTF_g(delta, theta, nu)     = sum w exp(-2 pi i k.x(delta)) / sum w, as above;
+ *   dOTF_g,k(delta, theta, nu)  = -2 pi i sum w (k.dx_k(delta)) exp(-2 pi i k.x(delta)) / sum w;
+ *   dOTF_g / d delta            = -2 pi i sum w (k.s) exp(-2 pi i k.x(delta)) / sum w, the through-focus derivative;
+ *   dC_g,k = sum w dQ_k / sum w, over the same rays: what a centre that follows the centroid adds, composed by the caller
+ *   as dOTF_k + 2 pi i (k.(dC_k.e1, dC_k.e2)) OTF + (dC_k.a) dOTF / d delta.
+ * Accuracy: the phasor is the MTF's (with the first-order correction folded into it once); a derivative carries, beside the
+ *   phasor's error times |k.dx_k|, the roundings of k.dx_k itself: tests/mtf_gradient_reference.py derives the bound
+ *   |dOTF~ - dOTF| <= 2 pi [mean_w(|g| e) + 29 2^-53 mean_w(G)] and states what is counted.
+ *
+ * prt_frame_mtf_gradient: rows DEVICE, ld, n_rows as above; jacobian, slopes DEVICE (K, 3, n_selected), K in [1, 16];
+ * reference DEVICE (n_groups, 3) or NULL for the centroids; axes HOST 9 doubles; frequencies, azimuths_deg, focus HOST with
+ * the MTF's limits; n_groups in [1, 65535]; n_groups * n_focus * n_azimuths * n_frequencies * 18 * 16 bytes (the slab of a
+ * call with 16 parameters, whatever K is) may not pass the 256 MiB cap.
+ * Out, DEVICE, overwritten: otf_out (n_groups, n_focus, n_azimuths, n_frequencies, 2); dotf_out (n_groups, K + 1, n_focus,
+ * n_azimuths, n_frequencies, 2), index K the focus derivative; record_out (n_groups, 7 + 3 K): C_g (3), sum w, rays used,
+ * n_missed, n_unfollowed, then dC_k (K vectors).  A group with no rays kept, or with sum w = 0, is NaN in otf_out, dotf_out, C_g (unless given) and
+ * dC_k.  workspace: prt_frame_mtf_gradient_workspace_bytes(n_selected, n_groups, K, n_frequencies, n_azimuths, n_focus)
+ * device bytes (-1 for arguments the call would refuse).
+ * Passes: centre chunks of 1024 selected rows in a fixed tree; the record; staging; the sum, a grid of (ray slice, output
+ * tile, chunk of at most 8 parameters) workgroups that read the ray tile through LDS; the fold in slice order.  Every
+ * partition depends only on a group's count of selected rows, on the output count and on n_groups -- never on n_rows or the
+ * frame's other rows, never on K --, a parameter's arithmetic does not depend on the others in the call, and there are no
+ * floating-point atomics: every output is the same, bit for bit, on every run, on any frame that holds the same selected
+ * rows, and for a parameter alone or among sixteen (where the kept set is the same).  All arguments are checked before a
+ * device is touched.  Stream-ordered; the call returns when the stream has reached its end. */
+int64_t prt_frame_mtf_gradient_workspace_bytes(int64_t n_selected, int n_groups, int n_parameters, int n_frequencies,
+                                               int n_azimuths, int n_focus);
+int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                           int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                           const double* jacobian, const double* slopes, int n_parameters, const double* reference,
+                           const double* axes, const double* frequencies, int n_frequencies, const double* azimuths_deg,
+                           int n_azimuths, const double* focus, int n_focus, double* otf_out, double* dotf_out,
+                           double* record_out, void* workspace, void* stream);
 
 /* Ray-aberration curves of the frame: each ray's row at a surface joined by ray id with the row where the ray was
  * launched (examples/lens_design.ipynb cells 12-13 join the two cuts of the frame with isin(id)), its transverse and

@@ -1221,7 +1221,7 @@ class DeviceFrame:
 
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
-                    rays_per_source=None, n_groups=None, wavefront=None):
+                    rays_per_source=None, n_groups=None, wavefront=None, slopes=False):
         """d(landing point)/d(parameter) at ``surface`` for motions, shape changes and index changes of parts, and for
         motions of the rays' launch and changes of their wavelength, from this one trace: a ``Sensitivity``.
         ``parameters``: up to 16 of ``Motion`` (a rigid motion), ``Deformation`` (an affine deformation: radii, a
@@ -1255,6 +1255,11 @@ class DeviceFrame:
         HELD FIXED (``dfield``, ``dopd``, ``dpupil``, ``dzernike()``, ``rms_opd_gradient``, ``step(merit="wavefront")``);
         ``jacobian`` and the landing-point sums keep their bits.  Without it nothing changes.
 
+        ``slopes=True``: the call goes through ``prt_frame_launch_sensitivity`` whatever the parameters are (with or
+        without ``wavefront=``; a parameter that is neither a ``SourceMotion`` nor a ``WavelengthChange`` has no flags
+        there) and the ``Sensitivity`` has ``slopes``, which ``mtf_gradient()`` needs; ``jacobian``, the sums and the
+        wavefront outputs keep their bits.  With the default every call takes the entry point it always took.
+
         Out of scope: a reference radius that changes with the parameter; rays whose path changes under the
         parameter, such as those at the edge of an aperture -- the result is the derivative at fixed path, as in every
         differential ray trace.  Known limits: an interface whose two indices are equal to the bit is differentiated
@@ -1276,6 +1281,7 @@ class DeviceFrame:
         design = not all(isinstance(m, Motion) for m in motions)
         launch = any(isinstance(m, (SourceMotion, WavelengthChange)) for m in motions)
         colour = any(isinstance(m, WavelengthChange) for m in motions)
+        launch_form = launch or bool(slopes)  # (the entry point that also writes the slopes)
         if len(motions) > 16:
             raise ValueError(f"sensitivity: at most 16 parameters a call (got {len(motions)})")
         if launch:
@@ -1397,7 +1403,7 @@ class DeviceFrame:
                 group_first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], pivots.ctypes.data,
                 jacobian.data_ptr() if n_selected else None, sums.data_ptr(), record.ctypes.data, work.data_ptr(),
                 engine._stream_ptr(torch, dev))
-        if design or wavefront is not None:  # (a call of Motions alone takes the entry point, the kernel and the workspace it always took)
+        if design or wavefront is not None or launch_form:  # (a call of Motions alone, without slopes=True, takes the entry point, the kernel and the workspace it always took)
             linear = np.ascontiguousarray([m.linear.reshape(-1) if isinstance(m, Deformation) else np.zeros(9)
                                            for m in motions], dtype=np.float64)
             named = [isinstance(m, IndexChange) for m in motions]
@@ -1405,7 +1411,7 @@ class DeviceFrame:
             index_lists = [sorted(m.surface_ids) if i else [] for m, i in zip(motions, named)]
             index_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in index_lists])]), dtype=np.int32)
             index_ids = np.ascontiguousarray([v for ids_ in index_lists for v in ids_] or [0], dtype=np.int64)
-        if launch:  # (the launch form: the design or wavefront form's arguments, the rays each parameter names, the glasses)
+        if launch_form:  # (the launch form: the design or wavefront form's arguments, the rays each parameter names, the glasses)
             ranges = np.ascontiguousarray([m.id_range if isinstance(m, (SourceMotion, WavelengthChange))
                                            else (0.0, 0.0) for m in motions], dtype=np.float64)
             flags = np.ascontiguousarray([1 if isinstance(m, SourceMotion) else 2 if isinstance(m, WavelengthChange)
@@ -1413,7 +1419,7 @@ class DeviceFrame:
             colour_rates = np.ascontiguousarray([m.rate if isinstance(m, WavelengthChange) else 0.0 for m in motions],
                                                 dtype=np.float64)
             mats = np.ascontiguousarray(snapshot.materials)
-            slopes = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
+            directions = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
             J, out, ptr, wave_args = 0, None, dict.fromkeys(("dfield", "dopd", "dpupil", "opd", "pupil", "sums")), (None,) * 3
             if wavefront is not None:
                 J = wavefront.terms
@@ -1429,7 +1435,7 @@ class DeviceFrame:
                            sums=torch.empty((n_groups, wide), dtype=torch.float64, device=dev))
                 ptr = {name: (t.data_ptr() if t.numel() else None) for name, t in out.items()}
                 if not n_rows:  # (the entry point reads opl == NULL as "no wavefront": there is no path to point at)
-                    raise ValueError("sensitivity: wavefront= with a SourceMotion or a WavelengthChange needs a frame with rows")
+                    raise ValueError("sensitivity: wavefront= with a SourceMotion, a WavelengthChange or slopes=True needs a frame with rows")
                 opl = self._optical_path()
                 wave_args = (opl.data_ptr(), groups.ctypes.data, axes.ctypes.data)
             work = torch.empty(int(engine._check(lib.prt_frame_launch_sensitivity_workspace_bytes(
@@ -1437,13 +1443,13 @@ class DeviceFrame:
             engine._check(lib.prt_frame_launch_sensitivity(
                 *head, linear.ctypes.data, rates.ctypes.data, index_ids.ctypes.data, index_first.ctypes.data, *tail[:8],
                 *wave_args, J, ranges.ctypes.data, flags.ctypes.data, colour_rates.ctypes.data, mats.ctypes.data, len(mats),
-                tail[8], tail[9], slopes.data_ptr() if n_selected else None, ptr["dfield"], ptr["dopd"], ptr["dpupil"],
+                tail[8], tail[9], directions.data_ptr() if n_selected else None, ptr["dfield"], ptr["dopd"], ptr["dpupil"],
                 ptr["opd"], ptr["pupil"], ptr["sums"], tail[10], work.data_ptr(), tail[12]))
             if out is not None:
                 out["sums"] = engine.to_host(out["sums"]).copy()
                 out["wavefront"] = wavefront
             return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
-                               wave=out, launch=dict(slopes=slopes, rows=rows, weights=weights, group_first=group_first))
+                               wave=out, launch=dict(slopes=directions, rows=rows, weights=weights, group_first=group_first))
         if wavefront is not None:
             J = wavefront.terms
             opl = self._optical_path()
@@ -1785,6 +1791,88 @@ class MTF:
         f_index = slice(None) if frequency is None else _positions(self.frequencies, [frequency], "frequency")
         merit = self.mtf[:, :, a_index][:, :, :, f_index].mean(axis=(2, 3))  # (groups, planes)
         return _best_plane(self.focus, merit)
+
+
+class MTFGradient:
+    """What ``Sensitivity.mtf_gradient`` returns (numpy arrays), G groups, K parameters, F focus shifts, A azimuths, N
+    frequencies.  ``otf`` (G, F, A, N) complex and ``mtf`` = |otf|, over the rays summed; ``dotf`` (G, K, F, A, N) complex,
+    d(otf)/d(parameter k), and ``dotf_dfocus`` (G, F, A, N), d(otf)/d(focus shift); ``dmtf`` = Re(conj(otf) dotf) / |otf|
+    (G, K, F, A, N), ``dmtf_dfocus``, and ``dptf`` = Im(conj(otf) dotf) / |otf|^2, the derivative of the phase in radians;
+    all three NaN where |otf| = 0.  ``reference``: "fixed" (the centre held fixed) or "centroid" (it follows the group's
+    centroid: ``dotf`` and ``dptf`` differ, ``dmtf`` does not but for rounding).  Per group ``centre`` (G, 3),
+    ``centroid_gradient`` (G, K, 3) (d(centroid of the rays summed)/d(parameter)), ``sum_weights``, ``n_rays`` (rays
+    summed), ``n_missed`` (left out by the MTF's rule), ``n_unfollowed`` (a Jacobian or slope that is not finite);
+    ``record`` is the device's (G, 7 + 3 K) block.  ``frequencies``, ``azimuths``, ``focus``, ``parameters``.  A group
+    without rays is NaN throughout."""
+
+    def __init__(self, otf, dotf, record, frequencies, azimuths, focus, axes, parameters, reference="fixed"):
+        self.otf = np.asarray(otf)
+        self.frequencies = np.asarray(frequencies, dtype=float)
+        self.azimuths = np.asarray(azimuths, dtype=float)
+        self.focus = np.asarray(focus, dtype=float)
+        self.parameters = tuple(parameters)
+        self.reference = reference
+        K = self.n_parameters = len(self.parameters)
+        self.record = np.asarray(record, dtype=float)
+        self.centre, self.sum_weights = self.record[:, :3], self.record[:, 3]
+        self.n_rays, self.n_missed, self.n_unfollowed = (np.nan_to_num(self.record[:, k]).astype(np.int64) for k in (4, 5, 6))
+        self.centroid_gradient = self.record[:, 7:].reshape(-1, K, 3)
+        dotf = np.asarray(dotf)
+        self.dotf, self.dotf_dfocus = dotf[:, :K], dotf[:, K]
+        if reference == "centroid":  # (the centre follows the centroid: the phase of the shift, and the plane's own motion)
+            a, e1, e2 = (np.asarray(axes, dtype=float)[k:k + 3] for k in (0, 3, 6))
+            angle = np.radians(self.azimuths)
+            kc, ks = np.cos(angle)[:, None] * self.frequencies, np.sin(angle)[:, None] * self.frequencies  # (A, N)
+            dc = self.centroid_gradient
+            shift = (dc @ e1)[:, :, None, None] * kc + (dc @ e2)[:, :, None, None] * ks  # (G, K, A, N)
+            self.dotf = (self.dotf + 2j * np.pi * shift[:, :, None] * self.otf[:, None]
+                         + (dc @ a)[:, :, None, None, None] * self.dotf_dfocus[:, None])
+        self.mtf = np.abs(self.otf)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            size = np.where(self.mtf > 0, self.mtf, np.nan)
+            turned = np.conj(self.otf)[:, None] * self.dotf
+            self.dmtf = turned.real / size[:, None]
+            self.dptf = turned.imag / (size * size)[:, None]
+            self.dmtf_dfocus = (np.conj(self.otf) * self.dotf_dfocus).real / size
+
+    def to_pandas(self):
+        """Long form: one row per (source_id, focus, azimuth, frequency) with its mtf, ``dmtf_dfocus`` and, per
+        parameter k, ``dmtf_k`` and ``dptf_k``."""
+        g, f, a, n = self.otf.shape
+        index = np.indices((g, f, a, n)).reshape(4, -1)
+        data = {"source_id": index[0], "focus": self.focus[index[1]], "azimuth": self.azimuths[index[2]],
+                "frequency": self.frequencies[index[3]], "mtf": self.mtf.reshape(-1),
+                "dmtf_dfocus": self.dmtf_dfocus.reshape(-1)}
+        for k in range(self.n_parameters):
+            data[f"dmtf_{k}"] = self.dmtf[:, k].reshape(-1)
+            data[f"dptf_{k}"] = self.dptf[:, k].reshape(-1)
+        return pd.DataFrame(data)
+
+    def step(self, damping=0.0, target=1.0, focus=0.0):
+        """Per group the change of the parameters that brings the MTF of the plane ``focus`` (a value of ``self.focus``)
+        closest to ``target`` to first order: Gauss-Newton on the residuals ``target - mtf`` over that plane's azimuths
+        and frequencies with ``dmtf`` as the Jacobian, the solution of (N + damping diag(N)) dp = rhs through
+        ``solve_normal_equations`` (the minimum-norm one where the outputs cannot tell the parameters apart).
+        (groups, K); NaN for a group without rays or with an output whose |otf| is 0."""
+        if not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("damping: a number >= 0")
+        if not np.isfinite(target):
+            raise ValueError("target: a finite number")
+        plane = _positions(self.focus, [focus], "focus")[0]
+        K = self.n_parameters
+        upper = np.triu_indices(K)
+        packed = np.zeros((len(self.otf), len(upper[0]) + K + 3))
+        for g in range(len(packed)):
+            jac = self.dmtf[g, :, plane].reshape(K, -1).T  # (outputs, K)
+            residual = (target - self.mtf[g, plane]).reshape(-1)
+            if not np.all(np.isfinite(jac)) or not np.all(np.isfinite(residual)):
+                continue
+            normal = jac.T @ jac / len(residual)
+            a = normal + damping * np.diag(np.diag(normal))
+            packed[g, :len(upper[0])] = a[upper]
+            packed[g, len(upper[0]):len(upper[0]) + K] = jac.T @ residual / len(residual)
+            packed[g, -3] = len(residual)
+        return solve_normal_equations(packed, K)[0]
 
 
 class EnclosedEnergy:
@@ -2606,7 +2694,9 @@ class Sensitivity:
 
     With a ``SourceMotion`` or a ``WavelengthChange`` among the parameters also ``slopes``: device (K, 3, n_selected)
     float64, the derivative of the selected rows' unit directions, NaN where ``jacobian`` is; on top of both
-    ``focus_gradient()``, ``transfer()`` and ``effective_focal_length()``.  ``slopes`` is None otherwise.
+    ``focus_gradient()``, ``transfer()`` and ``effective_focal_length()``; so also with ``sensitivity(slopes=True)``,
+    whatever the parameters are, and then ``mtf_gradient()`` gives d(OTF)/d(parameter) through focus.  ``slopes`` is None
+    otherwise.
 
     With ``sensitivity(wavefront=)`` also, against that ``Wavefront``'s reference sphere held fixed (device tensors in the
     order of ``rows()``, NaN for a ray that misses the sphere or could not be followed): ``dfield`` (K, n_selected), the
@@ -2714,8 +2804,65 @@ class Sensitivity:
 
     def _need_slopes(self, what):
         if self.slopes is None:
-            raise ValueError(f"{what}: this Sensitivity has no slopes (they come with a SourceMotion or a WavelengthChange "
-                             "among the parameters)")
+            raise ValueError(f"{what}: this Sensitivity has no slopes (they come with sensitivity(slopes=True), or with a "
+                             "SourceMotion or a WavelengthChange among the parameters)")
+
+    def mtf_gradient(self, frequencies, *, azimuths=(0.0, 90.0), focus=(0.0,), reference="fixed", centre=None, axis=None,
+                     basis=None):
+        """d(OTF)/d(parameter) of the geometric MTF of the selected rows, per group, at every focus shift, azimuth and
+        frequency, from this one trace: an ``MTFGradient``.  Needs ``slopes`` (``sensitivity(slopes=True)``): the MTF is
+        taken through focus, on planes a ray reaches as a straight line, so the derivative of its direction enters.
+
+        ``frequencies``, ``azimuths``, ``focus``, ``axis`` and ``basis`` as in ``DeviceFrame.mtf``; the weights are the
+        ``sensitivity()`` call's.  A ray is summed if ``mtf()`` would keep it and its ``jacobian`` and ``slopes`` are
+        finite for every parameter -- one set of rays for all parameters; the others are counted (``n_missed``,
+        ``n_unfollowed``) and contribute nothing.  ``centre``: None for the weighted centroid of the rays summed, or a
+        point, or a (groups, 3) array.  ``reference="fixed"``: the centre is held fixed under the parameter, the
+        kernel's own numbers (``prt_frame_mtf_gradient``; include/prt.h states the formulas).  ``"centroid"``: the
+        centre follows the group's centroid, composed on the host as
+        ``dotf_k + 2 pi i (k.(dC_k.e1, dC_k.e2)) otf + (dC_k.a) dotf_dfocus`` -- |OTF|, and so ``dmtf``, is the same
+        under both; the phase is not.  The result is the derivative at fixed path, as ``jacobian`` is."""
+        self._need_slopes("mtf_gradient")
+        import torch
+
+        from . import engine
+
+        if reference not in ("fixed", "centroid"):
+            raise ValueError('reference: "fixed" or "centroid"')
+        nu = _mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True)
+        theta = _mtf_values(azimuths, "azimuths", 16, "finite, in degrees")
+        planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
+        axes = pupil_axes(axis, basis)
+        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        dev = rows.device
+        n_groups, K, n_rows, n_selected = len(first) - 1, self.n_parameters, rows.shape[1], int(self._selected.shape[0])
+        centres = None
+        if centre is not None:
+            centres = torch.as_tensor(np.asarray(centre.cpu() if hasattr(centre, "cpu") else centre, dtype=float))
+            if centres.shape == (3,):
+                centres = centres.expand(n_groups, 3)
+            if tuple(centres.shape) != (n_groups, 3):
+                raise ValueError(f"centre: None, a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
+            centres = centres.to(dev, torch.float64).contiguous()
+        shape = (len(planes), len(theta), len(nu))
+        otf = torch.empty((n_groups,) + shape + (2,), dtype=torch.float64, device=dev)
+        dotf = torch.empty((n_groups, K + 1) + shape + (2,), dtype=torch.float64, device=dev)
+        record = torch.empty((n_groups, 7 + 3 * K), dtype=torch.float64, device=dev)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_mtf_gradient_workspace_bytes(n_selected, n_groups, K, len(nu),
+                                                                                        len(theta), len(planes)))),
+                           dtype=torch.uint8, device=dev)
+        jacobian, slopes = self.jacobian.contiguous(), self.slopes.contiguous()
+        engine._check(lib.prt_frame_mtf_gradient(
+            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), n_rows,
+            self._selected.data_ptr() if n_selected else None, n_selected, first.ctypes.data, n_groups,
+            -1 if weights is None else _INDEX[weights], jacobian.data_ptr() if n_selected else None,
+            slopes.data_ptr() if n_selected else None, K, None if centres is None else centres.data_ptr(),
+            axes.ctypes.data, nu.ctypes.data, len(nu), theta.ctypes.data, len(theta), planes.ctypes.data, len(planes),
+            otf.data_ptr(), dotf.data_ptr(), record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        pair, dpair = engine.to_host(otf), engine.to_host(dotf)
+        return MTFGradient(pair[..., 0] + 1j * pair[..., 1], dpair[..., 0] + 1j * dpair[..., 1],
+                           engine.to_host(record).copy(), nu, theta, planes, axes, self.parameters, reference)
 
     def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
         """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the
