@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient and their workspace functions.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient and their workspace functions (prt_frame_psf_gradient_workspace_bytes among them).  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -820,6 +820,64 @@ int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld, int64_t n
                            const double* axes, const double* frequencies, int n_frequencies, const double* azimuths_deg,
                            int n_azimuths, const double* focus, int n_focus, double* otf_out, double* dotf_out,
                            double* record_out, void* workspace, void* stream);
+
+/* PSF sensitivities: d(PSF)/d(parameter) and d(Strehl)/d(parameter) of the diffraction PSF above, from the rows and the
+ * wavefront outputs of one prt_frame_opd_sensitivity (or prt_frame_launch_sensitivity) call, without a re-trace.  The
+ * definitions of prt_frame_psf and of prt_frame_opd_sensitivity (below) are reused unchanged.
+ *
+ * Definitions.
+ * Rays: the selected rows of the sensitivity call, in its order (selected DEVICE n_selected int64 row numbers, ordered by
+ *   group, generation and id; group_first HOST n_groups + 1 int64).  opd and pupil are that call's opd_out and pupil_out;
+ *   group g's R and rho come from wavefront_groups (HOST (n_groups, 6), [3] and [5]); w is weight_column of rows (-1:
+ *   ones), the wavelength the row's wavelength column.
+ * Rays kept: a ray is kept if prt_frame_psf would keep it (OPD and pupil point finite, w finite and >= 0) and its 3 K
+ *   derivative inputs are finite.  There is one kept set for all K.  The others are counted per (group, wavelength):
+ *   n_missed by the PSF's rule, n_unfollowed by the second; they contribute exactly nothing.
+ * Staged per ray, s = 1 / lambda_w: p = pupil * rho, c = (OPD - R) s, a = sqrt(w).  Per parameter k, from the plain
+ *   arrays dphase (x_k) and dpoint (y_k, two components; NULL: zeros): e_k = x_k s, q_k = y_k rho s.  With x = dopd and
+ *   y = dpupil the result is the exact derivative of the sum prt_frame_psf forms on the changed system, the sphere
+ *   held fixed, each ray followed; with x = dfield and y = 0 it is the wavefront change at fixed pupil points.
+ * At pixel (u, v): d = sqrt(R^2 + u^2 + v^2 - 2 (u p1 + v p2)), phi = c + d s, and
+ *   g_k = e_k - (u q_k1 + v q_k2) / d, in cycles per unit parameter (d(phi)/dp_k: d moves with the ray's point p).
+ * Sums over the kept rays of wavelength l:
+ *   U_l     = s sum a exp(2 pi i phi)                 dU_l,k = 2 pi i s sum a g_k exp(2 pi i phi)
+ *   I       = sum_l |U_l|^2 / D_g                     dI_k   = 2 sum_l Re(conj(U_l) dU_l,k) / D_g
+ *   D_g     = sum_l (s_l sum a)^2, which does not depend on the parameter (the weights are held).
+ * Strehl and dStrehl_k are I and dI_k at (u, v) = (0, 0), where d = R and g_k = e_k, summed with fp64 sincospi in a
+ *   fixed tree, as prt_frame_psf's Strehl ratio is, whether or not P is a pixel.
+ * Accuracy: the phasor is prt_frame_psf's (eps above); a derivative carries, beside eps times |g_k|, the roundings of
+ *   g_k itself: tests/psf_gradient_reference.py derives |dU~ - dU| <= 2 pi s [sum a |g_k| eps + sum a gamma_k] and
+ *   states what is counted.
+ *
+ * prt_frame_psf_gradient: rows DEVICE, ld, n_rows as above; dphase DEVICE (K, n_selected), dpoint DEVICE (K, 2, n_selected)
+ * or NULL, K in [1, 16]; wavelengths_um, world_unit_um, nx, ny, du, dv, centre_uv as prt_frame_psf takes them, with its
+ * refusals; n_groups * n_wavelengths <= 16383; n_groups * n_wavelengths * nx * ny * 17 * 16 bytes (the slab of a call with
+ * 16 parameters, whatever K is) may not pass the 256 MiB cap.  A selected row number outside [0, n_rows), or a selected
+ * row of a wavelength that is not listed: PRT_ERR_ARG once the passes have run.
+ * Out, DEVICE, overwritten: amplitude_out (n_groups, n_wavelengths, nx, ny, 2), U_l; damplitude_out (n_groups, K,
+ * n_wavelengths, nx, ny, 2), dU_l,k; image_out (n_groups, n_wavelengths, nx, ny), the bucket's share of I;
+ * dimage_out (n_groups, K, n_wavelengths, nx, ny); strehl_out (n_groups, 1 + K): Strehl, then dStrehl_k; record_out
+ * (n_groups, n_wavelengths, 5): rays kept, n_missed, n_unfollowed, sum a, (s sum a)^2.  A group without kept rays is NaN.
+ * workspace: prt_frame_psf_gradient_workspace_bytes(n_selected, n_groups, K, n_wavelengths) device bytes (-1 for arguments
+ * the call would refuse).
+ * Passes: a stable counting sort of an index of the selected rows into (group, wavelength) buckets; the staged rays and,
+ * gathered through the index, the staged parameters; the fp64 Strehl sums; the Huygens sum, a grid of (pixel tile, ray
+ * slice, bucket x chunk of at most 4 parameters) workgroups that read the ray tile and its parameter chunk through LDS,
+ * the phase path of prt_frame_psf run once per (ray, pixel); the fold in slice order.  The slice count follows n_selected,
+ * the pixel count, the bucket count and the device's CU count, a slice's rays its bucket's kept count -- never n_rows or
+ * the frame's other rows, never K --, a parameter's arithmetic does not depend on the others in the call, and there are
+ * no floating-point atomics: every output is the same, bit for bit, on every run, on any frame that holds the same
+ * selected rows, and for a parameter alone or among sixteen (where the kept set is the same).  All arguments are checked
+ * before a device is touched.  Stream-ordered; the call reads one status word back and so returns when the stream has
+ * reached its end. */
+int64_t prt_frame_psf_gradient_workspace_bytes(int64_t n_selected, int n_groups, int n_parameters, int n_wavelengths);
+int prt_frame_psf_gradient(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                           int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                           const double* opd, const double* pupil, const double* wavefront_groups, const double* dphase,
+                           const double* dpoint, int n_parameters, const double* wavelengths_um, int n_wavelengths,
+                           double world_unit_um, int nx, int ny, double du, double dv, const double* centre_uv,
+                           double* amplitude_out, double* damplitude_out, double* image_out, double* dimage_out,
+                           double* strehl_out, double* record_out, void* workspace, void* stream);
 
 /* Ray-aberration curves of the frame: each ray's row at a surface joined by ray id with the row where the ray was
  * launched (examples/lens_design.ipynb cells 12-13 join the two cuts of the frame with isin(id)), its transverse and

@@ -210,6 +210,10 @@ def _declare(lib):
         "prt_frame_mtf_gradient_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_int, c_int]),
         "prt_frame_mtf_gradient": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_int, c_p,
                                            c_p, c_p, c_int, c_p, c_int, c_p, c_int, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_psf_gradient_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+        "prt_frame_psf_gradient": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p,
+                                           c_p, c_int, c_p, c_int, c_d, c_int, c_int, c_d, c_d, c_p, c_p, c_p, c_p, c_p,
+                                           c_p, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -244,6 +248,7 @@ EXPORTED_SYMBOLS = (
     "prt_frame_opd_sensitivity_workspace_bytes", "prt_frame_opd_sensitivity",
     "prt_frame_launch_sensitivity_workspace_bytes", "prt_frame_launch_sensitivity",
     "prt_frame_mtf_gradient_workspace_bytes", "prt_frame_mtf_gradient",
+    "prt_frame_psf_gradient_workspace_bytes", "prt_frame_psf_gradient",
 )
 
 

@@ -1449,7 +1449,8 @@ class DeviceFrame:
                 out["sums"] = engine.to_host(out["sums"]).copy()
                 out["wavefront"] = wavefront
             return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
-                               wave=out, launch=dict(slopes=directions, rows=rows, weights=weights, group_first=group_first))
+                               wave=out, launch=dict(slopes=directions, rows=rows, weights=weights, group_first=group_first,
+                                                     written=self.written))
         if wavefront is not None:
             J = wavefront.terms
             opl = self._optical_path()
@@ -1473,7 +1474,9 @@ class DeviceFrame:
                 work.data_ptr(), tail[12]))
             out["sums"] = engine.to_host(out["sums"]).copy()
             return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
-                               wave=dict(out, wavefront=wavefront))
+                               wave=dict(out, wavefront=wavefront),
+                               launch=dict(slopes=None, rows=rows, weights=weights, group_first=group_first,
+                                           written=self.written))
         if design:
             engine._check(lib.prt_frame_design_sensitivity(*head, linear.ctypes.data, rates.ctypes.data,
                                                            index_ids.ctypes.data, index_first.ctypes.data, *tail))
@@ -1865,6 +1868,78 @@ class MTFGradient:
         for g in range(len(packed)):
             jac = self.dmtf[g, :, plane].reshape(K, -1).T  # (outputs, K)
             residual = (target - self.mtf[g, plane]).reshape(-1)
+            if not np.all(np.isfinite(jac)) or not np.all(np.isfinite(residual)):
+                continue
+            normal = jac.T @ jac / len(residual)
+            a = normal + damping * np.diag(np.diag(normal))
+            packed[g, :len(upper[0])] = a[upper]
+            packed[g, len(upper[0]):len(upper[0]) + K] = jac.T @ residual / len(residual)
+            packed[g, -3] = len(residual)
+        return solve_normal_equations(packed, K)[0]
+
+
+class PSFGradient:
+    """What ``Sensitivity.psf_gradient`` returns (numpy arrays), G groups, K parameters, L wavelengths.  ``image``
+    (G, nx, ny) and ``image_by_wavelength`` (G, L, nx, ny): the normalised Huygens image over the rays kept, indexed as
+    ``PSF.image`` is; ``dimage`` (G, K, nx, ny) and ``dimage_by_wavelength`` (G, K, L, nx, ny): its derivative per unit
+    of parameter k; ``amplitude`` (G, L, nx, ny) and ``damplitude`` (G, K, L, nx, ny), complex: U_l and dU_l,k of
+    include/prt.h (not normalised); ``strehl`` (G) and ``dstrehl`` (G, K): the image and its derivative at P; ``u`` (nx)
+    and ``v`` (ny): the pixel centres; per group and wavelength ``n_rays`` (rays kept), ``n_missed`` (left out by the
+    PSF's rule) and ``n_unfollowed`` (a derivative that is not finite); ``record`` is the device's (G, L, 5) block;
+    ``follow``: "ray" or "pupil"; ``wavelengths`` (micrometres), ``parameters``, ``wavefront``.  A group without kept
+    rays is NaN throughout."""
+
+    def __init__(self, amplitude, damplitude, image_by_wavelength, dimage_by_wavelength, strehl, record, wavelengths,
+                 world_unit_um, pixels, pixel_size, centre, f_number, wavefront, parameters, follow):
+        self.amplitude, self.damplitude = np.asarray(amplitude), np.asarray(damplitude)
+        self.image_by_wavelength, self.dimage_by_wavelength = image_by_wavelength, dimage_by_wavelength
+        self.image, self.dimage = image_by_wavelength.sum(axis=1), dimage_by_wavelength.sum(axis=2)
+        strehl = np.asarray(strehl, dtype=float)
+        self.strehl, self.dstrehl = strehl[:, 0], strehl[:, 1:]
+        self.record, self.wavelengths = np.asarray(record, dtype=float), np.asarray(wavelengths, dtype=float)
+        self.world_unit_um, self.pixel_size, self.centre = world_unit_um, pixel_size, centre
+        self.f_number, self.wavefront, self.follow = f_number, wavefront, follow
+        self.parameters = tuple(parameters)
+        self.n_parameters = len(self.parameters)
+        nx, ny = pixels
+        self.u = centre[0] + (np.arange(nx) - 0.5 * (nx - 1)) * pixel_size[0]
+        self.v = centre[1] + (np.arange(ny) - 0.5 * (ny - 1)) * pixel_size[1]
+        self.n_rays, self.n_missed, self.n_unfollowed = (self.record[:, :, k].astype(np.int64) for k in (0, 1, 2))
+
+    def to_pandas(self):
+        """One row per group: strehl, ``dstrehl_k`` per parameter k, f_number, n_rays, n_missed, n_unfollowed."""
+        data = {"strehl": self.strehl}
+        for k in range(self.n_parameters):
+            data[f"dstrehl_{k}"] = self.dstrehl[:, k]
+        data.update(f_number=self.f_number, n_rays=self.n_rays.sum(axis=1), n_missed=self.n_missed.sum(axis=1),
+                    n_unfollowed=self.n_unfollowed.sum(axis=1))
+        frame = pd.DataFrame(data)
+        frame.index.name = "source_id"
+        return frame
+
+    def step(self, damping=0.0, target=None):
+        """Per group the change of the parameters that brings the image closest to ``target`` to first order:
+        Gauss-Newton on the residuals ``target - image`` over the pixels with ``dimage`` as the Jacobian, the solution of
+        (N + damping diag(N)) dp = rhs through ``solve_normal_equations`` (the minimum-norm one where the pixels cannot
+        tell the parameters apart).  ``target``: a (groups, nx, ny) array, or a ``PSF`` on the same grid -- a measured
+        star image, say.  (groups, K); NaN for a group without rays."""
+        if not (np.isfinite(damping) and damping >= 0):
+            raise ValueError("damping: a number >= 0")
+        if isinstance(target, PSF):
+            if target.image.shape != self.image.shape or not (np.array_equal(target.u, self.u) and np.array_equal(target.v, self.v)):
+                raise ValueError("target: a PSF on the same groups and pixel grid (pixels, pixel_size, centre)")
+            target = target.image
+        if target is None:
+            raise ValueError("target: a (groups, nx, ny) array or a PSF on the same grid")
+        wanted = np.asarray(target, dtype=float)
+        if wanted.shape != self.image.shape:
+            raise ValueError(f"target: shape {self.image.shape} (got {wanted.shape})")
+        K = self.n_parameters
+        upper = np.triu_indices(K)
+        packed = np.zeros((len(self.image), len(upper[0]) + K + 3))
+        for g in range(len(packed)):
+            jac = self.dimage[g].reshape(K, -1).T  # (pixels, K)
+            residual = (wanted[g] - self.image[g]).reshape(-1)
             if not np.all(np.isfinite(jac)) or not np.all(np.isfinite(residual)):
                 continue
             normal = jac.T @ jac / len(residual)
@@ -2705,7 +2780,8 @@ class Sensitivity:
     about the pivot and its pupil point as the pass evaluated them.  Per group: ``opd_sums`` (the layout of include/prt.h),
     ``n_missed``, ``dzernike()``, ``wavefront_variance_gradient`` and ``rms_opd_gradient`` (groups, K): the exact
     derivatives of the sample statistic that ``Wavefront.rms`` reports (from ``dopd``, piston removed), over the rays
-    that were followed.  ``wavefront`` is the Wavefront; None, and none of these, without the argument."""
+    that were followed; ``psf_gradient()`` gives d(PSF) and d(Strehl)/d(parameter) of the diffraction image.
+    ``wavefront`` is the Wavefront; None, and none of these, without the argument."""
 
     def __init__(self, jacobian, selected, sums, pivots, centred, record, parameters, wave=None, launch=None):
         self.slopes = None if launch is None else launch["slopes"]
@@ -2863,6 +2939,93 @@ class Sensitivity:
         pair, dpair = engine.to_host(otf), engine.to_host(dotf)
         return MTFGradient(pair[..., 0] + 1j * pair[..., 1], dpair[..., 0] + 1j * dpair[..., 1],
                            engine.to_host(record).copy(), nu, theta, planes, axes, self.parameters, reference)
+
+    def psf_gradient(self, *, world_unit_um, pixels=64, pixel_size=None, centre=(0.0, 0.0), follow="ray"):
+        """d(PSF)/d(parameter) and d(Strehl)/d(parameter) of the diffraction image of the selected rows, per group, from
+        this one trace: a ``PSFGradient``.  Needs ``sensitivity(wavefront=)``: the rays, their OPD and pupil points, the
+        reference sphere (held fixed) and the weights are that call's; ``world_unit_um``, ``pixels``, ``pixel_size`` (default
+        lambda_min * F / 4) and ``centre`` as in ``DeviceFrame.psf``.  One HIP pass (``prt_frame_psf_gradient``;
+        include/prt.h states the formulas): the Huygens sum of ``psf()`` with, per parameter, the derivative of every
+        ray's phase carried along.
+
+        ``follow="ray"``: every ray is followed, its OPD changing by ``dopd`` and its point on the sphere by ``dpupil``
+        -- the exact derivative of the sum ``psf()`` forms on the changed system with the sphere held fixed, the
+        counterpart of ``rms_opd_gradient``.  ``follow="pupil"``: the wavefront change ``dfield`` at fixed pupil points,
+        the sample positions held.  A ray is summed if ``psf()`` would keep it and its derivatives are finite for every
+        parameter -- one set of rays for all parameters; the others are counted (``n_missed``, ``n_unfollowed``) and
+        contribute nothing.  A ``WavelengthChange`` among the parameters is refused: it moves a ray between wavelengths.
+        The weights are held, and so is every ray's path, as ``jacobian`` holds it."""
+        self._need_wave("psf_gradient")
+        import torch
+
+        from . import engine
+
+        if follow not in ("ray", "pupil"):
+            raise ValueError('follow: "ray" or "pupil"')
+        if any(isinstance(m, WavelengthChange) for m in self.parameters):
+            raise ValueError("psf_gradient: a WavelengthChange among the parameters moves a ray between wavelengths; "
+                             "the PSF's derivative is taken for the other kinds of parameter")
+        unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
+        nx, ny = _pixel_counts(pixels)
+        step = None
+        if pixel_size is not None:
+            pair = np.asarray(pixel_size, dtype=float).reshape(-1)
+            pair = np.repeat(pair, 2) if pair.size == 1 else pair
+            if pair.shape != (2,) or not np.all(np.isfinite(pair)) or not np.all(pair > 0):
+                raise ValueError(f"pixel_size: a positive number or (du, dv), or None (got {pixel_size!r})")
+            step = (float(pair[0]), float(pair[1]))
+        uv0 = np.asarray(centre, dtype=float)
+        if uv0.shape != (2,) or not np.all(np.isfinite(uv0)):
+            raise ValueError(f"centre: (u0, v0), finite (got {centre!r})")
+        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        dev = rows.device
+        n_groups, K, n_rows, n_selected = len(first) - 1, self.n_parameters, rows.shape[1], int(self._selected.shape[0])
+        wave = self.wavefront
+        written = self._launch.get("written")
+        if written is not None and _INDEX["wavelength"] not in written:
+            raise ValueError("psf_gradient: the frame was recorded without the wavelength column (RecordPlan(columns=...))")
+        if not n_selected:
+            raise ValueError("psf_gradient: no row is selected at this surface")
+        values = rows[_INDEX["wavelength"]][self._selected].unique().cpu().numpy().astype(np.float64)
+        if not np.all(np.isfinite(values) & (values > 0)):
+            raise ValueError("psf_gradient: a selected row's wavelength is not finite and > 0")
+        if len(values) > 16:
+            raise ValueError(f"psf_gradient: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            f_number = np.where(np.asarray(wave.n_rays) > 0, np.asarray(wave.radius) / (2.0 * np.asarray(wave.pupil_radius)), np.nan)
+        if step is None:
+            finite = f_number[np.isfinite(f_number) & (f_number > 0)]
+            if not len(finite):
+                raise ValueError("psf_gradient: no group has rays that meet the reference sphere; give pixel_size")
+            side = float(values.min()) / unit * float(finite.min()) / 4.0
+            step = (side, side)
+        groups = np.ascontiguousarray(np.column_stack([wave.reference, wave.radius, wave.pivot, wave.pupil_radius]),
+                                      dtype=np.float64)
+        n_w = len(values)
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+        amplitude, damplitude = empty(n_groups, n_w, nx, ny, 2), empty(n_groups, K, n_w, nx, ny, 2)
+        image, dimage = empty(n_groups, n_w, nx, ny), empty(n_groups, K, n_w, nx, ny)
+        strehl, record = empty(n_groups, 1 + K), empty(n_groups, n_w, 5)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_psf_gradient_workspace_bytes(n_selected, n_groups, K, n_w))),
+                           dtype=torch.uint8, device=dev)
+        lam = np.ascontiguousarray(values, dtype=np.float64)
+        uv0 = np.ascontiguousarray(uv0)
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        dphase = (self.dopd if follow == "ray" else self.dfield).contiguous()
+        dpoint = self.dpupil.contiguous() if follow == "ray" else None
+        opd, pupil = self.opd.contiguous(), self.pupil.contiguous()
+        engine._check(lib.prt_frame_psf_gradient(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, self._selected.data_ptr(), n_selected,
+            first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], opd.data_ptr(), pupil.data_ptr(),
+            groups.ctypes.data, dphase.data_ptr(), None if dpoint is None else dpoint.data_ptr(), K, lam.ctypes.data, n_w,
+            unit, nx, ny, step[0], step[1], uv0.ctypes.data, amplitude.data_ptr(), damplitude.data_ptr(), image.data_ptr(),
+            dimage.data_ptr(), strehl.data_ptr(), record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        pair, dpair = engine.to_host(amplitude), engine.to_host(damplitude)
+        return PSFGradient(pair[..., 0] + 1j * pair[..., 1], dpair[..., 0] + 1j * dpair[..., 1],
+                           engine.to_host(image).copy(), engine.to_host(dimage).copy(), engine.to_host(strehl).copy(),
+                           engine.to_host(record).copy(), values, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])),
+                           f_number, wave, self.parameters, follow)
 
     def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
         """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the

@@ -1,0 +1,302 @@
+"""An extended-precision reference of the PSF sensitivities (d(PSF)/d(parameter) and d(Strehl)/d(parameter): the
+definitions of include/prt.h under prt_frame_psf_gradient), the error budget the kernels of prt_psf_gradient.hpp are held
+to, Python copies of the new partition rules and the inputs the tests run on.  It builds on tests/diffraction_reference.py
+(``psf_case``, ``huygens_amplitude``, ``phasor``, ``psf_epsilon``, ``psf_bound``, ``strehl_eta``) and changes nothing there.
+
+The formulas, per group g (R, rho) and wavelength l (s = 1 / lambda_w), over the rays kept:
+    p = pupil rho,  c = (OPD - R) s,  a = sqrt(w);  per parameter k  e_k = x_k s,  q_k = y_k rho s
+    d = sqrt(R^2 + u^2 + v^2 - 2 (u p1 + v p2)),  phi = c + d s,  g_k = e_k - (u q_k1 + v q_k2) / d
+    U_l = s sum a exp(2 pi i phi)                 dU_l,k = 2 pi i s sum a g_k exp(2 pi i phi)
+    I = sum_l |U_l|^2 / D_g                       dI_k = 2 sum_l Re(conj(U_l) dU_l,k) / D_g,   D_g = sum_l (s_l sum a)^2
+    Strehl, dStrehl_k: I, dI_k at (u, v) = (0, 0), where d = R and g_k = e_k.
+A ray is kept if the PSF keeps it (OPD, pupil finite; w finite and >= 0) and x_k, y_k are finite for every k.
+
+What counts as an input: opd, pupil, x_k (``dphase``), y_k (``dpoint``), R, rho, the weight and wavelength columns,
+1 / lambda_w as the library forms it and the pixel centres.
+
+The budget, u = 2^-53 (``gradient_reference`` evaluates it term by term).
+  U keeps the PSF's: |U~ - U| <= s eps sum a, eps = ``psf_epsilon`` per pixel (the phase path is k_psf_huygens's).
+  dU, per pixel and parameter:
+      |dU~_k - dU_k| <= 2 pi s [ sum a |g_k| eps + sum a gamma_k ]
+    The first term is the phasor's error times the factor it multiplies.  gamma_k bounds the roundings of g_k itself, to
+    first order, each relative to the magnitude it acts on, with T = (|u q_k1| + |v q_k2|) / d:
+      e_k = x_k s: 1 of |e_k|;  q_k = (y_k rho) s: 2 of T;
+      -u / d = (0.5 mu) inverse: the pixel centre one ulp of u, 2 (diffraction_reference counts the same ulp); d^2 is
+        within 5 kappa u of the exact one (diffraction_reference: k0's three roundings and the two fmas), kappa =
+        (k0 + 2 rho r) / (k0 - 2 rho r), so 1 / d moves by 2.5 kappa; ``inverse`` is one Newton step from h = 0.5 /
+        sqrt(x) of the Goldschmidt iteration (relative error under 2^-44 before the step, its square after it) against
+        the finished root, itself within an ulp (2): the step's two fmas 2 more, 4; the product 1: (2.5 kappa + 7) of T;
+      g_k = fma(hu, q_k1, fma(hv, q_k2, e_k)): the inner fma 1 of (|e_k| + T), the outer 1 of (|e_k| + T);
+      a g_k: 1 of |g_k| <= |e_k| + T; and 1 more of each for the terms of second order.
+    gamma_k = u [5 |e_k| + (2.5 kappa + 13) T].
+  dI: with A = |U~ - U| and B_k = |dU~_k - dU_k| per bucket,
+      |dI~_k - dI_k| <= 2 sum_l (A |dU_k| + |U| B_k + A B_k) / D_g.
+  Strehl keeps ``strehl_bound``.  dStrehl_k = 4 pi sum_l s^2 (S Ec - C Es) / D_g with C + i S = sum a exp(2 pi i OPD s) and
+  Ec + i Es = sum a e_k exp(2 pi i OPD s), all four summed in fp64 with sincospi: a phasor is within eta
+  (``strehl_eta``), a term a e_k (cos, sin) carries two more roundings (e_k and the product), and |C|, |S| <= sum a,
+  |Ec|, |Es| <= sum a |e_k|, so
+      |dStrehl~_k - dStrehl_k| <= 4 pi sum_l s^2 (2 (eta + 2 u) + (2 depth + 12) u) (sum a) (sum a |e_k|) / D_g.
+  What the budget leaves to EPS_TRIG's margin, as the PSF's does: the fp64 accumulation of the sums (at most
+  rays-per-slice times u of sum a |g_k|), the fold and the normalisation (a few u).
+"""
+import math
+import os
+import re
+from types import SimpleNamespace
+
+import numpy as np
+
+import diffraction_reference as R
+import mtf_gradient_reference as M
+
+LD = R.LD
+MAX_PARAMETERS = 16
+
+
+def kernel_constants():
+    """The static const ints of prt_psf_gradient.hpp (kPsfgParams, kPsfgMinSlice, ...)."""
+    found = {}
+    text = open(os.path.join(R.ROOT, "pyrayt_amd", "csrc", "prt_psf_gradient.hpp")).read()
+    for key, value in re.findall(r"static const (?:int|size_t) (k\w+) = ([^;]+);", text):
+        value = re.sub(r"(\d+)u\b", r"\1", value)
+        try:
+            found[key] = int(eval(value, {"__builtins__": {}}, dict(found)))
+        except (NameError, SyntaxError, TypeError):
+            pass  # (not a plain constant)
+    return SimpleNamespace(**found)
+
+
+K = kernel_constants()
+QUANTITIES = MAX_PARAMETERS + 1  # (kPsfgQuantities: the slab is sized for 16 parameters whatever K is)
+# Python copies of lines of prt_frame_psf_gradient, held to the header's text by tests/test_host_psf_gradient.py
+HOST_RULES = {
+    "prt_psf_gradient.hpp": (
+        "enum { PSFG_MAX_PARAMETERS = 16, PSFG_RECORD = 5, PSFG_BAD_WAVELENGTH = 1, PSFG_BAD_ROW = 2 };",
+        "static const int kPsfgQuantities = PSFG_MAX_PARAMETERS + 1;",
+        "int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);",
+        "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_selected / (buckets * kPsfgMinSlice)));",
+        "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * kPsfgQuantities * 16)));",
+        "slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));",
+        "const int whole = K / kPsfgParams, rest = K - whole * kPsfgParams;",
+        "if (rest > 2) sum(std::integral_constant<int, 4>(), 1, whole * kPsfgParams);",
+        "else if (rest == 2) sum(std::integral_constant<int, 2>(), 1, whole * kPsfgParams);",
+        "else if (rest == 1) sum(std::integral_constant<int, 1>(), 1, whole * kPsfgParams);",
+        "for (int64_t base = lo; base < hi; base += kPsfBlock) {"),
+}
+
+
+def slices(n_selected, buckets, npix, cus):
+    """The ray slices prt_frame_psf_gradient picks: they follow the selection's size, never n_rows and never K."""
+    tiles = -(-npix // R.K.kPsfTile)
+    s = (4 * cus + tiles * buckets - 1) // (tiles * buckets)
+    s = min(s, max(1, n_selected // (buckets * K.kPsfgMinSlice)))
+    s = min(s, R.K.kPsfSlabBytes // (buckets * npix * QUANTITIES * 16))
+    return max(1, min(s, R.K.kPsfMaxSlices))
+
+
+def parameter_chunks(n_parameters):
+    """The k_psfg_huygens launches of a call: (instantiation P, chunks of it, first parameter)."""
+    whole, rest = divmod(n_parameters, K.kPsfgParams)
+    out = [(K.kPsfgParams, whole, 0)] if whole else []
+    if rest:
+        out.append((4 if rest > 2 else rest, 1, whole * K.kPsfgParams))
+    return out
+
+
+# ---- the reference --------------------------------------------------------------------------------------------------------
+def kept_rays(inp, dphase, dpoint):
+    """(passes the PSF's rule, every derivative finite), per ray."""
+    usable = np.isfinite(inp.opd) & np.all(np.isfinite(inp.pupil), axis=1) & (inp.weight >= 0) & np.isfinite(inp.weight)
+    followed = np.all(np.isfinite(dphase), axis=0)
+    if dpoint is not None:
+        followed &= np.all(np.isfinite(dpoint), axis=(0, 1))
+    return usable, followed
+
+
+def gradient_reference(inp, dphase, dpoint=None, slices=1):
+    """The formulas of the module docstring on ``inp`` (diffraction_reference.psf_inputs, the rays in the selection's
+    order), ``dphase`` (K, n) and ``dpoint`` (K, 2, n) or None for zeros.  A namespace, G groups, L wavelengths, K
+    parameters, longdouble: amplitude (re, im) (G, L, nx, ny) and damplitude (re, im) (G, K, L, nx, ny);
+    image_by_wavelength, image, dimage_by_wavelength, dimage, strehl (G), dstrehl (G, K); float64: amplitude_bound,
+    damplitude_bound, bound_by_wavelength, bound, dbound_by_wavelength, dbound, strehl_bound, dstrehl_bound; n_rays,
+    n_missed, n_unfollowed (G, L).  A group without kept rays is NaN."""
+    dphase = np.asarray(dphase, dtype=np.float64)
+    dpoint = None if dpoint is None else np.asarray(dpoint, dtype=np.float64)
+    n_par = len(dphase)
+    nx, ny = len(inp.u), len(inp.v)
+    uu, vv = (x.ravel() for x in np.meshgrid(inp.u, inp.v, indexing="ij"))
+    npix = nx * ny
+    G, L = inp.n_groups, len(inp.wavelengths)
+    nan = lambda *shape, dtype=LD: np.full(shape, np.nan, dtype=dtype)  # noqa: E731
+    are, aim, abound = nan(G, L, npix), nan(G, L, npix), nan(G, L, npix, dtype=float)
+    dre, dim, dabound = nan(G, n_par, L, npix), nan(G, n_par, L, npix), nan(G, n_par, L, npix, dtype=float)
+    image, bound = nan(G, L, npix), nan(G, L, npix, dtype=float)
+    dimage, dbound = nan(G, n_par, L, npix), nan(G, n_par, L, npix, dtype=float)
+    strehl, strehl_bound = nan(G), nan(G, dtype=float)
+    dstrehl, dstrehl_bound = nan(G, n_par), nan(G, n_par, dtype=float)
+    n_rays, n_missed, n_unfollowed = (np.zeros((G, L), dtype=np.int64) for _ in range(3))
+    usable, followed = kept_rays(inp, dphase, dpoint)
+    U, V = uu.astype(LD)[:, None], vv.astype(LD)[:, None]
+    r_pix = np.hypot(uu, vv)
+    for g in range(G):
+        radius, rho = float(inp.radius[g]), float(inp.rho[g])
+        parts = []
+        for l, lam in enumerate(inp.wavelengths):
+            mine = (inp.group == g) & (inp.wavelength == lam)
+            m = mine & usable & followed
+            n_rays[g, l], n_missed[g, l] = int(m.sum()), int((mine & ~usable).sum())
+            n_unfollowed[g, l] = int((mine & usable & ~followed).sum())
+            s = R.inverse_wavelength(lam, inp.unit)
+            S, Rr = LD(s), LD(radius)
+            p1, p2 = (inp.pupil[m, c] * rho for c in (0, 1))  # (fp64, as k_psf_stage forms them)
+            opd, a = inp.opd[m], np.sqrt(inp.weight[m])
+            A = a.astype(LD)
+            e = dphase[:, m].astype(LD) * S                                                    # (K, n)
+            q = np.zeros((n_par, 2, int(m.sum())), dtype=LD) if dpoint is None else dpoint[:, :, m].astype(LD) * LD(rho) * S
+            re, im = R.huygens_amplitude(p1, p2, opd, a, radius, s, uu, vv)
+            dsum = np.zeros((2, n_par, npix), dtype=LD)
+            weight_g, weight_gamma = np.zeros((n_par, npix)), np.zeros((n_par, npix))
+            P1, P2, O = (x.astype(LD)[None, :] for x in (p1, p2, opd))
+            k0, cross = radius * radius + r_pix * r_pix, 2.0 * rho * r_pix
+            kappa = (k0 + cross) / np.maximum(k0 - cross, 1e-300) if int(m.sum()) else np.ones(npix)
+            for lo, hi in R._chunks(npix, max(1, int(m.sum()) * (n_par + 2))):
+                if not int(m.sum()):
+                    break
+                quad = U[lo:hi] * U[lo:hi] + V[lo:hi] * V[lo:hi] - 2 * (U[lo:hi] * P1 + V[lo:hi] * P2)
+                d = np.sqrt(Rr * Rr + quad)
+                cs, sn = R.phasor((O + quad / (d + Rr)) * S)
+                for k in range(n_par):
+                    t1, t2 = U[lo:hi] * q[k, 0][None, :] / d, V[lo:hi] * q[k, 1][None, :] / d
+                    gk = e[k][None, :] - t1 - t2
+                    dsum[0, k, lo:hi] = -(A * gk * sn).sum(axis=1)  # 2 pi i a g (c + i sn) = 2 pi a g (-sn + i c)
+                    dsum[1, k, lo:hi] = (A * gk * cs).sum(axis=1)
+                    T = (np.abs(t1) + np.abs(t2)).astype(np.float64)
+                    weight_g[k, lo:hi] = (a * np.abs(gk.astype(np.float64))).sum(axis=1)
+                    weight_gamma[k, lo:hi] = R.U64 * (a * (5.0 * np.abs(e[k].astype(np.float64))[None, :]
+                                                           + (2.5 * kappa[lo:hi, None] + 13.0) * T)).sum(axis=1)
+            wave = R.phasor(opd.astype(LD) * S)
+            c0, s0 = (A * wave[0]).sum(), (A * wave[1]).sum()
+            ec, es = (A * e * wave[0]).sum(axis=1), (A * e * wave[1]).sum(axis=1)
+            opd_max = float(np.abs(opd).max()) if len(opd) else 0.0
+            eps = R.psf_epsilon(radius, s, rho, opd_max, uu, vv) if len(opd) else np.zeros(npix)
+            parts.append(SimpleNamespace(s=s, re=re, im=im, dsum=dsum, sum_a=A.sum(), eps=eps, weight_g=weight_g,
+                                         weight_gamma=weight_gamma, c0=c0, s0=s0, ec=ec, es=es, opd_max=opd_max,
+                                         rays=int(m.sum()), sum_ae=(A * np.abs(e)).sum(axis=1)))
+        den = sum((LD(p.s) * p.sum_a) ** 2 for p in parts)
+        if not n_rays[g].sum() or not den > 0:
+            continue
+        strehl[g], strehl_bound[g], dstrehl[g], dstrehl_bound[g] = 0, 0, 0, 0
+        for l, p in enumerate(parts):
+            S = LD(p.s)
+            share = float((S * p.sum_a) ** 2 / den)
+            are[g, l], aim[g, l] = S * p.re, S * p.im
+            abound[g, l] = p.s * p.eps * float(p.sum_a)
+            image[g, l] = (are[g, l] ** 2 + aim[g, l] ** 2) / den
+            bound[g, l] = R.psf_bound(image[g, l], share, p.eps)
+            dre[g, :, l], dim[g, :, l] = R.TWO_PI * S * p.dsum[0], R.TWO_PI * S * p.dsum[1]
+            dabound[g, :, l] = 2 * math.pi * p.s * (p.weight_g * p.eps[None, :] + p.weight_gamma)
+            dimage[g, :, l] = 2 * (are[g, l][None] * dre[g, :, l] + aim[g, l][None] * dim[g, :, l]) / den
+            size_u = np.hypot(are[g, l], aim[g, l]).astype(float)
+            size_du = np.hypot(dre[g, :, l], dim[g, :, l]).astype(float)
+            dbound[g, :, l] = 2 * (abound[g, l][None] * size_du + size_u[None] * dabound[g, :, l]
+                                   + abound[g, l][None] * dabound[g, :, l]) / float(den)
+            part = S ** 2 * (p.c0 ** 2 + p.s0 ** 2) / den
+            eta, depth = R.strehl_eta(radius, p.s, p.opd_max, p.rays, slices)
+            strehl[g] += part
+            strehl_bound[g] += 2 * eta * math.sqrt(float(part) * share) + eta * eta * share + (2 * depth + 10) * R.U64 * float(part)
+            dstrehl[g] += 4 * R.PI * S ** 2 * (p.s0 * p.ec - p.c0 * p.es) / den
+            dstrehl_bound[g] += (4 * math.pi * p.s ** 2 * (2 * (eta + 2 * R.U64) + (2 * depth + 12) * R.U64)
+                                 * float(p.sum_a) * p.sum_ae.astype(float) / float(den))
+    shape, dshape = (G, L, nx, ny), (G, n_par, L, nx, ny)
+    return SimpleNamespace(
+        amplitude=(are.reshape(shape), aim.reshape(shape)), amplitude_bound=abound.reshape(shape),
+        damplitude=(dre.reshape(dshape), dim.reshape(dshape)), damplitude_bound=dabound.reshape(dshape),
+        image_by_wavelength=image.reshape(shape), image=image.reshape(shape).sum(axis=1),
+        bound_by_wavelength=bound.reshape(shape), bound=bound.reshape(shape).sum(axis=1),
+        dimage_by_wavelength=dimage.reshape(dshape), dimage=dimage.reshape(dshape).sum(axis=2),
+        dbound_by_wavelength=dbound.reshape(dshape), dbound=dbound.reshape(dshape).sum(axis=2),
+        strehl=strehl, strehl_bound=strehl_bound, dstrehl=dstrehl, dstrehl_bound=dstrehl_bound,
+        n_rays=n_rays, n_missed=n_missed, n_unfollowed=n_unfollowed, n_parameters=n_par)
+
+
+def moved_inputs(inp, dphase, dpoint, k, amount):
+    """``inp`` with parameter k changed by ``amount`` to first order: OPD + amount x_k, pupil + amount y_k."""
+    pupil = inp.pupil if dpoint is None else inp.pupil + amount * dpoint[k].T
+    return R.psf_inputs(inp.group, inp.wavelength, inp.opd + amount * dphase[k], pupil, inp.weight, inp.radius, inp.rho,
+                        inp.wavelengths, inp.unit, inp.u, inp.v, inp.n_groups)
+
+
+# ---- the inputs of the tests (CPU and GPU) ----------------------------------------------------------------------------------
+def gradient_case(counts, n_parameters, *, seed=5, missed=0, unfollowed=0, tilt=None, piston=None, **psf_case):
+    """A frame of diffraction_reference.psf_case and, for its selected rows in a sensitivity pass's order (group,
+    generation, id), the designed wavefront (``inputs(u, v)``) and synthetic derivatives: dopd and dfield (K, n) of
+    about a wave per unit parameter, smooth over the pupil plus noise, dpupil (K, 2, n) of order 0.2.  ``missed``: that
+    many rays of every bucket get a NaN OPD; ``unfollowed``: that many a NaN in dopd, dfield and dpupil of parameter
+    ``n_parameters // 2`` alone.  ``tilt`` = (k, (t1, t2)): parameter k is the pure tilt dopd = -(t1 p1 + t2 p2) / R,
+    dpupil = 0; ``piston`` = k: parameter k is a constant dopd, dpupil = 0."""
+    case = R.psf_case(counts, seed=seed, **psf_case)
+    G = case.options["n_groups"]
+    rows, group = M.selection(case.frame, R.SURFACE, case.options["rays_per_source"], G)
+    n = len(rows)
+    rng = np.random.default_rng(2000 + seed)
+    in_rows = case.inputs(np.zeros(1), np.zeros(1))          # (the rays in row order)
+    to_selection = np.argsort(in_rows.group, kind="stable")  # (ids follow the row order inside a group)
+    assert np.array_equal(np.flatnonzero(case.frame[:, 5] == R.SURFACE)[to_selection], rows)
+    unit, lam = case.options["world_unit_um"], min(case.inputs(np.zeros(1), np.zeros(1)).wavelengths)
+    wave = lam / unit
+    x, y = in_rows.pupil[to_selection].T
+    with np.errstate(invalid="ignore"):
+        x, y = np.nan_to_num(x), np.nan_to_num(y)
+    dopd = np.empty((n_parameters, n))
+    dpupil = rng.normal(0.0, 0.2, (n_parameters, 2, n))
+    for k in range(n_parameters):
+        c = rng.normal(0.0, 1.0, 5)
+        dopd[k] = wave * (c[0] * x + c[1] * y + c[2] * (2 * (x * x + y * y) - 1) + c[3] * x * y + 0.2 * c[4]
+                          + 0.1 * rng.normal(size=n)) * (1 + k) ** 0.5
+    dfield = dopd + wave * 0.05 * rng.normal(size=dopd.shape)
+    rho = in_rows.rho[group]
+    radius = in_rows.radius[group]
+    if tilt is not None:
+        k, (t1, t2) = tilt
+        dopd[k] = dfield[k] = -(t1 * x * rho + t2 * y * rho) / radius
+        dpupil[k] = 0.0
+    if piston is not None:
+        dopd[piston] = dfield[piston] = 3.0 * wave
+        dpupil[piston] = 0.0
+    opd = in_rows.opd[to_selection].copy()
+    spoiled = np.zeros(n, dtype=bool)
+    wavelength = in_rows.wavelength[to_selection]
+    for g in range(G):
+        for lam_k in in_rows.wavelengths:
+            mine = np.flatnonzero((group == g) & (wavelength == lam_k))
+            pick = mine[rng.permutation(len(mine))[:missed + unfollowed]]
+            opd[pick[:missed]] = np.nan
+            spoiled[pick[missed:]] = True
+    if unfollowed:
+        dopd[n_parameters // 2, spoiled] = np.nan
+        dfield[n_parameters // 2, spoiled] = np.nan
+        dpupil[n_parameters // 2, 1, spoiled] = np.nan
+
+    def inputs(u, v):
+        base = case.inputs(u, v)
+        return R.psf_inputs(group, wavelength, opd, base.pupil[to_selection], base.weight[to_selection], base.radius,
+                            base.rho, base.wavelengths, base.unit, u, v, G)
+
+    return SimpleNamespace(frame=case.frame, rows=rows, group=group, n_groups=G, dopd=dopd, dfield=dfield, dpupil=dpupil,
+                           inputs=inputs, options=case.options, counts=case.counts, spoiled=spoiled,
+                           n_parameters=n_parameters, to_selection=to_selection)
+
+
+def deviation(got, re, im=None):
+    """|got - reference| per value, the difference taken in longdouble."""
+    if im is None:
+        return np.abs(np.asarray(got).astype(LD) - re).astype(np.float64)
+    return np.hypot(np.real(got).astype(LD) - re, np.imag(got).astype(LD) - im).astype(np.float64)
+
+
+# ray counts about the LDS tile (kPsfBlock = 256) and the slice (kPsfgMinSlice = 2048)
+SIZES = (1, 63, 64, 65, 255, 256, 257, 2047, 2048, 2049, 4097)
+# pixel grids about the tile of kPsfTile = 1024 pixels: one pixel, a small odd grid, one tile exactly, one short, two tiles
+GRIDS = ((1, 1), (3, 5), (32, 32), (33, 31), (33, 32))
+# parameters about the chunk of kPsfgParams accumulator sets
+PARAMETER_COUNTS = (1, K.kPsfgParams - 1, K.kPsfgParams, K.kPsfgParams + 1, 2 * K.kPsfgParams + 1, 16)
