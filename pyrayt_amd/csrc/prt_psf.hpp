@@ -2,17 +2,23 @@
 // section 4.5).  It builds on prt_wavefront.hpp: the rows prt_frame_wavefront selected, its OPD, pupil points and group
 // records.  Definitions: include/prt.h.
 //
-//   k_psf_count     per wave of a contiguous run of rows: how many rows the wavefront's filter selects
-//   k_psf_scan      one workgroup: the waves' output offsets (the order of the wavefront's opd_out / pupil_out)
-//   k_psf_stage     per selected row, in row order: p1, p2, c = (OPD - R) s, a = sqrt(w) and its (group, wavelength)
-//                   bucket; per wave and bucket the rays kept; rays left out counted per bucket (integer atomics)
-//   k_psf_offsets   one workgroup: each bucket's start, and each wave's offset inside each bucket
-//   k_psf_scatter   the stable counting sort: every wave writes its rays, in order, at its offsets
-//   k_psf_strehl    per (ray slice, bucket): sum a, sum a cos / sin (2 pi OPD s) in fp64, a fixed tree order
-//   k_psf_record    per group: the slices folded in order, the record, the Strehl ratio and the normalisation
-//   k_psf_huygens   per (pixel tile, ray slice, bucket): the complex amplitude sum of the slice's rays at every pixel
-//                   of the tile, the rays walked through LDS; partial sums into a slab of its own
-//   k_psf_fold      per (bucket, pixel): the slices added in slice order, |U|^2 / lambda_w^2, normalised
+// The first part is the Huygens core that every diffraction pass stands on (this one, the polarised one and the
+// sensitivities): on the host the wavelength list, the grid checks, the plan of the sort and of the slices, the scratch
+// and the status word; on the device the wavelength of a row, the rule for keeping a ray, the two ballot loops of the
+// stable counting sort, a pixel's constants, the phase path, the tree reduction and the fold of the Strehl slab.
+//
+//   k_psf_count       per wave of a contiguous run of rows: how many rows the wavefront's filter selects
+//   k_psf_scan        one workgroup: the waves' output offsets (the order of the wavefront's opd_out / pupil_out)
+//   k_psf_stage       per selected row, in row order: p1, p2, c = (OPD - R) s, a = sqrt(w) and its (group, wavelength)
+//                     bucket; per wave and bucket the rays kept; rays left out counted per bucket (integer atomics)
+//   k_psf_offsets     one workgroup: each bucket's start, and each wave's offset inside each bucket
+//   k_psf_scatter     the stable counting sort: every wave writes its rays, in order, at its offsets
+//   k_psf_strehl      per (ray slice, bucket, quantity): sum a, sum a cos / sin (2 pi OPD s) in fp64, a fixed tree order;
+//                     with K parameters, quantity 1 + k: sum a e_k cos / sin (here K = 0)
+//   k_psf_record      per group: the slices folded in order, the record, the Strehl ratio and the normalisation
+//   k_psf_huygens     per (pixel tile, ray slice, bucket): the complex amplitude sum of the slice's rays at every pixel
+//                     of the tile, the rays walked through LDS; partial sums into a slab of its own
+//   k_psf_fold        per (bucket, pixel): the slices added in slice order, |U|^2 / lambda_w^2, normalised
 // No floating-point atomics: every output is the same, bit for bit, on every run.
 #pragma once
 
@@ -26,8 +32,228 @@ static const size_t kPsfSlabBytes = 256u << 20;   // cap on the (bucket, slice, 
 static const size_t kPsfCountBytes = 64u << 20;   // cap on the sort's (wave, bucket) counts
 
 struct PsfRay { double p1, p2, c, a; };
+struct PsfPar { double e, q1, q2; };  // a parameter's share of a ray: e_k = dphase_k s, q_k = dpoint_k rho s
 struct PsfLambda { double value[PSF_MAX_WAVELENGTHS], s[PSF_MAX_WAVELENGTHS]; int n; };
 
+// ---- the core, host side --------------------------------------------------------------------------------------------
+// `name` is the entry point's prefix of its messages
+static int psf_lambda(const char* name, const double* wavelengths_um, int n_wavelengths, double world_unit_um,
+                      PsfLambda& lambda) {
+  if (n_wavelengths < 1 || n_wavelengths > PSF_MAX_WAVELENGTHS)
+    return fail(PRT_ERR_ARG, std::string(name) + ": 1 to 16 distinct wavelengths");
+  if (!(world_unit_um > 0 && world_unit_um < PRT_INF)) return fail(PRT_ERR_ARG, "world_unit_um: finite and > 0");
+  lambda.n = n_wavelengths;
+  for (int k = 0; k < PSF_MAX_WAVELENGTHS; ++k) lambda.value[k] = lambda.s[k] = 0.0;
+  for (int k = 0; k < n_wavelengths; ++k) {
+    const double w = wavelengths_um[k];
+    if (!(w > 0 && w < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: finite and > 0");
+    for (int q = 0; q < k; ++q)
+      if (wavelengths_um[q] == w) return fail(PRT_ERR_ARG, "wavelengths: distinct");
+    lambda.value[k] = w;
+    lambda.s[k] = 1.0 / (w / world_unit_um);
+    if (!(lambda.s[k] < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: wavelength / world_unit_um underflows");
+  }
+  return PRT_OK;
+}
+
+static int psf_grid(const char* name, int nx, int ny, double du, double dv, const double* centre_uv) {
+  const std::string at = std::string(name) + ": ";
+  if (nx < 1 || nx > PSF_MAX_SIDE || ny < 1 || ny > PSF_MAX_SIDE) return fail(PRT_ERR_ARG, at + "nx, ny in 1..1024");
+  if (!(du > 0 && du < PRT_INF && dv > 0 && dv < PRT_INF)) return fail(PRT_ERR_ARG, at + "du, dv finite and > 0");
+  if (!(std::isfinite(centre_uv[0]) && std::isfinite(centre_uv[1]))) return fail(PRT_ERR_ARG, at + "centre finite");
+  return PRT_OK;
+}
+
+// The sort walks n_items (all rows of the frame, or the selection) into sort_buckets (group, wavelength) buckets; the
+// sums run per bucket of `buckets` (the polarised pass: a sort bucket per state) over npix pixels, tile_pixels a
+// workgroup.  pixel_bytes: a pixel of the partial-sum slab as the slices are capped; stored_bytes: as it is allocated
+// (the sensitivities cap for 16 parameters whatever K is, so that the slices do not follow K); strehl_sums: doubles
+// per (bucket, slice).  The slice count decides the order of the slice fold, and with it the bits.
+struct PsfPlan {
+  int64_t per_wave, all_waves, tiles, slices;
+  unsigned grid;
+  size_t count_bytes, strehl_bytes, slab_bytes;
+};
+static PsfPlan psf_plan(int cus, int64_t n_items, int64_t sort_buckets, int64_t buckets, int64_t npix,
+                        int64_t tile_pixels, size_t pixel_bytes, size_t stored_bytes, size_t strehl_sums) {
+  PsfPlan p;
+  // row passes: waves of contiguous rows, as many as the (wave, bucket) counts allow
+  int64_t waves = wf_waves(n_items, 1);
+  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kPsfCountBytes / ((size_t)sort_buckets * 8))));
+  p.per_wave = ((n_items + waves - 1) / waves + 63) / 64 * 64;
+  p.grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
+  p.all_waves = (int64_t)p.grid * (PRT_BLOCK / 64);
+  // ray slices: enough workgroups to fill the CUs, slices of at least kPsfMinSlice items of an average sort bucket
+  const int64_t tiles = (npix + tile_pixels - 1) / tile_pixels;
+  int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);
+  slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_items / (sort_buckets * kPsfMinSlice)));
+  slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * pixel_bytes)));
+  slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));
+  p.tiles = tiles;
+  p.slices = slices;
+  p.count_bytes = (size_t)p.all_waves * sort_buckets * 8;
+  p.strehl_bytes = (size_t)buckets * slices * strehl_sums * sizeof(double);
+  p.slab_bytes = (size_t)buckets * slices * npix * stored_bytes;
+  return p;
+}
+
+// the device, its CU count, and the scratch of a plan: the sort's counts zeroed, and `zeroed` (the workspace's counters
+// of rays left out, with the status word behind them)
+struct PsfScratch { char* base; int64_t* counts; double *strehl_slab, *slab; };
+static int psf_device(int device, int* cus) {
+  const int rc = ops_device(device);
+  return rc ? rc : hist_cus(device, cus);
+}
+static int psf_scratch(hipStream_t st, const PsfPlan& p, void* zeroed, size_t zeroed_bytes, PsfScratch& s) {
+  s.base = nullptr;
+  HIP_TRY(hipMallocAsync((void**)&s.base, p.count_bytes + p.strehl_bytes + p.slab_bytes, st));
+  s.counts = (int64_t*)s.base;
+  s.strehl_slab = (double*)(s.base + p.count_bytes);
+  s.slab = (double*)(s.base + p.count_bytes + p.strehl_bytes);
+  HIP_TRY(hipMemsetAsync(s.counts, 0, p.count_bytes, st));
+  HIP_TRY(hipMemsetAsync(zeroed, 0, zeroed_bytes, st));
+  return PRT_OK;
+}
+
+// after the last launch: the status word read back, the scratch freed, the stream drained
+static int psf_finish(hipStream_t st, const int* status, const PsfScratch& s, int* host_status) {
+  *host_status = 0;
+  HIP_TRY(hipMemcpyAsync(host_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipFreeAsync(s.base, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (a caller's host arrays outlive their copies)
+  HIP_TRY(hipGetLastError());
+  return PRT_OK;
+}
+
+// ---- the core, device side ------------------------------------------------------------------------------------------
+// the place of a row's wavelength in the list, -1 if it is not there
+__device__ __forceinline__ int psf_wavelength(const PsfLambda& lambda, double wavelength) {
+  int k = -1;
+  for (int q = 0; q < lambda.n; ++q)
+    if (k < 0 && lambda.value[q] == wavelength) k = q;
+  return k;
+}
+
+// a ray is summed if its OPD and pupil point are numbers and its weight is finite and not negative
+__device__ __forceinline__ bool psf_keep(double o, double x, double y, double w) {
+  return o == o && x == x && y == y && w >= 0.0 && w < PRT_INF;
+}
+
+// a wave's 64 rows, `bucket` < 0 for a row left out: mine[b] += the rows of bucket b
+__device__ __forceinline__ void psf_tally(int lane, int bucket, int64_t* mine) {
+  unsigned long long pending = __ballot(bucket >= 0);
+  while (pending) {  // one turn per bucket present in the 64 rows: almost always exactly one
+    const int leader = __ffsll((long long)pending) - 1;
+    const int b = __shfl(bucket, leader);
+    const unsigned long long take = __ballot(bucket == b);
+    if (lane == 0) mine[b] += __popcll(take);
+    pending &= ~take;
+  }
+}
+
+// a wave's staged rays [from, to): move(r, pos) for every ray r kept, pos its place in its bucket -- the wave's offset
+// mine[b], advanced as it goes, so that the rays of a bucket keep their order
+template <class Move>
+__device__ __forceinline__ void psf_place(int64_t from, int64_t to, const int* __restrict__ bucket_of, int64_t* mine,
+                                          Move move) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t base = from; base < to; base += 64) {
+    const int64_t r = base + lane;
+    const int bucket = r < to ? bucket_of[r] : -1;
+    unsigned long long pending = __ballot(bucket >= 0);
+    while (pending) {
+      const int leader = __ffsll((long long)pending) - 1;
+      const int b = __shfl(bucket, leader);
+      const unsigned long long take = __ballot(bucket == b);
+      int64_t at = lane == 0 ? mine[b] : 0;
+      at = __shfl(at, 0);
+      if (bucket == b) move(r, at + __popcll(take & ((1ull << lane) - 1ull)));
+      if (lane == 0) mine[b] = at + __popcll(take);
+      pending &= ~take;
+    }
+  }
+}
+
+// the rays [lo, hi) of bucket b's slice
+__device__ __forceinline__ void psf_slice(const int64_t* __restrict__ bucket_total,
+                                          const int64_t* __restrict__ bucket_start, int b, int slice, int slices,
+                                          int64_t& lo, int64_t& hi) {
+  const int64_t n = bucket_total[b], per = (n + slices - 1) / slices;
+  lo = bucket_start[b] + (int64_t)slice * per;
+  hi = bucket_start[b] + n;
+  if (lo + per < hi) hi = lo + per;
+}
+
+// pixel `pix` of the grid (past the grid: pixel 0, computed and not stored): its place (u, v) in the image plane.  What
+// a kernel keeps of it it forms itself, mu = -2 u, mv = -2 v and k0 = R^2 + u^2 + v^2 with |x - E|^2 = mu p1 + mv p2 + k0:
+// formed in here, the compiler orders the set-up otherwise and numbers the registers of the kernels' loops otherwise
+__device__ __forceinline__ void psf_pixel(int64_t pix, int64_t npix, int nx, int ny, double du, double dv, double u0,
+                                          double v0, double& u, double& v) {
+  const int i = pix < npix ? (int)(pix / ny) : 0, j = pix < npix ? (int)(pix - (int64_t)(pix / ny) * ny) : 0;
+  u = u0 + ((double)i - 0.5 * (nx - 1)) * du;
+  v = v0 + ((double)j - 0.5 * (ny - 1)) * dv;
+}
+
+// sqrt in fp64 for an argument far from 0 and from the denormals (|x - E|^2 ~ R^2): the hardware's reciprocal square
+// root refined by Goldschmidt's iteration, as the compiler's own expansion does without its scaling steps.  And
+// 1 / sqrt(x) from the same reciprocal square root: h = 0.5 / sqrt(x) after its one Goldschmidt step, doubled, and one
+// Newton step against the finished root (three instructions that go where the caller drops it)
+__device__ __forceinline__ double psf_sqrt(double x, double& inverse) {
+  const double y = __builtin_amdgcn_rsq(x);
+  double g = x * y, h = 0.5 * y;
+  const double r = fma(-h, g, 0.5);
+  g = fma(g, r, g);
+  h = fma(h, r, h);
+  double d = fma(-g, g, x);
+  g = fma(d, h, g);
+  d = fma(-g, g, x);
+  g = fma(d, h, g);
+  const double i = h + h;
+  inverse = fma(fma(-g, i, 1.0), i, i);
+  return g;
+}
+
+// The phase path of a (ray, pixel): cos and sin of 2 pi (OPD + d - R) / lambda_w, and 1 / d
+struct PsfPhase { double cs, sn, inverse; };
+__device__ __forceinline__ PsfPhase psf_phase(double mu, double mv, double k0, double p1, double p2, double c,
+                                              double s) {
+  PsfPhase out;
+  const double d2 = fma(mu, p1, fma(mv, p2, k0));      // |x - E|^2
+  const double phase = fma(psf_sqrt(d2, out.inverse), s, c);     // (OPD + d - R) / lambda_w, cycles
+  const float turn = (float)__builtin_amdgcn_fract(phase);       // [0, 1)
+  out.cs = (double)__builtin_amdgcn_cosf(turn);                  // (v_cos_f32 / v_sin_f32 take turns)
+  out.sn = (double)__builtin_amdgcn_sinf(turn);
+  return out;
+}
+
+// the phase of a ray at P itself, for the Strehl sums: OPD / lambda_w in cycles, fp64 sincospi
+__device__ __forceinline__ void psf_chief_phase(double radius, double s, double c, double& sn, double& cs) {
+  const double phase = fma(radius, s, c);
+  sincospi(2.0 * (phase - rint(phase)), &sn, &cs);
+}
+
+// red[k][0] = the sum of red[k][0 .. kPsfBlock) for every k, a fixed tree
+template <int N>
+__device__ __forceinline__ void psf_tree(double (&red)[N][kPsfBlock], int t) {
+  for (int half = kPsfBlock / 2; half > 0; half >>= 1) {
+    __syncthreads();
+    if (t < half)
+      for (int k = 0; k < N; ++k) red[k][t] += red[k][t + half];
+  }
+  __syncthreads();
+}
+
+// strehl_slab: (bucket, slice, 1 + K, 3).  The slices of (bucket b, quantity) added in slice order
+__device__ __forceinline__ void psf_strehl_fold(const double* __restrict__ strehl_slab, int slices, int K, int b,
+                                                int quantity, double& a, double& c, double& s) {
+  a = c = s = 0.0;
+  for (int q = 0; q < slices; ++q) {
+    const double* p = strehl_slab + (((size_t)b * slices + q) * (1 + K) + quantity) * 3;
+    a += p[0]; c += p[1]; s += p[2];
+  }
+}
+
+// ---- the kernels ----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool psf_row(const double* __restrict__ rows, int64_t ld, int64_t j, double surface,
                                         double generation, double rays_per_source, int n_groups, int& group) {
   group = -1;
@@ -93,17 +319,14 @@ k_psf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
     int bucket = -1;
     if (chosen) {
       const int64_t pos = at + __popcll(ballot & ((1ull << lane) - 1ull));
-      const double wavelength = rows[PRT_COL_WAVELENGTH * ld + j];
-      int k = -1;
-      for (int q = 0; q < lambda.n; ++q)
-        if (k < 0 && lambda.value[q] == wavelength) k = q;
+      const int k = psf_wavelength(lambda, rows[PRT_COL_WAVELENGTH * ld + j]);
       if (k < 0) {
         atomicOr(status, PSF_BAD_WAVELENGTH);
       } else {
         const double* g = group_record + (size_t)group * WF_GROUP;
         const double o = opd[pos], x = pupil[2 * pos], y = pupil[2 * pos + 1];
         const double w = weight_column >= 0 ? rows[(int64_t)weight_column * ld + j] : 1.0;
-        if (o == o && x == x && y == y && w >= 0.0 && w < PRT_INF) {
+        if (psf_keep(o, x, y, w)) {
           bucket = group * lambda.n + k;
           const double rho = g[5], s = lambda.s[k];
           stage[pos] = PsfRay{x * rho, y * rho, (o - g[3]) * s, sqrt(w)};
@@ -114,14 +337,7 @@ k_psf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
       bucket_of[pos] = bucket;
     }
     at += __popcll(ballot);
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {  // one turn per bucket present in the slice: almost always exactly one
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      if (lane == 0) mine[b] += __popcll(take);
-      pending &= ~take;
-    }
+    psf_tally(lane, bucket, mine);
   }
 }
 
@@ -154,65 +370,43 @@ __global__ void __launch_bounds__(PRT_BLOCK)
 k_psf_scatter(const int64_t* __restrict__ wave_rows, const int64_t* __restrict__ wave_offset,
               const int* __restrict__ bucket_of, const PsfRay* __restrict__ stage, int64_t* __restrict__ offsets,
               int buckets, PsfRay* __restrict__ sorted) {
-  const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t from = wave_offset[wave], to = from + wave_rows[wave];
-  int64_t* const mine = offsets + wave * buckets;  // (only this wave reads and writes here)
-  for (int64_t base = from; base < to; base += 64) {
-    const int64_t r = base + lane;
-    const int bucket = r < to ? bucket_of[r] : -1;
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      int64_t at = lane == 0 ? mine[b] : 0;
-      at = __shfl(at, 0);
-      if (bucket == b) sorted[at + __popcll(take & ((1ull << lane) - 1ull))] = stage[r];
-      if (lane == 0) mine[b] = at + __popcll(take);
-      pending &= ~take;
-    }
-  }
+  const int64_t from = wave_offset[wave];  // (offsets + wave * buckets: only this wave reads and writes there)
+  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets,
+            [&](int64_t r, int64_t pos) { sorted[pos] = stage[r]; });
 }
 
-// the rays [lo, hi) of bucket b's slice
-__device__ __forceinline__ void psf_slice(const int64_t* __restrict__ bucket_total,
-                                          const int64_t* __restrict__ bucket_start, int b, int slice, int slices,
-                                          int64_t& lo, int64_t& hi) {
-  const int64_t n = bucket_total[b], per = (n + slices - 1) / slices;
-  lo = bucket_start[b] + (int64_t)slice * per;
-  hi = bucket_start[b] + n;
-  if (lo + per < hi) hi = lo + per;
-}
-
+// strehl_slab: (bucket, slice, 1 + K, 3).  Quantity 0: sum a, sum a cos, sum a sin; quantity 1 + k: 0, sum a e_k cos,
+// sum a e_k sin with e_k at par[k * n_items + ray] (no par where K is 0).  A group's record is group_ld doubles
 __global__ void __launch_bounds__(kPsfBlock)
-k_psf_strehl(const PsfRay* __restrict__ sorted, const int64_t* __restrict__ bucket_total,
-             const int64_t* __restrict__ bucket_start, const double* __restrict__ group_record, PsfLambda lambda,
-             int slices, double* __restrict__ strehl_slab) {
+k_psf_strehl(const PsfRay* __restrict__ sorted, const PsfPar* __restrict__ par, int64_t n_items,
+             const int64_t* __restrict__ bucket_total, const int64_t* __restrict__ bucket_start,
+             const double* __restrict__ groups, PsfLambda lambda, int group_ld, int slices, int K,
+             double* __restrict__ strehl_slab) {
   __shared__ double red[3][kPsfBlock];
-  const int t = threadIdx.x, slice = blockIdx.x, b = blockIdx.y;
+  const int t = threadIdx.x, slice = blockIdx.x, b = blockIdx.y, quantity = blockIdx.z;
   const int g = b / lambda.n;
-  const double s = lambda.s[b - g * lambda.n], radius = group_record[(size_t)g * WF_GROUP + 3];
+  const double s = lambda.s[b - g * lambda.n], radius = groups[(size_t)g * group_ld + 3];
   int64_t lo, hi;
   psf_slice(bucket_total, bucket_start, b, slice, slices, lo, hi);
   double sum_a = 0.0, sum_c = 0.0, sum_s = 0.0;
   for (int64_t r = lo + t; r < hi; r += kPsfBlock) {
     const PsfRay ray = sorted[r];
-    const double phase = fma(radius, s, ray.c);  // OPD / lambda_w, in cycles
     double sn, cs;
-    sincospi(2.0 * (phase - rint(phase)), &sn, &cs);
-    sum_a += ray.a;
-    sum_c += ray.a * cs;
-    sum_s += ray.a * sn;
+    psf_chief_phase(radius, s, ray.c, sn, cs);
+    if (quantity == 0) {
+      sum_a += ray.a;
+      sum_c += ray.a * cs;
+      sum_s += ray.a * sn;
+    } else {
+      const double ae = ray.a * par[(int64_t)(quantity - 1) * n_items + r].e;
+      sum_c += ae * cs;
+      sum_s += ae * sn;
+    }
   }
   red[0][t] = sum_a; red[1][t] = sum_c; red[2][t] = sum_s;
-  for (int half = kPsfBlock / 2; half > 0; half >>= 1) {  // (a fixed tree)
-    __syncthreads();
-    if (t < half)
-      for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + half];
-  }
-  __syncthreads();
-  if (t < 3) strehl_slab[((size_t)b * slices + slice) * 3 + t] = red[t][0];
+  psf_tree(red, t);
+  if (t < 3) strehl_slab[(((size_t)b * slices + slice) * (1 + K) + quantity) * 3 + t] = red[t][0];
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
@@ -224,11 +418,8 @@ k_psf_record(const double* __restrict__ strehl_slab, int slices, int n_groups, P
   double numerator = 0.0, denominator = 0.0;
   for (int k = 0; k < lambda.n; ++k) {
     const int b = g * lambda.n + k;
-    double a = 0.0, c = 0.0, s = 0.0;
-    for (int q = 0; q < slices; ++q) {
-      const double* p = strehl_slab + ((size_t)b * slices + q) * 3;
-      a += p[0]; c += p[1]; s += p[2];
-    }
+    double a, c, s;
+    psf_strehl_fold(strehl_slab, slices, 0, b, 0, a, c, s);
     const double inv = lambda.s[k], num = inv * inv * (c * c + s * s), den = (inv * a) * (inv * a);
     double* o = record_out + (size_t)b * PSF_RECORD;
     o[0] = (double)bucket_total[b];
@@ -240,20 +431,6 @@ k_psf_record(const double* __restrict__ strehl_slab, int slices, int n_groups, P
   }
   norm[g] = denominator;
   strehl_out[g] = denominator > 0.0 ? numerator / denominator : __longlong_as_double(0x7ff8000000000000ll);
-}
-
-// sqrt in fp64 for an argument far from 0 and from the denormals (|x - E|^2 ~ R^2): the hardware's reciprocal square
-// root refined by Goldschmidt's iteration, as the compiler's own expansion does without its scaling steps
-__device__ __forceinline__ double psf_sqrt(double x) {
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, h = 0.5 * y;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  return fma(d, h, g);
 }
 
 __global__ void __launch_bounds__(kPsfBlock)
@@ -268,9 +445,8 @@ k_psf_huygens(const PsfRay* __restrict__ sorted, const int64_t* __restrict__ buc
   double mu[kPsfPix], mv[kPsfPix], k0[kPsfPix], re[kPsfPix], im[kPsfPix];
 #pragma unroll
   for (int q = 0; q < kPsfPix; ++q) {
-    const int64_t pix = (int64_t)blockIdx.x * kPsfTile + q * kPsfBlock + t;
-    const int i = pix < npix ? (int)(pix / ny) : 0, j = pix < npix ? (int)(pix - (int64_t)(pix / ny) * ny) : 0;
-    const double u = u0 + ((double)i - 0.5 * (nx - 1)) * du, v = v0 + ((double)j - 0.5 * (ny - 1)) * dv;
+    double u, v;
+    psf_pixel((int64_t)blockIdx.x * kPsfTile + q * kPsfBlock + t, npix, nx, ny, du, dv, u0, v0, u, v);
     mu[q] = -2.0 * u;
     mv[q] = -2.0 * v;
     k0[q] = radius * radius + u * u + v * v;
@@ -287,11 +463,9 @@ k_psf_huygens(const PsfRay* __restrict__ sorted, const int64_t* __restrict__ buc
       const PsfRay ray = tile[r];
 #pragma unroll
       for (int q = 0; q < kPsfPix; ++q) {
-        const double d2 = fma(mu[q], ray.p1, fma(mv[q], ray.p2, k0[q]));  // |x - E|^2
-        const double phase = fma(psf_sqrt(d2), s, ray.c);                  // (OPD + d - R) / lambda_w, cycles
-        const float turn = (float)__builtin_amdgcn_fract(phase);           // [0, 1)
-        re[q] = fma(ray.a, (double)__builtin_amdgcn_cosf(turn), re[q]);    // (v_cos_f32 / v_sin_f32 take turns)
-        im[q] = fma(ray.a, (double)__builtin_amdgcn_sinf(turn), im[q]);
+        const PsfPhase at = psf_phase(mu[q], mv[q], k0[q], ray.p1, ray.p2, ray.c, s);
+        re[q] = fma(ray.a, at.cs, re[q]);
+        im[q] = fma(ray.a, at.sn, im[q]);
       }
     }
   }
@@ -349,32 +523,16 @@ extern "C" int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t
     return fail(PRT_ERR_ARG, "bad buffers");
   if (!(rays_per_source > 0) && n_groups != 1) return fail(PRT_ERR_ARG, "one group without rays_per_source");
   if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
-  if (n_wavelengths < 1 || n_wavelengths > PSF_MAX_WAVELENGTHS)
-    return fail(PRT_ERR_ARG, "psf: 1 to 16 distinct wavelengths");
-  if (!(world_unit_um > 0 && world_unit_um < PRT_INF)) return fail(PRT_ERR_ARG, "world_unit_um: finite and > 0");
   PsfLambda lambda;
-  lambda.n = n_wavelengths;
-  for (int k = 0; k < PSF_MAX_WAVELENGTHS; ++k) lambda.value[k] = lambda.s[k] = 0.0;
-  for (int k = 0; k < n_wavelengths; ++k) {
-    const double w = wavelengths_um[k];
-    if (!(w > 0 && w < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: finite and > 0");
-    for (int q = 0; q < k; ++q)
-      if (wavelengths_um[q] == w) return fail(PRT_ERR_ARG, "wavelengths: distinct");
-    lambda.value[k] = w;
-    lambda.s[k] = 1.0 / (w / world_unit_um);
-    if (!(lambda.s[k] < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: wavelength / world_unit_um underflows");
-  }
-  if (nx < 1 || nx > PSF_MAX_SIDE || ny < 1 || ny > PSF_MAX_SIDE) return fail(PRT_ERR_ARG, "psf: nx, ny in 1..1024");
-  if (!(du > 0 && du < PRT_INF && dv > 0 && dv < PRT_INF)) return fail(PRT_ERR_ARG, "psf: du, dv finite and > 0");
-  if (!(std::isfinite(centre_uv[0]) && std::isfinite(centre_uv[1]))) return fail(PRT_ERR_ARG, "psf: centre finite");
+  int rc = psf_lambda("psf", wavelengths_um, n_wavelengths, world_unit_um, lambda);
+  if (!rc) rc = psf_grid("psf", nx, ny, du, dv, centre_uv);
+  if (rc) return rc;
   const int64_t buckets = (int64_t)n_groups * n_wavelengths, npix = (int64_t)nx * ny;
   if (buckets > 65535) return fail(PRT_ERR_ARG, "psf: n_groups * n_wavelengths <= 65535");
   if ((size_t)buckets * npix * 2 * sizeof(double) > kPsfSlabBytes)
     return fail(PRT_ERR_ARG, "psf: n_groups * n_wavelengths * nx * ny * 16 bytes above the 256 MiB slab cap");
-  int rc = ops_device(device);
-  if (rc) return rc;
   int cus = 1;
-  rc = hist_cus(device, &cus);
+  rc = psf_device(device, &cus);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_psf_workspace_bytes)
@@ -388,52 +546,34 @@ extern "C" int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t
   PsfRay* stage = (PsfRay*)(((uintptr_t)(norm + n_groups) + 31) & ~(uintptr_t)31);
   PsfRay* sorted = stage + n_rows;
   int* bucket_of = (int*)(sorted + n_rows);
-  // row passes: waves of contiguous rows, as many as the (wave, bucket) counts allow
-  int64_t waves = wf_waves(n_rows, 1);
-  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kPsfCountBytes / ((size_t)buckets * 8))));
-  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  // ray slices: enough workgroups to fill the CUs, slices of at least kPsfMinSlice rays of an average bucket
-  const int64_t tiles = (npix + kPsfTile - 1) / kPsfTile;
-  int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);
-  slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_rows / (buckets * kPsfMinSlice)));
-  slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * 16)));
-  slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));
-  const size_t count_bytes = (size_t)all_waves * buckets * 8;
-  const size_t slab_bytes = (size_t)buckets * slices * npix * 2 * sizeof(double);
-  const size_t strehl_bytes = (size_t)buckets * slices * 3 * sizeof(double);
-  char* scratch = nullptr;
-  HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + strehl_bytes + slab_bytes, st));
-  int64_t* counts = (int64_t*)scratch;
-  double* strehl_slab = (double*)(scratch + count_bytes);
-  double* slab = (double*)(scratch + count_bytes + strehl_bytes);
-  HIP_TRY(hipMemsetAsync(counts, 0, count_bytes, st));
-  HIP_TRY(hipMemsetAsync(skipped, 0, (size_t)buckets * 8 + 8, st));  // (and the status word)
-  hipLaunchKernelGGL(k_psf_count, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, per_wave, wave_rows);
-  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, wave_rows, wave_offset);
-  hipLaunchKernelGGL(k_psf_stage, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, per_wave, wave_offset, opd, pupil, group_record, weight_column, lambda,
-                     stage, bucket_of, counts, (int)buckets, skipped, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, (int)buckets, counts,
+  const PsfPlan plan = psf_plan(cus, n_rows, buckets, buckets, npix, kPsfTile, 16, 16, 3);
+  const int slices = (int)plan.slices, all_waves = (int)plan.all_waves;
+  PsfScratch scratch;
+  rc = psf_scratch(st, plan, skipped, (size_t)buckets * 8 + 8, scratch);  // (the skips and the status word)
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_psf_count, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, plan.per_wave, wave_rows);
+  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, wave_rows, wave_offset);
+  hipLaunchKernelGGL(k_psf_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, plan.per_wave, wave_offset, opd, pupil, group_record, weight_column,
+                     lambda, stage, bucket_of, scratch.counts, (int)buckets, skipped, status);
+  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, (int)buckets, scratch.counts,
                      bucket_total, bucket_start);
-  hipLaunchKernelGGL(k_psf_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
-                     counts, (int)buckets, sorted);
+  hipLaunchKernelGGL(k_psf_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
+                     scratch.counts, (int)buckets, sorted);
   hipLaunchKernelGGL(k_psf_strehl, dim3((unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st, sorted,
-                     bucket_total, bucket_start, group_record, lambda, (int)slices, strehl_slab);
+                     (const PsfPar*)nullptr, n_rows, bucket_total, bucket_start, group_record, lambda, (int)WF_GROUP,
+                     slices, 0, scratch.strehl_slab);
   hipLaunchKernelGGL(k_psf_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
-                     strehl_slab, (int)slices, n_groups, lambda, bucket_total, skipped, record_out, strehl_out, norm);
-  hipLaunchKernelGGL(k_psf_huygens, dim3((unsigned)tiles, (unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st,
-                     sorted, bucket_total, bucket_start, group_record, lambda, nx, ny, du, dv, centre_uv[0],
-                     centre_uv[1], (int)slices, slab);
+                     scratch.strehl_slab, slices, n_groups, lambda, bucket_total, skipped, record_out, strehl_out, norm);
+  hipLaunchKernelGGL(k_psf_huygens, dim3((unsigned)plan.tiles, (unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0,
+                     st, sorted, bucket_total, bucket_start, group_record, lambda, nx, ny, du, dv, centre_uv[0],
+                     centre_uv[1], slices, scratch.slab);
   hipLaunchKernelGGL(k_psf_fold, dim3((unsigned)((buckets * npix + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0,
-                     st, slab, (int)slices, (int)buckets, npix, lambda, norm, image_out);
-  int host_status = 0;
-  HIP_TRY(hipMemcpyAsync(&host_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipFreeAsync(scratch, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipGetLastError());
+                     st, scratch.slab, slices, (int)buckets, npix, lambda, norm, image_out);
+  int host_status;
+  rc = psf_finish(st, status, scratch, &host_status);
+  if (rc) return rc;
   if (host_status & PSF_BAD_WAVELENGTH) return fail(PRT_ERR_ARG, "psf: a selected row's wavelength is not in the list");
   return PRT_OK;
 }

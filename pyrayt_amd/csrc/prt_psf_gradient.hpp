@@ -1,7 +1,7 @@
 // prt_psf_gradient.hpp -- d(PSF)/d(parameter) and d(Strehl)/d(parameter) of the diffraction PSF, on the device
 // (DESIGN.md section 4.5), from the rows, the OPD, the pupil points and their derivatives that a wavefront sensitivity
-// pass left there.  It builds on prt_psf.hpp (PsfRay, PsfLambda, psf_slice, k_psf_offsets, the phase path of
-// k_psf_huygens).  Definitions: include/prt.h.
+// pass left there.  It stands on prt_psf.hpp: the Huygens core, k_psf_offsets and the Strehl kernel itself -- the scalar
+// PSF's is its case without parameters.  Definitions: include/prt.h.
 //
 //   k_psfg_stage      per selected row, in the selection's order: kept / missed / unfollowed, (p1, p2, c, a) and the
 //                     row's (group, wavelength) bucket; per wave and bucket the rays kept; the others counted per bucket
@@ -10,10 +10,10 @@
 //   k_psfg_scatter    the stable counting sort of an index: every wave writes its rays' slots, in order, at its offsets,
 //                     and the staged ray beside them
 //   k_psfg_stage_par  per sorted ray and parameter, gathered through the index: (e_k, q_k1, q_k2)
-//   k_psfg_strehl     per (ray slice, bucket, quantity): sum a, sum a (cos, sin) -- k_psf_strehl's sums -- or, for
-//                     parameter k, sum a e_k (cos, sin), fp64 sincospi, a fixed tree
+//   k_psf_strehl      (prt_psf.hpp) per (ray slice, bucket, quantity): sum a, sum a (cos, sin) or, for parameter k,
+//                     sum a e_k (cos, sin), fp64 sincospi, a fixed tree
 //   k_psfg_record     per group: the slices folded in order, the record, Strehl, dStrehl_k and the normalisation D_g
-//   k_psfg_huygens<P> per (pixel tile, ray slice, bucket x chunk of P parameters): the phase path of k_psf_huygens once
+//   k_psfg_huygens<P> per (pixel tile, ray slice, bucket x chunk of P parameters): the phase path (psf_phase) once
 //                     per (ray, pixel), then per parameter two multiply-adds for g_k, one product a g_k and two
 //                     accumulates; the ray tile and its parameter chunk go through LDS; partial sums into a slab
 //   k_psfg_fold       per (bucket, quantity, pixel): the slices added in slice order; U, dU_k, I and dI_k
@@ -29,8 +29,7 @@ enum { PSFG_MAX_PARAMETERS = 16, PSFG_RECORD = 5, PSFG_BAD_WAVELENGTH = 1, PSFG_
 static const int kPsfgParams = 4;                  // parameters of a chunk at most (fp64 accumulators in registers)
 static const int kPsfgQuantities = PSFG_MAX_PARAMETERS + 1;  // the slab holds U and K parameters: sized for 16
 static const int kPsfgMinSlice = 2048;             // selected rows a slice should hold at least
-
-struct PsfgPar { double e, q1, q2; };
+static_assert(kPsfgMinSlice == kPsfMinSlice, "psf_plan cuts the slices of every pass by kPsfMinSlice");
 
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_psfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const int64_t* __restrict__ selected,
@@ -54,9 +53,7 @@ k_psfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const 
       const int group = mtf_owner(group_first, n_groups, r);
       int k = -1;
       if (j >= 0 && j < n_rows && group >= 0) {
-        const double wavelength = rows[PRT_COL_WAVELENGTH * ld + j];
-        for (int q = 0; q < lambda.n; ++q)
-          if (k < 0 && lambda.value[q] == wavelength) k = q;
+        k = psf_wavelength(lambda, rows[PRT_COL_WAVELENGTH * ld + j]);
         if (k < 0) atomicOr(status, PSFG_BAD_WAVELENGTH);
       } else {
         atomicOr(status, PSFG_BAD_ROW);
@@ -66,7 +63,7 @@ k_psfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const 
         const double* g = groups + (size_t)group * 6;
         const double o = opd[r], x = pupil[2 * r], y = pupil[2 * r + 1];
         const double w = weight_column >= 0 ? rows[(int64_t)weight_column * ld + j] : 1.0;
-        if (o == o && x == x && y == y && w >= 0.0 && w < PRT_INF) {  // (prt_frame_psf's rule)
+        if (psf_keep(o, x, y, w)) {
           bool followed = true;
           for (int p = 0; p < K; ++p) {
             followed = followed && fabs(dphase[(int64_t)p * n_selected + r]) < PRT_INF;
@@ -87,14 +84,7 @@ k_psfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const 
       }
       bucket_of[r] = bucket;
     }
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {  // one turn per bucket present in the 64 rows: almost always exactly one
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      if (lane == 0) mine[b] += __popcll(take);
-      pending &= ~take;
-    }
+    psf_tally(lane, bucket, mine);
   }
 }
 
@@ -102,30 +92,13 @@ __global__ void __launch_bounds__(PRT_BLOCK)
 k_psfg_scatter(int64_t n_selected, int64_t per_wave, const int* __restrict__ bucket_of,
                const PsfRay* __restrict__ stage, int64_t* __restrict__ offsets, int buckets,
                PsfRay* __restrict__ sorted, int64_t* __restrict__ order) {
-  const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t from = wave * per_wave;
-  const int64_t to = from + per_wave < n_selected ? from + per_wave : n_selected;
-  int64_t* const mine = offsets + wave * buckets;  // (only this wave reads and writes here)
-  for (int64_t base = from; base < to; base += 64) {
-    const int64_t r = base + lane;
-    const int bucket = r < to ? bucket_of[r] : -1;
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      int64_t at = lane == 0 ? mine[b] : 0;
-      at = __shfl(at, 0);
-      if (bucket == b) {
-        const int64_t pos = at + __popcll(take & ((1ull << lane) - 1ull));
-        sorted[pos] = stage[r];
-        order[pos] = r;
-      }
-      if (lane == 0) mine[b] = at + __popcll(take);
-      pending &= ~take;
-    }
-  }
+  const int64_t from = wave * per_wave;  // (offsets + wave * buckets: only this wave reads and writes there)
+  psf_place(from, from + per_wave < n_selected ? from + per_wave : n_selected, bucket_of, offsets + wave * buckets,
+            [&](int64_t r, int64_t pos) {
+              sorted[pos] = stage[r];
+              order[pos] = r;
+            });
 }
 
 // per sorted ray i, slot = order[i]: e_k = dphase_k s, q_k = dpoint_k rho s (zeros without dpoint), at par[k * n_selected + i]
@@ -134,71 +107,21 @@ k_psfg_stage_par(const double* __restrict__ rows, int64_t ld, const int64_t* __r
                  int n_groups, const int64_t* __restrict__ group_first, const double* __restrict__ groups,
                  PsfLambda lambda, const int64_t* __restrict__ bucket_total, const int64_t* __restrict__ bucket_start,
                  int buckets, const int64_t* __restrict__ order, const double* __restrict__ dphase,
-                 const double* __restrict__ dpoint, int K, PsfgPar* __restrict__ par) {
+                 const double* __restrict__ dpoint, int K, PsfPar* __restrict__ par) {
   const int64_t i = (int64_t)blockIdx.x * PRT_BLOCK + threadIdx.x;
   if (i >= n_selected || i >= bucket_start[buckets - 1] + bucket_total[buckets - 1]) return;
   const int64_t slot = order[i];
   const int group = mtf_owner(group_first, n_groups, slot);
-  const double wavelength = rows[PRT_COL_WAVELENGTH * ld + selected[slot]];
-  double s = 0.0;
-  for (int q = 0; q < lambda.n; ++q)
-    if (lambda.value[q] == wavelength) s = lambda.s[q];
+  const int l = psf_wavelength(lambda, rows[PRT_COL_WAVELENGTH * ld + selected[slot]]);
+  const double s = l < 0 ? 0.0 : lambda.s[l];
   const double rho = groups[(size_t)group * 6 + 5];
   for (int k = 0; k < K; ++k) {
-    PsfgPar p{dphase[(int64_t)k * n_selected + slot] * s, 0.0, 0.0};
+    PsfPar p{dphase[(int64_t)k * n_selected + slot] * s, 0.0, 0.0};
     if (dpoint) {
       p.q1 = dpoint[(int64_t)(2 * k) * n_selected + slot] * rho * s;
       p.q2 = dpoint[(int64_t)(2 * k + 1) * n_selected + slot] * rho * s;
     }
     par[(int64_t)k * n_selected + i] = p;
-  }
-}
-
-// strehl_slab: (bucket, slice, 1 + K, 3).  Quantity 0: sum a, sum a cos, sum a sin, as k_psf_strehl forms them;
-// quantity 1 + k: 0, sum a e_k cos, sum a e_k sin
-__global__ void __launch_bounds__(kPsfBlock)
-k_psfg_strehl(const PsfRay* __restrict__ sorted, const PsfgPar* __restrict__ par, int64_t n_selected,
-              const int64_t* __restrict__ bucket_total, const int64_t* __restrict__ bucket_start,
-              const double* __restrict__ groups, PsfLambda lambda, int slices, int K, double* __restrict__ strehl_slab) {
-  __shared__ double red[3][kPsfBlock];
-  const int t = threadIdx.x, slice = blockIdx.x, b = blockIdx.y, quantity = blockIdx.z;
-  const int g = b / lambda.n;
-  const double s = lambda.s[b - g * lambda.n], radius = groups[(size_t)g * 6 + 3];
-  int64_t lo, hi;
-  psf_slice(bucket_total, bucket_start, b, slice, slices, lo, hi);
-  double sum_a = 0.0, sum_c = 0.0, sum_s = 0.0;
-  for (int64_t r = lo + t; r < hi; r += kPsfBlock) {
-    const PsfRay ray = sorted[r];
-    const double phase = fma(radius, s, ray.c);  // OPD / lambda_w, in cycles
-    double sn, cs;
-    sincospi(2.0 * (phase - rint(phase)), &sn, &cs);
-    if (quantity == 0) {
-      sum_a += ray.a;
-      sum_c += ray.a * cs;
-      sum_s += ray.a * sn;
-    } else {
-      const double ae = ray.a * par[(int64_t)(quantity - 1) * n_selected + r].e;
-      sum_c += ae * cs;
-      sum_s += ae * sn;
-    }
-  }
-  red[0][t] = sum_a; red[1][t] = sum_c; red[2][t] = sum_s;
-  for (int half = kPsfBlock / 2; half > 0; half >>= 1) {  // (a fixed tree)
-    __syncthreads();
-    if (t < half)
-      for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + half];
-  }
-  __syncthreads();
-  if (t < 3) strehl_slab[(((size_t)b * slices + slice) * (1 + K) + quantity) * 3 + t] = red[t][0];
-}
-
-// the slices of (bucket b, quantity) added in slice order
-__device__ __forceinline__ void psfg_strehl_fold(const double* __restrict__ strehl_slab, int slices, int K, int b,
-                                                 int quantity, double& a, double& c, double& s) {
-  a = c = s = 0.0;
-  for (int q = 0; q < slices; ++q) {
-    const double* p = strehl_slab + (((size_t)b * slices + q) * (1 + K) + quantity) * 3;
-    a += p[0]; c += p[1]; s += p[2];
   }
 }
 
@@ -216,7 +139,7 @@ k_psfg_record(const double* __restrict__ strehl_slab, int slices, int n_groups, 
   for (int l = 0; l < lambda.n; ++l) {
     const int b = g * lambda.n + l;
     double a, c, s;
-    psfg_strehl_fold(strehl_slab, slices, K, b, 0, a, c, s);
+    psf_strehl_fold(strehl_slab, slices, K, b, 0, a, c, s);
     const double inv = lambda.s[l], num = inv * inv * (c * c + s * s), den = (inv * a) * (inv * a);
     double* o = record_out + (size_t)b * PSFG_RECORD;
     o[0] = (double)bucket_total[b];
@@ -236,8 +159,8 @@ k_psfg_record(const double* __restrict__ strehl_slab, int slices, int n_groups, 
     for (int l = 0; l < lambda.n; ++l) {
       const int b = g * lambda.n + l;
       double a, c, s, ec, es;
-      psfg_strehl_fold(strehl_slab, slices, K, b, 0, a, c, s);
-      psfg_strehl_fold(strehl_slab, slices, K, b, 1 + k, a, ec, es);
+      psf_strehl_fold(strehl_slab, slices, K, b, 0, a, c, s);
+      psf_strehl_fold(strehl_slab, slices, K, b, 1 + k, a, ec, es);
       const double inv = lambda.s[l];
       sum += inv * inv * (s * ec - c * es);
     }
@@ -245,34 +168,18 @@ k_psfg_record(const double* __restrict__ strehl_slab, int slices, int n_groups, 
   }
 }
 
-// psf_sqrt's steps, and 1 / sqrt(x) from the same reciprocal square root: h = 0.5 / sqrt(x) after its one Goldschmidt
-// step, doubled, and one Newton step against the finished root
-__device__ __forceinline__ double psfg_sqrt(double x, double& inverse) {
-  const double y = __builtin_amdgcn_rsq(x);
-  double g = x * y, h = 0.5 * y;
-  const double r = fma(-h, g, 0.5);
-  g = fma(g, r, g);
-  h = fma(h, r, h);
-  double d = fma(-g, g, x);
-  g = fma(d, h, g);
-  d = fma(-g, g, x);
-  g = fma(d, h, g);
-  const double i = h + h;
-  inverse = fma(fma(-g, i, 1.0), i, i);
-  return g;
-}
-
 // Each thread owns kPsfPix pixels of the tile and, for each, the accumulators of P parameters [first, first + P) (those
-// past K are zeros that are not stored).  The workgroup whose chunk starts at parameter 0 also sums U.
+// past K are zeros that are not stored).  The workgroup whose chunk starts at parameter 0 also sums U, as
+// k_psf_huygens does and through the same psf_pixel and psf_phase.
 // slab: (bucket, slice, quantity, pixel, 2), quantity 0 is sum a (cos, sin), 1 + k is sum a g_k (sin, cos).
 template <int P>
 __global__ void __launch_bounds__(kPsfBlock)
-k_psfg_huygens(const PsfRay* __restrict__ sorted, const PsfgPar* __restrict__ par, int64_t n_selected,
-               const int64_t* __restrict__ bucket_total, const int64_t* __restrict__ bucket_start,
-               const double* __restrict__ groups, PsfLambda lambda, int K, int first_parameter, int chunks, int nx,
-               int ny, double du, double dv, double u0, double v0, int slices, double* __restrict__ slab) {
+k_psfg_huygens(const PsfRay* __restrict__ sorted, const PsfPar* __restrict__ par, int64_t n_items,
+              const int64_t* __restrict__ bucket_total, const int64_t* __restrict__ bucket_start,
+              const double* __restrict__ groups, PsfLambda lambda, int K, int first_parameter, int chunks,
+              int nx, int ny, double du, double dv, double u0, double v0, int slices, double* __restrict__ slab) {
   __shared__ PsfRay tile[kPsfBlock];
-  __shared__ PsfgPar tile_par[P][kPsfBlock];
+  __shared__ PsfPar tile_par[P][kPsfBlock];
   const int t = threadIdx.x, slice = blockIdx.y;
   const int b = (int)blockIdx.z / chunks, first = first_parameter + ((int)blockIdx.z - b * chunks) * P;
   const bool head = first == 0;
@@ -282,15 +189,14 @@ k_psfg_huygens(const PsfRay* __restrict__ sorted, const PsfgPar* __restrict__ pa
   double mu[kPsfPix], mv[kPsfPix], k0[kPsfPix], re[kPsfPix], im[kPsfPix], are[kPsfPix][P], aim[kPsfPix][P];
 #pragma unroll
   for (int q = 0; q < kPsfPix; ++q) {
-    const int64_t pix = (int64_t)blockIdx.x * kPsfTile + q * kPsfBlock + t;
-    const int i = pix < npix ? (int)(pix / ny) : 0, j = pix < npix ? (int)(pix - (int64_t)(pix / ny) * ny) : 0;
-    const double u = u0 + ((double)i - 0.5 * (nx - 1)) * du, v = v0 + ((double)j - 0.5 * (ny - 1)) * dv;
+    double u, v;
+    psf_pixel((int64_t)blockIdx.x * kPsfTile + q * kPsfBlock + t, npix, nx, ny, du, dv, u0, v0, u, v);
     mu[q] = -2.0 * u;
     mv[q] = -2.0 * v;
     k0[q] = radius * radius + u * u + v * v;
     re[q] = im[q] = 0.0;
 #pragma unroll
-    for (int j2 = 0; j2 < P; ++j2) are[q][j2] = aim[q][j2] = 0.0;
+    for (int j = 0; j < P; ++j) are[q][j] = aim[q][j] = 0.0;
   }
   int64_t lo, hi;
   psf_slice(bucket_total, bucket_start, b, slice, slices, lo, hi);
@@ -301,29 +207,25 @@ k_psfg_huygens(const PsfRay* __restrict__ sorted, const PsfgPar* __restrict__ pa
       tile[t] = sorted[base + t];
 #pragma unroll
       for (int j = 0; j < P; ++j)
-        tile_par[j][t] = first + j < K ? par[(int64_t)(first + j) * n_selected + base + t] : PsfgPar{0.0, 0.0, 0.0};
+        tile_par[j][t] = first + j < K ? par[(int64_t)(first + j) * n_items + base + t] : PsfPar{0.0, 0.0, 0.0};
     }
     __syncthreads();
     for (int r = 0; r < count; ++r) {
       const PsfRay ray = tile[r];
 #pragma unroll
       for (int q = 0; q < kPsfPix; ++q) {
-        const double d2 = fma(mu[q], ray.p1, fma(mv[q], ray.p2, k0[q]));  // |x - E|^2
-        double inverse;
-        const double phase = fma(psfg_sqrt(d2, inverse), s, ray.c);        // (OPD + d - R) / lambda_w, cycles
-        const float turn = (float)__builtin_amdgcn_fract(phase);           // [0, 1)
-        const double c = (double)__builtin_amdgcn_cosf(turn), sn = (double)__builtin_amdgcn_sinf(turn);
+        const PsfPhase at = psf_phase(mu[q], mv[q], k0[q], ray.p1, ray.p2, ray.c, s);
         if (head) {
-          re[q] = fma(ray.a, c, re[q]);
-          im[q] = fma(ray.a, sn, im[q]);
+          re[q] = fma(ray.a, at.cs, re[q]);
+          im[q] = fma(ray.a, at.sn, im[q]);
         }
-        const double hu = (0.5 * mu[q]) * inverse, hv = (0.5 * mv[q]) * inverse;  // -u / d, -v / d
+        const double hu = (0.5 * mu[q]) * at.inverse, hv = (0.5 * mv[q]) * at.inverse;  // -u / d, -v / d
 #pragma unroll
         for (int j = 0; j < P; ++j) {
-          const PsfgPar p = tile_par[j][r];
+          const PsfPar p = tile_par[j][r];
           const double ag = ray.a * fma(hu, p.q1, fma(hv, p.q2, p.e));  // a g_k, g_k = e_k - (u q_k1 + v q_k2) / d
-          are[q][j] = fma(ag, sn, are[q][j]);
-          aim[q][j] = fma(ag, c, aim[q][j]);
+          are[q][j] = fma(ag, at.sn, are[q][j]);
+          aim[q][j] = fma(ag, at.cs, aim[q][j]);
         }
       }
     }
@@ -396,17 +298,8 @@ extern "C" int64_t prt_frame_psf_gradient_workspace_bytes(int64_t n_selected, in
   // the staged and the sorted rays, the sort's index, the rays' buckets, the staged parameters
   return ((int64_t)n_groups + 1) * 8 + (int64_t)n_groups * 6 * 8 + 4 * psf_buckets_bytes(n_groups, n_wavelengths) + 8 +
          (int64_t)n_groups * 8 +
-         n_selected * (int64_t)(2 * sizeof(PsfRay) + sizeof(int64_t) + sizeof(int) + (size_t)n_parameters * sizeof(PsfgPar)) +
+         n_selected * (int64_t)(2 * sizeof(PsfRay) + sizeof(int64_t) + sizeof(int) + (size_t)n_parameters * sizeof(PsfPar)) +
          64;
-}
-
-template <int P>
-static void psfg_launch_huygens(dim3 grid, hipStream_t st, const PsfRay* sorted, const PsfgPar* par, int64_t n_selected,
-                                const int64_t* bucket_total, const int64_t* bucket_start, const double* groups,
-                                PsfLambda lambda, int K, int first, int chunks, int nx, int ny, double du, double dv,
-                                double u0, double v0, int slices, double* slab) {
-  hipLaunchKernelGGL(k_psfg_huygens<P>, grid, dim3(kPsfBlock), 0, st, sorted, par, n_selected, bucket_total,
-                     bucket_start, groups, lambda, K, first, chunks, nx, ny, du, dv, u0, v0, slices, slab);
 }
 
 extern "C" int prt_frame_psf_gradient(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
@@ -432,25 +325,10 @@ extern "C" int prt_frame_psf_gradient(int device, const double* rows, int64_t ld
   for (int g = 0; g < n_groups; ++g)
     if (group_first[g] > group_first[g + 1]) return fail(PRT_ERR_ARG, "psf_gradient: group_first does not decrease");
   if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
-  if (n_wavelengths < 1 || n_wavelengths > PSF_MAX_WAVELENGTHS)
-    return fail(PRT_ERR_ARG, "psf_gradient: 1 to 16 distinct wavelengths");
-  if (!(world_unit_um > 0 && world_unit_um < PRT_INF)) return fail(PRT_ERR_ARG, "world_unit_um: finite and > 0");
   PsfLambda lambda;
-  lambda.n = n_wavelengths;
-  for (int k = 0; k < PSF_MAX_WAVELENGTHS; ++k) lambda.value[k] = lambda.s[k] = 0.0;
-  for (int k = 0; k < n_wavelengths; ++k) {
-    const double w = wavelengths_um[k];
-    if (!(w > 0 && w < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: finite and > 0");
-    for (int q = 0; q < k; ++q)
-      if (wavelengths_um[q] == w) return fail(PRT_ERR_ARG, "wavelengths: distinct");
-    lambda.value[k] = w;
-    lambda.s[k] = 1.0 / (w / world_unit_um);
-    if (!(lambda.s[k] < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: wavelength / world_unit_um underflows");
-  }
-  if (nx < 1 || nx > PSF_MAX_SIDE || ny < 1 || ny > PSF_MAX_SIDE)
-    return fail(PRT_ERR_ARG, "psf_gradient: nx, ny in 1..1024");
-  if (!(du > 0 && du < PRT_INF && dv > 0 && dv < PRT_INF)) return fail(PRT_ERR_ARG, "psf_gradient: du, dv finite and > 0");
-  if (!(std::isfinite(centre_uv[0]) && std::isfinite(centre_uv[1]))) return fail(PRT_ERR_ARG, "psf_gradient: centre finite");
+  int rc = psf_lambda("psf_gradient", wavelengths_um, n_wavelengths, world_unit_um, lambda);
+  if (!rc) rc = psf_grid("psf_gradient", nx, ny, du, dv, centre_uv);
+  if (rc) return rc;
   const int64_t buckets = (int64_t)n_groups * n_wavelengths, npix = (int64_t)nx * ny;
   // (the grid's z holds bucket x chunk: sized for 16 parameters whatever K is)
   if (buckets > 65535 / (PSFG_MAX_PARAMETERS / kPsfgParams))
@@ -458,10 +336,8 @@ extern "C" int prt_frame_psf_gradient(int device, const double* rows, int64_t ld
   // the slab is sized for 16 parameters whatever K is, so that the slices do not follow K
   if ((size_t)buckets * npix * kPsfgQuantities * 16 > kPsfSlabBytes)
     return fail(PRT_ERR_ARG, "psf_gradient: n_groups * n_wavelengths * nx * ny * 17 * 16 bytes above the 256 MiB slab cap");
-  int rc = ops_device(device);
-  if (rc) return rc;
   int cus = 1;
-  rc = hist_cus(device, &cus);
+  rc = psf_device(device, &cus);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_psf_gradient_workspace_bytes)
@@ -476,71 +352,55 @@ extern "C" int prt_frame_psf_gradient(int device, const double* rows, int64_t ld
   PsfRay* stage = (PsfRay*)(((uintptr_t)(norm + n_groups) + 31) & ~(uintptr_t)31);
   PsfRay* sorted = stage + n_selected;
   int64_t* order = (int64_t*)(sorted + n_selected);
-  PsfgPar* par = (PsfgPar*)(order + n_selected);
+  PsfPar* par = (PsfPar*)(order + n_selected);
   int* bucket_of = (int*)(par + (size_t)K * n_selected);
-  // the sort's passes: waves of contiguous selected rows, as many as the (wave, bucket) counts allow
-  int64_t waves = wf_waves(n_selected, 1);
-  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kPsfCountBytes / ((size_t)buckets * 8))));
-  const int64_t per_wave = ((n_selected + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  // ray slices: enough workgroups to fill the CUs, slices of at least kPsfgMinSlice rows of an average bucket
-  const int64_t tiles = (npix + kPsfTile - 1) / kPsfTile;
-  int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);
-  slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_selected / (buckets * kPsfgMinSlice)));
-  slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * kPsfgQuantities * 16)));
-  slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));
-  if (tiles > 0x7fffffff || (n_selected + PRT_BLOCK - 1) / PRT_BLOCK > 0x7fffffff ||
+  // the sort walks the selection; the slab is capped for 16 parameters and allocated for K
+  const PsfPlan plan = psf_plan(cus, n_selected, buckets, buckets, npix, kPsfTile, kPsfgQuantities * 16, (K + 1) * 16,
+                                (1 + K) * 3);
+  const int slices = (int)plan.slices;
+  if (plan.tiles > 0x7fffffff || (n_selected + PRT_BLOCK - 1) / PRT_BLOCK > 0x7fffffff ||
       (buckets * (K + 1) * npix + PRT_BLOCK - 1) / PRT_BLOCK > 0x7fffffff)
     return fail(PRT_ERR_ARG, "psf_gradient: too many rows or outputs for one launch");
-  const size_t count_bytes = (size_t)all_waves * buckets * 8;
-  const size_t strehl_bytes = (size_t)buckets * slices * (1 + K) * 3 * sizeof(double);
-  const size_t slab_bytes = (size_t)buckets * slices * (K + 1) * npix * 2 * sizeof(double);
-  char* scratch = nullptr;
-  HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + strehl_bytes + slab_bytes, st));
-  int64_t* counts = (int64_t*)scratch;
-  double* strehl_slab = (double*)(scratch + count_bytes);
-  double* slab = (double*)(scratch + count_bytes + strehl_bytes);
+  PsfScratch scratch;
+  rc = psf_scratch(st, plan, missed, (size_t)buckets * 16 + 8, scratch);  // (missed, unfollowed and the status word)
+  if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(d_group, group_first, ((size_t)n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(groups, wavefront_groups, (size_t)n_groups * 6 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(counts, 0, count_bytes, st));
-  HIP_TRY(hipMemsetAsync(missed, 0, (size_t)buckets * 16 + 8, st));  // (missed, unfollowed and the status word)
-  hipLaunchKernelGGL(k_psfg_stage, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, selected, n_selected, n_groups,
-                     d_group, opd, pupil, groups, weight_column, lambda, dphase, dpoint, K, per_wave, stage, bucket_of,
-                     counts, (int)buckets, missed, unfollowed, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, (int)buckets, counts,
-                     bucket_total, bucket_start);
-  hipLaunchKernelGGL(k_psfg_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, n_selected, per_wave, bucket_of, stage, counts,
-                     (int)buckets, sorted, order);
+  hipLaunchKernelGGL(k_psfg_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, selected, n_selected,
+                     n_groups, d_group, opd, pupil, groups, weight_column, lambda, dphase, dpoint, K, plan.per_wave, stage,
+                     bucket_of, scratch.counts, (int)buckets, missed, unfollowed, status);
+  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)plan.all_waves, (int)buckets,
+                     scratch.counts, bucket_total, bucket_start);
+  hipLaunchKernelGGL(k_psfg_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, n_selected, plan.per_wave, bucket_of,
+                     stage, scratch.counts, (int)buckets, sorted, order);
   if (n_selected)
     hipLaunchKernelGGL(k_psfg_stage_par, dim3((unsigned)((n_selected + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0,
                        st, rows, ld, selected, n_selected, n_groups, d_group, groups, lambda, bucket_total, bucket_start,
                        (int)buckets, order, dphase, dpoint, K, par);
-  hipLaunchKernelGGL(k_psfg_strehl, dim3((unsigned)slices, (unsigned)buckets, (unsigned)(1 + K)), dim3(kPsfBlock), 0, st,
-                     sorted, par, n_selected, bucket_total, bucket_start, groups, lambda, (int)slices, K, strehl_slab);
+  hipLaunchKernelGGL(k_psf_strehl, dim3((unsigned)slices, (unsigned)buckets, (unsigned)(1 + K)), dim3(kPsfBlock), 0, st,
+                     sorted, par, n_selected, bucket_total, bucket_start, groups, lambda, 6, slices, K,
+                     scratch.strehl_slab);
   hipLaunchKernelGGL(k_psfg_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
-                     strehl_slab, (int)slices, n_groups, K, lambda, bucket_total, missed, unfollowed, record_out,
+                     scratch.strehl_slab, slices, n_groups, K, lambda, bucket_total, missed, unfollowed, record_out,
                      strehl_out, norm);
   // whole chunks of kPsfgParams parameters in one launch, then the rest in the smallest instantiation that holds it
   const int whole = K / kPsfgParams, rest = K - whole * kPsfgParams;
   auto sum = [&](auto chunk, int chunks, int first) {
-    psfg_launch_huygens<decltype(chunk)::value>(dim3((unsigned)tiles, (unsigned)slices, (unsigned)(buckets * chunks)), st,
-                                                sorted, par, n_selected, bucket_total, bucket_start, groups, lambda, K,
-                                                first, chunks, nx, ny, du, dv, centre_uv[0], centre_uv[1], (int)slices,
-                                                slab);
+    hipLaunchKernelGGL(k_psfg_huygens<decltype(chunk)::value>,
+                       dim3((unsigned)plan.tiles, (unsigned)slices, (unsigned)(buckets * chunks)), dim3(kPsfBlock), 0, st,
+                       sorted, par, n_selected, bucket_total, bucket_start, groups, lambda, K, first, chunks, nx, ny, du,
+                       dv, centre_uv[0], centre_uv[1], slices, scratch.slab);
   };
   if (whole) sum(std::integral_constant<int, kPsfgParams>(), whole, 0);
   if (rest > 2) sum(std::integral_constant<int, 4>(), 1, whole * kPsfgParams);
   else if (rest == 2) sum(std::integral_constant<int, 2>(), 1, whole * kPsfgParams);
   else if (rest == 1) sum(std::integral_constant<int, 1>(), 1, whole * kPsfgParams);
   hipLaunchKernelGGL(k_psfg_fold, dim3((unsigned)((buckets * (K + 1) * npix + PRT_BLOCK - 1) / PRT_BLOCK)),
-                     dim3(PRT_BLOCK), 0, st, slab, (int)slices, (int)buckets, K, npix, lambda, norm, amplitude_out,
+                     dim3(PRT_BLOCK), 0, st, scratch.slab, slices, (int)buckets, K, npix, lambda, norm, amplitude_out,
                      damplitude_out, image_out, dimage_out);
-  int host_status = 0;
-  HIP_TRY(hipMemcpyAsync(&host_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipFreeAsync(scratch, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host arrays outlive their copies)
-  HIP_TRY(hipGetLastError());
+  int host_status;
+  rc = psf_finish(st, status, scratch, &host_status);
+  if (rc) return rc;
   if (host_status & PSFG_BAD_ROW) return fail(PRT_ERR_ARG, "psf_gradient: a selected row number is outside the frame");
   if (host_status & PSFG_BAD_WAVELENGTH)
     return fail(PRT_ERR_ARG, "psf_gradient: a selected row's wavelength is not in the list");

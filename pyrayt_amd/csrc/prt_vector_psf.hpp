@@ -1,12 +1,13 @@
 // prt_vector_psf.hpp -- the polarised diffraction PSF: the Huygens sum of prt_psf.hpp with the complex field vectors of
 // prt_fresnel.hpp / prt_coatings.hpp as the rays' amplitudes.  Definitions: include/prt.h.
-// It reuses prt_psf.hpp's k_psf_count, k_psf_scan, k_psf_offsets, psf_slice and psf_sqrt; the rays are sorted into
-// (group, wavelength) buckets exactly as there, and the one or two states of a ray lie in planes of n_rows rays, so a
-// (group, wavelength, state) bucket is the bucket's range in the state's plane.
+// It stands on prt_psf.hpp's Huygens core (the wavelength list, the plan, the scratch, psf_wavelength, psf_keep, psf_tally,
+// psf_place, psf_slice, psf_pixel, psf_phase, psf_tree) and reuses k_psf_count, k_psf_scan and k_psf_offsets; the rays are
+// sorted into (group, wavelength) buckets exactly as there, and the one or two states of a ray lie in planes of n_rows
+// rays, so a (group, wavelength, state) bucket is the bucket's range in the state's plane.
 //
 //   k_vpsf_stage    per selected row, in row order: p1, p2, c = (OPD - R) s and, per state, the amplitude sqrt(w) E
 //                   projected once on (e1, e2, a); beside it sqrt(w) and |E|^2; rays left out counted (integer atomics)
-//   k_vpsf_scatter  the stable counting sort of k_psf_scatter on the 72-byte rays, state by state
+//   k_vpsf_scatter  the stable counting sort (psf_place) on the 72-byte rays, state by state
 //   k_vpsf_strehl   per (ray slice, bucket): the six sums of c_k exp(2 pi i OPD s) in fp64, sum sqrt(w), sum |A|,
 //                   sum w |E|^2 and sum w, a fixed tree order
 //   k_vpsf_record   per group: the slices folded in order, the record, the two Strehl ratios, the throughput, D_g
@@ -49,10 +50,7 @@ k_vpsf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
     int bucket = -1;
     if (chosen) {
       const int64_t pos = at + __popcll(ballot & ((1ull << lane) - 1ull));
-      const double wavelength = rows[PRT_COL_WAVELENGTH * ld + j];
-      int k = -1;
-      for (int q = 0; q < lambda.n; ++q)
-        if (k < 0 && lambda.value[q] == wavelength) k = q;
+      const int k = psf_wavelength(lambda, rows[PRT_COL_WAVELENGTH * ld + j]);
       if (k < 0) {
         atomicOr(status, PSF_BAD_WAVELENGTH);
       } else {
@@ -69,7 +67,7 @@ k_vpsf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
             ei[s][q] = s < n_states && field_planes == 12 ? field[(int64_t)(6 + 3 * s + q) * field_ld + j] : 0.0;
             finite = finite && fabs(er[s][q]) < PRT_INF && fabs(ei[s][q]) < PRT_INF;  // (false for a NaN)
           }
-        if (o == o && x == x && y == y && w >= 0.0 && w < PRT_INF && finite) {
+        if (psf_keep(o, x, y, w) && finite) {
           bucket = group * lambda.n + k;
           const double rho = g[5], sl = lambda.s[k], a = sqrt(w);
 #pragma unroll
@@ -97,14 +95,7 @@ k_vpsf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
       bucket_of[pos] = bucket;
     }
     at += __popcll(ballot);
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {  // one turn per bucket present in the slice: almost always exactly one
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      if (lane == 0) mine[b] += __popcll(take);
-      pending &= ~take;
-    }
+    psf_tally(lane, bucket, mine);
   }
 }
 
@@ -113,31 +104,14 @@ k_vpsf_scatter(const int64_t* __restrict__ wave_rows, const int64_t* __restrict_
                const int* __restrict__ bucket_of, const VpsfRay* __restrict__ stage,
                const VpsfSide* __restrict__ stage_side, int64_t* __restrict__ offsets, int buckets, int64_t n_rows,
                int n_states, VpsfRay* __restrict__ sorted, VpsfSide* __restrict__ sorted_side) {
-  const int lane = threadIdx.x & 63;
   const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t from = wave_offset[wave], to = from + wave_rows[wave];
-  int64_t* const mine = offsets + wave * buckets;  // (only this wave reads and writes here)
-  for (int64_t base = from; base < to; base += 64) {
-    const int64_t r = base + lane;
-    const int bucket = r < to ? bucket_of[r] : -1;
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      int64_t at = lane == 0 ? mine[b] : 0;
-      at = __shfl(at, 0);
-      if (bucket == b) {
-        const int64_t to_row = at + __popcll(take & ((1ull << lane) - 1ull));
-        for (int s = 0; s < n_states; ++s) {
-          sorted[(int64_t)s * n_rows + to_row] = stage[(int64_t)s * n_rows + r];
-          sorted_side[(int64_t)s * n_rows + to_row] = stage_side[(int64_t)s * n_rows + r];
-        }
-      }
-      if (lane == 0) mine[b] = at + __popcll(take);
-      pending &= ~take;
+  const int64_t from = wave_offset[wave];  // (offsets + wave * buckets: only this wave reads and writes there)
+  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets, [&](int64_t r, int64_t pos) {
+    for (int s = 0; s < n_states; ++s) {
+      sorted[(int64_t)s * n_rows + pos] = stage[(int64_t)s * n_rows + r];
+      sorted_side[(int64_t)s * n_rows + pos] = stage_side[(int64_t)s * n_rows + r];
     }
-  }
+  });
 }
 
 // bucket = (group * n_wavelengths + wavelength) * n_states + state
@@ -158,9 +132,8 @@ k_vpsf_strehl(const VpsfRay* __restrict__ sorted, const VpsfSide* __restrict__ s
   for (int64_t r = lo + t; r < hi; r += kPsfBlock) {
     const VpsfRay ray = rays[r];
     const VpsfSide side = sides[r];
-    const double phase = fma(radius, s, ray.c);  // OPD / lambda_w, in cycles
     double sn, cs;
-    sincospi(2.0 * (phase - rint(phase)), &sn, &cs);
+    psf_chief_phase(radius, s, ray.c, sn, cs);
     for (int k = 0; k < 3; ++k) {
       sum[2 * k] += ray.re[k] * cs - ray.im[k] * sn;
       sum[2 * k + 1] += ray.re[k] * sn + ray.im[k] * cs;
@@ -171,12 +144,7 @@ k_vpsf_strehl(const VpsfRay* __restrict__ sorted, const VpsfSide* __restrict__ s
     sum[9] += side.a * side.a;
   }
   for (int k = 0; k < VPSF_SUMS; ++k) red[k][t] = sum[k];
-  for (int half = kPsfBlock / 2; half > 0; half >>= 1) {  // (a fixed tree)
-    __syncthreads();
-    if (t < half)
-      for (int k = 0; k < VPSF_SUMS; ++k) red[k][t] += red[k][t + half];
-  }
-  __syncthreads();
+  psf_tree(red, t);
   if (t < VPSF_SUMS) strehl_slab[((size_t)b * slices + slice) * VPSF_SUMS + t] = red[t][0];
 }
 
@@ -242,9 +210,8 @@ k_vpsf_huygens(const VpsfRay* __restrict__ sorted, int64_t n_rows, int n_states,
   double mu[kVpsfPix], mv[kVpsfPix], k0[kVpsfPix], re[3][kVpsfPix], im[3][kVpsfPix];
 #pragma unroll
   for (int q = 0; q < kVpsfPix; ++q) {
-    const int64_t pix = (int64_t)blockIdx.x * kVpsfTile + q * kPsfBlock + t;
-    const int i = pix < npix ? (int)(pix / ny) : 0, j = pix < npix ? (int)(pix - (int64_t)(pix / ny) * ny) : 0;
-    const double u = u0 + ((double)i - 0.5 * (nx - 1)) * du, v = v0 + ((double)j - 0.5 * (ny - 1)) * dv;
+    double u, v;
+    psf_pixel((int64_t)blockIdx.x * kVpsfTile + q * kPsfBlock + t, npix, nx, ny, du, dv, u0, v0, u, v);
     mu[q] = -2.0 * u;
     mv[q] = -2.0 * v;
     k0[q] = radius * radius + u * u + v * v;
@@ -263,11 +230,8 @@ k_vpsf_huygens(const VpsfRay* __restrict__ sorted, int64_t n_rows, int n_states,
       const VpsfRay ray = tile[r];
 #pragma unroll
       for (int q = 0; q < kVpsfPix; ++q) {
-        const double d2 = fma(mu[q], ray.p1, fma(mv[q], ray.p2, k0[q]));  // |x - E|^2
-        const double phase = fma(psf_sqrt(d2), s, ray.c);                  // (OPD + d - R) / lambda_w, cycles
-        const float turn = (float)__builtin_amdgcn_fract(phase);           // [0, 1)
-        const double cs = (double)__builtin_amdgcn_cosf(turn);             // (v_cos_f32 / v_sin_f32 take turns)
-        const double sn = (double)__builtin_amdgcn_sinf(turn);
+        const PsfPhase at = psf_phase(mu[q], mv[q], k0[q], ray.p1, ray.p2, ray.c, s);
+        const double cs = at.cs, sn = at.sn;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {  // (re + i im) += (ray.re + i ray.im)(cs + i sn)
           re[k][q] = fma(ray.re[k], cs, fma(-ray.im[k], sn, re[k][q]));
@@ -343,13 +307,10 @@ extern "C" int prt_frame_vector_psf(int device, const double* rows, int64_t ld, 
     return fail(PRT_ERR_ARG, "bad buffers");
   if (!(rays_per_source > 0) && n_groups != 1) return fail(PRT_ERR_ARG, "one group without rays_per_source");
   if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
-  if (n_wavelengths < 1 || n_wavelengths > PSF_MAX_WAVELENGTHS)
-    return fail(PRT_ERR_ARG, "vector psf: 1 to 16 distinct wavelengths");
   if (field_planes != 6 && field_planes != 12)
     return fail(PRT_ERR_ARG, "vector psf: field_planes is 6 (real fields) or 12 (real parts, then imaginary parts)");
   if (n_states != 1 && n_states != 2) return fail(PRT_ERR_ARG, "vector psf: n_states is 1 (Ea) or 2 (Ea and Eb)");
   if (field_ld < n_rows) return fail(PRT_ERR_ARG, "vector psf: field_ld below n_rows");
-  if (!(world_unit_um > 0 && world_unit_um < PRT_INF)) return fail(PRT_ERR_ARG, "world_unit_um: finite and > 0");
   VpsfAxes frame;  // (the wavefront's order is a, e1, e2)
   for (int k = 0; k < 3; ++k) {
     if (!(std::isfinite(axes[k]) && std::isfinite(axes[3 + k]) && std::isfinite(axes[6 + k])))
@@ -359,30 +320,17 @@ extern "C" int prt_frame_vector_psf(int device, const double* rows, int64_t ld, 
     frame.e[2][k] = axes[k];
   }
   PsfLambda lambda;
-  lambda.n = n_wavelengths;
-  for (int k = 0; k < PSF_MAX_WAVELENGTHS; ++k) lambda.value[k] = lambda.s[k] = 0.0;
-  for (int k = 0; k < n_wavelengths; ++k) {
-    const double w = wavelengths_um[k];
-    if (!(w > 0 && w < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: finite and > 0");
-    for (int q = 0; q < k; ++q)
-      if (wavelengths_um[q] == w) return fail(PRT_ERR_ARG, "wavelengths: distinct");
-    lambda.value[k] = w;
-    lambda.s[k] = 1.0 / (w / world_unit_um);
-    if (!(lambda.s[k] < PRT_INF)) return fail(PRT_ERR_ARG, "wavelengths: wavelength / world_unit_um underflows");
-  }
-  if (nx < 1 || nx > PSF_MAX_SIDE || ny < 1 || ny > PSF_MAX_SIDE) return fail(PRT_ERR_ARG, "psf: nx, ny in 1..1024");
-  if (!(du > 0 && du < PRT_INF && dv > 0 && dv < PRT_INF)) return fail(PRT_ERR_ARG, "psf: du, dv finite and > 0");
-  if (!(std::isfinite(centre_uv[0]) && std::isfinite(centre_uv[1]))) return fail(PRT_ERR_ARG, "psf: centre finite");
+  int rc = psf_lambda("vector psf", wavelengths_um, n_wavelengths, world_unit_um, lambda);
+  if (!rc) rc = psf_grid("psf", nx, ny, du, dv, centre_uv);
+  if (rc) return rc;
   const int64_t group_waves = (int64_t)n_groups * n_wavelengths, buckets = group_waves * n_states;
   const int64_t npix = (int64_t)nx * ny;
   if (buckets > 65535) return fail(PRT_ERR_ARG, "vector psf: n_groups * n_wavelengths * n_states <= 65535");
   if ((size_t)buckets * npix * kVpsfPixelBytes > kPsfSlabBytes)
     return fail(PRT_ERR_ARG,
                 "vector psf: n_groups * n_wavelengths * n_states * nx * ny * 48 bytes above the 256 MiB slab cap");
-  int rc = ops_device(device);
-  if (rc) return rc;
   int cus = 1;
-  rc = hist_cus(device, &cus);
+  rc = psf_device(device, &cus);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_vector_psf_workspace_bytes)
@@ -398,55 +346,37 @@ extern "C" int prt_frame_vector_psf(int device, const double* rows, int64_t ld, 
   VpsfSide* stage_side = (VpsfSide*)(sorted + n_states * n_rows);
   VpsfSide* sorted_side = stage_side + n_states * n_rows;
   int* bucket_of = (int*)(sorted_side + n_states * n_rows);
-  // row passes: waves of contiguous rows, as many as the (wave, bucket) counts allow
-  int64_t waves = wf_waves(n_rows, 1);
-  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kPsfCountBytes / ((size_t)group_waves * 8))));
-  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  // ray slices: enough workgroups to fill the CUs, slices of at least kPsfMinSlice rays of an average bucket
-  const int64_t tiles = (npix + kVpsfTile - 1) / kVpsfTile;
-  int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);
-  slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_rows / (group_waves * kPsfMinSlice)));
-  slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * kVpsfPixelBytes)));
-  slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));
-  const size_t count_bytes = (size_t)all_waves * group_waves * 8;
-  const size_t slab_bytes = (size_t)buckets * slices * npix * kVpsfPixelBytes;
-  const size_t strehl_bytes = (size_t)buckets * slices * VPSF_SUMS * sizeof(double);
-  char* scratch = nullptr;
-  HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + strehl_bytes + slab_bytes, st));
-  int64_t* counts = (int64_t*)scratch;
-  double* strehl_slab = (double*)(scratch + count_bytes);
-  double* slab = (double*)(scratch + count_bytes + strehl_bytes);
-  HIP_TRY(hipMemsetAsync(counts, 0, count_bytes, st));
-  HIP_TRY(hipMemsetAsync(skipped, 0, (size_t)group_waves * 8 + 8, st));  // (and the status word)
-  hipLaunchKernelGGL(k_psf_count, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, per_wave, wave_rows);
-  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, wave_rows, wave_offset);
-  hipLaunchKernelGGL(k_vpsf_stage, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, per_wave, wave_offset, opd, pupil, group_record, weight_column, lambda,
-                     field, field_ld, field_planes, n_states, frame, stage, stage_side, bucket_of, counts,
+  const PsfPlan plan =
+      psf_plan(cus, n_rows, group_waves, buckets, npix, kVpsfTile, kVpsfPixelBytes, kVpsfPixelBytes, VPSF_SUMS);
+  const int slices = (int)plan.slices, all_waves = (int)plan.all_waves;
+  PsfScratch scratch;
+  rc = psf_scratch(st, plan, skipped, (size_t)group_waves * 8 + 8, scratch);  // (the skips and the status word)
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_psf_count, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, plan.per_wave, wave_rows);
+  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, wave_rows, wave_offset);
+  hipLaunchKernelGGL(k_vpsf_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, plan.per_wave, wave_offset, opd, pupil, group_record, weight_column, lambda,
+                     field, field_ld, field_planes, n_states, frame, stage, stage_side, bucket_of, scratch.counts,
                      (int)group_waves, skipped, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)all_waves, (int)group_waves, counts,
+  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, (int)group_waves, scratch.counts,
                      bucket_total, bucket_start);
-  hipLaunchKernelGGL(k_vpsf_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
-                     stage_side, counts, (int)group_waves, n_rows, n_states, sorted, sorted_side);
+  hipLaunchKernelGGL(k_vpsf_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
+                     stage_side, scratch.counts, (int)group_waves, n_rows, n_states, sorted, sorted_side);
   hipLaunchKernelGGL(k_vpsf_strehl, dim3((unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st, sorted,
-                     sorted_side, n_rows, n_states, bucket_total, bucket_start, group_record, lambda, (int)slices,
-                     strehl_slab);
+                     sorted_side, n_rows, n_states, bucket_total, bucket_start, group_record, lambda, slices,
+                     scratch.strehl_slab);
   hipLaunchKernelGGL(k_vpsf_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
-                     strehl_slab, (int)slices, n_groups, n_states, lambda, bucket_total, skipped, record_out,
+                     scratch.strehl_slab, slices, n_groups, n_states, lambda, bucket_total, skipped, record_out,
                      strehl_out, norm);
-  hipLaunchKernelGGL(k_vpsf_huygens, dim3((unsigned)tiles, (unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0,
+  hipLaunchKernelGGL(k_vpsf_huygens, dim3((unsigned)plan.tiles, (unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0,
                      st, sorted, n_rows, n_states, bucket_total, bucket_start, group_record, lambda, nx, ny, du, dv,
-                     centre_uv[0], centre_uv[1], (int)slices, slab);
+                     centre_uv[0], centre_uv[1], slices, scratch.slab);
   hipLaunchKernelGGL(k_vpsf_fold, dim3((unsigned)((group_waves * npix + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK),
-                     0, st, slab, (int)slices, (int)group_waves, n_states, npix, lambda, norm, stokes_out);
-  int host_status = 0;
-  HIP_TRY(hipMemcpyAsync(&host_status, status, sizeof(int), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipFreeAsync(scratch, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipGetLastError());
+                     0, st, scratch.slab, slices, (int)group_waves, n_states, npix, lambda, norm, stokes_out);
+  int host_status;
+  rc = psf_finish(st, status, scratch, &host_status);
+  if (rc) return rc;
   if (host_status & PSF_BAD_WAVELENGTH)
     return fail(PRT_ERR_ARG, "vector psf: a selected row's wavelength is not in the list");
   return PRT_OK;

@@ -604,16 +604,7 @@ class DeviceFrame:
                 raise ValueError("psf: the fields were not kept (fresnel(fields=True))")
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         nx, ny = _pixel_counts(pixels)
-        step = None
-        if pixel_size is not None:
-            pair = np.asarray(pixel_size, dtype=float).reshape(-1)
-            pair = np.repeat(pair, 2) if pair.size == 1 else pair
-            if pair.shape != (2,) or not np.all(np.isfinite(pair)) or not np.all(pair > 0):
-                raise ValueError(f"pixel_size: a positive number or (du, dv), or None (got {pixel_size!r})")
-            step = (float(pair[0]), float(pair[1]))
-        uv0 = np.asarray(centre, dtype=float)
-        if uv0.shape != (2,) or not np.all(np.isfinite(uv0)):
-            raise ValueError(f"centre: (u0, v0), finite (got {centre!r})")
+        step, uv0 = _pixel_grid(pixel_size, centre)
         if weights is not None and weights not in _INDEX:
             raise ValueError(f"weights: None or a column name (got {weights!r})")
         self._need_whole("psf")
@@ -622,14 +613,7 @@ class DeviceFrame:
         wavelengths = self._psf_wavelengths(surface_id, generation)
         wave, rows, surface_id, n_groups, record = self._wavefront(
             surface_id, reference, radius, axis, basis, None, 15, weights, generation, rays_per_source, n_groups)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            f_number = np.where(wave.n_rays > 0, wave.radius / (2.0 * wave.pupil_radius), np.nan)
-        if step is None:
-            finite = f_number[np.isfinite(f_number) & (f_number > 0)]
-            if not len(finite):
-                raise ValueError("psf: no group has rays that meet the reference sphere; give pixel_size")
-            side = float(wavelengths.min()) / unit * float(finite.min()) / 4.0
-            step = (side, side)
+        f_number, step = _f_number_and_step(wave, wavelengths, unit, step, "psf")
         dev = rows.device
         n_rows = rows.shape[1]
         n_w = len(wavelengths)
@@ -718,11 +702,7 @@ class DeviceFrame:
             values = np.unique(np.asarray(lam, dtype=np.float64))
         if not len(values):
             raise ValueError("psf: no row is selected at this surface")
-        if not np.all(np.isfinite(values) & (values > 0)):
-            raise ValueError("psf: a selected row's wavelength is not finite and > 0")
-        if len(values) > 16:
-            raise ValueError(f"psf: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
-        return values
+        return _distinct_wavelengths(values, "psf")
 
     # --- geometric MTF through focus (no counterpart upstream) --------------------------------------------------------
     def mtf(self, surface, frequencies, *, azimuths=(0.0, 90.0), focus=(0.0,), reference="centroid", axis=None,
@@ -2967,16 +2947,7 @@ class Sensitivity:
                              "the PSF's derivative is taken for the other kinds of parameter")
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         nx, ny = _pixel_counts(pixels)
-        step = None
-        if pixel_size is not None:
-            pair = np.asarray(pixel_size, dtype=float).reshape(-1)
-            pair = np.repeat(pair, 2) if pair.size == 1 else pair
-            if pair.shape != (2,) or not np.all(np.isfinite(pair)) or not np.all(pair > 0):
-                raise ValueError(f"pixel_size: a positive number or (du, dv), or None (got {pixel_size!r})")
-            step = (float(pair[0]), float(pair[1]))
-        uv0 = np.asarray(centre, dtype=float)
-        if uv0.shape != (2,) or not np.all(np.isfinite(uv0)):
-            raise ValueError(f"centre: (u0, v0), finite (got {centre!r})")
+        step, uv0 = _pixel_grid(pixel_size, centre)
         rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
         dev = rows.device
         n_groups, K, n_rows, n_selected = len(first) - 1, self.n_parameters, rows.shape[1], int(self._selected.shape[0])
@@ -2986,19 +2957,9 @@ class Sensitivity:
             raise ValueError("psf_gradient: the frame was recorded without the wavelength column (RecordPlan(columns=...))")
         if not n_selected:
             raise ValueError("psf_gradient: no row is selected at this surface")
-        values = rows[_INDEX["wavelength"]][self._selected].unique().cpu().numpy().astype(np.float64)
-        if not np.all(np.isfinite(values) & (values > 0)):
-            raise ValueError("psf_gradient: a selected row's wavelength is not finite and > 0")
-        if len(values) > 16:
-            raise ValueError(f"psf_gradient: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
-        with np.errstate(invalid="ignore", divide="ignore"):
-            f_number = np.where(np.asarray(wave.n_rays) > 0, np.asarray(wave.radius) / (2.0 * np.asarray(wave.pupil_radius)), np.nan)
-        if step is None:
-            finite = f_number[np.isfinite(f_number) & (f_number > 0)]
-            if not len(finite):
-                raise ValueError("psf_gradient: no group has rays that meet the reference sphere; give pixel_size")
-            side = float(values.min()) / unit * float(finite.min()) / 4.0
-            step = (side, side)
+        values = _distinct_wavelengths(
+            rows[_INDEX["wavelength"]][self._selected].unique().cpu().numpy().astype(np.float64), "psf_gradient")
+        f_number, step = _f_number_and_step(wave, values, unit, step, "psf_gradient")
         groups = np.ascontiguousarray(np.column_stack([wave.reference, wave.radius, wave.pivot, wave.pupil_radius]),
                                       dtype=np.float64)
         n_w = len(values)
@@ -3310,6 +3271,43 @@ def _pixel_counts(pixels):
                                  for k in pair):
         raise ValueError(f"pixels: an int or (nx, ny), each 1..1024 (got {pixels!r})")
     return int(pair[0]), int(pair[1])
+
+
+def _pixel_grid(pixel_size, centre):
+    """pixel_size: a number, (du, dv) or None; centre: (u0, v0).  Returns the step (None: the default) and the centre."""
+    step = None
+    if pixel_size is not None:
+        pair = np.asarray(pixel_size, dtype=float).reshape(-1)
+        pair = np.repeat(pair, 2) if pair.size == 1 else pair
+        if pair.shape != (2,) or not np.all(np.isfinite(pair)) or not np.all(pair > 0):
+            raise ValueError(f"pixel_size: a positive number or (du, dv), or None (got {pixel_size!r})")
+        step = (float(pair[0]), float(pair[1]))
+    uv0 = np.asarray(centre, dtype=float)
+    if uv0.shape != (2,) or not np.all(np.isfinite(uv0)):
+        raise ValueError(f"centre: (u0, v0), finite (got {centre!r})")
+    return step, uv0
+
+
+def _distinct_wavelengths(values, name):
+    """The distinct wavelengths of the selected rows as the Huygens passes take them: finite, > 0, at most 16."""
+    if not np.all(np.isfinite(values) & (values > 0)):
+        raise ValueError(f"{name}: a selected row's wavelength is not finite and > 0")
+    if len(values) > 16:
+        raise ValueError(f"{name}: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
+    return values
+
+
+def _f_number_and_step(wave, wavelengths, unit, step, name):
+    """F = R / (2 rho_max) per group (NaN without rays); the step: the caller's, or lambda_min * F_min / 4 both ways."""
+    n_rays, radius, rho = (np.asarray(v) for v in (wave.n_rays, wave.radius, wave.pupil_radius))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        f_number = np.where(n_rays > 0, radius / (2.0 * rho), np.nan)
+    if step is None:
+        finite = f_number[np.isfinite(f_number) & (f_number > 0)]
+        if not len(finite):
+            raise ValueError(f"{name}: no group has rays that meet the reference sphere; give pixel_size")
+        step = (float(wavelengths.min()) / unit * float(finite.min()) / 4.0,) * 2
+    return f_number, step
 
 
 RANK_RCOND = 1e-10  # singular values of Z^T W Z below this share of the largest are dropped (of Z: below 1e-5)

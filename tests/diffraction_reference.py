@@ -92,15 +92,18 @@ def kernel_constants():
 
 
 K = kernel_constants()
-# The host rules below (psf_slices, mtf_slices, mtf_lanes) are Python copies of lines of prt_frame_psf / prt_frame_mtf:
+# The host rules below (psf_slices, mtf_slices, mtf_lanes) are Python copies of lines of psf_plan (with the arguments
+# prt_frame_psf gives it) / prt_frame_mtf:
 # the device's own slice count is not observable, so tests/test_host_diffraction_reference.py holds the copies to the
 # header text (HOST_RULES), and a change of a rule there fails that test instead of moving the GPU tests off their edges.
 HOST_RULES = {
     "prt_psf.hpp": (
+        "const int64_t tiles = (npix + tile_pixels - 1) / tile_pixels;",
         "int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);",
-        "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_rows / (buckets * kPsfMinSlice)));",
-        "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * 16)));",
+        "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_items / (sort_buckets * kPsfMinSlice)));",
+        "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * pixel_bytes)));",
         "slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));",
+        "const PsfPlan plan = psf_plan(cus, n_rows, buckets, buckets, npix, kPsfTile, 16, 16, 3);",
         "const int64_t n = bucket_total[b], per = (n + slices - 1) / slices;"),
     "prt_mtf.hpp": (
         "const int64_t s = (count + kMtfMinSlice - 1) / kMtfMinSlice;",

@@ -15,7 +15,7 @@ What counts as an input: opd, pupil, x_k (``dphase``), y_k (``dpoint``), R, rho,
 1 / lambda_w as the library forms it and the pixel centres.
 
 The budget, u = 2^-53 (``gradient_reference`` evaluates it term by term).
-  U keeps the PSF's: |U~ - U| <= s eps sum a, eps = ``psf_epsilon`` per pixel (the phase path is k_psf_huygens's).
+  U keeps the PSF's: |U~ - U| <= s eps sum a, eps = ``psf_epsilon`` per pixel (the phase path is psf_phase, the function k_psf_huygens calls too).
   dU, per pixel and parameter:
       |dU~_k - dU_k| <= 2 pi s [ sum a |g_k| eps + sum a gamma_k ]
     The first term is the phasor's error times the factor it multiplies.  gamma_k bounds the roundings of g_k itself, to
@@ -68,20 +68,25 @@ def kernel_constants():
 
 K = kernel_constants()
 QUANTITIES = MAX_PARAMETERS + 1  # (kPsfgQuantities: the slab is sized for 16 parameters whatever K is)
-# Python copies of lines of prt_frame_psf_gradient, held to the header's text by tests/test_host_psf_gradient.py
+# Python copies of lines of prt_frame_psf_gradient and of psf_plan (prt_psf.hpp) as it calls it, held
+# to the headers' text by tests/test_host_psf_gradient.py
 HOST_RULES = {
     "prt_psf_gradient.hpp": (
         "enum { PSFG_MAX_PARAMETERS = 16, PSFG_RECORD = 5, PSFG_BAD_WAVELENGTH = 1, PSFG_BAD_ROW = 2 };",
         "static const int kPsfgQuantities = PSFG_MAX_PARAMETERS + 1;",
-        "int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);",
-        "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_selected / (buckets * kPsfgMinSlice)));",
-        "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * kPsfgQuantities * 16)));",
-        "slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));",
+        "static_assert(kPsfgMinSlice == kPsfMinSlice,",
+        "psf_plan(cus, n_selected, buckets, buckets, npix, kPsfTile, kPsfgQuantities * 16, (K + 1) * 16,",
         "const int whole = K / kPsfgParams, rest = K - whole * kPsfgParams;",
         "if (rest > 2) sum(std::integral_constant<int, 4>(), 1, whole * kPsfgParams);",
         "else if (rest == 2) sum(std::integral_constant<int, 2>(), 1, whole * kPsfgParams);",
         "else if (rest == 1) sum(std::integral_constant<int, 1>(), 1, whole * kPsfgParams);",
         "for (int64_t base = lo; base < hi; base += kPsfBlock) {"),
+    "prt_psf.hpp": (
+        "const int64_t tiles = (npix + tile_pixels - 1) / tile_pixels;",
+        "int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);",
+        "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_items / (sort_buckets * kPsfMinSlice)));",
+        "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * pixel_bytes)));",
+        "slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));"),
 }
 
 

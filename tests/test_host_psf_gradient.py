@@ -1,6 +1,6 @@
 """The longdouble reference of the PSF sensitivities (tests/psf_gradient_reference.py) against central differences of the
 PSF's own reference and against closed forms; the Python copies of the partition rules against the header's text; what
-``psf_gradient`` and the entry point refuse without a GPU; the code objects of k_psfg_huygens."""
+``psf_gradient`` and the entry point refuse without a GPU; the code objects of k_psfg_huygens and k_psf_huygens."""
 import os
 import re
 
@@ -117,9 +117,10 @@ def test_step_solves_the_linearised_residuals():
 
 
 def test_the_partition_rules_are_the_headers_own_lines():
-    text = " ".join(open(os.path.join(ROOT, "pyrayt_amd", "csrc", "prt_psf_gradient.hpp")).read().split())
-    for line in P.HOST_RULES["prt_psf_gradient.hpp"]:
-        assert " ".join(line.split()) in text, line
+    for name, lines in P.HOST_RULES.items():
+        text = " ".join(open(os.path.join(ROOT, "pyrayt_amd", "csrc", name)).read().split())
+        for line in lines:
+            assert " ".join(line.split()) in text, (name, line)
     assert (P.K.kPsfgParams, P.K.kPsfgMinSlice, R.K.kPsfBlock, R.K.kPsfTile) == (4, 2048, 256, 1024)
     assert [P.slices(n, 1, 15, 256) for n in (0, 1, 2048, 4095, 4096, 4097, 10 ** 6)] == [1, 1, 1, 1, 2, 2, 488]
     assert P.slices(10 ** 6, 1, 128 * 128, 256) == (256 << 20) // (128 * 128 * 17 * 16) == 60  # (the slab cap, for 16 parameters)
@@ -208,7 +209,8 @@ def test_library_checks_psf_gradient_arguments_without_a_gpu():
 
 
 def test_the_huygens_kernel_uses_no_scratch():
-    """Every k_psfg_huygens instantiation keeps its fp64 accumulators in registers: no private segment, no spills."""
+    """Every k_psfg_huygens instantiation, and the scalar k_psf_huygens that shares their phase path, keeps its fp64
+    accumulators in registers: no private segment, no spills; the scalar kernel fits seven waves per SIMD."""
     import importlib.util
 
     spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
@@ -220,8 +222,10 @@ def test_the_huygens_kernel_uses_no_scratch():
         pytest.skip("llvm-readelf not available")
     if not os.path.exists(engine.LIB_PATH):
         pytest.skip("libprt_hip.so is not built")
-    kernels = {name: res for name, res in mod.kernel_resources(engine.LIB_PATH).items() if "k_psfg_huygens" in name}
-    assert len(kernels) == 3, sorted(kernels)
+    kernels = {name: res for name, res in mod.kernel_resources(engine.LIB_PATH).items() if "k_psfg_huygens" in name or "k_psf_huygens" in name}
+    assert len(kernels) == 4, sorted(kernels)  # (P = 1, 2, 4 and the scalar kernel)
+    scalar = [res for name, res in kernels.items() if "k_psf_huygens" in name]
+    assert len(scalar) == 1 and scalar[0]["vgpr_count"] <= 72, kernels  # (512 / 72: seven waves per SIMD)
     for name, res in kernels.items():
         assert res["private_segment_fixed_size"] == 0, (name, res)
         assert res["vgpr_spill_count"] == 0 and res["sgpr_spill_count"] == 0, (name, res)

@@ -102,11 +102,13 @@ def test_library_checks_vector_psf_arguments_without_a_gpu():
 
 
 def test_the_partition_rules_are_the_headers_own():
-    """vpsf_slices restates lines of prt_frame_vector_psf and the GPU tests place their cases by it; the constants are
+    """vpsf_slices restates lines of psf_plan as prt_frame_vector_psf calls it and the GPU tests place their cases by it; the constants are
     read from the header."""
+    for name, lines in V.HOST_RULES.items():
+        text = open(os.path.join(ROOT, "pyrayt_amd", "csrc", name)).read()
+        for line in lines:
+            assert line in text, (name, line)
     text = open(os.path.join(ROOT, "pyrayt_amd", "csrc", "prt_vector_psf.hpp")).read()
-    for line in V.HOST_RULES:
-        assert line in text, line
     K = V.K
     assert K.kVpsfPix in (2, 4) and K.kVpsfTile == K.kPsfBlock * K.kVpsfPix and K.kVpsfPixelBytes == 6 * 8
     assert "struct VpsfRay { double p1, p2, c, re[3], im[3]; };" in text and K.kPsfBlock * 72 == 18 * 1024

@@ -12,8 +12,8 @@ The field.  huygens_amplitude is linear in ``a``: with c_k = x + i y, U_k = H(x)
 complex sum (re, im) that huygens_amplitude returns.  A component that is 0 on every ray is not summed.
 
 The budget (derived, not measured).  u, ulp, EPS_TRIG and psf_epsilon's count of roundings are diffraction_reference's.
-  * k_vpsf_huygens computes the phase exactly as k_psf_huygens does (the same fma chain, psf_sqrt, v_fract_f64, then
-    v_cos_f32 / v_sin_f32 on the float turn), so a ray's phasor is within eps = psf_epsilon(...) of the definition's and
+  * k_vpsf_huygens computes the phase with the function k_psf_huygens calls (psf_phase: the fma chain, psf_sqrt,
+    v_fract_f64, then v_cos_f32 / v_sin_f32 on the float turn), so a ray's phasor is within eps = psf_epsilon(...) of the definition's and
     |U~_k - U_k| <= eps sum_r |c_{r,k}| / lambda, |c| the complex modulus: (x + i y)(cs + i sn) moves by |c| times the
     phasor's error.  The complex multiply-add's four fmas are four roundings of magnitude |c|, a few u: under EPS_TRIG's
     margin (eps_hw itself, 1.4e-7), as diffraction_reference's docstring argues for the accumulation.
@@ -58,15 +58,20 @@ def kernel_constants():
 
 
 K = kernel_constants()
-# vpsf_slices is a Python copy of lines of prt_frame_vector_psf, as diffraction_reference.psf_slices is of
-# prt_frame_psf's: tests/test_host_vector_psf.py holds the copy to the header's text
-HOST_RULES = (
-    "const int64_t tiles = (npix + kVpsfTile - 1) / kVpsfTile;",
-    "int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);",
-    "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_rows / (group_waves * kPsfMinSlice)));",
-    "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * kVpsfPixelBytes)));",
-    "slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));",
-    "const int64_t group_waves = (int64_t)n_groups * n_wavelengths, buckets = group_waves * n_states;")
+# vpsf_slices is a Python copy of lines of psf_plan (prt_psf.hpp) with the arguments prt_frame_vector_psf gives it, as
+# diffraction_reference.psf_slices is with prt_frame_psf's: tests/test_host_vector_psf.py holds the copy to the headers'
+# text
+HOST_RULES = {
+    "prt_psf.hpp": (
+        "const int64_t tiles = (npix + tile_pixels - 1) / tile_pixels;",
+        "int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);",
+        "slices = std::min<int64_t>(slices, std::max<int64_t>(1, n_items / (sort_buckets * kPsfMinSlice)));",
+        "slices = std::min<int64_t>(slices, (int64_t)(kPsfSlabBytes / ((size_t)buckets * npix * pixel_bytes)));",
+        "slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));"),
+    "prt_vector_psf.hpp": (
+        "const int64_t group_waves = (int64_t)n_groups * n_wavelengths, buckets = group_waves * n_states;",
+        "psf_plan(cus, n_rows, group_waves, buckets, npix, kVpsfTile, kVpsfPixelBytes, kVpsfPixelBytes, VPSF_SUMS);"),
+}
 
 
 def vpsf_slices(n_rows, group_waves, n_states, npix, cus):
