@@ -2,8 +2,8 @@
 // (DESIGN.md section 4.5).  Like the MTF it needs only each ray's end point and direction at the detector.  Definitions:
 // include/prt.h.
 //
-// The MTF's staging runs as it is (k_mtf_count / offsets / starts / scatter / centre / record / stage): per group, in
-// row order, each ray's (p1, p2, s1, s2, w) about the group's centre.  Then
+// The MTF's staging pass runs as it is (mtf_stage_rows of prt_mtf.hpp: k_mtf_count / offsets / starts / scatter /
+// centre / record / stage): per group, in row order, each ray's (p1, p2, s1, s2, w) about the group's centre.  Then
 //   k_energy_centre   per (group, chunk of 4096 rays): sum w, sum w p, sum w s in a fixed tree; the chunk's largest
 //                     weight into the group's w_max (one integer atomic max on the double's bits per workgroup)
 //   k_energy_record   per group: the chunks folded in order into pbar, sbar and sum w; the shift 62 - E - B; the record
@@ -45,16 +45,6 @@ __device__ __forceinline__ double energy_distance(const MtfRay& r, double delta,
   if (shape == PRT_ENERGY_CIRCLE) return sqrt(x1 * x1 + x2 * x2);
   if (shape == PRT_ENERGY_SQUARE) return a1 > a2 ? a1 : a2;
   return shape == PRT_ENERGY_SLIT_E2 ? a1 : a2;
-}
-
-// the rays [lo, hi) of slice s of group g (the MTF's slices)
-__device__ __forceinline__ void energy_slice(const int64_t* __restrict__ slice_start,
-                                             const int64_t* __restrict__ bucket_total,
-                                             const int64_t* __restrict__ bucket_start, int g, int64_t s, int64_t& lo,
-                                             int64_t& hi) {
-  const int64_t n = bucket_total[g], slices = slice_start[g + 1] - slice_start[g], per = (n + slices - 1) / slices;
-  lo = bucket_start[g] + (s - slice_start[g]) * per;
-  hi = lo + per < bucket_start[g] + n ? lo + per : bucket_start[g] + n;
 }
 
 // the power-of-two rule that makes the weights integers: with w_max = f 2^E (0.5 <= f < 1; its bit image is given) and
@@ -177,7 +167,7 @@ k_energy_curve(int n_groups, const int64_t* __restrict__ slice_start, const int6
   const double pb1 = follow ? centroid[4 * g] : 0.0, pb2 = follow ? centroid[4 * g + 1] : 0.0;
   const double sb1 = follow ? centroid[4 * g + 2] : 0.0, sb2 = follow ? centroid[4 * g + 3] : 0.0;
   int64_t lo, hi;
-  energy_slice(slice_start, bucket_total, bucket_start, g, s, lo, hi);
+  mtf_slice(slice_start, bucket_start, bucket_total[g], g, s, lo, hi);  // (the MTF's slices)
   for (int64_t r = lo + t; r < hi; r += kEnergyBlock) {
     const MtfRay ray = stage[r];
     const u64 weight = q[r];
@@ -257,7 +247,7 @@ k_energy_select(int n_groups, const int64_t* __restrict__ slice_start, const int
   const double c1 = follow ? centroid[4 * g] + delta * centroid[4 * g + 2] : 0.0;
   const double c2 = follow ? centroid[4 * g + 1] + delta * centroid[4 * g + 3] : 0.0;
   int64_t lo, hi;
-  energy_slice(slice_start, bucket_total, bucket_start, g, s, lo, hi);
+  mtf_slice(slice_start, bucket_start, bucket_total[g], g, s, lo, hi);  // (the MTF's slices)
   for (int64_t r = lo + t; r < hi; r += kEnergyBlock) {
     const u64 weight = q[r];
     if (!weight) continue;
@@ -363,16 +353,16 @@ extern "C" int prt_frame_energy(int device, const double* rows, int64_t ld, int6
     if (!(fractions[k] > 0 && fractions[k] <= 1)) return fail(PRT_ERR_ARG, "energy: fractions in (0, 1]");
   for (int k = 0; k < n_focus; ++k)
     if (!std::isfinite(focus[k])) return fail(PRT_ERR_ARG, "energy: focus shifts finite");
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(axes[k])) return fail(PRT_ERR_ARG, "axes: finite");
+  MtfAxes ax;
+  int rc = mtf_axes(axes, ax);
+  if (rc) return rc;
   if ((size_t)n_groups * n_focus * n_radii * 8 > kEnergySlabBytes)
     return fail(PRT_ERR_ARG, "energy: n_groups * n_focus * n_radii * 8 bytes above the 256 MiB slab cap");
   if ((size_t)n_groups * n_focus * n_fractions * kEnergyDigits * 8 > kEnergySlabBytes)
     return fail(PRT_ERR_ARG, "energy: n_groups * n_focus * n_fractions * 16 KiB above the 256 MiB slab cap");
-  MtfAxes ax;
-  for (int k = 0; k < 3; ++k) { ax.a[k] = axes[k]; ax.e1[k] = axes[3 + k]; ax.e2[k] = axes[6 + k]; }
-  const int64_t chunk_grid = (n_rows + kMtfChunk - 1) / kMtfChunk + n_groups;
-  const int64_t slice_grid = std::min<int64_t>((int64_t)n_groups * kMtfMaxSlices, n_rows / kMtfMinSlice + n_groups);
+  // (the slices are the MTF's with no slab to cap them: kMtfMaxSlices a group)
+  const MtfRowPlan row = mtf_row_plan(n_rows, n_groups, kMtfMaxSlices);
+  const int64_t chunk_grid = row.chunk_grid, slice_grid = row.slice_grid;
   if (chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff)
     return fail(PRT_ERR_ARG, "energy: too many rows for one launch");
   const int planes_per_tile = n_radii ? std::max(1, std::min(n_focus, kEnergyWindow / n_radii)) : 1;
@@ -381,75 +371,51 @@ extern "C" int prt_frame_energy(int device, const double* rows, int64_t ld, int6
   for (int k = 0; k < n_radii; ++k) host[k] = radii[k];
   for (int k = 0; k < n_fractions; ++k) host[(size_t)n_radii + k] = fractions[k];
   for (int k = 0; k < n_focus; ++k) host[(size_t)n_radii + n_fractions + k] = focus[k];
-  int rc = ops_device(device);
+  rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_energy_workspace_bytes)
-  int64_t* bucket_total = (int64_t*)workspace;
-  int64_t* bucket_start = bucket_total + (n_groups + 1);
-  int64_t* chunk_start = bucket_start + (n_groups + 1);
-  int64_t* slice_start = chunk_start + (n_groups + 1);
-  u64* missed = (u64*)(slice_start + (n_groups + 1));
-  u64* w_max = missed + n_groups;  // (missed, w_max and total are cleared together)
+  MtfStaging s;
+  u64* w_max = (u64*)mtf_staging_words(workspace, n_groups, s);  // (missed, w_max and total are cleared together)
   u64* total = w_max + n_groups;
   int* shift = (int*)(total + n_groups);
-  double* centre = (double*)(total + 2 * (size_t)n_groups);
-  double* mtf_record = centre + 3 * (size_t)n_groups;
-  double* centroid = mtf_record + (size_t)MTF_RECORD * n_groups;
+  s.centre = (double*)(total + 2 * (size_t)n_groups);
+  s.record = s.centre + 3 * (size_t)n_groups;
+  double* centroid = s.record + (size_t)MTF_RECORD * n_groups;
   double* d_radii = centroid + 4 * (size_t)n_groups;
   double* d_fractions = d_radii + n_radii;
   double* planes = d_fractions + n_fractions;
   u64* state = (u64*)(planes + n_focus);
   const size_t items = (size_t)n_groups * n_focus * n_fractions;
-  MtfRaw* sorted = (MtfRaw*)(((uintptr_t)(state + 2 * items) + 31) & ~(uintptr_t)31);
-  MtfRay* stage = (MtfRay*)(sorted + n_rows);
-  u64* q = (u64*)(stage + n_rows);
-  // row passes: waves of contiguous rows, as many as the (wave, group) counts allow
-  const int64_t waves = mtf_waves(n_rows, n_groups);
-  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  const size_t count_bytes = (size_t)all_waves * n_groups * 8;
-  const size_t centre_bytes = (size_t)chunk_grid * 4 * sizeof(double);
+  s.sorted = (MtfRaw*)(((uintptr_t)(state + 2 * items) + 31) & ~(uintptr_t)31);
+  s.stage = (MtfRay*)(s.sorted + n_rows);
+  u64* q = (u64*)(s.stage + n_rows);
+  const size_t count_bytes = row.count_bytes, centre_bytes = row.centre_bytes;
   const size_t chunk_bytes = (size_t)chunk_grid * 5 * sizeof(double);
   const size_t bin_bytes = (size_t)n_groups * n_focus * n_radii * 8;
   const size_t window_bytes = items * kEnergyDigits * 8;
   char* scratch = nullptr;
   HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + centre_bytes + chunk_bytes + bin_bytes + window_bytes, st));
-  int64_t* counts = (int64_t*)scratch;
-  double* centre_slab = (double*)(scratch + count_bytes);
+  s.counts = (int64_t*)scratch;
+  s.centre_slab = (double*)(scratch + count_bytes);
   double* chunk_slab = (double*)(scratch + count_bytes + centre_bytes);
   u64* bins = (u64*)(scratch + count_bytes + centre_bytes + chunk_bytes);
   u64* windows = (u64*)(scratch + count_bytes + centre_bytes + chunk_bytes + bin_bytes);
-  HIP_TRY(hipMemsetAsync(counts, 0, count_bytes, st));
-  HIP_TRY(hipMemsetAsync(missed, 0, (size_t)n_groups * 3 * 8, st));
   if (bin_bytes + window_bytes) HIP_TRY(hipMemsetAsync(bins, 0, bin_bytes + window_bytes, st));
   HIP_TRY(hipMemcpyAsync(d_radii, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  rc = mtf_stage_rows(st, row, s, (size_t)n_groups * 3 * 8, rows, ld, n_rows, surface, generation, rays_per_source,
+                      n_groups, reference, ax, weight_column, kMtfMaxSlices);
+  if (rc) return rc;
   const unsigned group_grid = (unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK);
-  hipLaunchKernelGGL(k_mtf_count, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, ax, weight_column, per_wave, counts, missed);
-  hipLaunchKernelGGL(k_mtf_offsets, dim3((unsigned)n_groups), dim3(kMtfScanBlock), 0, st, (int)all_waves, n_groups,
-                     counts, bucket_total);
-  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kMtfScanBlock), 0, st, n_groups, (int64_t)kMtfMaxSlices, bucket_total,
-                     bucket_start, chunk_start, slice_start);
-  hipLaunchKernelGGL(k_mtf_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, ax, weight_column, per_wave, counts, bucket_start, sorted);
-  if (!reference)
-    hipLaunchKernelGGL(k_mtf_centre, dim3((unsigned)chunk_grid), dim3(kMtfBlock), 0, st, n_groups, chunk_start,
-                       bucket_total, bucket_start, sorted, centre_slab);
-  hipLaunchKernelGGL(k_mtf_record, dim3(group_grid), dim3(PRT_BLOCK), 0, st, n_groups, chunk_start, centre_slab,
-                     reference, centre, mtf_record);
-  hipLaunchKernelGGL(k_mtf_stage, dim3((unsigned)chunk_grid), dim3(kMtfBlock), 0, st, n_groups, chunk_start,
-                     bucket_total, bucket_start, sorted, centre, ax, stage);
-  hipLaunchKernelGGL(k_energy_centre, dim3((unsigned)chunk_grid), dim3(kEnergyBlock), 0, st, n_groups, chunk_start,
-                     bucket_total, bucket_start, stage, chunk_slab, w_max);
-  hipLaunchKernelGGL(k_energy_record, dim3(group_grid), dim3(PRT_BLOCK), 0, st, n_groups, chunk_start, chunk_slab,
-                     centre, bucket_total, missed, w_max, centroid, shift, record_out);
-  hipLaunchKernelGGL(k_energy_scale, dim3((unsigned)chunk_grid), dim3(kEnergyBlock), 0, st, n_groups, chunk_start,
-                     bucket_total, bucket_start, stage, shift, q, total);
+  hipLaunchKernelGGL(k_energy_centre, dim3((unsigned)chunk_grid), dim3(kEnergyBlock), 0, st, n_groups, s.chunk_start,
+                     s.bucket_total, s.bucket_start, s.stage, chunk_slab, w_max);
+  hipLaunchKernelGGL(k_energy_record, dim3(group_grid), dim3(PRT_BLOCK), 0, st, n_groups, s.chunk_start, chunk_slab,
+                     s.centre, s.bucket_total, s.missed, w_max, centroid, shift, record_out);
+  hipLaunchKernelGGL(k_energy_scale, dim3((unsigned)chunk_grid), dim3(kEnergyBlock), 0, st, n_groups, s.chunk_start,
+                     s.bucket_total, s.bucket_start, s.stage, shift, q, total);
   if (n_radii) {
     hipLaunchKernelGGL(k_energy_curve, dim3((unsigned)slice_grid, (unsigned)plane_tiles), dim3(kEnergyBlock), 0, st,
-                       n_groups, slice_start, bucket_total, bucket_start, stage, q, total, centroid, planes, n_focus,
+                       n_groups, s.slice_start, s.bucket_total, s.bucket_start, s.stage, q, total, centroid, planes, n_focus,
                        planes_per_tile, shape, follow_centroid ? 1 : 0, d_radii, n_radii, bins);
     hipLaunchKernelGGL(k_energy_finish, dim3((unsigned)(((int64_t)n_groups * n_focus + PRT_BLOCK - 1) / PRT_BLOCK)),
                        dim3(PRT_BLOCK), 0, st, n_groups, n_focus, n_radii, bins, total, energy_out);
@@ -460,7 +426,7 @@ extern "C" int prt_frame_energy(int device, const double* rows, int64_t ld, int6
     for (int pass = 0; pass < kEnergyPasses; ++pass) {
       for (int first = 0; first < n_fractions; first += kEnergyFractionTile)
         hipLaunchKernelGGL(k_energy_select, dim3((unsigned)slice_grid, (unsigned)n_focus), dim3(kEnergyBlock), 0, st,
-                           n_groups, slice_start, bucket_total, bucket_start, stage, q, total, centroid, planes,
+                           n_groups, s.slice_start, s.bucket_total, s.bucket_start, s.stage, q, total, centroid, planes,
                            n_focus, shape, follow_centroid ? 1 : 0, n_fractions, first,
                            std::min(kEnergyFractionTile, n_fractions - first), kEnergyLow[pass], kEnergyWidth[pass],
                            state, windows);
@@ -468,8 +434,5 @@ extern "C" int prt_frame_energy(int device, const double* rows, int64_t ld, int6
                          kEnergyWidth[pass], pass == kEnergyPasses - 1 ? 1 : 0, total, windows, state, radius_out);
     }
   }
-  HIP_TRY(hipFreeAsync(scratch, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host table outlives its copy)
-  HIP_TRY(hipGetLastError());
-  return PRT_OK;
+  return mtf_finish(st, scratch);
 }

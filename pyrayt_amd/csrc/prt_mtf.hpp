@@ -2,6 +2,11 @@
 // each ray's end point and direction at the detector, so it runs on any frame that holds those rows.  Definitions:
 // include/prt.h.
 //
+// The first part is the core that the geometric image passes stand on (this one, the MTF sensitivities, the enclosed
+// energy): on the host the checks and the plan of the outputs (mtf_plan), the plan of the row passes (mtf_row_plan), the
+// staging pass (mtf_stage_rows: the seven launches k_mtf_count to k_mtf_stage) and an entry's tail (mtf_finish); on the
+// device the rule for keeping a ray, the scan, a chunk's and a slice's rays, a ray about its centre and the fp32 phasor.
+//
 //   k_mtf_count     per wave of a contiguous run of rows: the rays kept per group; rays left out counted per group
 //                   (integer atomics)
 //   k_mtf_offsets   per group: the waves' counts scanned in parallel into each wave's offset inside the group's bucket
@@ -34,6 +39,111 @@ struct MtfAxes { double a[3], e1[3], e2[3]; };
 struct MtfRaw { double q[3], u[3], w; };
 struct MtfRay { double p1, p2, s1, s2, w, pad; };  // (48 bytes: three 16-byte LDS reads)
 
+// ---- the core, host side --------------------------------------------------------------------------------------------
+static int mtf_axes(const double* axes, MtfAxes& ax) {
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(axes[k])) return fail(PRT_ERR_ARG, "axes: finite");
+  for (int k = 0; k < 3; ++k) { ax.a[k] = axes[k]; ax.e1[k] = axes[3 + k]; ax.e2[k] = axes[6 + k]; }
+  return PRT_OK;
+}
+
+// The outputs of a pass that sums phasors: `name` is the entry point's prefix of its messages; cell_bytes a (slice,
+// output) of its slab of partial sums as the slices are capped; a sum workgroup has `block` threads, each owning `out`
+// outputs.  max_slices decides the order of the slice fold, and with it the bits.
+struct MtfPlan {
+  MtfAxes ax;
+  int n_k, lanes;
+  int64_t n_out, max_slices, tiles;
+  std::vector<double> host;  // (kc, ks) per (azimuth, frequency), then the planes
+};
+static int mtf_plan(const char* name, const double* frequencies, int n_frequencies, const double* azimuths_deg,
+                    int n_azimuths, const double* focus, int n_focus, const double* axes, int n_groups,
+                    size_t cell_bytes, int out, int block, MtfPlan& p) {
+  const std::string at = std::string(name) + ": ";
+  if (!frequencies || n_frequencies < 1 || n_frequencies > MTF_MAX_FREQUENCIES)
+    return fail(PRT_ERR_ARG, at + "1 to 4096 frequencies");
+  if (!azimuths_deg || n_azimuths < 1 || n_azimuths > MTF_MAX_AZIMUTHS) return fail(PRT_ERR_ARG, at + "1 to 16 azimuths");
+  if (!focus || n_focus < 1 || n_focus > MTF_MAX_FOCUS) return fail(PRT_ERR_ARG, at + "1 to 256 focus shifts");
+  for (int k = 0; k < n_frequencies; ++k)
+    if (!(frequencies[k] >= 0 && frequencies[k] < PRT_INF)) return fail(PRT_ERR_ARG, at + "frequencies finite and >= 0");
+  for (int k = 0; k < n_azimuths; ++k)
+    if (!std::isfinite(azimuths_deg[k])) return fail(PRT_ERR_ARG, at + "azimuths finite");
+  for (int k = 0; k < n_focus; ++k)
+    if (!std::isfinite(focus[k])) return fail(PRT_ERR_ARG, at + "focus shifts finite");
+  if (const int rc = mtf_axes(axes, p.ax)) return rc;
+  p.n_k = n_azimuths * n_frequencies;
+  const int64_t n_out = p.n_out = (int64_t)n_focus * p.n_k;
+  const size_t cells = (size_t)n_groups * n_out * cell_bytes;
+  if (cells > kMtfSlabBytes)
+    return fail(PRT_ERR_ARG, at + "n_groups * n_focus * n_azimuths * n_frequencies * " +
+                                 (cell_bytes > 16 ? std::to_string(cell_bytes / 16) + " * 16" : std::string("16")) +
+                                 " bytes above the 256 MiB slab cap");
+  // slices are launched for the most the rows could need; each group's share follows from its own count
+  p.max_slices = std::max<int64_t>(1, std::min<int64_t>(kMtfMaxSlices, (int64_t)(kMtfSlabBytes / cells)));
+  const int lanes = n_out <= out * block / 4 ? 4 : (n_out <= out * block / 2 ? 2 : 1);
+  const int64_t tile = (int64_t)out * (block / lanes), tiles = (n_out + tile - 1) / tile;
+  p.lanes = lanes, p.tiles = tiles;
+  // k = nu (cos theta, sin theta), theta in degrees from e1 towards e2; then the planes
+  p.host.resize(2 * (size_t)p.n_k + n_focus);
+  for (int a = 0; a < n_azimuths; ++a) {
+    const double theta = azimuths_deg[a] * (M_PI / 180.0), c = std::cos(theta), s = std::sin(theta);
+    for (int f = 0; f < n_frequencies; ++f) {
+      p.host[2 * ((size_t)a * n_frequencies + f)] = frequencies[f] * c;
+      p.host[2 * ((size_t)a * n_frequencies + f) + 1] = frequencies[f] * s;
+    }
+  }
+  for (int k = 0; k < n_focus; ++k) p.host[2 * (size_t)p.n_k + k] = focus[k];
+  return PRT_OK;
+}
+
+// The staging pass (mtf_stage_rows) over n_rows rows in n_groups groups.  Row passes: waves of contiguous rows, as many
+// as the (wave, group) counts allow; chunks and slices are launched for the most the rows could need.
+struct MtfRowPlan {
+  int64_t per_wave, all_waves, chunk_grid, slice_grid;
+  unsigned grid;
+  size_t count_bytes, centre_bytes;
+};
+static MtfRowPlan mtf_row_plan(int64_t n_rows, int n_groups, int64_t max_slices) {
+  MtfRowPlan p;
+  int64_t waves = wf_waves(n_rows, 1);
+  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kMtfCountBytes / ((size_t)n_groups * 8))));
+  p.per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
+  p.grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
+  p.all_waves = (int64_t)p.grid * (PRT_BLOCK / 64);
+  p.count_bytes = (size_t)p.all_waves * n_groups * 8;
+  p.chunk_grid = (n_rows + kMtfChunk - 1) / kMtfChunk + n_groups;
+  p.slice_grid = std::min<int64_t>((int64_t)n_groups * max_slices, n_rows / kMtfMinSlice + n_groups);
+  p.centre_bytes = (size_t)p.chunk_grid * 4 * sizeof(double);
+  return p;
+}
+
+// what the staging pass reads and writes: the head of an entry's workspace (mtf_staging_words), the entry's own centre,
+// record, sorted and staged rays, and in its scratch the sort's counts and the centre chunks
+struct MtfStaging {
+  int64_t *bucket_total, *bucket_start, *chunk_start, *slice_start, *counts;
+  unsigned long long* missed;
+  double *centre, *record, *centre_slab;
+  MtfRaw* sorted; MtfRay* stage;
+};
+// bucket totals and starts, chunk and slice starts (n_groups + 1 each), then the misses; returns what follows them
+static void* mtf_staging_words(void* workspace, int n_groups, MtfStaging& s) {
+  s.bucket_total = (int64_t*)workspace;
+  s.bucket_start = s.bucket_total + (n_groups + 1);
+  s.chunk_start = s.bucket_start + (n_groups + 1);
+  s.slice_start = s.chunk_start + (n_groups + 1);
+  s.missed = (unsigned long long*)(s.slice_start + (n_groups + 1));
+  return s.missed + n_groups;
+}
+
+// the tail of an entry: the scratch freed, the stream drained
+static int mtf_finish(hipStream_t st, void* scratch) {
+  HIP_TRY(hipFreeAsync(scratch, st));
+  HIP_TRY(hipStreamSynchronize(st));  // (the host table outlives its copy)
+  HIP_TRY(hipGetLastError());
+  return PRT_OK;
+}
+
+// ---- the core, device side ------------------------------------------------------------------------------------------
 // the ray of row j if it is kept: end point, direction, weight; false if a value it needs is not finite, u.a == 0 or
 // the weight is not finite and >= 0
 __device__ __forceinline__ bool mtf_ray(const double* __restrict__ rows, int64_t ld, int64_t j, const MtfAxes& ax,
@@ -49,6 +159,94 @@ __device__ __forceinline__ bool mtf_ray(const double* __restrict__ rows, int64_t
   return ok && ua != 0.0 && fabs(s1) < PRT_INF && fabs(s2) < PRT_INF;
 }
 
+// an exclusive scan of n int64 values by one workgroup of kMtfScanBlock threads, each owning a contiguous run:
+// get(k) reads value k, put(k, before) receives the sum of the values before it; returns the total
+template <class Get, class Put>
+__device__ int64_t mtf_scan(int64_t n, Get get, Put put, int64_t* __restrict__ scan) {
+  const int64_t per = (n + kMtfScanBlock - 1) / kMtfScanBlock;
+  const int64_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
+  int64_t mine = 0;
+  for (int64_t k = lo; k < hi; ++k) mine += get(k);
+  __syncthreads();  // (scan may still be read by a previous call)
+  scan[threadIdx.x] = mine;
+  __syncthreads();
+  for (int off = 1; off < kMtfScanBlock; off <<= 1) {
+    const int64_t add = (int)threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
+    __syncthreads();
+    scan[threadIdx.x] += add;
+    __syncthreads();
+  }
+  int64_t at = scan[threadIdx.x] - mine;
+  for (int64_t k = lo; k < hi; ++k) {
+    const int64_t v = get(k);
+    put(k, at);
+    at += v;
+  }
+  return scan[kMtfScanBlock - 1];
+}
+
+// the slices of a group of `count` rays: at least kMtfMinSlice rays each while the group has them, max_slices at most
+__host__ __device__ __forceinline__ int64_t mtf_slices(int64_t count, int64_t max_slices) {
+  const int64_t s = (count + kMtfMinSlice - 1) / kMtfMinSlice;
+  return s < 1 ? 1 : (s > max_slices ? max_slices : s);
+}
+
+// the group whose run [start[g], start[g + 1]) holds item (start: n_groups + 1 non-decreasing entries); -1 past the end
+__device__ __forceinline__ int mtf_owner(const int64_t* __restrict__ start, int n_groups, int64_t item) {
+  if (item >= start[n_groups]) return -1;
+  int lo = 0, hi = n_groups - 1;
+  while (lo < hi) {  // the last g with start[g] <= item: the one non-empty run that holds it
+    const int mid = (lo + hi + 1) >> 1;
+    if (start[mid] <= item) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// the rays [lo, hi) of a group's chunk
+__device__ __forceinline__ void mtf_chunk(const int64_t* __restrict__ chunk_start,
+                                          const int64_t* __restrict__ bucket_total,
+                                          const int64_t* __restrict__ bucket_start, int g, int64_t chunk, int64_t& lo,
+                                          int64_t& hi) {
+  lo = bucket_start[g] + (chunk - chunk_start[g]) * kMtfChunk;
+  const int64_t end = bucket_start[g] + bucket_total[g];
+  hi = lo + kMtfChunk < end ? lo + kMtfChunk : end;
+}
+
+// the rays [lo, hi) of slice s of group g, whose `count` rays begin at first[g]
+__device__ __forceinline__ void mtf_slice(const int64_t* __restrict__ slice_start, const int64_t* __restrict__ first,
+                                          int64_t count, int g, int64_t s, int64_t& lo, int64_t& hi) {
+  const int64_t slices = slice_start[g + 1] - slice_start[g], per = (count + slices - 1) / slices;
+  lo = first[g] + (s - slice_start[g]) * per;
+  hi = lo + per < first[g] + count ? lo + per : first[g] + count;
+}
+
+// a ray about the centre c: d = Q - C, s = (u.e1, u.e2) / u.a, p = (d.e1, d.e2) - s (d.a); also s, da = d.a and ua = u.a
+__device__ __forceinline__ MtfRay mtf_stage_ray(const MtfRaw& ray, const double c[3], const MtfAxes& ax, double& s1,
+                                                double& s2, double& da, double& ua) {
+  const double d[3] = {ray.q[0] - c[0], ray.q[1] - c[1], ray.q[2] - c[2]};
+  ua = ray.u[0] * ax.a[0] + ray.u[1] * ax.a[1] + ray.u[2] * ax.a[2];
+  s1 = (ray.u[0] * ax.e1[0] + ray.u[1] * ax.e1[1] + ray.u[2] * ax.e1[2]) / ua;
+  s2 = (ray.u[0] * ax.e2[0] + ray.u[1] * ax.e2[1] + ray.u[2] * ax.e2[2]) / ua;
+  da = d[0] * ax.a[0] + d[1] * ax.a[1] + d[2] * ax.a[2];
+  const double d1 = d[0] * ax.e1[0] + d[1] * ax.e1[1] + d[2] * ax.e1[2];
+  const double d2 = d[0] * ax.e2[0] + d[1] * ax.e2[1] + d[2] * ax.e2[2];
+  return MtfRay{d1 - s1 * da, d2 - s2 * da, s1, s2, ray.w, 0.0};
+}
+
+// k.x(delta) = kc p1 + ks p2 + delta (kc s1 + ks s2), in cycles; the cosine and sine of its fraction from
+// v_cos_f32 / v_sin_f32 (they take turns).  Returns the angle that the conversion to fp32 drops: the caller corrects
+// (c, sn) for it to first order, each sum kernel in its own way
+__device__ __forceinline__ double mtf_phasor(double kc, double ks, double kcd, double ksd, const MtfRay& ray, double& c,
+                                             double& sn) {
+  const double phase = fma(kc, ray.p1, fma(ks, ray.p2, fma(kcd, ray.s1, ksd * ray.s2)));
+  const double turn = __builtin_amdgcn_fract(phase);
+  const float tf = (float)turn;
+  c = (double)__builtin_amdgcn_cosf(tf);
+  sn = (double)__builtin_amdgcn_sinf(tf);
+  return 6.283185307179586 * (turn - (double)tf);
+}
+
+// ---- the staging pass -----------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_mtf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
             double rays_per_source, int n_groups, MtfAxes ax, int weight_column, int64_t per_wave,
@@ -79,32 +277,6 @@ k_mtf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
   }
 }
 
-// an exclusive scan of n int64 values by one workgroup of kMtfScanBlock threads, each owning a contiguous run:
-// get(k) reads value k, put(k, before) receives the sum of the values before it; returns the total
-template <class Get, class Put>
-__device__ int64_t mtf_scan(int64_t n, Get get, Put put, int64_t* __restrict__ scan) {
-  const int64_t per = (n + kMtfScanBlock - 1) / kMtfScanBlock;
-  const int64_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  int64_t mine = 0;
-  for (int64_t k = lo; k < hi; ++k) mine += get(k);
-  __syncthreads();  // (scan may still be read by a previous call)
-  scan[threadIdx.x] = mine;
-  __syncthreads();
-  for (int off = 1; off < kMtfScanBlock; off <<= 1) {
-    const int64_t add = (int)threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-    __syncthreads();
-    scan[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int64_t at = scan[threadIdx.x] - mine;
-  for (int64_t k = lo; k < hi; ++k) {
-    const int64_t v = get(k);
-    put(k, at);
-    at += v;
-  }
-  return scan[kMtfScanBlock - 1];
-}
-
 // per group (one workgroup each): counts[wave][g] -> the wave's first position inside the bucket, in place
 __global__ void __launch_bounds__(kMtfScanBlock)
 k_mtf_offsets(int waves, int n_groups, int64_t* __restrict__ counts, int64_t* __restrict__ bucket_total) {
@@ -114,11 +286,6 @@ k_mtf_offsets(int waves, int n_groups, int64_t* __restrict__ counts, int64_t* __
       waves, [&](int64_t w) { return counts[w * n_groups + g]; },
       [&](int64_t w, int64_t before) { counts[w * n_groups + g] = before; }, scan);
   if (threadIdx.x == 0) bucket_total[g] = total;
-}
-
-__device__ __forceinline__ int64_t mtf_slices(int64_t count, int64_t max_slices) {
-  const int64_t s = (count + kMtfMinSlice - 1) / kMtfMinSlice;
-  return s < 1 ? 1 : (s > max_slices ? max_slices : s);
 }
 
 // one workgroup: bucket starts, and the first centre chunk and first sum slice of each group (n_groups + 1 entries)
@@ -170,27 +337,6 @@ k_mtf_scatter(const double* __restrict__ rows, int64_t ld, int64_t n_rows, doubl
   }
 }
 
-// the group whose run [start[g], start[g + 1]) holds item (start: n_groups + 1 non-decreasing entries); -1 past the end
-__device__ __forceinline__ int mtf_owner(const int64_t* __restrict__ start, int n_groups, int64_t item) {
-  if (item >= start[n_groups]) return -1;
-  int lo = 0, hi = n_groups - 1;
-  while (lo < hi) {  // the last g with start[g] <= item: the one non-empty run that holds it
-    const int mid = (lo + hi + 1) >> 1;
-    if (start[mid] <= item) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
-// the rays [lo, hi) of a group's chunk
-__device__ __forceinline__ void mtf_chunk(const int64_t* __restrict__ chunk_start,
-                                          const int64_t* __restrict__ bucket_total,
-                                          const int64_t* __restrict__ bucket_start, int g, int64_t chunk, int64_t& lo,
-                                          int64_t& hi) {
-  lo = bucket_start[g] + (chunk - chunk_start[g]) * kMtfChunk;
-  const int64_t end = bucket_start[g] + bucket_total[g];
-  hi = lo + kMtfChunk < end ? lo + kMtfChunk : end;
-}
-
 // per (group, chunk): [0] sum w  [1..3] sum w Q -- each thread over its strided rays in order, then a fixed tree
 __global__ void __launch_bounds__(kMtfBlock)
 k_mtf_centre(int n_groups, const int64_t* __restrict__ chunk_start, const int64_t* __restrict__ bucket_total,
@@ -239,7 +385,7 @@ k_mtf_record(int n_groups, const int64_t* __restrict__ chunk_start, const double
   }
 }
 
-// per (group, chunk), each ray: d = Q - C, s = (u.e1, u.e2) / u.a, p = (d.e1, d.e2) - s (d.a)
+// per (group, chunk), each ray: mtf_stage_ray about the group's centre
 __global__ void __launch_bounds__(kMtfBlock)
 k_mtf_stage(int n_groups, const int64_t* __restrict__ chunk_start, const int64_t* __restrict__ bucket_total,
             const int64_t* __restrict__ bucket_start, const MtfRaw* __restrict__ sorted, const double* __restrict__ centre,
@@ -251,18 +397,39 @@ k_mtf_stage(int n_groups, const int64_t* __restrict__ chunk_start, const int64_t
   mtf_chunk(chunk_start, bucket_total, bucket_start, g, chunk, lo, hi);
   const double c[3] = {centre[3 * g], centre[3 * g + 1], centre[3 * g + 2]};
   for (int64_t r = lo + threadIdx.x; r < hi; r += kMtfBlock) {
-    const MtfRaw ray = sorted[r];
-    const double d[3] = {ray.q[0] - c[0], ray.q[1] - c[1], ray.q[2] - c[2]};
-    const double ua = ray.u[0] * ax.a[0] + ray.u[1] * ax.a[1] + ray.u[2] * ax.a[2];
-    const double s1 = (ray.u[0] * ax.e1[0] + ray.u[1] * ax.e1[1] + ray.u[2] * ax.e1[2]) / ua;
-    const double s2 = (ray.u[0] * ax.e2[0] + ray.u[1] * ax.e2[1] + ray.u[2] * ax.e2[2]) / ua;
-    const double da = d[0] * ax.a[0] + d[1] * ax.a[1] + d[2] * ax.a[2];
-    const double d1 = d[0] * ax.e1[0] + d[1] * ax.e1[1] + d[2] * ax.e1[2];
-    const double d2 = d[0] * ax.e2[0] + d[1] * ax.e2[1] + d[2] * ax.e2[2];
-    stage[r] = MtfRay{d1 - s1 * da, d2 - s2 * da, s1, s2, ray.w, 0.0};
+    double s1, s2, da, ua;
+    stage[r] = mtf_stage_ray(sorted[r], c, ax, s1, s2, da, ua);
   }
 }
 
+// The staging pass: per group, in row order, each kept ray's (p1, p2, s1, s2, w) about the group's centre into s.stage,
+// the centre into s.centre and s.record[0..2], the rays left out into s.missed.  `cleared` bytes from s.missed on are
+// zeroed (an entry's own counters may follow the misses).
+static int mtf_stage_rows(hipStream_t st, const MtfRowPlan& p, const MtfStaging& s, size_t cleared, const double* rows,
+                          int64_t ld, int64_t n_rows, double surface, double generation, double rays_per_source,
+                          int n_groups, const double* reference, const MtfAxes& ax, int weight_column,
+                          int64_t max_slices) {
+  HIP_TRY(hipMemsetAsync(s.counts, 0, p.count_bytes, st));
+  HIP_TRY(hipMemsetAsync(s.missed, 0, cleared, st));
+  hipLaunchKernelGGL(k_mtf_count, dim3(p.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, ax, weight_column, p.per_wave, s.counts, s.missed);
+  hipLaunchKernelGGL(k_mtf_offsets, dim3((unsigned)n_groups), dim3(kMtfScanBlock), 0, st, (int)p.all_waves, n_groups,
+                     s.counts, s.bucket_total);
+  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kMtfScanBlock), 0, st, n_groups, max_slices, s.bucket_total,
+                     s.bucket_start, s.chunk_start, s.slice_start);
+  hipLaunchKernelGGL(k_mtf_scatter, dim3(p.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
+                     rays_per_source, n_groups, ax, weight_column, p.per_wave, s.counts, s.bucket_start, s.sorted);
+  if (!reference)
+    hipLaunchKernelGGL(k_mtf_centre, dim3((unsigned)p.chunk_grid), dim3(kMtfBlock), 0, st, n_groups, s.chunk_start,
+                       s.bucket_total, s.bucket_start, s.sorted, s.centre_slab);
+  hipLaunchKernelGGL(k_mtf_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
+                     n_groups, s.chunk_start, s.centre_slab, reference, s.centre, s.record);
+  hipLaunchKernelGGL(k_mtf_stage, dim3((unsigned)p.chunk_grid), dim3(kMtfBlock), 0, st, n_groups, s.chunk_start,
+                     s.bucket_total, s.bucket_start, s.sorted, s.centre, ax, s.stage);
+  return PRT_OK;
+}
+
+// ---- the MTF's own kernels ------------------------------------------------------------------------------------------
 // A workgroup is `lanes` lanes of kMtfBlock / lanes threads; each thread owns kMtfOut outputs of the tile.  With
 // lanes > 1 the lanes (whole waves) split the LDS tile's rays between them -- one ray per wave per step, an LDS
 // broadcast -- and their sums are added in lane order.  table: (kc, ks) per (azimuth, frequency); focus: delta per plane.
@@ -291,10 +458,8 @@ k_mtf_sum(int n_groups, const int64_t* __restrict__ slice_start, const int64_t* 
     re[q] = im[q] = 0.0;
   }
   double sw = 0.0;
-  const int64_t n = bucket_total[g], slices = slice_start[g + 1] - slice_start[g], per = (n + slices - 1) / slices;
-  const int64_t lo = bucket_start[g] + (s - slice_start[g]) * per;
-  const int64_t hi = lo + per < bucket_start[g] + n ? lo + per : bucket_start[g] + n;
-  const double two_pi = 6.283185307179586;
+  int64_t lo, hi;
+  mtf_slice(slice_start, bucket_start, bucket_total[g], g, s, lo, hi);
   for (int64_t base = lo; base < hi; base += kMtfBlock) {
     __syncthreads();  // (the previous tile is read)
     if (base + t < hi) tile[t] = stage[base + t];
@@ -305,13 +470,9 @@ k_mtf_sum(int n_groups, const int64_t* __restrict__ slice_start, const int64_t* 
       sw += ray.w;
 #pragma unroll
       for (int q = 0; q < kMtfOut; ++q) {
-        // k.x(delta) = kc p1 + ks p2 + delta (kc s1 + ks s2), in cycles; the sine and cosine of its fraction from
-        // v_sin_f32 / v_cos_f32 (they take turns), corrected to first order for what the conversion to fp32 drops
-        const double phase = fma(kc[q], ray.p1, fma(ks[q], ray.p2, fma(kcd[q], ray.s1, ksd[q] * ray.s2)));
-        const double turn = __builtin_amdgcn_fract(phase);
-        const float tf = (float)turn;
-        const double c = (double)__builtin_amdgcn_cosf(tf), sn = (double)__builtin_amdgcn_sinf(tf);
-        const double wd = ray.w * (two_pi * (turn - (double)tf));
+        // the phasor corrected to first order for what the conversion to fp32 drops (mtf_phasor)
+        double c, sn;
+        const double wd = ray.w * mtf_phasor(kc[q], ks[q], kcd[q], ksd[q], ray, c, sn);
         re[q] = fma(-wd, sn, fma(ray.w, c, re[q]));
         im[q] = fma(wd, c, fma(ray.w, sn, im[q]));
       }
@@ -378,12 +539,6 @@ k_mtf_fold(int n_groups, int64_t n_out, const int64_t* __restrict__ slice_start,
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------
-static int64_t mtf_waves(int64_t n_rows, int n_groups) {
-  int64_t waves = (n_rows + kWfRowsPerWave - 1) / kWfRowsPerWave;
-  waves = std::min<int64_t>(std::max<int64_t>(waves, 1), kWfMaxWaves);
-  return std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kMtfCountBytes / ((size_t)n_groups * 8))));
-}
-
 extern "C" int64_t prt_frame_mtf_workspace_bytes(int64_t n_rows, int n_groups, int n_frequencies, int n_azimuths,
                                                  int n_focus) {
   if (n_rows < 0 || n_groups < 1 || n_frequencies < 1 || n_frequencies > MTF_MAX_FREQUENCIES || n_azimuths < 1 ||
@@ -406,98 +561,42 @@ extern "C" int prt_frame_mtf(int device, const double* rows, int64_t ld, int64_t
     return fail(PRT_ERR_ARG, "bad buffers");
   if (!(rays_per_source > 0) && n_groups != 1) return fail(PRT_ERR_ARG, "one group without rays_per_source");
   if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
-  if (!frequencies || n_frequencies < 1 || n_frequencies > MTF_MAX_FREQUENCIES)
-    return fail(PRT_ERR_ARG, "mtf: 1 to 4096 frequencies");
-  if (!azimuths_deg || n_azimuths < 1 || n_azimuths > MTF_MAX_AZIMUTHS) return fail(PRT_ERR_ARG, "mtf: 1 to 16 azimuths");
-  if (!focus || n_focus < 1 || n_focus > MTF_MAX_FOCUS) return fail(PRT_ERR_ARG, "mtf: 1 to 256 focus shifts");
-  for (int k = 0; k < n_frequencies; ++k)
-    if (!(frequencies[k] >= 0 && frequencies[k] < PRT_INF)) return fail(PRT_ERR_ARG, "mtf: frequencies finite and >= 0");
-  for (int k = 0; k < n_azimuths; ++k)
-    if (!std::isfinite(azimuths_deg[k])) return fail(PRT_ERR_ARG, "mtf: azimuths finite");
-  for (int k = 0; k < n_focus; ++k)
-    if (!std::isfinite(focus[k])) return fail(PRT_ERR_ARG, "mtf: focus shifts finite");
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(axes[k])) return fail(PRT_ERR_ARG, "axes: finite");
-  MtfAxes ax;
-  for (int k = 0; k < 3; ++k) { ax.a[k] = axes[k]; ax.e1[k] = axes[3 + k]; ax.e2[k] = axes[6 + k]; }
-  const int n_k = n_azimuths * n_frequencies;
-  const int64_t n_out = (int64_t)n_focus * n_k;
-  if ((size_t)n_groups * n_out * 16 > kMtfSlabBytes)
-    return fail(PRT_ERR_ARG, "mtf: n_groups * n_focus * n_azimuths * n_frequencies * 16 bytes above the 256 MiB slab cap");
-  // chunks and slices are launched for the most the rows could need; each group's share follows from its own count
-  const int64_t max_slices =
-      std::max<int64_t>(1, std::min<int64_t>(kMtfMaxSlices, (int64_t)(kMtfSlabBytes / ((size_t)n_groups * n_out * 16))));
-  const int64_t chunk_grid = (n_rows + kMtfChunk - 1) / kMtfChunk + n_groups;
-  const int64_t slice_grid = std::min<int64_t>((int64_t)n_groups * max_slices, n_rows / kMtfMinSlice + n_groups);
-  const int lanes = n_out <= kMtfOut * kMtfBlock / 4 ? 4 : (n_out <= kMtfOut * kMtfBlock / 2 ? 2 : 1);
-  const int64_t tile = (int64_t)kMtfOut * (kMtfBlock / lanes), tiles = (n_out + tile - 1) / tile;
-  if (chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff || tiles > 65535)
+  MtfPlan plan;
+  int rc = mtf_plan("mtf", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups, 16,
+                    kMtfOut, kMtfBlock, plan);
+  if (rc) return rc;
+  const int64_t n_out = plan.n_out;
+  const MtfRowPlan row = mtf_row_plan(n_rows, n_groups, plan.max_slices);
+  if (row.chunk_grid > 0x7fffffff || row.slice_grid > 0x7fffffff || plan.tiles > 65535)
     return fail(PRT_ERR_ARG, "mtf: too many rows or outputs for one launch");
-  // k = nu (cos theta, sin theta), theta in degrees from e1 towards e2; then the planes
-  std::vector<double> host(2 * (size_t)n_k + n_focus);
-  for (int a = 0; a < n_azimuths; ++a) {
-    const double theta = azimuths_deg[a] * (M_PI / 180.0), c = std::cos(theta), s = std::sin(theta);
-    for (int f = 0; f < n_frequencies; ++f) {
-      host[2 * ((size_t)a * n_frequencies + f)] = frequencies[f] * c;
-      host[2 * ((size_t)a * n_frequencies + f) + 1] = frequencies[f] * s;
-    }
-  }
-  for (int k = 0; k < n_focus; ++k) host[2 * (size_t)n_k + k] = focus[k];
-  int rc = ops_device(device);
+  rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_mtf_workspace_bytes)
-  int64_t* bucket_total = (int64_t*)workspace;
-  int64_t* bucket_start = bucket_total + (n_groups + 1);
-  int64_t* chunk_start = bucket_start + (n_groups + 1);
-  int64_t* slice_start = chunk_start + (n_groups + 1);
-  unsigned long long* missed = (unsigned long long*)(slice_start + (n_groups + 1));
-  double* centre = (double*)(missed + n_groups);
-  double* table = centre + 3 * (size_t)n_groups;
-  double* planes = table + 2 * (size_t)n_k;
-  MtfRaw* sorted = (MtfRaw*)(((uintptr_t)(planes + n_focus) + 31) & ~(uintptr_t)31);
-  MtfRay* stage = (MtfRay*)(sorted + n_rows);
-  // row passes: waves of contiguous rows, as many as the (wave, group) counts allow
-  const int64_t waves = mtf_waves(n_rows, n_groups);
-  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  const size_t count_bytes = (size_t)all_waves * n_groups * 8;
-  const size_t centre_bytes = (size_t)chunk_grid * 4 * sizeof(double);
-  const size_t weight_bytes = (size_t)slice_grid * sizeof(double);
-  const size_t slab_bytes = (size_t)slice_grid * n_out * 2 * sizeof(double);
+  MtfStaging s;
+  s.centre = (double*)mtf_staging_words(workspace, n_groups, s);
+  s.record = record_out;
+  double* table = s.centre + 3 * (size_t)n_groups;
+  double* planes = table + 2 * (size_t)plan.n_k;
+  s.sorted = (MtfRaw*)(((uintptr_t)(planes + n_focus) + 31) & ~(uintptr_t)31);
+  s.stage = (MtfRay*)(s.sorted + n_rows);
+  const size_t weight_bytes = (size_t)row.slice_grid * sizeof(double);
+  const size_t slab_bytes = (size_t)row.slice_grid * n_out * 2 * sizeof(double);
   char* scratch = nullptr;
-  HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + centre_bytes + weight_bytes + slab_bytes, st));
-  int64_t* counts = (int64_t*)scratch;
-  double* centre_slab = (double*)(scratch + count_bytes);
-  double* weight_slab = (double*)(scratch + count_bytes + centre_bytes);
-  double* slab = (double*)(scratch + count_bytes + centre_bytes + weight_bytes);
-  HIP_TRY(hipMemsetAsync(counts, 0, count_bytes, st));
-  HIP_TRY(hipMemsetAsync(missed, 0, (size_t)n_groups * 8, st));
-  HIP_TRY(hipMemcpyAsync(table, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_mtf_count, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, ax, weight_column, per_wave, counts, missed);
-  hipLaunchKernelGGL(k_mtf_offsets, dim3((unsigned)n_groups), dim3(kMtfScanBlock), 0, st, (int)all_waves, n_groups,
-                     counts, bucket_total);
-  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kMtfScanBlock), 0, st, n_groups, max_slices, bucket_total,
-                     bucket_start, chunk_start, slice_start);
-  hipLaunchKernelGGL(k_mtf_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
-                     rays_per_source, n_groups, ax, weight_column, per_wave, counts, bucket_start, sorted);
-  if (!reference)
-    hipLaunchKernelGGL(k_mtf_centre, dim3((unsigned)chunk_grid), dim3(kMtfBlock), 0, st, n_groups, chunk_start,
-                       bucket_total, bucket_start, sorted, centre_slab);
-  hipLaunchKernelGGL(k_mtf_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
-                     n_groups, chunk_start, centre_slab, reference, centre, record_out);
-  hipLaunchKernelGGL(k_mtf_stage, dim3((unsigned)chunk_grid), dim3(kMtfBlock), 0, st, n_groups, chunk_start,
-                     bucket_total, bucket_start, sorted, centre, ax, stage);
-  hipLaunchKernelGGL(k_mtf_sum, dim3((unsigned)slice_grid, (unsigned)tiles), dim3(kMtfBlock), 0, st, n_groups,
-                     slice_start, bucket_total, bucket_start, stage, table, planes, n_k, n_out, lanes, slab,
-                     weight_slab);
+  HIP_TRY(hipMallocAsync((void**)&scratch, row.count_bytes + row.centre_bytes + weight_bytes + slab_bytes, st));
+  s.counts = (int64_t*)scratch;
+  s.centre_slab = (double*)(scratch + row.count_bytes);
+  double* weight_slab = (double*)(scratch + row.count_bytes + row.centre_bytes);
+  double* slab = (double*)(scratch + row.count_bytes + row.centre_bytes + weight_bytes);
+  HIP_TRY(hipMemcpyAsync(table, plan.host.data(), plan.host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  rc = mtf_stage_rows(st, row, s, (size_t)n_groups * 8, rows, ld, n_rows, surface, generation, rays_per_source, n_groups,
+                      reference, plan.ax, weight_column, plan.max_slices);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_mtf_sum, dim3((unsigned)row.slice_grid, (unsigned)plan.tiles), dim3(kMtfBlock), 0, st, n_groups,
+                     s.slice_start, s.bucket_total, s.bucket_start, s.stage, table, planes, plan.n_k, n_out, plan.lanes,
+                     slab, weight_slab);
   hipLaunchKernelGGL(k_mtf_fold, dim3((unsigned)(((int64_t)n_groups * n_out + PRT_BLOCK - 1) / PRT_BLOCK)),
-                     dim3(PRT_BLOCK), 0, st, n_groups, n_out, slice_start, slab, weight_slab, bucket_total, missed,
+                     dim3(PRT_BLOCK), 0, st, n_groups, n_out, s.slice_start, slab, weight_slab, s.bucket_total, s.missed,
                      otf_out, record_out);
-  HIP_TRY(hipFreeAsync(scratch, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host table outlives its copy)
-  HIP_TRY(hipGetLastError());
-  return PRT_OK;
+  return mtf_finish(st, scratch);
 }

@@ -15,6 +15,8 @@
 // w = 0.  Every partition of the rays (chunks, slices, tiles) depends only on the group's count of selected rows, on the
 // output count and on n_groups, never on the frame's other rows and never on K; a parameter's arithmetic does not depend
 // on its place in the call.  No floating-point atomics: every output is the same, bit for bit, on every run.
+// The checks and the plan of the outputs (mtf_plan), the slice rule (mtf_slices, mtf_slice), a ray about its centre
+// (mtf_stage_ray), the phase with its fp32 phasor (mtf_phasor) and the tail (mtf_finish) are the core's, in prt_mtf.hpp.
 #pragma once
 
 #include <type_traits>
@@ -30,6 +32,8 @@ static const int kMtfgMinSlice = 2048;             // selected rows a sum slice 
 static const int kMtfgMaxSlices = 256;             // slices of a group at most (the fold walks them in series)
 static const int kMtfgQuantities = MTFG_MAX_PARAMETERS + 2;  // the slab holds OTF, K parameters and the focus: sized for 16
 static const size_t kMtfgSlabBytes = 256u << 20;   // cap on the (slice, quantity, output) partial sums
+static_assert(kMtfgMinSlice == kMtfMinSlice && kMtfgMaxSlices == kMtfMaxSlices && kMtfgSlabBytes == kMtfSlabBytes,
+              "the slices are the MTF's: mtf_slices and mtf_plan apply its constants");
 
 struct MtfgPar { double dp1, dp2, ds1, ds2; };     // (32 bytes: two 16-byte LDS reads)
 
@@ -141,14 +145,8 @@ k_mtfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const 
   }
   const int g = mtf_owner(group_first, n_groups, r);
   const double c[3] = {centre[3 * g], centre[3 * g + 1], centre[3 * g + 2]};
-  const double d[3] = {ray.q[0] - c[0], ray.q[1] - c[1], ray.q[2] - c[2]};
-  const double ua = ray.u[0] * ax.a[0] + ray.u[1] * ax.a[1] + ray.u[2] * ax.a[2];
-  const double s1 = (ray.u[0] * ax.e1[0] + ray.u[1] * ax.e1[1] + ray.u[2] * ax.e1[2]) / ua;
-  const double s2 = (ray.u[0] * ax.e2[0] + ray.u[1] * ax.e2[1] + ray.u[2] * ax.e2[2]) / ua;
-  const double da = d[0] * ax.a[0] + d[1] * ax.a[1] + d[2] * ax.a[2];
-  const double d1 = d[0] * ax.e1[0] + d[1] * ax.e1[1] + d[2] * ax.e1[2];
-  const double d2 = d[0] * ax.e2[0] + d[1] * ax.e2[1] + d[2] * ax.e2[2];
-  stage[r] = MtfRay{d1 - s1 * da, d2 - s2 * da, s1, s2, ray.w, 0.0};
+  double s1, s2, da, ua;
+  stage[r] = mtf_stage_ray(ray, c, ax, s1, s2, da, ua);
   const double unit_a = ua / sqrt(ray.u[0] * ray.u[0] + ray.u[1] * ray.u[1] + ray.u[2] * ray.u[2]);
   for (int k = 0; k < K; ++k) {
     double dq[3], du[3];
@@ -202,11 +200,8 @@ k_mtfg_sum(int n_groups, const int64_t* __restrict__ slice_start, const int64_t*
     for (int j = 0; j < P; ++j) are[q][j] = aim[q][j] = 0.0;
   }
   double sw = 0.0;
-  const int64_t n = group_first[g + 1] - group_first[g], slices = slice_start[g + 1] - slice_start[g];
-  const int64_t per = (n + slices - 1) / slices;
-  const int64_t lo = group_first[g] + (s - slice_start[g]) * per;
-  const int64_t hi = lo + per < group_first[g + 1] ? lo + per : group_first[g + 1];
-  const double two_pi = 6.283185307179586;
+  int64_t lo, hi;
+  mtf_slice(slice_start, group_first, group_first[g + 1] - group_first[g], g, s, lo, hi);
   for (int64_t base = lo; base < hi; base += kMtfgTile) {
     const int count = hi - base < kMtfgTile ? (int)(hi - base) : kMtfgTile;
     __syncthreads();  // (the previous tile is read)
@@ -222,13 +217,10 @@ k_mtfg_sum(int n_groups, const int64_t* __restrict__ slice_start, const int64_t*
       sw += ray.w;
 #pragma unroll
       for (int q = 0; q < kMtfgOut; ++q) {
-        // the phase and its phasor as k_mtf_sum forms them; the first-order correction for what the conversion to fp32
-        // drops is folded into the phasor once: (c', sn') = (c - theta sn, sn + theta c)
-        const double phase = fma(kc[q], ray.p1, fma(ks[q], ray.p2, fma(kcd[q], ray.s1, ksd[q] * ray.s2)));
-        const double turn = __builtin_amdgcn_fract(phase);
-        const float tf = (float)turn;
-        const double c = (double)__builtin_amdgcn_cosf(tf), sn = (double)__builtin_amdgcn_sinf(tf);
-        const double theta = two_pi * (turn - (double)tf);
+        // the phase and its phasor as k_mtf_sum has them (mtf_phasor); the first-order correction for what the
+        // conversion to fp32 drops is folded into the phasor once: (c', sn') = (c - theta sn, sn + theta c)
+        double c, sn;
+        const double theta = mtf_phasor(kc[q], ks[q], kcd[q], ksd[q], ray, c, sn);
         const double wc = ray.w * fma(-theta, sn, c), ws = ray.w * fma(theta, c, sn);
         if (head) {
           re[q] += wc;
@@ -319,11 +311,6 @@ k_mtfg_fold(int n_groups, int K, int64_t n_out, const int64_t* __restrict__ slic
 }
 
 // ---- entry points ---------------------------------------------------------------------------------------------------
-static int64_t mtfg_slices(int64_t count, int64_t max_slices) {
-  const int64_t s = (count + kMtfgMinSlice - 1) / kMtfgMinSlice;
-  return s < 1 ? 1 : (s > max_slices ? max_slices : s);
-}
-
 extern "C" int64_t prt_frame_mtf_gradient_workspace_bytes(int64_t n_selected, int n_groups, int n_parameters,
                                                           int n_frequencies, int n_azimuths, int n_focus) {
   if (n_selected < 0 || n_groups < 1 || n_groups > 65535 || n_parameters < 1 || n_parameters > MTFG_MAX_PARAMETERS ||
@@ -334,15 +321,6 @@ extern "C" int64_t prt_frame_mtf_gradient_workspace_bytes(int64_t n_selected, in
   return (3 * ((int64_t)n_groups + 1) + 3 * (int64_t)n_groups) * 8 +
          (int64_t)(2 * n_frequencies * n_azimuths + n_focus) * 8 +
          n_selected * (int64_t)(sizeof(MtfRay) + (size_t)n_parameters * sizeof(MtfgPar)) + 64;
-}
-
-template <int P>
-static void mtfg_launch_sum(dim3 grid, hipStream_t st, int n_groups, const int64_t* slice_start, const int64_t* group_first,
-                            const MtfRay* stage, const MtfgPar* stage_par, int64_t n_selected, int K, int first,
-                            const double* table, const double* planes, int n_k, int64_t n_out, int lanes, double* slab,
-                            double* weight_slab) {
-  hipLaunchKernelGGL(k_mtfg_sum<P>, grid, dim3(kMtfgBlock), 0, st, n_groups, slice_start, group_first, stage, stage_par,
-                     n_selected, K, first, table, planes, n_k, n_out, lanes, slab, weight_slab);
 }
 
 extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
@@ -366,31 +344,13 @@ extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld
   for (int g = 0; g < n_groups; ++g)
     if (group_first[g] > group_first[g + 1]) return fail(PRT_ERR_ARG, "mtf_gradient: group_first does not decrease");
   if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
-  if (!frequencies || n_frequencies < 1 || n_frequencies > MTF_MAX_FREQUENCIES)
-    return fail(PRT_ERR_ARG, "mtf_gradient: 1 to 4096 frequencies");
-  if (!azimuths_deg || n_azimuths < 1 || n_azimuths > MTF_MAX_AZIMUTHS)
-    return fail(PRT_ERR_ARG, "mtf_gradient: 1 to 16 azimuths");
-  if (!focus || n_focus < 1 || n_focus > MTF_MAX_FOCUS) return fail(PRT_ERR_ARG, "mtf_gradient: 1 to 256 focus shifts");
-  for (int k = 0; k < n_frequencies; ++k)
-    if (!(frequencies[k] >= 0 && frequencies[k] < PRT_INF))
-      return fail(PRT_ERR_ARG, "mtf_gradient: frequencies finite and >= 0");
-  for (int k = 0; k < n_azimuths; ++k)
-    if (!std::isfinite(azimuths_deg[k])) return fail(PRT_ERR_ARG, "mtf_gradient: azimuths finite");
-  for (int k = 0; k < n_focus; ++k)
-    if (!std::isfinite(focus[k])) return fail(PRT_ERR_ARG, "mtf_gradient: focus shifts finite");
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(axes[k])) return fail(PRT_ERR_ARG, "axes: finite");
-  MtfAxes ax;
-  for (int k = 0; k < 3; ++k) { ax.a[k] = axes[k]; ax.e1[k] = axes[3 + k]; ax.e2[k] = axes[6 + k]; }
-  const int n_k = n_azimuths * n_frequencies;
-  const int64_t n_out = (int64_t)n_focus * n_k;
   // the slab is sized for 16 parameters whatever K is, so that the slices do not follow K
-  if ((size_t)n_groups * n_out * kMtfgQuantities * 16 > kMtfgSlabBytes)
-    return fail(PRT_ERR_ARG, "mtf_gradient: n_groups * n_focus * n_azimuths * n_frequencies * 18 * 16 bytes above the 256 MiB slab cap");
-  const int64_t max_slices = std::max<int64_t>(
-      1, std::min<int64_t>(kMtfgMaxSlices, (int64_t)(kMtfgSlabBytes / ((size_t)n_groups * n_out * kMtfgQuantities * 16))));
-  const int lanes = n_out <= kMtfgOut * kMtfgBlock / 4 ? 4 : (n_out <= kMtfgOut * kMtfgBlock / 2 ? 2 : 1);
-  const int64_t tile = (int64_t)kMtfgOut * (kMtfgBlock / lanes), tiles = (n_out + tile - 1) / tile;
+  MtfPlan plan;
+  int rc = mtf_plan("mtf_gradient", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups,
+                    kMtfgQuantities * 16, kMtfgOut, kMtfgBlock, plan);
+  if (rc) return rc;
+  const int n_k = plan.n_k, lanes = plan.lanes;
+  const int64_t n_out = plan.n_out, tiles = plan.tiles;
   // group, chunk and slice starts: each group's share follows from its own count of selected rows
   std::vector<int64_t> starts(3 * ((size_t)n_groups + 1));
   int64_t* const h_group = starts.data();
@@ -401,23 +361,13 @@ extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld
   for (int g = 0; g < n_groups; ++g) {
     const int64_t count = group_first[g + 1] - group_first[g];
     h_chunk[g + 1] = h_chunk[g] + (count + kMtfgChunk - 1) / kMtfgChunk;
-    h_slice[g + 1] = h_slice[g] + mtfg_slices(count, max_slices);
+    h_slice[g + 1] = h_slice[g] + mtf_slices(count, plan.max_slices);
   }
   const int64_t chunk_grid = h_chunk[n_groups], slice_grid = h_slice[n_groups];
   if (chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff || tiles > 65535 ||
       (n_selected + kMtfgBlock - 1) / kMtfgBlock > 0x7fffffff)
     return fail(PRT_ERR_ARG, "mtf_gradient: too many rows or outputs for one launch");
-  // k = nu (cos theta, sin theta), theta in degrees from e1 towards e2; then the planes
-  std::vector<double> host(2 * (size_t)n_k + n_focus);
-  for (int a = 0; a < n_azimuths; ++a) {
-    const double theta = azimuths_deg[a] * (M_PI / 180.0), c = std::cos(theta), s = std::sin(theta);
-    for (int f = 0; f < n_frequencies; ++f) {
-      host[2 * ((size_t)a * n_frequencies + f)] = frequencies[f] * c;
-      host[2 * ((size_t)a * n_frequencies + f) + 1] = frequencies[f] * s;
-    }
-  }
-  for (int k = 0; k < n_focus; ++k) host[2 * (size_t)n_k + k] = focus[k];
-  int rc = ops_device(device);
+  rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   // the workspace (prt_frame_mtf_gradient_workspace_bytes)
@@ -439,24 +389,24 @@ extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld
   double* weight_slab = (double*)(scratch + centre_bytes);
   double* slab = (double*)(scratch + centre_bytes + weight_bytes);
   HIP_TRY(hipMemcpyAsync(d_group, starts.data(), starts.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(table, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(table, plan.host.data(), plan.host.size() * sizeof(double), hipMemcpyHostToDevice, st));
   if (chunk_grid)
     hipLaunchKernelGGL(k_mtfg_centre, dim3((unsigned)chunk_grid), dim3(kMtfgBlock), 0, st, rows, ld, n_rows, selected,
-                       n_selected, n_groups, d_group, d_chunk, ax, weight_column, jacobian, slopes, K, centre_slab);
+                       n_selected, n_groups, d_group, d_chunk, plan.ax, weight_column, jacobian, slopes, K, centre_slab);
   hipLaunchKernelGGL(k_mtfg_centre_fold, dim3((unsigned)(n_groups * n_q)), dim3(64), 0, st, n_groups, K, d_chunk,
                      centre_slab, record_out);
   hipLaunchKernelGGL(k_mtfg_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
                      n_groups, K, reference, centre, record_out);
   if (n_selected)
     hipLaunchKernelGGL(k_mtfg_stage, dim3((unsigned)((n_selected + kMtfgBlock - 1) / kMtfgBlock)), dim3(kMtfgBlock), 0, st,
-                       rows, ld, n_rows, selected, n_selected, n_groups, d_group, centre, ax, weight_column, jacobian,
+                       rows, ld, n_rows, selected, n_selected, n_groups, d_group, centre, plan.ax, weight_column, jacobian,
                        slopes, K, stage, stage_par);
   // whole chunks of kMtfgParams parameters in one launch, then the rest in the smallest instantiation that holds it
   const int whole = K / kMtfgParams, rest = K - whole * kMtfgParams;
   auto sum = [&](auto chunk, int chunks, int first) {
-    mtfg_launch_sum<decltype(chunk)::value>(dim3((unsigned)slice_grid, (unsigned)tiles, (unsigned)chunks), st, n_groups,
-                                            d_slice, d_group, stage, stage_par, n_selected, K, first, table, planes, n_k,
-                                            n_out, lanes, slab, weight_slab);
+    hipLaunchKernelGGL(k_mtfg_sum<decltype(chunk)::value>, dim3((unsigned)slice_grid, (unsigned)tiles, (unsigned)chunks),
+                       dim3(kMtfgBlock), 0, st, n_groups, d_slice, d_group, stage, stage_par, n_selected, K, first, table,
+                       planes, n_k, n_out, lanes, slab, weight_slab);
   };
   if (whole) sum(std::integral_constant<int, kMtfgParams>(), whole, 0);
   if (rest > 4) sum(std::integral_constant<int, 8>(), 1, whole * kMtfgParams);
@@ -466,8 +416,5 @@ extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld
   hipLaunchKernelGGL(k_mtfg_fold,
                      dim3((unsigned)(((int64_t)n_groups * (K + 2) * n_out + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK),
                      0, st, n_groups, K, n_out, d_slice, slab, weight_slab, otf_out, dotf_out, record_out);
-  HIP_TRY(hipFreeAsync(scratch, st));
-  HIP_TRY(hipStreamSynchronize(st));  // (the host tables outlive their copies)
-  HIP_TRY(hipGetLastError());
-  return PRT_OK;
+  return mtf_finish(st, scratch);  // (it drains the stream: the host starts outlive their copy, too)
 }

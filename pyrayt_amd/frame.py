@@ -499,7 +499,7 @@ class DeviceFrame:
         axes = pupil_axes(axis, basis)
         if isinstance(reference, str) and reference != "centroid":
             raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
-        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
+        surface_id = None if surface is None else float(_surface_id(surface))
         self._need_whole("wavefront")
         if weights is not None:
             self._need(weights)
@@ -510,14 +510,7 @@ class DeviceFrame:
         else:
             n_groups = 1
         dev = self.rows.device
-        centres = None
-        if not isinstance(reference, str):
-            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
-            if centres.shape == (3,):
-                centres = centres.expand(n_groups, 3)
-            if tuple(centres.shape) != (n_groups, 3):
-                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
-            centres = centres.to(dev, torch.float64).contiguous()
+        centres = None if isinstance(reference, str) else _group_points(reference, n_groups, dev, "reference: a point")
         radii = None
         if radius is not None:
             radii = torch.as_tensor(np.broadcast_to(np.asarray(radius, dtype=float), (n_groups,)).copy()).to(dev)
@@ -704,6 +697,35 @@ class DeviceFrame:
             raise ValueError("psf: no row is selected at this surface")
         return _distinct_wavelengths(values, "psf")
 
+    # --- what the image passes ask of their caller (mtf, enclosed_energy, ray_aberrations) -----------------------------
+    def _image_selection(self, what, surface, generation, rays_per_source, n_groups, weights, whole=None):
+        """``(surface_id, generation, n_groups)`` of a pass over the rows at ``surface``: the surface's id or None,
+        "last" resolved, the groups counted from the largest ray id where ``n_groups`` is None.  The frame must hold
+        the columns the pass reads -- ``whole``: the columns of a pass that joins by ray id and so needs the whole
+        frame of a trace -- and ``weights`` must be None or a column."""
+        if weights is not None and weights not in _INDEX:
+            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        surface_id = None if surface is None else float(_surface_id(surface))
+        needed = ([] if whole is not None else list(_MTF_COLUMNS)) + ([weights] if weights is not None else [])
+        if whole is None:
+            needed += (["id"] if rays_per_source else []) + (["surface"] if surface_id is not None else [])
+            needed += ["generation"] if generation is not None else []
+        try:
+            if whole is not None:
+                self._need_whole(what, whole)
+            self._need(*needed)
+        except KeyError as error:
+            raise ValueError(f"{what}: {error.args[0]}") from None
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        if rays_per_source:
+            if n_groups is None:
+                top = float(self["id"].max()) if len(self) else -1.0
+                n_groups = max(1, int(top // rays_per_source) + 1)
+        else:
+            n_groups = 1
+        return surface_id, generation, int(n_groups)
+
     # --- geometric MTF through focus (no counterpart upstream) --------------------------------------------------------
     def mtf(self, surface, frequencies, *, azimuths=(0.0, 90.0), focus=(0.0,), reference="centroid", axis=None,
             basis=None, weights="intensity", generation=None, rays_per_source=None, n_groups=None, group=None):
@@ -730,40 +752,15 @@ class DeviceFrame:
 
         if group is not None:
             raise NotImplementedError("mtf() of a sharded frame (group=) is not supported yet")
-        nu = _mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True)
-        theta = _mtf_values(azimuths, "azimuths", 16, "finite, in degrees")
-        planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        nu, theta, planes = _mtf_sampling(frequencies, azimuths, focus)
         axes = pupil_axes(axis, basis)
         if isinstance(reference, str) and reference != "centroid":
             raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
-        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
-        needed = list(_MTF_COLUMNS) + ([weights] if weights is not None else []) + (["id"] if rays_per_source else [])
-        needed += (["surface"] if surface_id is not None else []) + (["generation"] if generation is not None else [])
-        try:
-            self._need(*needed)
-        except KeyError as error:
-            raise ValueError(f"mtf: {error.args[0]}") from None
-        if generation == "last":
-            generation = self.last_generation_number() or 0
-        if rays_per_source:
-            if n_groups is None:
-                top = float(self["id"].max()) if len(self) else -1.0
-                n_groups = max(1, int(top // rays_per_source) + 1)
-        else:
-            n_groups = 1
-        n_groups = int(n_groups)
+        surface_id, generation, n_groups = self._image_selection("mtf", surface, generation, rays_per_source, n_groups,
+                                                                 weights)
         rows = self._contiguous_rows()
         dev = rows.device
-        centres = None
-        if not isinstance(reference, str):
-            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
-            if centres.shape == (3,):
-                centres = centres.expand(n_groups, 3)
-            if tuple(centres.shape) != (n_groups, 3):
-                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
-            centres = centres.to(dev, torch.float64).contiguous()
+        centres = None if isinstance(reference, str) else _group_points(reference, n_groups, dev, "reference: a point")
         n_rows = rows.shape[1]
         otf = torch.empty((n_groups, len(planes), len(theta), len(nu), 2), dtype=torch.float64, device=dev)
         record = torch.empty((n_groups, 6), dtype=torch.float64, device=dev)
@@ -821,37 +818,14 @@ class DeviceFrame:
         if not isinstance(shape, str) or shape not in _ENERGY_SHAPES:
             raise ValueError(f"shape: one of {sorted(_ENERGY_SHAPES)} (got {shape!r})")
         planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
         axes = pupil_axes(axis, basis)
         if isinstance(reference, str) and reference != "centroid":
             raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
-        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
-        needed = list(_MTF_COLUMNS) + ([weights] if weights is not None else []) + (["id"] if rays_per_source else [])
-        needed += (["surface"] if surface_id is not None else []) + (["generation"] if generation is not None else [])
-        try:
-            self._need(*needed)
-        except KeyError as error:
-            raise ValueError(f"enclosed_energy: {error.args[0]}") from None
-        if generation == "last":
-            generation = self.last_generation_number() or 0
-        if rays_per_source:
-            if n_groups is None:
-                top = float(self["id"].max()) if len(self) else -1.0
-                n_groups = max(1, int(top // rays_per_source) + 1)
-        else:
-            n_groups = 1
-        n_groups = int(n_groups)
+        surface_id, generation, n_groups = self._image_selection("enclosed_energy", surface, generation, rays_per_source,
+                                                                 n_groups, weights)
         rows = self._contiguous_rows()
         dev = rows.device
-        centres = None
-        if not isinstance(reference, str):
-            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
-            if centres.shape == (3,):
-                centres = centres.expand(n_groups, 3)
-            if tuple(centres.shape) != (n_groups, 3):
-                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
-            centres = centres.to(dev, torch.float64).contiguous()
+        centres = None if isinstance(reference, str) else _group_points(reference, n_groups, dev, "reference: a point")
         n_rows = rows.shape[1]
         energy = torch.empty((n_groups, len(planes), len(edges)), dtype=torch.float64, device=dev)
         radius = torch.empty((n_groups, len(planes), len(phi)), dtype=torch.float64, device=dev)
@@ -957,8 +931,6 @@ class DeviceFrame:
         if isinstance(zones, bool) or not isinstance(zones, (int, np.integer)) or not 0 <= zones <= 1024:
             raise ValueError(f"zones: the number of rings, 0 to 1024 (got {zones!r})")
         terms, zones = int(terms), int(zones)
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
         if pupil_radius is not None and not (np.isfinite(pupil_radius) and pupil_radius > 0):
             raise ValueError("pupil_radius: a positive number, or None for the group's largest extent")
         origin = np.ascontiguousarray(np.asarray(launch_origin, dtype=np.float64))
@@ -967,32 +939,12 @@ class DeviceFrame:
         axes = pupil_axes(axis, basis)
         if isinstance(reference, str) and reference not in ("centroid", "chief"):
             raise ValueError('reference: "centroid", "chief", a point or an (n_groups, 3) array')
-        surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
-        try:
-            self._need_whole("ray_aberrations", _JOIN_COLUMNS)
-            if weights is not None:
-                self._need(weights)
-        except KeyError as error:
-            raise ValueError(f"ray_aberrations: {error.args[0]}") from None
-        if generation == "last":
-            generation = self.last_generation_number() or 0
-        if rays_per_source:
-            if n_groups is None:
-                top = float(self["id"].max()) if len(self) else -1.0
-                n_groups = max(1, int(top // rays_per_source) + 1)
-        else:
-            n_groups = 1
-        n_groups = int(n_groups)
+        surface_id, generation, n_groups = self._image_selection("ray_aberrations", surface, generation, rays_per_source,
+                                                                 n_groups, weights, whole=_JOIN_COLUMNS)
         rows = self._contiguous_rows()
         dev = rows.device
-        centres, mode = None, {"centroid": 0, "chief": 2}.get(reference if isinstance(reference, str) else None, 1)
-        if mode == 1:
-            centres = torch.as_tensor(np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float))
-            if centres.shape == (3,):
-                centres = centres.expand(n_groups, 3)
-            if tuple(centres.shape) != (n_groups, 3):
-                raise ValueError(f"reference: a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
-            centres = centres.to(dev, torch.float64).contiguous()
+        mode = {"centroid": 0, "chief": 2}.get(reference if isinstance(reference, str) else None, 1)
+        centres = None if isinstance(reference, str) else _group_points(reference, n_groups, dev, "reference: a point")
         index = self._launch_index()
         n_rows = rows.shape[1]
         if generation is not None:  # (generation-major: at most one generation's rows are selected)
@@ -2885,21 +2837,12 @@ class Sensitivity:
 
         if reference not in ("fixed", "centroid"):
             raise ValueError('reference: "fixed" or "centroid"')
-        nu = _mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True)
-        theta = _mtf_values(azimuths, "azimuths", 16, "finite, in degrees")
-        planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
+        nu, theta, planes = _mtf_sampling(frequencies, azimuths, focus)
         axes = pupil_axes(axis, basis)
         rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
         dev = rows.device
         n_groups, K, n_rows, n_selected = len(first) - 1, self.n_parameters, rows.shape[1], int(self._selected.shape[0])
-        centres = None
-        if centre is not None:
-            centres = torch.as_tensor(np.asarray(centre.cpu() if hasattr(centre, "cpu") else centre, dtype=float))
-            if centres.shape == (3,):
-                centres = centres.expand(n_groups, 3)
-            if tuple(centres.shape) != (n_groups, 3):
-                raise ValueError(f"centre: None, a point or an ({n_groups}, 3) array (got shape {tuple(centres.shape)})")
-            centres = centres.to(dev, torch.float64).contiguous()
+        centres = None if centre is None else _group_points(centre, n_groups, dev, "centre: None, a point")
         shape = (len(planes), len(theta), len(nu))
         otf = torch.empty((n_groups,) + shape + (2,), dtype=torch.float64, device=dev)
         dotf = torch.empty((n_groups, K + 1) + shape + (2,), dtype=torch.float64, device=dev)
@@ -3241,6 +3184,26 @@ def _mtf_values(values, name, cap, rule, non_negative=False):
     if not np.all(np.isfinite(array)) or (non_negative and np.any(array < 0)):
         raise ValueError(f"{name}: 1 to {cap} numbers, {rule}")
     return array
+
+
+def _mtf_sampling(frequencies, azimuths, focus):
+    """The frequencies, azimuths and focus shifts of ``mtf()`` and ``mtf_gradient()`` as arrays."""
+    return (_mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True),
+            _mtf_values(azimuths, "azimuths", 16, "finite, in degrees"),
+            _mtf_values(focus, "focus", 256, "finite shifts along the axis"))
+
+
+def _group_points(value, n_groups, device, rule):
+    """A point, or one per group, as an (n_groups, 3) float64 tensor on ``device``.  ``rule``: the argument's name and
+    what else it takes, the head of the message."""
+    import torch
+
+    points = torch.as_tensor(np.asarray(value.cpu() if hasattr(value, "cpu") else value, dtype=float))
+    if points.shape == (3,):
+        points = points.expand(n_groups, 3)
+    if tuple(points.shape) != (n_groups, 3):
+        raise ValueError(f"{rule} or an ({n_groups}, 3) array (got shape {tuple(points.shape)})")
+    return points.to(device, torch.float64).contiguous()
 
 
 def _positions(sampled, wanted, name):

@@ -93,7 +93,7 @@ def kernel_constants():
 
 K = kernel_constants()
 # The host rules below (psf_slices, mtf_slices, mtf_lanes) are Python copies of lines of psf_plan (with the arguments
-# prt_frame_psf gives it) / prt_frame_mtf:
+# prt_frame_psf gives it) / mtf_slices and mtf_plan (with the arguments prt_frame_mtf gives it):
 # the device's own slice count is not observable, so tests/test_host_diffraction_reference.py holds the copies to the
 # header text (HOST_RULES), and a change of a rule there fails that test instead of moving the GPU tests off their edges.
 HOST_RULES = {
@@ -108,9 +108,12 @@ HOST_RULES = {
     "prt_mtf.hpp": (
         "const int64_t s = (count + kMtfMinSlice - 1) / kMtfMinSlice;",
         "return s < 1 ? 1 : (s > max_slices ? max_slices : s);",
-        "std::max<int64_t>(1, std::min<int64_t>(kMtfMaxSlices, (int64_t)(kMtfSlabBytes / ((size_t)n_groups * n_out * 16))));",
-        "const int lanes = n_out <= kMtfOut * kMtfBlock / 4 ? 4 : (n_out <= kMtfOut * kMtfBlock / 2 ? 2 : 1);",
-        "const int64_t tile = (int64_t)kMtfOut * (kMtfBlock / lanes), tiles = (n_out + tile - 1) / tile;"),
+        "const size_t cells = (size_t)n_groups * n_out * cell_bytes;",
+        "p.max_slices = std::max<int64_t>(1, std::min<int64_t>(kMtfMaxSlices, (int64_t)(kMtfSlabBytes / cells)));",
+        "const int lanes = n_out <= out * block / 4 ? 4 : (n_out <= out * block / 2 ? 2 : 1);",
+        "const int64_t tile = (int64_t)out * (block / lanes), tiles = (n_out + tile - 1) / tile;",
+        'int rc = mtf_plan("mtf", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups, 16,',
+        "kMtfOut, kMtfBlock, plan);"),
 }
 
 

@@ -69,16 +69,16 @@ def kernel_constants():
 
 K = kernel_constants()
 QUANTITIES = MAX_PARAMETERS + 2  # (kMtfgQuantities: the slab is sized for 16 parameters whatever K is)
-# Python copies of lines of prt_frame_mtf_gradient, held to the header's text by tests/test_host_mtf_gradient.py
+# Python copies of lines of prt_frame_mtf_gradient and of mtf_slices and mtf_plan (prt_mtf.hpp) as it calls them, held to
+# the headers' text by tests/test_host_mtf_gradient.py
 HOST_RULES = {
     "prt_mtf_gradient.hpp": (
         "static const int kMtfgQuantities = MTFG_MAX_PARAMETERS + 2;",
         "enum { MTFG_MAX_PARAMETERS = 16, MTFG_RECORD = 7 };",
-        "const int64_t s = (count + kMtfgMinSlice - 1) / kMtfgMinSlice;",
-        "return s < 1 ? 1 : (s > max_slices ? max_slices : s);",
-        "1, std::min<int64_t>(kMtfgMaxSlices, (int64_t)(kMtfgSlabBytes / ((size_t)n_groups * n_out * kMtfgQuantities * 16))));",
-        "const int lanes = n_out <= kMtfgOut * kMtfgBlock / 4 ? 4 : (n_out <= kMtfgOut * kMtfgBlock / 2 ? 2 : 1);",
-        "const int64_t tile = (int64_t)kMtfgOut * (kMtfgBlock / lanes), tiles = (n_out + tile - 1) / tile;",
+        "static_assert(kMtfgMinSlice == kMtfMinSlice && kMtfgMaxSlices == kMtfMaxSlices && kMtfgSlabBytes == kMtfSlabBytes,",
+        'int rc = mtf_plan("mtf_gradient", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups,',
+        "kMtfgQuantities * 16, kMtfgOut, kMtfgBlock, plan);",
+        "h_slice[g + 1] = h_slice[g] + mtf_slices(count, plan.max_slices);",
         "h_chunk[g + 1] = h_chunk[g] + (count + kMtfgChunk - 1) / kMtfgChunk;",
         "const int whole = K / kMtfgParams, rest = K - whole * kMtfgParams;",
         "if (rest > 4) sum(std::integral_constant<int, 8>(), 1, whole * kMtfgParams);",
@@ -86,6 +86,13 @@ HOST_RULES = {
         "else if (rest == 2) sum(std::integral_constant<int, 2>(), 1, whole * kMtfgParams);",
         "else if (rest == 1) sum(std::integral_constant<int, 1>(), 1, whole * kMtfgParams);",
         "for (int64_t base = lo; base < hi; base += kMtfgTile) {"),
+    "prt_mtf.hpp": (
+        "const int64_t s = (count + kMtfMinSlice - 1) / kMtfMinSlice;",
+        "return s < 1 ? 1 : (s > max_slices ? max_slices : s);",
+        "const size_t cells = (size_t)n_groups * n_out * cell_bytes;",
+        "p.max_slices = std::max<int64_t>(1, std::min<int64_t>(kMtfMaxSlices, (int64_t)(kMtfSlabBytes / cells)));",
+        "const int lanes = n_out <= out * block / 4 ? 4 : (n_out <= out * block / 2 ? 2 : 1);",
+        "const int64_t tile = (int64_t)out * (block / lanes), tiles = (n_out + tile - 1) / tile;"),
 }
 
 

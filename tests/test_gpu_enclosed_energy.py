@@ -239,3 +239,43 @@ def test_cut_frames_give_the_same_bits_and_trace_enclosed_energy():
     assert np.array_equal(tracer.trace().to_numpy(dtype=float), spot)
     with pytest.raises(ValueError, match="without the column"):
         tracer.trace_device().enclosed_energy(det, radii)
+
+
+# ---- the staging pass shared with mtf() ---------------------------------------------------------------------------------
+def test_mtf_and_enclosed_energy_stage_the_same_rays():
+    """mtf() and enclosed_energy() of one frame and one set of arguments run one staging pass: each group's centre, sum
+    of weights, rays used and rays left out are the same bits in both records.  1, 2049 and 4097 rays among 4196 rows of
+    another surface (one chunk and one slice, two slices, two chunks and three slices), and three groups of which the
+    middle one keeps no ray; every group also holds a row with a NaN end point, one with u.a == 0 and one with a
+    negative weight, so that ``missed`` is not zero -- which the host reference says before the device is asked.  The
+    two passes add up sum w in different orders (slices, chunks), so the weights are multiples of 1/8 below 8: their
+    sum is exact in any order."""
+    import diffraction_reference as R
+    from pyrayt_amd.frame import pupil_axes
+
+    for counts, filler in (([1], 4196), ([2049], 4196), ([4097], 4196), ([300, 0, 2049], 0)):
+        case = R.mtf_case(counts, filler=filler, left_out=3, seed=130 + counts[0])
+        frame = case.frame
+        here = frame[:, IX["surface"]] == R.SURFACE
+        frame[here, IX["intensity"]] = np.where(frame[here, IX["intensity"]] < 0, -1.0,
+                                                np.floor(frame[here, IX["intensity"]] % 7 * 8 + 8) / 8)
+        rows, group = R.select_rows(frame, R.SURFACE, case.rays_per_source, case.n_groups)
+        kept = R.mtf_kept(rows[:, 9:12], rows[:, 12:15], rows[:, IX["intensity"]], pupil_axes())
+        missed = np.bincount(group[~kept], minlength=case.n_groups)
+        used = np.bincount(group[kept], minlength=case.n_groups)
+        assert list(used) == counts and list(missed) == [3] * len(counts)  # (a vacuous case must not pass)
+        assert np.isnan(rows[~kept, 10]).sum() == len(counts) and (rows[~kept, 12] == 0.0).sum() == len(counts)
+        device = device_frame(frame)
+        given = np.linspace(-1e-3, 2e-3, 3 * case.n_groups).reshape(case.n_groups, 3)
+        for reference in ("centroid", given):
+            options = dict(case.options, reference=reference, focus=(0.0, 0.03))
+            mtf = device.mtf(R.SURFACE, [0.0, 40.0], **options)
+            energy = device.enclosed_energy(R.SURFACE, [0.01], **options)
+            what = (counts, "centroid" if isinstance(reference, str) else "given")
+            assert list(mtf.record[:, 5]) == list(missed) and list(mtf.record[:, 4]) == counts, what
+            for ours, theirs in ((slice(0, 3), slice(0, 3)), (3, 7), (4, 8), (5, 9)):
+                a = np.ascontiguousarray(mtf.record[:, ours]).view(np.uint64)
+                b = np.ascontiguousarray(energy.record[:, theirs]).view(np.uint64)
+                assert np.array_equal(a, b), (what, ours, mtf.record[:, ours], energy.record[:, theirs])
+            if not isinstance(reference, str):
+                assert np.array_equal(mtf.record[:, :3], given)

@@ -145,9 +145,10 @@ def test_step_solves_the_linearised_residuals():
 
 
 def test_the_partition_rules_are_the_headers_own_lines():
-    text = " ".join(open(os.path.join(ROOT, "pyrayt_amd", "csrc", "prt_mtf_gradient.hpp")).read().split())
-    for line in M.HOST_RULES["prt_mtf_gradient.hpp"]:
-        assert " ".join(line.split()) in text, line
+    for name, lines in M.HOST_RULES.items():
+        text = " ".join(open(os.path.join(ROOT, "pyrayt_amd", "csrc", name)).read().split())
+        for line in lines:
+            assert " ".join(line.split()) in text, (name, line)
     K = M.K
     assert (K.kMtfgBlock, K.kMtfgTile, K.kMtfgOut, K.kMtfgParams, K.kMtfgChunk, K.kMtfgMinSlice, K.kMtfgMaxSlices) == (
         256, 128, 2, 8, 1024, 2048, 256)
