@@ -40,6 +40,20 @@
 // so each lane bisects the table in the workspace and loads its own 200-byte entry with vector loads, which hit in the
 // cache after the first wave.  And k_sens_partials keeps 206 x 4 doubles (6.5 KB) of LDS so that a workgroup needs one
 // barrier for all its entries instead of two an entry; k_sens_step itself uses the 64 bytes of the counters and no more.
+//
+// The host side (from "entry points" down) has the Fresnel pass's shape.  The four entry points describe their call once
+// -- SensCall, what all of them are given, and the parts a form adds: SensDesignCall, SensOpdCall, SensLaunchCall -- and
+// which parts are present is the form.  sens_run is a sequence of steps with one job each:
+//   sens_check      the buffers and sizes; gives n_rows and the rows of the largest group
+//   sens_table      the surface table from the primitives
+//   sens_rigid      the twists, and through sens_mark (the one bisection of the surface ids) the moved_by bits
+//   sens_design     S, the index rates and the index_by bits
+//   sens_launch     the seeds and the glass table
+//   sens_layout     every pointer carved from the workspace, for every form; the four *_workspace_bytes functions are this
+//                   layout from address 0
+//   sens_upload, sens_steps (the form's step kernel, chosen once as a lambda), sens_sums, sens_report (the status words)
+// Everything is refused before a device is touched, in the order of the steps.  The five __global__ step wrappers are
+// written out one by one on purpose: profiles and kernel traces name them, and their arguments are their identity.
 #pragma once
 
 enum { SENS_BAD_SELECTION = JOIN_OWN_BIT };
@@ -769,10 +783,17 @@ k_sens_opd_partials(const double* __restrict__ rows, int64_t ld, int64_t n_rows,
     if (el[q] >= 0) out[threadIdx.x + q * kSensBlock] = acc[q];
 }
 
-// ---- entry points ----------------------------------------------------------------------------------------------------------
-struct SensWork { SensWords* words; SensSurface* table; int64_t* first; double* pivots; double* state; int64_t* last_row; int* stamp; double* partials; };
-// what the wavefront form has behind the others' workspace: the group records and the partials of its own sums
-struct SensOpdWork { double* groups; double* partials; };
+// ---- entry points: what the four forms share ---------------------------------------------------------------------------------
+// what every entry point is given
+struct SensCall {
+  int device; const double* rows; int64_t ld; const int64_t* rows_per_generation; int n_generations; double id0; int64_t n_ids;
+  const prt_prim* surfaces; int n_surfaces; const double* twists; const int64_t* parameter_ids; const int32_t* parameter_first;
+  int n_parameters; const int64_t* row_slot; const int64_t* selected; int64_t n_selected; const int64_t* group_first;
+  int n_groups, weight_column; const double* pivots; double *jacobian_out, *sums_out; int64_t* record_out;
+  void *workspace, *stream;
+};
+// the design form's arguments on the host: linear HOST (K, 9), index_rates HOST K, index_ids and index_first as parameter_*
+struct SensDesignCall { const double* linear; const double* index_rates; const int64_t* index_ids; const int32_t* index_first; };
 // the wavefront form's arguments on the host: opl DEVICE n_rows; groups HOST (n_groups, 6); axes HOST 9; the outputs DEVICE
 struct SensOpdCall {
   const double* opl; const double* groups; const double* axes; int n_terms;
@@ -785,117 +806,133 @@ struct SensLaunchCall {
   double* slopes;
 };
 
+// ---- the workspace: one layout for every form -----------------------------------------------------------------------------------
+struct SensSizes { int64_t n_ids; int n_surfaces, n_parameters, n_groups; int64_t max_group_rows; };
+// every form: the words, the surface table, group_first, the pivots, the state, per id its previous row, the partials of
+// the sums, the stamps.  The wavefront form has behind that the group records and the partials of its own sums; the
+// launch form, behind everything the other forms carve, the glass table.  `end`: the first byte the call leaves alone
+struct SensWork {
+  SensWords* words; SensSurface* table; int64_t* first; double* pivots; double* state; int64_t* last_row; int* stamp; double* partials;
+  double *opd_groups, *opd_partials;
+  SensGlass* glass;
+  char* end;
+};
 
 static int64_t sens_chunks(int64_t max_group_rows) { return (max_group_rows + kSensBlock - 1) / kSensBlock; }
 
-static SensOpdWork sens_opd_carve(char* after, int n_parameters, int n_groups, int64_t max_group_rows, int n_terms, char** end) {
-  SensOpdWork w;
-  w.groups = (double*)(((uintptr_t)after + 7) & ~(uintptr_t)7);
-  w.partials = w.groups + (int64_t)n_groups * SENS_OPD_GROUP;
-  *end = (char*)(w.partials + (int64_t)n_groups * sens_chunks(max_group_rows) * sens_opd_entries(n_parameters, n_terms));
-  return w;
+static bool sens_sizes_ok(const SensSizes& s) {
+  return join_n_ids_ok(s.n_ids) && s.n_surfaces >= 1 && s.n_surfaces <= (1 << 20) && s.n_parameters >= 1 &&
+         s.n_parameters <= SENS_MAX_PARAMETERS && s.n_groups >= 1 && s.n_groups <= 65535 && s.max_group_rows >= 0 &&
+         sens_chunks(s.max_group_rows) <= 0x7fffffff;
 }
 
-static bool sens_sizes_ok(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups, int64_t max_group_rows) {
-  return join_n_ids_ok(n_ids) && n_surfaces >= 1 && n_surfaces <= (1 << 20) && n_parameters >= 1 &&
-         n_parameters <= SENS_MAX_PARAMETERS && n_groups >= 1 && n_groups <= 65535 && max_group_rows >= 0 &&
-         sens_chunks(max_group_rows) <= 0x7fffffff;
-}
-
-static SensWork sens_carve(void* workspace, int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
-                           int64_t max_group_rows, char** end, int planes = 6) {
+// `planes` of state a parameter and id (6 rigid, 7 design, 8 with dL); n_terms: the wavefront's Zernike terms, or 0
+static SensWork sens_layout(void* workspace, const SensSizes& s, int planes, int n_terms, bool with_glasses) {
+  const int64_t group_chunks = (int64_t)s.n_groups * sens_chunks(s.max_group_rows);
+  const auto to8 = [](char* at) { return ((uintptr_t)at + 7) & ~(uintptr_t)7; };
   SensWork w;
   w.words = (SensWords*)(((uintptr_t)workspace + 63) & ~(uintptr_t)63);
   w.table = (SensSurface*)((char*)w.words + 64);
-  w.first = (int64_t*)(w.table + n_surfaces);
-  w.pivots = (double*)(w.first + n_groups + 1);
-  w.state = w.pivots + 3 * (int64_t)n_groups;
-  w.last_row = (int64_t*)(w.state + planes * (int64_t)n_parameters * n_ids);
-  w.partials = (double*)(w.last_row + n_ids);
-  w.stamp = (int*)(w.partials + (int64_t)n_groups * sens_chunks(max_group_rows) * sens_entries(n_parameters));
-  *end = (char*)(w.stamp + n_ids);
+  w.first = (int64_t*)(w.table + s.n_surfaces);
+  w.pivots = (double*)(w.first + s.n_groups + 1);
+  w.state = w.pivots + 3 * (int64_t)s.n_groups;
+  w.last_row = (int64_t*)(w.state + planes * (int64_t)s.n_parameters * s.n_ids);
+  w.partials = (double*)(w.last_row + s.n_ids);
+  w.stamp = (int*)(w.partials + group_chunks * sens_entries(s.n_parameters));
+  w.end = (char*)(w.stamp + s.n_ids);
+  w.opd_groups = w.opd_partials = nullptr;
+  if (n_terms) {
+    w.opd_groups = (double*)to8(w.end);
+    w.opd_partials = w.opd_groups + (int64_t)s.n_groups * SENS_OPD_GROUP;
+    w.end = (char*)(w.opd_partials + group_chunks * sens_opd_entries(s.n_parameters, n_terms));
+  }
+  w.glass = nullptr;
+  if (with_glasses) {
+    w.glass = (SensGlass*)to8(w.end);
+    w.end = (char*)(w.glass + s.n_surfaces);
+  }
   return w;
+}
+
+// the layout from address 0, and 64 bytes for the alignment of the words
+static int64_t sens_workspace_bytes(const SensSizes& s, int planes, int n_terms, bool with_glasses) {
+  if (!sens_sizes_ok(s)) return PRT_ERR_ARG;
+  return (int64_t)(uintptr_t)sens_layout(nullptr, s, planes, n_terms, with_glasses).end + 64;
 }
 
 extern "C" int64_t prt_frame_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
                                                          int64_t max_group_rows) {
-  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows)) return PRT_ERR_ARG;
-  char* end;
-  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end);
-  (void)w;
-  return (int64_t)(uintptr_t)end + 64;
+  return sens_workspace_bytes({n_ids, n_surfaces, n_parameters, n_groups, max_group_rows}, 6, 0, false);
 }
 
 extern "C" int64_t prt_frame_design_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters,
                                                                 int n_groups, int64_t max_group_rows) {
-  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows)) return PRT_ERR_ARG;
-  char* end;
-  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end, 7);
-  (void)w;
-  return (int64_t)(uintptr_t)end + 64;
+  return sens_workspace_bytes({n_ids, n_surfaces, n_parameters, n_groups, max_group_rows}, 7, 0, false);
 }
 
 extern "C" int64_t prt_frame_opd_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters, int n_groups,
                                                              int64_t max_group_rows, int n_terms) {
-  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows) || n_terms < 1 || n_terms > WF_MAX_TERMS)
-    return PRT_ERR_ARG;
-  char *mid, *end;
-  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &mid, 8);
-  (void)w;
-  const SensOpdWork o = sens_opd_carve(mid, n_parameters, n_groups, max_group_rows, n_terms, &end);
-  (void)o;
-  return (int64_t)(uintptr_t)end + 64;
+  if (n_terms < 1 || n_terms > WF_MAX_TERMS) return PRT_ERR_ARG;
+  return sens_workspace_bytes({n_ids, n_surfaces, n_parameters, n_groups, max_group_rows}, 8, n_terms, false);
 }
 
-// the entry points: `design` chooses the form, `wave` (not null: with design) the wavefront form; linear, index_rates, index_ids and index_first are read by the design form
-static int sens_run(bool design, int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
-                    int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces, int n_surfaces,
-                    const double* twists, const int64_t* parameter_ids, const int32_t* parameter_first,
-                    const double* linear, const double* index_rates, const int64_t* index_ids,
-                    const int32_t* index_first, int n_parameters, const int64_t* row_slot, const int64_t* selected,
-                    int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
-                    const double* pivots, double* jacobian_out, double* sums_out, int64_t* record_out, void* workspace,
-                    void* stream, const SensOpdCall* wave = nullptr, const SensLaunchCall* launch = nullptr) {
-  const int64_t n_rows = join_rows(rows_per_generation, n_generations, ld, kSensBlock, "sensitivity");
-  if (n_rows < 0) return (int)n_rows;
-  if (!record_out || !workspace || !sums_out || !surfaces || !twists || !parameter_first || !group_first || !pivots ||
-      n_selected < 0 || n_selected > n_rows || (n_rows && (!rows || !row_slot)) ||
-      (n_selected && (!selected || !jacobian_out)) || (design && (!linear || !index_rates || !index_first)))
+extern "C" int64_t prt_frame_launch_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters,
+                                                                int n_groups, int64_t max_group_rows, int n_terms) {
+  if (n_terms < 0 || n_terms > WF_MAX_TERMS) return PRT_ERR_ARG;
+  return sens_workspace_bytes({n_ids, n_surfaces, n_parameters, n_groups, max_group_rows}, n_terms ? 8 : 7, n_terms, true);
+}
+
+// ---- the steps of a call, in the order sens_run takes them ------------------------------------------------------------------------
+// the buffers and the sizes; the number of rows (or an error) and the rows of the largest group
+static int64_t sens_check(const SensCall& c, const SensDesignCall* design, const SensOpdCall* wave, int64_t& max_group_rows) {
+  const int64_t n_rows = join_rows(c.rows_per_generation, c.n_generations, c.ld, kSensBlock, "sensitivity");
+  if (n_rows < 0) return n_rows;
+  if (!c.record_out || !c.workspace || !c.sums_out || !c.surfaces || !c.twists || !c.parameter_first || !c.group_first ||
+      !c.pivots || c.n_selected < 0 || c.n_selected > n_rows || (n_rows && (!c.rows || !c.row_slot)) ||
+      (c.n_selected && (!c.selected || !c.jacobian_out)) ||
+      (design && (!design->linear || !design->index_rates || !design->index_first)))
     return fail(PRT_ERR_ARG, "bad buffers");
   if (wave) {
     if (!wave->groups || !wave->axes || !wave->sums || (n_rows && !wave->opl) ||
-        (n_selected && (!wave->dfield || !wave->dopd || !wave->dpupil || !wave->opd || !wave->pupil)))
+        (c.n_selected && (!wave->dfield || !wave->dopd || !wave->dpupil || !wave->opd || !wave->pupil)))
       return fail(PRT_ERR_ARG, "bad buffers");
     if (wave->n_terms < 1 || wave->n_terms > WF_MAX_TERMS) return fail(PRT_ERR_ARG, "opd sensitivity: 1 to 36 Zernike terms");
     for (int k = 0; k < 9; ++k)
       if (!std::isfinite(wave->axes[k])) return fail(PRT_ERR_ARG, "opd sensitivity: axes finite");
   }
-  int rc = join_ids(id0, n_ids);
+  const int rc = join_ids(c.id0, c.n_ids);
   if (rc) return rc;
-  if (n_parameters < 1 || n_parameters > SENS_MAX_PARAMETERS)
+  if (c.n_parameters < 1 || c.n_parameters > SENS_MAX_PARAMETERS)
     return fail(PRT_ERR_ARG, "sensitivity: 1 to 16 parameters a call");
-  if (n_groups < 1 || n_groups > 65535) return fail(PRT_ERR_ARG, "sensitivity: 1 to 65535 groups");
-  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "sensitivity: weight_column");
-  if (n_surfaces < 1 || n_surfaces > (1 << 20)) return fail(PRT_ERR_ARG, "sensitivity: 1 to 2^20 surfaces in the table");
-  int64_t max_group_rows = 0;
-  if (group_first[0] != 0 || group_first[n_groups] != n_selected)
+  if (c.n_groups < 1 || c.n_groups > 65535) return fail(PRT_ERR_ARG, "sensitivity: 1 to 65535 groups");
+  if (c.weight_column < -1 || c.weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "sensitivity: weight_column");
+  if (c.n_surfaces < 1 || c.n_surfaces > (1 << 20)) return fail(PRT_ERR_ARG, "sensitivity: 1 to 2^20 surfaces in the table");
+  max_group_rows = 0;
+  if (c.group_first[0] != 0 || c.group_first[c.n_groups] != c.n_selected)
     return fail(PRT_ERR_ARG, "sensitivity: group_first runs from 0 to n_selected");
-  for (int g = 0; g < n_groups; ++g) {
-    if (group_first[g + 1] < group_first[g]) return fail(PRT_ERR_ARG, "sensitivity: group_first ascends");
-    max_group_rows = std::max(max_group_rows, group_first[g + 1] - group_first[g]);
+  for (int g = 0; g < c.n_groups; ++g) {
+    if (c.group_first[g + 1] < c.group_first[g]) return fail(PRT_ERR_ARG, "sensitivity: group_first ascends");
+    max_group_rows = std::max(max_group_rows, c.group_first[g + 1] - c.group_first[g]);
   }
-  for (int k = 0; k < 3 * n_groups; ++k)
-    if (!(std::fabs(pivots[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: pivots finite");
+  for (int k = 0; k < 3 * c.n_groups; ++k)
+    if (!(std::fabs(c.pivots[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: pivots finite");
   if (wave)  // (a group without rows has a NaN record and no row reads it; a pupil radius must divide)
-    for (int g = 0; g < n_groups; ++g)
-      if (group_first[g + 1] > group_first[g] && !(wave->groups[SENS_OPD_GROUP * g + 5] > 0.0 && wave->groups[SENS_OPD_GROUP * g + 5] < PRT_INF))
+    for (int g = 0; g < c.n_groups; ++g) {
+      const double radius = wave->groups[SENS_OPD_GROUP * g + 5];
+      if (c.group_first[g + 1] > c.group_first[g] && !(radius > 0.0 && radius < PRT_INF))
         return fail(PRT_ERR_ARG, "opd sensitivity: a group's pupil radius is not a positive number");
-  std::vector<SensSurface> table((size_t)n_surfaces);
-  for (int s = 0; s < n_surfaces; ++s) {
-    const prt_prim& pr = surfaces[s];
+    }
+  return n_rows;
+}
+
+// the surface table: of every primitive what world_normal_len reads, no bits yet
+static int sens_table(const SensCall& c, std::vector<SensSurface>& table) {
+  table.resize((size_t)c.n_surfaces);
+  for (int s = 0; s < c.n_surfaces; ++s) {
+    const prt_prim& pr = c.surfaces[s];
     if (pr.type < PRT_PRIM_SPHERE || pr.type > PRT_PRIM_PARABOLOID || (pr.normal_scale != 1 && pr.normal_scale != -1))
       return fail(PRT_ERR_ARG, "sensitivity: a surface of unknown kind or normal_scale");
-    if (s && !(surfaces[s - 1].surface_id < pr.surface_id))
+    if (s && !(c.surfaces[s - 1].surface_id < pr.surface_id))
       return fail(PRT_ERR_ARG, "sensitivity: the surface table is sorted by id, ids distinct");
     SensSurface& out = table[s];
     std::memset(&out, 0, sizeof(out));
@@ -908,179 +945,236 @@ static int sens_run(bool design, int device, const double* rows, int64_t ld, con
     out.type = pr.type;
     out.normal_scale = pr.normal_scale;
   }
-  SensArgs args;
+  return PRT_OK;
+}
+
+// bit k of `by` (moved_by or index_by) in the table's entry of each of ids[from, to), found by bisection of the sorted
+// surfaces; `refusal`: what is said of an id that no surface has
+static int sens_mark(const SensCall& c, const int64_t* ids, int from, int to, uint32_t SensSurface::*by, int k,
+                     std::vector<SensSurface>& table, const char* refusal) {
+  for (int at = from; at < to; ++at) {
+    int lo = 0, hi = c.n_surfaces;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (c.surfaces[mid].surface_id < ids[at]) lo = mid + 1; else hi = mid;
+    }
+    if (lo == c.n_surfaces || c.surfaces[lo].surface_id != ids[at]) return fail(PRT_ERR_ARG, refusal);
+    table[lo].*by |= 1u << k;
+  }
+  return PRT_OK;
+}
+
+// the rigid parameters: the twists, and which surfaces each moves
+static int sens_rigid(const SensCall& c, SensArgs& args, std::vector<SensSurface>& table) {
   std::memset(&args, 0, sizeof(args));
-  args.n_parameters = n_parameters;
-  args.n_surfaces = n_surfaces;
-  if (parameter_first[0] != 0) return fail(PRT_ERR_ARG, "sensitivity: parameter_first starts at 0");
-  for (int k = 0; k < n_parameters; ++k) {
-    const int from = parameter_first[k], to = parameter_first[k + 1];
-    if (to < from || to - from > SENS_MAX_IDS || (to > from && !parameter_ids))
+  args.n_parameters = c.n_parameters;
+  args.n_surfaces = c.n_surfaces;
+  if (c.parameter_first[0] != 0) return fail(PRT_ERR_ARG, "sensitivity: parameter_first starts at 0");
+  for (int k = 0; k < c.n_parameters; ++k) {
+    const int from = c.parameter_first[k], to = c.parameter_first[k + 1];
+    if (to < from || to - from > SENS_MAX_IDS || (to > from && !c.parameter_ids))
       return fail(PRT_ERR_ARG, "sensitivity: at most 64 surface ids a parameter");
-    for (int c = 0; c < 9; ++c) {
-      const double value = twists[9 * k + c];
+    for (int i = 0; i < 9; ++i) {
+      const double value = c.twists[9 * k + i];
       if (!(std::fabs(value) < PRT_INF)) return fail(PRT_ERR_ARG, "sensitivity: a twist is not finite");
-      (c < 3 ? args.twist[k].v[c] : c < 6 ? args.twist[k].w[c - 3] : args.twist[k].c[c - 6]) = value;
+      (i < 3 ? args.twist[k].v[i] : i < 6 ? args.twist[k].w[i - 3] : args.twist[k].c[i - 6]) = value;
     }
-    for (int at = from; at < to; ++at) {
-      int lo = 0, hi = n_surfaces;
-      while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (surfaces[mid].surface_id < parameter_ids[at]) lo = mid + 1; else hi = mid;
+    const int rc = sens_mark(c, c.parameter_ids, from, to, &SensSurface::moved_by, k, table,
+                             "sensitivity: a parameter moves a surface that is not in the table");
+    if (rc) return rc;
+  }
+  return PRT_OK;
+}
+
+// the design part: S and the index rate per parameter, and which surfaces' index each changes
+static int sens_design(const SensCall& c, const SensDesignCall& d, SensDesign& shape, std::vector<SensSurface>& table) {
+  if (d.index_first[0] != 0) return fail(PRT_ERR_ARG, "design sensitivity: index_first starts at 0");
+  for (int k = 0; k < c.n_parameters; ++k) {
+    for (int i = 0; i < 9; ++i) {
+      const double value = d.linear[9 * k + i];
+      if (!(std::fabs(value) < PRT_INF)) return fail(PRT_ERR_ARG, "design sensitivity: linear is not finite");
+      shape.S[k][i] = value;
+      if (value != 0.0) shape.linear |= 1u << k;
+    }
+    if (!(std::fabs(d.index_rates[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "design sensitivity: an index rate is not finite");
+    shape.rate[k] = d.index_rates[k];
+    const int from = d.index_first[k], to = d.index_first[k + 1];
+    if (to < from || to - from > SENS_MAX_IDS || (to > from && !d.index_ids))
+      return fail(PRT_ERR_ARG, "design sensitivity: at most 64 surface ids an index parameter");
+    const int rc = sens_mark(c, d.index_ids, from, to, &SensSurface::index_by, k, table,
+                             "design sensitivity: an index parameter names a surface that is not in the table");
+    if (rc) return rc;
+    if (to > from) shape.index |= 1u << k;
+  }
+  return PRT_OK;
+}
+
+// the launch part: the rays each parameter names and what it does to them (the seeds), and the glass behind every surface
+static int sens_launch(const SensCall& c, const SensLaunchCall& l, SensLaunch& seed, SensDesign& shape,
+                       std::vector<SensGlass>& glasses) {
+  if (!l.ranges || !l.flags || !l.rates || !l.materials || (c.n_selected && !l.slopes)) return fail(PRT_ERR_ARG, "bad buffers");
+  for (int k = 0; k < c.n_parameters; ++k) {
+    const double lo = l.ranges[2 * k], hi = l.ranges[2 * k + 1];
+    if (l.flags[k] < 0 || l.flags[k] > 3) return fail(PRT_ERR_ARG, "launch sensitivity: flags are 0 to 3");
+    if (!(lo <= hi)) return fail(PRT_ERR_ARG, "launch sensitivity: a parameter's ray ids [lo, hi) are not a range");
+    if (!(std::fabs(l.rates[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "launch sensitivity: a wavelength rate is not finite");
+    if (l.flags[k] && c.parameter_first[k + 1] != c.parameter_first[k])
+      return fail(PRT_ERR_ARG, "launch sensitivity: a launch parameter names no surfaces");
+    seed.lo[k] = lo; seed.hi[k] = hi; seed.rate[k] = l.rates[k];
+    if (l.flags[k] & 1) seed.seeds |= 1u << k;
+    if (l.flags[k] & 2) { seed.colour |= 1u << k; shape.index |= 1u << k; }  // (the dnu plane is the parameter's)
+  }
+  glasses.resize((size_t)c.n_surfaces);
+  for (int s = 0; s < c.n_surfaces; ++s) {
+    const int m = c.surfaces[s].material;
+    if (m < 0 || m >= l.n_materials) return fail(PRT_ERR_ARG, "launch sensitivity: a surface's material is not in materials");
+    const prt_material& mat = l.materials[m];
+    std::memset(&glasses[s], 0, sizeof(SensGlass));
+    if (mat.kind == PRT_MAT_SELLMEIER) {
+      for (int i = 0; i < 6; ++i) {
+        if (!(std::fabs(mat.coef[i]) < PRT_INF)) return fail(PRT_ERR_ARG, "launch sensitivity: a Sellmeier coefficient is not finite");
+        glasses[s].coef[i] = mat.coef[i];
       }
-      if (lo == n_surfaces || surfaces[lo].surface_id != parameter_ids[at])
-        return fail(PRT_ERR_ARG, "sensitivity: a parameter moves a surface that is not in the table");
-      table[lo].moved_by |= 1u << k;
+    } else if (seed.colour && (mat.kind < PRT_MAT_NONE || mat.kind > PRT_MAT_CONST_INDEX)) {
+      return fail(PRT_ERR_ARG, "launch sensitivity: a wavelength parameter needs glasses whose dispersion the device has "
+                               "(a table or host material is in the table)");
     }
+    glasses[s].kind = mat.kind;
   }
-  SensDesign shape;
-  std::memset(&shape, 0, sizeof(shape));
-  if (design) {
-    if (index_first[0] != 0) return fail(PRT_ERR_ARG, "design sensitivity: index_first starts at 0");
-    for (int k = 0; k < n_parameters; ++k) {
-      for (int c = 0; c < 9; ++c) {
-        const double value = linear[9 * k + c];
-        if (!(std::fabs(value) < PRT_INF)) return fail(PRT_ERR_ARG, "design sensitivity: linear is not finite");
-        shape.S[k][c] = value;
-        if (value != 0.0) shape.linear |= 1u << k;
-      }
-      if (!(std::fabs(index_rates[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "design sensitivity: an index rate is not finite");
-      shape.rate[k] = index_rates[k];
-      const int from = index_first[k], to = index_first[k + 1];
-      if (to < from || to - from > SENS_MAX_IDS || (to > from && !index_ids))
-        return fail(PRT_ERR_ARG, "design sensitivity: at most 64 surface ids an index parameter");
-      for (int at = from; at < to; ++at) {
-        int lo = 0, hi = n_surfaces;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (surfaces[mid].surface_id < index_ids[at]) lo = mid + 1; else hi = mid;
-        }
-        if (lo == n_surfaces || surfaces[lo].surface_id != index_ids[at])
-          return fail(PRT_ERR_ARG, "design sensitivity: an index parameter names a surface that is not in the table");
-        table[lo].index_by |= 1u << k;
-        shape.index |= 1u << k;
-      }
-    }
-  }
-  SensLaunch seed;
-  std::memset(&seed, 0, sizeof(seed));
-  std::vector<SensGlass> glasses;
-  if (launch) {
-    if (!launch->ranges || !launch->flags || !launch->rates || !launch->materials || (n_selected && !launch->slopes))
-      return fail(PRT_ERR_ARG, "bad buffers");
-    for (int k = 0; k < n_parameters; ++k) {
-      const double lo = launch->ranges[2 * k], hi = launch->ranges[2 * k + 1];
-      if (launch->flags[k] < 0 || launch->flags[k] > 3) return fail(PRT_ERR_ARG, "launch sensitivity: flags are 0 to 3");
-      if (!(lo <= hi)) return fail(PRT_ERR_ARG, "launch sensitivity: a parameter's ray ids [lo, hi) are not a range");
-      if (!(std::fabs(launch->rates[k]) < PRT_INF)) return fail(PRT_ERR_ARG, "launch sensitivity: a wavelength rate is not finite");
-      if (launch->flags[k] && parameter_first[k + 1] != parameter_first[k])
-        return fail(PRT_ERR_ARG, "launch sensitivity: a launch parameter names no surfaces");
-      seed.lo[k] = lo; seed.hi[k] = hi; seed.rate[k] = launch->rates[k];
-      if (launch->flags[k] & 1) seed.seeds |= 1u << k;
-      if (launch->flags[k] & 2) { seed.colour |= 1u << k; shape.index |= 1u << k; }  // (the dnu plane is the parameter's)
-    }
-    glasses.resize((size_t)n_surfaces);
-    for (int s = 0; s < n_surfaces; ++s) {
-      const int m = surfaces[s].material;
-      if (m < 0 || m >= launch->n_materials) return fail(PRT_ERR_ARG, "launch sensitivity: a surface's material is not in materials");
-      const prt_material& mat = launch->materials[m];
-      std::memset(&glasses[s], 0, sizeof(SensGlass));
-      if (mat.kind == PRT_MAT_SELLMEIER) {
-        for (int c = 0; c < 6; ++c) {
-          if (!(std::fabs(mat.coef[c]) < PRT_INF)) return fail(PRT_ERR_ARG, "launch sensitivity: a Sellmeier coefficient is not finite");
-          glasses[s].coef[c] = mat.coef[c];
-        }
-      } else if (seed.colour && (mat.kind < PRT_MAT_NONE || mat.kind > PRT_MAT_CONST_INDEX)) {
-        return fail(PRT_ERR_ARG, "launch sensitivity: a wavelength parameter needs glasses whose dispersion the device has "
-                                 "(a table or host material is in the table)");
-      }
-      glasses[s].kind = mat.kind;
-    }
-  }
-  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows))
-    return fail(PRT_ERR_ARG, "sensitivity: too many rows in a group");
-  for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = 0;
-  rc = ops_device(device);
-  if (rc) return rc;
-  char* end;
-  const SensWork w = sens_carve(workspace, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end,
-                                wave ? 8 : design ? 7 : 6);
-  hipStream_t st = (hipStream_t)stream;
-  const int entries = sens_entries(n_parameters);
-  SensOpd field;
-  SensOpdWork ow = {nullptr, nullptr};
-  std::memset(&field, 0, sizeof(field));
-  if (wave) {
-    char* opd_end;
-    ow = sens_opd_carve(end, n_parameters, n_groups, max_group_rows, wave->n_terms, &opd_end);
-    HIP_TRY(hipMemcpyAsync(ow.groups, wave->groups, (size_t)n_groups * SENS_OPD_GROUP * sizeof(double), hipMemcpyHostToDevice, st));
-    field.opl = wave->opl; field.groups = ow.groups; field.first = w.first; field.n_groups = n_groups;
-    for (int k = 0; k < 3; ++k) { field.e1[k] = wave->axes[3 + k]; field.e2[k] = wave->axes[6 + k]; }
-    field.dfield = wave->dfield; field.dopd = wave->dopd; field.dpupil = wave->dpupil; field.opd = wave->opd;
-    field.pupil = wave->pupil;
-    end = opd_end;
-  }
-  SensGlass* glass_table = nullptr;  // (the launch form: behind everything the other forms carve)
-  if (launch) {
-    glass_table = (SensGlass*)(((uintptr_t)end + 7) & ~(uintptr_t)7);
-    HIP_TRY(hipMemcpyAsync(glass_table, glasses.data(), glasses.size() * sizeof(SensGlass), hipMemcpyHostToDevice, st));
-  }
+  return PRT_OK;
+}
+
+// the uploads: what the kernels read from the workspace, and the words and stamps cleared
+static int sens_upload(const SensCall& c, const SensWork& w, const std::vector<SensSurface>& table,
+                       const std::vector<SensGlass>& glasses, const SensOpdCall* wave) {
+  hipStream_t st = (hipStream_t)c.stream;
+  if (wave)
+    HIP_TRY(hipMemcpyAsync(w.opd_groups, wave->groups, (size_t)c.n_groups * SENS_OPD_GROUP * sizeof(double), hipMemcpyHostToDevice, st));
+  if (w.glass)
+    HIP_TRY(hipMemcpyAsync(w.glass, glasses.data(), glasses.size() * sizeof(SensGlass), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemsetAsync(w.words, 0, 64, st));
-  HIP_TRY(hipMemsetAsync(w.stamp, 0, (size_t)n_ids * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(w.stamp, 0, (size_t)c.n_ids * sizeof(int), st));
   HIP_TRY(hipMemcpyAsync(w.table, table.data(), table.size() * sizeof(SensSurface), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(w.first, group_first, (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(w.pivots, pivots, (size_t)n_groups * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.first, c.group_first, (size_t)(c.n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w.pivots, c.pivots, (size_t)c.n_groups * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+  return PRT_OK;
+}
+
+// the steps, one launch per generation in order (`launch(grid, start, count, generation)`)
+template <class Launch>
+static void sens_steps(const SensCall& c, Launch launch) {
   int64_t start = 0;
-  for (int g = 0; g < n_generations; ++g) {
-    const int64_t count = rows_per_generation[g];
-    const dim3 grid((unsigned)((count + kSensBlock - 1) / kSensBlock));
-    if (count && launch && wave)
-      hipLaunchKernelGGL(k_sens_launch_opd_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0,
-                         n_ids, args, shape, field, seed, w.table, glass_table, w.state, w.last_row, w.stamp, w.words,
-                         row_slot, n_selected, jacobian_out, launch->slopes);
-    else if (count && launch)
-      hipLaunchKernelGGL(k_sens_launch_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
-                         args, shape, seed, w.table, glass_table, w.state, w.last_row, w.stamp, w.words, row_slot,
-                         n_selected, jacobian_out, launch->slopes);
-    else if (count && wave)
-      hipLaunchKernelGGL(k_sens_opd_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
-                         args, shape, field, w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected,
-                         jacobian_out);
-    else if (count && design)
-      hipLaunchKernelGGL(k_sens_design_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids,
-                         args, shape, w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected, jacobian_out);
-    else if (count)
-      hipLaunchKernelGGL(k_sens_step, grid, dim3(kSensBlock), 0, st, rows, ld, n_rows, start, count, g, id0, n_ids, args,
-                         w.table, w.state, w.last_row, w.stamp, w.words, row_slot, n_selected, jacobian_out);
+  for (int g = 0; g < c.n_generations; ++g) {
+    const int64_t count = c.rows_per_generation[g];
+    if (count) launch(dim3((unsigned)((count + kSensBlock - 1) / kSensBlock)), start, count, g);
     start += count;
   }
-  const int chunks = (int)sens_chunks(max_group_rows);
+}
+
+// the sums: the partials of every group's chunks, folded in a fixed order; the wavefront form's own behind them
+static void sens_sums(const SensCall& c, const SensWork& w, const SensOpdCall* wave, int64_t n_rows, int chunks) {
+  hipStream_t st = (hipStream_t)c.stream;
+  const int K = c.n_parameters, entries = sens_entries(K);
+  const dim3 grid((unsigned)chunks, (unsigned)c.n_groups);
   if (chunks)
-    hipLaunchKernelGGL(k_sens_partials, dim3((unsigned)chunks, (unsigned)n_groups), dim3(kSensBlock), 0, st, rows, ld,
-                       n_rows, selected, n_selected, w.first, n_parameters, weight_column, w.pivots, jacobian_out,
-                       w.partials, &w.words->status);
-  hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)n_groups * entries)), dim3(64), 0, st, w.partials, chunks,
-                     entries, n_groups, sums_out);
-  if (wave) {
-    const int opd_entries = sens_opd_entries(n_parameters, wave->n_terms);
-    const size_t lds = (size_t)SENS_OPD_TILE * sens_opd_stride(n_parameters, wave->n_terms) * sizeof(double);
-    if (chunks)
-      hipLaunchKernelGGL(k_sens_opd_partials, dim3((unsigned)chunks, (unsigned)n_groups), dim3(kSensBlock), lds, st, rows,
-                         ld, n_rows, selected, n_selected, w.first, n_parameters, wave->n_terms, weight_column,
-                         jacobian_out, wave->opd, wave->pupil, wave->dfield, wave->dopd, ow.partials, &w.words->status);
-    hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)n_groups * opd_entries)), dim3(64), 0, st, ow.partials, chunks,
-                       opd_entries, n_groups, wave->sums);
-  }
+    hipLaunchKernelGGL(k_sens_partials, grid, dim3(kSensBlock), 0, st, c.rows, c.ld, n_rows, c.selected, c.n_selected,
+                       w.first, K, c.weight_column, w.pivots, c.jacobian_out, w.partials, &w.words->status);
+  hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)c.n_groups * entries)), dim3(64), 0, st, w.partials, chunks,
+                     entries, c.n_groups, c.sums_out);
+  if (!wave) return;
+  const int opd_entries = sens_opd_entries(K, wave->n_terms);
+  const size_t lds = (size_t)SENS_OPD_TILE * sens_opd_stride(K, wave->n_terms) * sizeof(double);
+  if (chunks)
+    hipLaunchKernelGGL(k_sens_opd_partials, grid, dim3(kSensBlock), lds, st, c.rows, c.ld, n_rows, c.selected,
+                       c.n_selected, w.first, K, wave->n_terms, c.weight_column, c.jacobian_out, wave->opd, wave->pupil,
+                       wave->dfield, wave->dopd, w.opd_partials, &w.words->status);
+  hipLaunchKernelGGL(k_sens_fold, dim3((unsigned)((int64_t)c.n_groups * opd_entries)), dim3(64), 0, st, w.opd_partials,
+                     chunks, opd_entries, c.n_groups, wave->sums);
+}
+
+// the status words read back: what the kernels refused, and the counters
+static int sens_report(const SensCall& c, const SensWork& w) {
+  hipStream_t st = (hipStream_t)c.stream;
   SensWords host_words;
   HIP_TRY(hipMemcpyAsync(&host_words, w.words, sizeof(SensWords), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   HIP_TRY(hipGetLastError());
-  rc = join_refusal(host_words.status, "sensitivity");
+  const int rc = join_refusal(host_words.status, "sensitivity");
   if (rc) return rc;
   if (host_words.status & SENS_BAD_SELECTION)
     return fail(PRT_ERR_ARG, "sensitivity: row_slot or selected points outside the selection or the frame");
-  for (int k = 0; k < SENS_COUNTERS; ++k) record_out[k] = (int64_t)host_words.count[k];
+  for (int k = 0; k < SENS_COUNTERS; ++k) c.record_out[k] = (int64_t)host_words.count[k];
   return PRT_OK;
+}
+
+// A call: the parts that are present choose the form.  None: the rigid form (sens_row<false>, six planes of state);
+// `design`: seven planes; `wave` (with design): eight, and the wavefront outputs and sums; `launch` (with design, with or
+// without wave): the seeds, the glass table and the slopes.  Everything is checked before a device is touched
+static int sens_run(const SensCall& c, const SensDesignCall* design, const SensOpdCall* wave, const SensLaunchCall* launch) {
+  int64_t max_group_rows = 0;
+  const int64_t n_rows = sens_check(c, design, wave, max_group_rows);
+  if (n_rows < 0) return (int)n_rows;
+  std::vector<SensSurface> table;
+  std::vector<SensGlass> glasses;
+  SensArgs args;
+  SensDesign shape;
+  SensLaunch seed;
+  std::memset(&shape, 0, sizeof(shape));
+  std::memset(&seed, 0, sizeof(seed));
+  int rc = sens_table(c, table);
+  if (!rc) rc = sens_rigid(c, args, table);
+  if (!rc && design) rc = sens_design(c, *design, shape, table);
+  if (!rc && launch) rc = sens_launch(c, *launch, seed, shape, glasses);
+  if (rc) return rc;
+  const SensSizes sizes = {c.n_ids, c.n_surfaces, c.n_parameters, c.n_groups, max_group_rows};
+  if (!sens_sizes_ok(sizes)) return fail(PRT_ERR_ARG, "sensitivity: too many rows in a group");
+  for (int k = 0; k < SENS_COUNTERS; ++k) c.record_out[k] = 0;
+  rc = ops_device(c.device);
+  if (rc) return rc;
+  const SensWork w = sens_layout(c.workspace, sizes, wave ? 8 : design ? 7 : 6, wave ? wave->n_terms : 0, launch != nullptr);
+  SensOpd field;
+  std::memset(&field, 0, sizeof(field));
+  if (wave) {
+    field.opl = wave->opl; field.groups = w.opd_groups; field.first = w.first; field.n_groups = c.n_groups;
+    for (int k = 0; k < 3; ++k) { field.e1[k] = wave->axes[3 + k]; field.e2[k] = wave->axes[6 + k]; }
+    field.dfield = wave->dfield; field.dopd = wave->dopd; field.dpupil = wave->dpupil; field.opd = wave->opd;
+    field.pupil = wave->pupil;
+  }
+  rc = sens_upload(c, w, table, glasses, wave);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)c.stream;
+  const dim3 block(kSensBlock);
+  // the step of the form, chosen once
+  if (launch && wave)
+    sens_steps(c, [&](dim3 grid, int64_t start, int64_t count, int g) {
+      hipLaunchKernelGGL(k_sens_launch_opd_step, grid, block, 0, st, c.rows, c.ld, n_rows, start, count, g, c.id0, c.n_ids,
+                         args, shape, field, seed, w.table, w.glass, w.state, w.last_row, w.stamp, w.words, c.row_slot,
+                         c.n_selected, c.jacobian_out, launch->slopes);
+    });
+  else if (launch)
+    sens_steps(c, [&](dim3 grid, int64_t start, int64_t count, int g) {
+      hipLaunchKernelGGL(k_sens_launch_step, grid, block, 0, st, c.rows, c.ld, n_rows, start, count, g, c.id0, c.n_ids, args,
+                         shape, seed, w.table, w.glass, w.state, w.last_row, w.stamp, w.words, c.row_slot, c.n_selected,
+                         c.jacobian_out, launch->slopes);
+    });
+  else if (wave)
+    sens_steps(c, [&](dim3 grid, int64_t start, int64_t count, int g) {
+      hipLaunchKernelGGL(k_sens_opd_step, grid, block, 0, st, c.rows, c.ld, n_rows, start, count, g, c.id0, c.n_ids, args,
+                         shape, field, w.table, w.state, w.last_row, w.stamp, w.words, c.row_slot, c.n_selected,
+                         c.jacobian_out);
+    });
+  else if (design)
+    sens_steps(c, [&](dim3 grid, int64_t start, int64_t count, int g) {
+      hipLaunchKernelGGL(k_sens_design_step, grid, block, 0, st, c.rows, c.ld, n_rows, start, count, g, c.id0, c.n_ids, args,
+                         shape, w.table, w.state, w.last_row, w.stamp, w.words, c.row_slot, c.n_selected, c.jacobian_out);
+    });
+  else
+    sens_steps(c, [&](dim3 grid, int64_t start, int64_t count, int g) {
+      hipLaunchKernelGGL(k_sens_step, grid, block, 0, st, c.rows, c.ld, n_rows, start, count, g, c.id0, c.n_ids, args, w.table,
+                         w.state, w.last_row, w.stamp, w.words, c.row_slot, c.n_selected, c.jacobian_out);
+    });
+  sens_sums(c, w, wave, n_rows, (int)sens_chunks(max_group_rows));
+  return sens_report(c, w);
 }
 
 extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
@@ -1090,10 +1184,10 @@ extern "C" int prt_frame_sensitivity(int device, const double* rows, int64_t ld,
                                      const int64_t* selected, int64_t n_selected, const int64_t* group_first,
                                      int n_groups, int weight_column, const double* pivots, double* jacobian_out,
                                      double* sums_out, int64_t* record_out, void* workspace, void* stream) {
-  return sens_run(false, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
-                  parameter_ids, parameter_first, nullptr, nullptr, nullptr, nullptr, n_parameters, row_slot, selected,
-                  n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out, workspace,
-                  stream);
+  const SensCall call = {device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                         parameter_ids, parameter_first, n_parameters, row_slot, selected, n_selected, group_first,
+                         n_groups, weight_column, pivots, jacobian_out, sums_out, record_out, workspace, stream};
+  return sens_run(call, nullptr, nullptr, nullptr);
 }
 
 extern "C" int prt_frame_design_sensitivity(int device, const double* rows, int64_t ld,
@@ -1105,10 +1199,11 @@ extern "C" int prt_frame_design_sensitivity(int device, const double* rows, int6
                                             const int64_t* selected, int64_t n_selected, const int64_t* group_first,
                                             int n_groups, int weight_column, const double* pivots, double* jacobian_out,
                                             double* sums_out, int64_t* record_out, void* workspace, void* stream) {
-  return sens_run(true, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
-                  parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
-                  selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
-                  workspace, stream);
+  const SensCall call = {device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                         parameter_ids, parameter_first, n_parameters, row_slot, selected, n_selected, group_first,
+                         n_groups, weight_column, pivots, jacobian_out, sums_out, record_out, workspace, stream};
+  const SensDesignCall design = {linear, index_rates, index_ids, index_first};
+  return sens_run(call, &design, nullptr, nullptr);
 }
 
 extern "C" int prt_frame_opd_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
@@ -1122,29 +1217,16 @@ extern "C" int prt_frame_opd_sensitivity(int device, const double* rows, int64_t
                                          double* jacobian_out, double* sums_out, double* dfield_out, double* dopd_out,
                                          double* dpupil_out, double* opd_out, double* pupil_out, double* opd_sums_out,
                                          int64_t* record_out, void* workspace, void* stream) {
+  const SensCall call = {device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                         parameter_ids, parameter_first, n_parameters, row_slot, selected, n_selected, group_first,
+                         n_groups, weight_column, pivots, jacobian_out, sums_out, record_out, workspace, stream};
+  const SensDesignCall design = {linear, index_rates, index_ids, index_first};
   const SensOpdCall wave = {opl, wavefront_groups, axes, n_terms, dfield_out, dopd_out, dpupil_out, opd_out, pupil_out,
                             opd_sums_out};
-  return sens_run(true, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
-                  parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
-                  selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
-                  workspace, stream, &wave);
+  return sens_run(call, &design, &wave, nullptr);
 }
 
-extern "C" int64_t prt_frame_launch_sensitivity_workspace_bytes(int64_t n_ids, int n_surfaces, int n_parameters,
-                                                                int n_groups, int64_t max_group_rows, int n_terms) {
-  if (!sens_sizes_ok(n_ids, n_surfaces, n_parameters, n_groups, max_group_rows) || n_terms < 0 || n_terms > WF_MAX_TERMS)
-    return PRT_ERR_ARG;
-  char* end;
-  const SensWork w = sens_carve(nullptr, n_ids, n_surfaces, n_parameters, n_groups, max_group_rows, &end, n_terms ? 8 : 7);
-  (void)w;
-  if (n_terms) {
-    char* mid = end;
-    const SensOpdWork o = sens_opd_carve(mid, n_parameters, n_groups, max_group_rows, n_terms, &end);
-    (void)o;
-  }
-  return (int64_t)(((uintptr_t)end + 7) & ~(uintptr_t)7) + (int64_t)n_surfaces * (int64_t)sizeof(SensGlass) + 64;
-}
-
+// (opl == NULL: the launch form without the wavefront)
 extern "C" int prt_frame_launch_sensitivity(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
                                             int n_generations, double id0, int64_t n_ids, const prt_prim* surfaces,
                                             int n_surfaces, const double* twists, const int64_t* parameter_ids,
@@ -1159,11 +1241,12 @@ extern "C" int prt_frame_launch_sensitivity(int device, const double* rows, int6
                                             double* sums_out, double* slopes_out, double* dfield_out, double* dopd_out,
                                             double* dpupil_out, double* opd_out, double* pupil_out, double* opd_sums_out,
                                             int64_t* record_out, void* workspace, void* stream) {
+  const SensCall call = {device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
+                         parameter_ids, parameter_first, n_parameters, row_slot, selected, n_selected, group_first,
+                         n_groups, weight_column, pivots, jacobian_out, sums_out, record_out, workspace, stream};
+  const SensDesignCall design = {linear, index_rates, index_ids, index_first};
   const SensOpdCall wave = {opl, wavefront_groups, axes, n_terms, dfield_out, dopd_out, dpupil_out, opd_out, pupil_out,
                             opd_sums_out};
   const SensLaunchCall launch = {launch_ranges, launch_flags, wavelength_rates, materials, n_materials, slopes_out};
-  return sens_run(true, device, rows, ld, rows_per_generation, n_generations, id0, n_ids, surfaces, n_surfaces, twists,
-                  parameter_ids, parameter_first, linear, index_rates, index_ids, index_first, n_parameters, row_slot,
-                  selected, n_selected, group_first, n_groups, weight_column, pivots, jacobian_out, sums_out, record_out,
-                  workspace, stream, opl ? &wave : nullptr, &launch);
+  return sens_run(call, &design, opl ? &wave : nullptr, &launch);
 }

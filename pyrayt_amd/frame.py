@@ -431,6 +431,10 @@ class DeviceFrame:
             raise ValueError(f"{what}: an id is not an integer in the frame's id range")
         return id0, int(top - id0) + 1, top
 
+    def _top_id(self):
+        """The largest ray id of the frame (a host read), -1 for an empty frame: what ``_group_count`` counts from."""
+        return float(self["id"].max()) if len(self) else -1.0
+
     def optical_path(self):
         """The cumulative optical path length of every row, a device tensor of ``len(self)`` float64: the row's segment
         ``index * sqrt(dx*dx + dy*dy + dz*dz)`` plus the cumulative OPL of the same ray's row in the previous generation
@@ -492,23 +496,16 @@ class DeviceFrame:
         terms = int(zernike)
         if terms != zernike or not 1 <= terms <= 36:
             raise ValueError(f"zernike: the number of terms, 1 to 36 (got {zernike!r})")
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        _check_weights(weights)
         if pupil_radius is not None and not (np.isfinite(pupil_radius) and pupil_radius > 0):
             raise ValueError("pupil_radius: a positive number, or None for the group's largest radial extent")
         axes = pupil_axes(axis, basis)
-        if isinstance(reference, str) and reference != "centroid":
-            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        _check_reference_name(reference)
         surface_id = None if surface is None else float(_surface_id(surface))
         self._need_whole("wavefront")
         if weights is not None:
             self._need(weights)
-        if rays_per_source:
-            if n_groups is None:
-                top = float(self["id"].max()) if len(self) else -1.0
-                n_groups = max(1, int(top // rays_per_source) + 1)
-        else:
-            n_groups = 1
+        n_groups = _group_count(rays_per_source, n_groups, self._top_id)
         dev = self.rows.device
         centres = None if isinstance(reference, str) else _group_points(reference, n_groups, dev, "reference: a point")
         radii = None
@@ -598,8 +595,7 @@ class DeviceFrame:
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         nx, ny = _pixel_counts(pixels)
         step, uv0 = _pixel_grid(pixel_size, centre)
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        _check_weights(weights)
         self._need_whole("psf")
         self._need("wavelength", *(() if weights is None else (weights,)))
         surface_id = None if surface is None else float(surface.get_id() if hasattr(surface, "get_id") else surface)
@@ -703,8 +699,7 @@ class DeviceFrame:
         "last" resolved, the groups counted from the largest ray id where ``n_groups`` is None.  The frame must hold
         the columns the pass reads -- ``whole``: the columns of a pass that joins by ray id and so needs the whole
         frame of a trace -- and ``weights`` must be None or a column."""
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        _check_weights(weights)
         surface_id = None if surface is None else float(_surface_id(surface))
         needed = ([] if whole is not None else list(_MTF_COLUMNS)) + ([weights] if weights is not None else [])
         if whole is None:
@@ -718,13 +713,7 @@ class DeviceFrame:
             raise ValueError(f"{what}: {error.args[0]}") from None
         if generation == "last":
             generation = self.last_generation_number() or 0
-        if rays_per_source:
-            if n_groups is None:
-                top = float(self["id"].max()) if len(self) else -1.0
-                n_groups = max(1, int(top // rays_per_source) + 1)
-        else:
-            n_groups = 1
-        return surface_id, generation, int(n_groups)
+        return surface_id, generation, int(_group_count(rays_per_source, n_groups, self._top_id))
 
     # --- geometric MTF through focus (no counterpart upstream) --------------------------------------------------------
     def mtf(self, surface, frequencies, *, azimuths=(0.0, 90.0), focus=(0.0,), reference="centroid", axis=None,
@@ -754,8 +743,7 @@ class DeviceFrame:
             raise NotImplementedError("mtf() of a sharded frame (group=) is not supported yet")
         nu, theta, planes = _mtf_sampling(frequencies, azimuths, focus)
         axes = pupil_axes(axis, basis)
-        if isinstance(reference, str) and reference != "centroid":
-            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        _check_reference_name(reference)
         surface_id, generation, n_groups = self._image_selection("mtf", surface, generation, rays_per_source, n_groups,
                                                                  weights)
         rows = self._contiguous_rows()
@@ -819,8 +807,7 @@ class DeviceFrame:
             raise ValueError(f"shape: one of {sorted(_ENERGY_SHAPES)} (got {shape!r})")
         planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
         axes = pupil_axes(axis, basis)
-        if isinstance(reference, str) and reference != "centroid":
-            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        _check_reference_name(reference)
         surface_id, generation, n_groups = self._image_selection("enclosed_energy", surface, generation, rays_per_source,
                                                                  n_groups, weights)
         rows = self._contiguous_rows()
@@ -1014,8 +1001,7 @@ class DeviceFrame:
 
         from . import engine
 
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
+        _check_weights(weights)
         if isinstance(max_paths, bool) or not isinstance(max_paths, (int, np.integer)) or not 1 <= max_paths <= 65536:
             raise ValueError(f"max_paths: the most nodes the tree may have, 1 to 65536 (got {max_paths!r})")
         columns = [name for name in _PATHS_COLUMNS if name != "intensity" or weights == "intensity"]
@@ -1201,48 +1187,18 @@ class DeviceFrame:
         import torch
 
         from . import engine
-        from .scene import PRIM_DTYPE, SceneSnapshot
 
-        from . import materials as matl
-
-        kinds = (Motion, Deformation, IndexChange, SourceMotion, WavelengthChange)
-        motions = [parameters] if isinstance(parameters, kinds) else list(parameters)
-        if not motions or not all(isinstance(m, kinds) for m in motions):
-            raise ValueError("sensitivity: parameters is a Motion, a Deformation, an IndexChange, a SourceMotion or a "
-                             "WavelengthChange, or a list of them")
-        design = not all(isinstance(m, Motion) for m in motions)
-        launch = any(isinstance(m, (SourceMotion, WavelengthChange)) for m in motions)
-        colour = any(isinstance(m, WavelengthChange) for m in motions)
-        launch_form = launch or bool(slopes)  # (the entry point that also writes the slopes)
-        if len(motions) > 16:
-            raise ValueError(f"sensitivity: at most 16 parameters a call (got {len(motions)})")
-        if launch:
-            motions = [m.resolved(rays_per_source) if isinstance(m, SourceMotion) else m for m in motions]
-        if weights is not None and weights not in _INDEX:
-            raise ValueError(f"weights: None or a column name (got {weights!r})")
-        if isinstance(reference, str) and reference != "centroid":
-            raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+        motions, form = _sens_parameters(parameters, rays_per_source, slopes)
+        _check_weights(weights)
+        _check_reference_name(reference)
         if surface is None:
             raise ValueError("sensitivity: surface is an id or an object with get_id()")
         surface_id = float(_surface_id(surface))
         if wavefront is not None and wavefront is not True and not isinstance(wavefront, Wavefront):
             raise ValueError("wavefront: a Wavefront of this frame, True or None")
-        snapshot = system if hasattr(system, "prims") else SceneSnapshot(system)
-        prims = np.sort(np.asarray(snapshot.prims, dtype=PRIM_DTYPE), order="surface_id")
-        if len(prims) == 0:
-            raise ValueError("sensitivity: system has no surfaces")
-        if len(np.unique(prims["surface_id"])) != len(prims):
-            raise ValueError("sensitivity: a surface id repeats in system")
-        known = set(int(v) for v in prims["surface_id"])
-        for k, motion in enumerate(motions):
-            missing = sorted(set(motion.surface_ids) - known)
-            if missing:
-                raise ValueError(f"sensitivity: parameter {k} moves surfaces that are not in system: {missing}")
-        if colour and any(int(kind) == matl.TABLE for kind in np.asarray(snapshot.materials)["kind"][prims["material"]]):
-            raise ValueError("sensitivity: a WavelengthChange needs the dispersion of every glass in system, and a table "
-                             "glass's index_at is host code without a derivative")
+        snapshot, prims = _sens_primitives(system, motions, form["colour"])
         try:
-            self._need_whole("sensitivity", columns=_PATH_COLUMNS + (("wavelength",) if colour else ())
+            self._need_whole("sensitivity", columns=_PATH_COLUMNS + (("wavelength",) if form["colour"] else ())
                              + ((weights,) if weights else ()))
         except KeyError as error:
             raise ValueError(f"sensitivity: {error.args[0]}") from None
@@ -1250,19 +1206,10 @@ class DeviceFrame:
         dev = rows.device
         n_rows = rows.shape[1]
         id0, n_ids, top = self._id_range("sensitivity", rows)
-        if rays_per_source:
-            if n_groups is None:
-                n_groups = max(1, int(top // rays_per_source) + 1)
-        else:
-            n_groups = 1
-        n_groups = int(n_groups)
+        n_groups = int(_group_count(rays_per_source, n_groups, lambda: top))
         if not 1 <= n_groups <= 65535:
             raise ValueError("sensitivity: 1 to 65535 groups")
         K = len(motions)
-        # the selection, in the order (group, generation, id): what makes the sums independent of the rows' order
-        # (plumbing with a price: the id range above, group_first and the pivots below are each read back to the host
-        # and wait for the stream, before a call that synchronises itself: part of the call's fixed cost, see
-        # profiles/sensitivity/README.md)
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
         if generation == "last":
             generation = self.last_generation_number() or 0
@@ -1270,151 +1217,59 @@ class DeviceFrame:
             wavefront = self.wavefront(surface_id, weights=weights, generation=generation,
                                        rays_per_source=rays_per_source, n_groups=n_groups)
         if wavefront is not None:
-            made = getattr(wavefront, "_made_of", None)
-            mine = dict(frame=self, surface=surface_id, generation=None if generation is None else int(generation),
-                        rays_per_source=float(rays_per_source or 0), n_groups=n_groups, weights=weights)
-            if made is None:
-                raise ValueError("sensitivity: wavefront was not made by this frame's wavefront()")
-            for name, value in mine.items():
-                if (made[name] is not value) if name == "frame" else (made[name] != value):
-                    raise ValueError(f"sensitivity: wavefront is of another {name} ({made[name]!r}, this call: {value!r}): "
-                                     "it must be this frame's, at the same surface, generation, groups and weights")
-        mask = rows[_INDEX["surface"]] == surface_id
-        if generation is not None:
-            mask = mask & (rows[_INDEX["generation"]] == float(generation))
-        ids = rows[_INDEX["id"]]
-        group = torch.zeros_like(ids, dtype=torch.int64)
-        if rays_per_source:
-            group = torch.floor(ids / float(rays_per_source)).to(torch.int64)
-        mask = mask & (group >= 0) & (group < n_groups)
-        picked = torch.nonzero(mask).reshape(-1)
-        key = ((group[picked] * max(len(counts), 1) + rows[_INDEX["generation"]][picked].to(torch.int64)) * n_ids
-               + (ids[picked] - id0).to(torch.int64))
-        order = torch.argsort(key)
-        selected = picked[order].contiguous()
+            made = _sens_made_of(wavefront, dict(
+                frame=self, surface=surface_id, generation=None if generation is None else int(generation),
+                rays_per_source=float(rays_per_source or 0), n_groups=n_groups, weights=weights))
+        # (plumbing with a price: the id range above, group_first and the pivots below are each read back to the host
+        # and wait for the stream, before a call that synchronises itself: part of the call's fixed cost, see
+        # profiles/sensitivity/README.md)
+        selected, row_slot, group_first = _sens_selection(rows, surface_id, generation, rays_per_source, n_groups, id0,
+                                                          n_ids, len(counts))
         n_selected = int(selected.shape[0])
-        row_slot = torch.full((max(n_rows, 1),), -1, dtype=torch.int64, device=dev)
-        row_slot[selected] = torch.arange(n_selected, dtype=torch.int64, device=dev)
-        group_first = torch.searchsorted(group[selected].contiguous(),
-                                         torch.arange(n_groups + 1, dtype=torch.int64, device=dev))
-        group_first = np.ascontiguousarray(group_first.cpu().numpy(), dtype=np.int64)
-        centred = isinstance(reference, str)
-        if centred:  # (the sums are taken about a point of the group, its first row's; the centroid follows from them)
-            pivots = np.zeros((n_groups, 3))
-            some = np.flatnonzero(np.diff(group_first) > 0)
-            if len(some):
-                first_rows = selected[torch.as_tensor(group_first[some], device=dev)]
-                pivots[some] = rows[_INDEX["x1"]:_INDEX["z1"] + 1][:, first_rows].T.cpu().numpy()
-            pivots[~np.isfinite(pivots)] = 0.0
-        else:
-            pivots = np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float)
-            if pivots.shape == (3,):
-                pivots = np.broadcast_to(pivots, (n_groups, 3))
-            if pivots.shape != (n_groups, 3) or not np.all(np.isfinite(pivots)):
-                raise ValueError(f"reference: \"centroid\", a finite point or an ({n_groups}, 3) array")
-        pivots = np.ascontiguousarray(pivots, dtype=np.float64)
-        index = [isinstance(m, (IndexChange, WavelengthChange)) for m in motions]
-        twists = np.ascontiguousarray([np.zeros(9) if i else m.twist for m, i in zip(motions, index)], dtype=np.float64)
-        id_lists = [[] if i else sorted(m.surface_ids) for m, i in zip(motions, index)]
-        parameter_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in id_lists])]), dtype=np.int32)
-        parameter_ids = np.ascontiguousarray([v for ids_ in id_lists for v in ids_] or [0], dtype=np.int64)
-        entries = 6 + 4 * K + K * (K + 1) // 2
-        lib = engine.library()
-        max_group_rows = int(np.diff(group_first).max())
-        bytes_of = lib.prt_frame_design_sensitivity_workspace_bytes if design else lib.prt_frame_sensitivity_workspace_bytes
-        work = torch.empty(0 if wavefront is not None  # (the wavefront form sizes its own, below)
-                           else int(engine._check(bytes_of(n_ids, len(prims), K, n_groups, max_group_rows))),
-                           dtype=torch.uint8, device=dev)
-        jacobian = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
-        sums = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
+        pivots, centred = _sens_pivots(rows, reference, selected, group_first, n_groups)
+        # (a call of Motions alone, without slopes=True, takes the entry point, the kernel and the workspace it always took)
+        name = ("launch" if form["launch_form"] else "wavefront" if wavefront is not None else "design" if form["design"]
+                else "rigid")
+        if name == "launch" and wavefront is not None and not n_rows:
+            # (the entry point reads opl == NULL as "no wavefront": there is no path to point at)
+            raise ValueError("sensitivity: wavefront= with a SourceMotion, a WavelengthChange or slopes=True needs a frame with rows")
+        size, size_extra, entry, order = _SENS_FORMS[name]
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+        jacobian, sums = empty(K, 3, n_selected), empty(n_groups, 6 + 4 * K + K * (K + 1) // 2)
+        directions = empty(K, 3, n_selected) if name == "launch" else None
         record = np.zeros(4, dtype=np.int64)
-        head = (dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
-                len(counts), id0, n_ids, prims.ctypes.data, len(prims), twists.ctypes.data, parameter_ids.ctypes.data,
-                parameter_first.ctypes.data)
-        tail = (K, row_slot.data_ptr(), selected.data_ptr() if n_selected else None, n_selected,
-                group_first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], pivots.ctypes.data,
-                jacobian.data_ptr() if n_selected else None, sums.data_ptr(), record.ctypes.data, work.data_ptr(),
-                engine._stream_ptr(torch, dev))
-        if design or wavefront is not None or launch_form:  # (a call of Motions alone, without slopes=True, takes the entry point, the kernel and the workspace it always took)
-            linear = np.ascontiguousarray([m.linear.reshape(-1) if isinstance(m, Deformation) else np.zeros(9)
-                                           for m in motions], dtype=np.float64)
-            named = [isinstance(m, IndexChange) for m in motions]
-            rates = np.ascontiguousarray([m.rate if i else 0.0 for m, i in zip(motions, named)], dtype=np.float64)
-            index_lists = [sorted(m.surface_ids) if i else [] for m, i in zip(motions, named)]
-            index_first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in index_lists])]), dtype=np.int32)
-            index_ids = np.ascontiguousarray([v for ids_ in index_lists for v in ids_] or [0], dtype=np.int64)
-        if launch_form:  # (the launch form: the design or wavefront form's arguments, the rays each parameter names, the glasses)
-            ranges = np.ascontiguousarray([m.id_range if isinstance(m, (SourceMotion, WavelengthChange))
-                                           else (0.0, 0.0) for m in motions], dtype=np.float64)
-            flags = np.ascontiguousarray([1 if isinstance(m, SourceMotion) else 2 if isinstance(m, WavelengthChange)
-                                          else 0 for m in motions], dtype=np.int32)
-            colour_rates = np.ascontiguousarray([m.rate if isinstance(m, WavelengthChange) else 0.0 for m in motions],
-                                                dtype=np.float64)
-            mats = np.ascontiguousarray(snapshot.materials)
-            directions = torch.empty((K, 3, n_selected), dtype=torch.float64, device=dev)
-            J, out, ptr, wave_args = 0, None, dict.fromkeys(("dfield", "dopd", "dpupil", "opd", "pupil", "sums")), (None,) * 3
-            if wavefront is not None:
-                J = wavefront.terms
-                groups = np.ascontiguousarray(np.column_stack([wavefront.reference, wavefront.radius, wavefront.pivot,
-                                                               wavefront.pupil_radius]), dtype=np.float64)
-                axes = np.ascontiguousarray(made["axes"], dtype=np.float64)
-                wide = 5 + J * (K + 3) + 4 * K + K * (K + 1) // 2
-                out = dict(dfield=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
-                           dopd=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
-                           dpupil=torch.empty((K, 2, n_selected), dtype=torch.float64, device=dev),
-                           opd=torch.empty(n_selected, dtype=torch.float64, device=dev),
-                           pupil=torch.empty((n_selected, 2), dtype=torch.float64, device=dev),
-                           sums=torch.empty((n_groups, wide), dtype=torch.float64, device=dev))
-                ptr = {name: (t.data_ptr() if t.numel() else None) for name, t in out.items()}
-                if not n_rows:  # (the entry point reads opl == NULL as "no wavefront": there is no path to point at)
-                    raise ValueError("sensitivity: wavefront= with a SourceMotion, a WavelengthChange or slopes=True needs a frame with rows")
-                opl = self._optical_path()
-                wave_args = (opl.data_ptr(), groups.ctypes.data, axes.ctypes.data)
-            work = torch.empty(int(engine._check(lib.prt_frame_launch_sensitivity_workspace_bytes(
-                n_ids, len(prims), K, n_groups, max_group_rows, J))), dtype=torch.uint8, device=dev)
-            engine._check(lib.prt_frame_launch_sensitivity(
-                *head, linear.ctypes.data, rates.ctypes.data, index_ids.ctypes.data, index_first.ctypes.data, *tail[:8],
-                *wave_args, J, ranges.ctypes.data, flags.ctypes.data, colour_rates.ctypes.data, mats.ctypes.data, len(mats),
-                tail[8], tail[9], directions.data_ptr() if n_selected else None, ptr["dfield"], ptr["dopd"], ptr["dpupil"],
-                ptr["opd"], ptr["pupil"], ptr["sums"], tail[10], work.data_ptr(), tail[12]))
-            if out is not None:
-                out["sums"] = engine.to_host(out["sums"]).copy()
-                out["wavefront"] = wavefront
-            return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
-                               wave=out, launch=dict(slopes=directions, rows=rows, weights=weights, group_first=group_first,
-                                                     written=self.written))
+        pieces = dict.fromkeys(_SENS_WAVE_IN + _SENS_WAVE_OUT)  # (the launch form without wavefront= passes these as NULL)
+        pieces.update(_sens_host_arrays(motions, name, snapshot.materials), n_terms=0, device=dev.index or 0, rows=rows,
+                      ld=max(rows.stride(0), n_rows, 1), counts=counts, n_generations=len(counts), id0=id0, n_ids=n_ids,
+                      prims=prims, n_prims=len(prims), K=K,
+                      row_slot=row_slot, selected=selected, n_selected=n_selected, group_first=group_first,
+                      n_groups=n_groups, weight_column=-1 if weights is None else _INDEX[weights], pivots=pivots,
+                      jacobian=jacobian, sums=sums, slopes=directions, record=record,
+                      stream=engine._stream_ptr(torch, dev))
+        wave = None
         if wavefront is not None:
             J = wavefront.terms
-            opl = self._optical_path()
-            groups = np.ascontiguousarray(np.column_stack([wavefront.reference, wavefront.radius, wavefront.pivot,
-                                                           wavefront.pupil_radius]), dtype=np.float64)
-            axes = np.ascontiguousarray(made["axes"], dtype=np.float64)
-            wide = 5 + J * (K + 3) + 4 * K + K * (K + 1) // 2
-            out = dict(dfield=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
-                       dopd=torch.empty((K, n_selected), dtype=torch.float64, device=dev),
-                       dpupil=torch.empty((K, 2, n_selected), dtype=torch.float64, device=dev),
-                       opd=torch.empty(n_selected, dtype=torch.float64, device=dev),
-                       pupil=torch.empty((n_selected, 2), dtype=torch.float64, device=dev),
-                       sums=torch.empty((n_groups, wide), dtype=torch.float64, device=dev))
-            work = torch.empty(int(engine._check(lib.prt_frame_opd_sensitivity_workspace_bytes(
-                n_ids, len(prims), K, n_groups, max_group_rows, J))), dtype=torch.uint8, device=dev)
-            ptr = {name: (t.data_ptr() if t.numel() else None) for name, t in out.items()}
-            engine._check(lib.prt_frame_opd_sensitivity(
-                *head, linear.ctypes.data, rates.ctypes.data, index_ids.ctypes.data, index_first.ctypes.data, *tail[:8],
-                opl.data_ptr() if n_rows else None, groups.ctypes.data, axes.ctypes.data, J, tail[8], tail[9],
-                ptr["dfield"], ptr["dopd"], ptr["dpupil"], ptr["opd"], ptr["pupil"], out["sums"].data_ptr(), tail[10],
-                work.data_ptr(), tail[12]))
-            out["sums"] = engine.to_host(out["sums"]).copy()
-            return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions,
-                               wave=dict(out, wavefront=wavefront),
-                               launch=dict(slopes=None, rows=rows, weights=weights, group_first=group_first,
-                                           written=self.written))
-        if design:
-            engine._check(lib.prt_frame_design_sensitivity(*head, linear.ctypes.data, rates.ctypes.data,
-                                                           index_ids.ctypes.data, index_first.ctypes.data, *tail))
-        else:
-            engine._check(lib.prt_frame_sensitivity(*head, *tail))
-        return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions)
+            wave = dict(dfield=empty(K, n_selected), dopd=empty(K, n_selected), dpupil=empty(K, 2, n_selected),
+                        opd=empty(n_selected), pupil=empty(n_selected, 2),
+                        sums=empty(n_groups, 5 + J * (K + 3) + 4 * K + K * (K + 1) // 2))
+            pieces.update({q: wave[q] for q in _SENS_WAVE_OUT[:-1]}, opd_sums=wave["sums"], n_terms=J,
+                          opl=self._optical_path(),
+                          groups=np.ascontiguousarray(np.column_stack([wavefront.reference, wavefront.radius,
+                                                                       wavefront.pivot, wavefront.pupil_radius]),
+                                                      dtype=np.float64),
+                          axes=np.ascontiguousarray(made["axes"], dtype=np.float64))
+        lib = engine.library()
+        pieces["work"] = torch.empty(int(engine._check(getattr(lib, size)(
+            n_ids, len(prims), K, n_groups, int(np.diff(group_first).max()), *(pieces[q] for q in size_extra)))),
+            dtype=torch.uint8, device=dev)
+        engine._check(getattr(lib, entry)(*(_sens_pointer(pieces[q]) for q in order)))
+        if wave is not None:
+            wave.update(sums=engine.to_host(wave["sums"]).copy(), wavefront=wavefront)
+        launch = None
+        if name in ("wavefront", "launch"):
+            launch = dict(slopes=directions, rows=rows, weights=weights, group_first=group_first, written=self.written)
+        return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions, wave=wave,
+                           launch=launch)
 
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
@@ -3074,6 +2929,179 @@ class Sensitivity:
         return pd.DataFrame(data)
 
 
+# --- what DeviceFrame.sensitivity() is made of ---------------------------------------------------------------------------
+# The arguments of the four entry points, by name and in the order of include/prt.h: each form is its size function and
+# what that takes after (n_ids, n_surfaces, K, n_groups, max_group_rows), its entry point, and the pieces of its call.
+_SENS_COMMON = ("device", "rows", "ld", "counts", "n_generations", "id0", "n_ids", "prims", "n_prims", "twists",
+              "parameter_ids", "parameter_first")
+_SENS_DESIGN = ("linear", "index_rates", "index_ids", "index_first")
+_SENS_SELECTION = ("K", "row_slot", "selected", "n_selected", "group_first", "n_groups", "weight_column", "pivots")
+_SENS_WAVE_IN = ("opl", "groups", "axes", "n_terms")
+_SENS_LAUNCH_IN = ("ranges", "flags", "colour_rates", "materials", "n_materials")
+_SENS_WAVE_OUT = ("dfield", "dopd", "dpupil", "opd", "pupil", "opd_sums")
+_SENS_LAST = ("record", "work", "stream")
+_SENS_FORMS = {
+    "rigid": ("prt_frame_sensitivity_workspace_bytes", (), "prt_frame_sensitivity",
+              _SENS_COMMON + _SENS_SELECTION + ("jacobian", "sums") + _SENS_LAST),
+    "design": ("prt_frame_design_sensitivity_workspace_bytes", (), "prt_frame_design_sensitivity",
+               _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + ("jacobian", "sums") + _SENS_LAST),
+    "wavefront": ("prt_frame_opd_sensitivity_workspace_bytes", ("n_terms",), "prt_frame_opd_sensitivity",
+                  _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + _SENS_WAVE_IN + ("jacobian", "sums") + _SENS_WAVE_OUT
+                  + _SENS_LAST),
+    "launch": ("prt_frame_launch_sensitivity_workspace_bytes", ("n_terms",), "prt_frame_launch_sensitivity",
+               _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + _SENS_WAVE_IN + _SENS_LAUNCH_IN
+               + ("jacobian", "sums", "slopes") + _SENS_WAVE_OUT + _SENS_LAST),
+}
+
+
+def _sens_pointer(piece):
+    """What the library is given for a piece of a call: the address of a device tensor (NULL for one without elements)
+    or of a host array; a number as it is."""
+    if hasattr(piece, "data_ptr"):
+        return piece.data_ptr() if piece.numel() else None
+    return piece.ctypes.data if isinstance(piece, np.ndarray) else piece
+
+
+def _sens_parameters(parameters, rays_per_source, slopes):
+    """``(motions, form)``: the parameters as a list, every ``SourceMotion``'s rays resolved, and what they ask of the
+    call -- ``design``: not Motions alone; ``launch``: a SourceMotion or a WavelengthChange; ``colour``: a
+    WavelengthChange; ``launch_form``: the entry point that also writes the slopes."""
+    kinds = (Motion, Deformation, IndexChange, SourceMotion, WavelengthChange)
+    motions = [parameters] if isinstance(parameters, kinds) else list(parameters)
+    if not motions or not all(isinstance(m, kinds) for m in motions):
+        raise ValueError("sensitivity: parameters is a Motion, a Deformation, an IndexChange, a SourceMotion or a "
+                         "WavelengthChange, or a list of them")
+    form = dict(design=not all(isinstance(m, Motion) for m in motions),
+                launch=any(isinstance(m, (SourceMotion, WavelengthChange)) for m in motions),
+                colour=any(isinstance(m, WavelengthChange) for m in motions))
+    form["launch_form"] = form["launch"] or bool(slopes)
+    if len(motions) > 16:
+        raise ValueError(f"sensitivity: at most 16 parameters a call (got {len(motions)})")
+    if form["launch"]:
+        motions = [m.resolved(rays_per_source) if isinstance(m, SourceMotion) else m for m in motions]
+    return motions, form
+
+
+def _sens_primitives(system, motions, colour):
+    """``(snapshot, prims)``: the snapshot of ``system`` (the components, or their ``SceneSnapshot``) and its primitives
+    sorted by surface id.  The ids are distinct, every surface a parameter names is among them, and with a
+    ``WavelengthChange`` (``colour``) no glass is a table glass: ``ValueError`` otherwise."""
+    from . import materials as matl
+    from .scene import PRIM_DTYPE, SceneSnapshot
+
+    snapshot = system if hasattr(system, "prims") else SceneSnapshot(system)
+    prims = np.sort(np.asarray(snapshot.prims, dtype=PRIM_DTYPE), order="surface_id")
+    if len(prims) == 0:
+        raise ValueError("sensitivity: system has no surfaces")
+    if len(np.unique(prims["surface_id"])) != len(prims):
+        raise ValueError("sensitivity: a surface id repeats in system")
+    known = set(int(v) for v in prims["surface_id"])
+    for k, motion in enumerate(motions):
+        missing = sorted(set(motion.surface_ids) - known)
+        if missing:
+            raise ValueError(f"sensitivity: parameter {k} moves surfaces that are not in system: {missing}")
+    if colour and any(int(kind) == matl.TABLE for kind in np.asarray(snapshot.materials)["kind"][prims["material"]]):
+        raise ValueError("sensitivity: a WavelengthChange needs the dispersion of every glass in system, and a table "
+                         "glass's index_at is host code without a derivative")
+    return snapshot, prims
+
+
+def _sens_made_of(wavefront, mine):
+    """What ``wavefront`` was made of (``Wavefront._made_of``), held to this call's frame, surface, generation, groups
+    and weights (``mine``): ``ValueError`` for a Wavefront of anything else."""
+    made = getattr(wavefront, "_made_of", None)
+    if made is None:
+        raise ValueError("sensitivity: wavefront was not made by this frame's wavefront()")
+    for name, value in mine.items():
+        if (made[name] is not value) if name == "frame" else (made[name] != value):
+            raise ValueError(f"sensitivity: wavefront is of another {name} ({made[name]!r}, this call: {value!r}): "
+                             "it must be this frame's, at the same surface, generation, groups and weights")
+    return made
+
+
+def _sens_selection(rows, surface_id, generation, rays_per_source, n_groups, id0, n_ids, n_generations):
+    """``(selected, row_slot, group_first)``: the rows that end on the surface (of ``generation``, where given) in the
+    order (group, generation, id) -- what makes the sums independent of the rows' order --, per row its slot in that
+    selection or -1, and on the host the first slot of every group and the end (a read that waits for the stream)."""
+    import torch
+
+    dev = rows.device
+    mask = rows[_INDEX["surface"]] == surface_id
+    if generation is not None:
+        mask = mask & (rows[_INDEX["generation"]] == float(generation))
+    ids = rows[_INDEX["id"]]
+    group = torch.zeros_like(ids, dtype=torch.int64)
+    if rays_per_source:
+        group = torch.floor(ids / float(rays_per_source)).to(torch.int64)
+    mask = mask & (group >= 0) & (group < n_groups)
+    picked = torch.nonzero(mask).reshape(-1)
+    key = ((group[picked] * max(n_generations, 1) + rows[_INDEX["generation"]][picked].to(torch.int64)) * n_ids
+           + (ids[picked] - id0).to(torch.int64))
+    selected = picked[torch.argsort(key)].contiguous()
+    row_slot = torch.full((max(rows.shape[1], 1),), -1, dtype=torch.int64, device=dev)
+    row_slot[selected] = torch.arange(selected.shape[0], dtype=torch.int64, device=dev)
+    group_first = torch.searchsorted(group[selected].contiguous(), torch.arange(n_groups + 1, dtype=torch.int64, device=dev))
+    return selected, row_slot, np.ascontiguousarray(group_first.cpu().numpy(), dtype=np.int64)
+
+
+def _sens_pivots(rows, reference, selected, group_first, n_groups):
+    """``(pivots, centred)``: per group the point its sums are taken about, (n_groups, 3) on the host.  "centroid"
+    (``centred``): a point of the group, its first row's (a read that waits for the stream) -- the centroid follows from
+    the sums; else the reference itself, a point or one a group."""
+    import torch
+
+    centred = isinstance(reference, str)
+    if centred:
+        pivots = np.zeros((n_groups, 3))
+        some = np.flatnonzero(np.diff(group_first) > 0)
+        if len(some):
+            first_rows = selected[torch.as_tensor(group_first[some], device=rows.device)]
+            pivots[some] = rows[_INDEX["x1"]:_INDEX["z1"] + 1][:, first_rows].T.cpu().numpy()
+        pivots[~np.isfinite(pivots)] = 0.0
+    else:
+        pivots = np.asarray(reference.cpu() if hasattr(reference, "cpu") else reference, dtype=float)
+        if pivots.shape == (3,):
+            pivots = np.broadcast_to(pivots, (n_groups, 3))
+        if pivots.shape != (n_groups, 3) or not np.all(np.isfinite(pivots)):
+            raise ValueError(f"reference: \"centroid\", a finite point or an ({n_groups}, 3) array")
+    return np.ascontiguousarray(pivots, dtype=np.float64), centred
+
+
+def _packed_ids(id_lists):
+    """``(ids, first)``: one list of surface ids a parameter as the library reads them -- the ids end to end (int64; a
+    single 0 where there are none) and, int32, where each parameter's begin and the last one's end."""
+    first = np.ascontiguousarray(np.concatenate([[0], np.cumsum([len(v) for v in id_lists])]), dtype=np.int32)
+    return np.ascontiguousarray([v for ids in id_lists for v in ids] or [0], dtype=np.int64), first
+
+
+def _sens_host_arrays(motions, form, materials):
+    """The parameters packed for the entry point of ``form`` ("rigid", "design", "wavefront", "launch"), by the names of
+    ``_SENS_FORMS``: the twists and the surfaces each parameter moves; but for the rigid form S, the index rates and the
+    surfaces whose index each changes; for the launch form the rays each parameter names, what it does to them and the
+    glasses.  A parameter that has no such part has zeros and an empty list there."""
+    def rows_of(kind, value, zero):
+        return [value(m) if isinstance(m, kind) else zero for m in motions]
+
+    host = dict(twists=np.ascontiguousarray(rows_of((Motion, Deformation, SourceMotion), lambda m: m.twist, np.zeros(9)),
+                                            dtype=np.float64))
+    host["parameter_ids"], host["parameter_first"] = _packed_ids(
+        rows_of((Motion, Deformation, SourceMotion), lambda m: sorted(m.surface_ids), []))
+    if form != "rigid":
+        host["linear"] = np.ascontiguousarray(rows_of(Deformation, lambda m: m.linear.reshape(-1), np.zeros(9)),
+                                              dtype=np.float64)
+        host["index_rates"] = np.ascontiguousarray(rows_of(IndexChange, lambda m: m.rate, 0.0), dtype=np.float64)
+        host["index_ids"], host["index_first"] = _packed_ids(rows_of(IndexChange, lambda m: sorted(m.surface_ids), []))
+    if form == "launch":
+        host["ranges"] = np.ascontiguousarray(rows_of((SourceMotion, WavelengthChange), lambda m: m.id_range, (0.0, 0.0)),
+                                              dtype=np.float64)
+        host["flags"] = np.ascontiguousarray([1 if isinstance(m, SourceMotion) else 2 if isinstance(m, WavelengthChange)
+                                              else 0 for m in motions], dtype=np.int32)
+        host["colour_rates"] = np.ascontiguousarray(rows_of(WavelengthChange, lambda m: m.rate, 0.0), dtype=np.float64)
+        host["materials"] = np.ascontiguousarray(materials)
+        host["n_materials"] = len(host["materials"])
+    return host
+
+
 def _coating_stacks(coatings, ids_lossless):
     """``coatings`` of ``fresnel()`` as (the distinct Coatings, {surface id: its number among them})."""
     from .materials import Coating
@@ -3191,6 +3219,24 @@ def _mtf_sampling(frequencies, azimuths, focus):
     return (_mtf_values(frequencies, "frequencies", 4096, "finite and >= 0", non_negative=True),
             _mtf_values(azimuths, "azimuths", 16, "finite, in degrees"),
             _mtf_values(focus, "focus", 256, "finite shifts along the axis"))
+
+
+def _check_weights(weights):
+    if weights is not None and weights not in _INDEX:
+        raise ValueError(f"weights: None or a column name (got {weights!r})")
+
+
+def _check_reference_name(reference):
+    if isinstance(reference, str) and reference != "centroid":
+        raise ValueError('reference: "centroid", a point or an (n_groups, 3) array')
+
+
+def _group_count(rays_per_source, n_groups, top):
+    """The number of groups ``id // rays_per_source`` of a pass: ``n_groups`` where it is given, else counted from the
+    largest ray id ``top()``, read only then; 1 without ``rays_per_source``."""
+    if not rays_per_source:
+        return 1
+    return max(1, int(top() // rays_per_source) + 1) if n_groups is None else n_groups
 
 
 def _group_points(value, n_groups, device, rule):

@@ -450,3 +450,73 @@ def test_workspace_is_carved_to_the_byte_and_the_old_sizes_stand():
     for size, whole in sizes:
         assert bool((whole[size:] == 0xA5).all()), size
     assert np.all(np.isfinite(got.rms_opd_gradient))
+
+
+@pytest.mark.parametrize("scene, n, nobody", [("two_fields", 300, False), ("singlet", 1, False), ("singlet", 1, True)])
+def test_every_form_runs_through_the_one_layout_and_the_motions_keep_their_bits(scene, n, nobody):
+    """The five forms (rigid, design, wavefront, launch without and with wavefront=) and slopes=True with no launch
+    parameter, each inside a workspace of exactly the size its own function names with a patterned guard behind it; the
+    launch form's size from the others' ends; jacobian and sums of the two Motions the same bits in all of them.  The
+    frame of the test above, then one ray in one group, then a surface no row ends on (no chunk, a fold of nothing)."""
+    from pyrayt_amd import Motion, SourceMotion, engine
+
+    lib = engine.library()
+    case = cases.build(scene, n)
+    dev = device_frame(case.frame, case.counts)
+    glass, det = case.parts
+    surface = 10 ** 6 if nobody else case.surface
+    if scene == "two_fields":
+        kw, n_ids, n_groups = dict(rays_per_source=300, n_groups=2, weights="intensity"), 600, 2
+        wavefront = dev.wavefront(surface, zernike=15, **kw)
+    else:  # (one ray has no radial extent to normalise by: a pupil radius is a property of the call)
+        kw, n_ids, n_groups = dict(weights=None), 1, 1
+        wavefront = dev.wavefront(surface, zernike=4, pupil_radius=0.25, **kw)
+    J, prims, most = wavefront.terms, 3 + 1, 0 if nobody else n
+    motions = [Motion(glass, translate=(0, 1, 0)), Motion(det, rotate=(0, 0, 1), pivot=(1, 0.1, 0))]
+    shaped = motions + [case.parameters[2], case.parameters[4]]  # (a radius and the index)
+    launched = motions + [SourceMotion(None, translate=(0, 1, 0))]
+
+    def size(name, K, *more):
+        return getattr(lib, f"prt_frame_{name}_workspace_bytes")(n_ids, prims, K, n_groups, most, *more)
+
+    up8 = lambda v: (v + 7) // 8 * 8  # noqa: E731
+    for K in (2, 3, 4):
+        assert size("launch_sensitivity", K, J) == up8(size("opd_sensitivity", K, J) - 64) + 56 * prims + 64
+        assert size("launch_sensitivity", K, 0) == up8(size("design_sensitivity", K) - 64) + 56 * prims + 64
+    forms = [("rigid", motions, {}, size("sensitivity", 2)),
+             ("design", shaped, {}, size("design_sensitivity", 4)),
+             ("wavefront", shaped, dict(wavefront=wavefront), size("opd_sensitivity", 4, J)),
+             ("launch", launched, {}, size("launch_sensitivity", 3, 0)),
+             ("launch with wavefront", launched, dict(wavefront=wavefront), size("launch_sensitivity", 3, J)),
+             ("slopes=True", motions, dict(slopes=True), size("launch_sensitivity", 2, 0))]
+    real_empty, first = torch.empty, None
+    for what, parameters, more, want in forms:
+        sizes = []
+
+        def guarded(size, *a, **k):
+            if k.get("dtype") is torch.uint8 and isinstance(size, int) and size > 0:
+                whole = torch.full((size + 4096,), 0xA5, dtype=torch.uint8, device=k["device"])
+                sizes.append((size, whole))
+                return whole[:size]
+            return real_empty(size, *a, **k)
+
+        torch.empty = guarded
+        try:
+            got = dev.sensitivity(surface, parameters, case.parts, **kw, **more)
+        finally:
+            torch.empty = real_empty
+        assert want > 0 and want in [size for size, _ in sizes], (what, want, [size for size, _ in sizes])
+        for size_, whole in sizes:
+            assert bool((whole[size_:] == 0xA5).all()), (what, size_)
+        K = got.n_parameters
+        assert got.jacobian.shape == (K, 3, 0 if nobody else n * n_groups)
+        assert (got.slopes is not None) == what.startswith(("launch", "slopes")), what
+        assert (got.wavefront is not None) == ("wavefront" in more), what
+        assert bool(torch.isfinite(got.jacobian).all()) and np.array_equal(got.count, [most] * n_groups), what
+        own = np.concatenate([got.sums[:, :6 + 3 * 2], got.sums[:, 6 + 3 * K:6 + 3 * K + 2],
+                              got.sums[:, 6 + 4 * K:6 + 4 * K + 3]], axis=1)  # (the entries of parameters 0 and 1)
+        if first is None:
+            first = (got.jacobian[:2].cpu().numpy(), own)
+            assert nobody or float(np.abs(first[0]).max()) > 1e-3
+        helpers.assert_same_bits(got.jacobian[:2].cpu().numpy(), first[0], f"jacobian, {what}")
+        helpers.assert_same_bits(own, first[1], f"sums, {what}")
