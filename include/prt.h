@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient and their workspace functions (prt_frame_psf_gradient_workspace_bytes among them).  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them).  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -668,6 +668,49 @@ int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t n_rows, do
                   const double* group_record, int weight_column, const double* wavelengths_um, int n_wavelengths,
                   double world_unit_um, int nx, int ny, double du, double dv, const double* centre_uv,
                   double* image_out, double* strehl_out, double* record_out, void* workspace, void* stream);
+
+/* Diffraction PSF and Strehl ratio through focus: the Huygens sum above on n_focus planes shifted along the axis, from
+ * one wavefront and without a re-trace (no counterpart upstream).
+ *
+ * Definitions.
+ * Everything of prt_frame_psf stays: the rays, p1, p2, OPD_r, a_r, lambda_w, the buckets, the normalisation (its
+ *   denominator, which no plane moves) and record_out.
+ * Sphere point: E_r = P + p1 e1 + p2 e2 + p3 a with p3 = (E_r - P).a, formed by extending the row to the sphere again
+ *   as prt_frame_wavefront does (its sign is that of -(u.a), u the ray's direction).  A ray is kept under
+ *   prt_frame_psf's rule and a finite p3: the same rays, buckets and order.
+ * Planes: plane f lies through P + delta_f a, perpendicular to a; delta has the sign of prt_frame_mtf's focus.  Pixel
+ *   (i, j) of plane f of group g lies at x = P + u e1 + v e2 + delta_f a with u = cu_gf + (i - (nx-1)/2) du and
+ *   v = cv_gf + (j - (ny-1)/2) dv.
+ * Distance: d_r(x) = sqrt(R^2 + u^2 + v^2 + delta^2 - 2 (u p1 + v p2 + delta p3)); phase and amplitude as above.
+ * Chief line: the line through P and the weighted mean of the group's sphere points.  Per unit of delta it moves by
+ *   t_i = (sum w_r p_i) / (sum w_r p3), i = 1, 2, the sums over the group's kept rays of all wavelengths (w_r = a_r^2):
+ *   the slope (u.e_i) / (u.a) of a ray that runs from the mean sphere point to P.  track = 1: the centre of plane f
+ *   is (cu, cv)_gf = (u0 + delta_f t1, v0 + delta_f t2), each one fma; track = 0: t = 0 and every centre is (u0, v0).
+ * Strehl through focus: the normalised intensity at P + delta_f (t1 e1 + t2 e2 + a), whatever the grid:
+ *   sum_l |sum a_r exp(2 pi i (OPD_r + d_r - R) / lambda_w)|^2 / lambda_w^2 over prt_frame_psf's denominator, d_r from
+ *   a correctly rounded fp64 square root and the phasor from fp64 sincospi.
+ * Bits: a plane with delta = 0.0 has the image, the Strehl ratio and the record of prt_frame_psf on the same arguments;
+ *   a plane's bits do not depend on the other planes, their number or their order (the ray slices are those
+ *   prt_frame_psf picks for one plane's grid; planes past the slab cap run in chunks of planes).
+ * Accuracy: prt_frame_psf's eps with the roundings of the new terms; tests/psf_focus_reference.py derives it.
+ *
+ * prt_frame_psf_focus: the arguments of prt_frame_psf, and: axes HOST 9 doubles (a, e1, e2), the ones
+ * prt_frame_wavefront was given; focus HOST n_focus (1..256) finite shifts; track 0 or 1.  Out, DEVICE, overwritten:
+ * image_out (n_groups, n_focus, n_wavelengths, nx, ny); strehl_out (n_groups, n_focus); record_out (n_groups,
+ * n_wavelengths, 4) as prt_frame_psf's; axial_out (n_rows; the first n_selected are written): p3 per selected row in
+ * the wavefront's order, NaN where the pupil point is NaN; line_out (n_groups, 2): t1, t2 (NaN for a group without
+ * rays under track = 1); centres_out (n_groups, n_focus, 2).  The cap of prt_frame_psf's slab holds for one plane.
+ * workspace: prt_frame_psf_focus_workspace_bytes(n_rows, n_groups, n_wavelengths, n_focus) device bytes (-1 for
+ * arguments the call would refuse).  All arguments are checked before a device is touched.  Stream-ordered; the call
+ * reads one status word back and so returns when the stream has reached its end. */
+int64_t prt_frame_psf_focus_workspace_bytes(int64_t n_rows, int n_groups, int n_wavelengths, int n_focus);
+int prt_frame_psf_focus(int device, const double* rows, int64_t ld, int64_t n_rows, double surface, double generation,
+                        double rays_per_source, int n_groups, const double* opd, const double* pupil,
+                        const double* group_record, int weight_column, const double* wavelengths_um,
+                        int n_wavelengths, double world_unit_um, int nx, int ny, double du, double dv,
+                        const double* centre_uv, const double* axes, const double* focus, int n_focus, int track,
+                        double* image_out, double* strehl_out, double* record_out, double* axial_out,
+                        double* line_out, double* centres_out, void* workspace, void* stream);
 
 /* Polarised diffraction PSF of the frame: the Huygens sum above with the Fresnel pass's complex field vectors as the
  * rays' amplitudes (no counterpart upstream).  The scalar PSF sees the Fresnel losses as apodisation only; this sum

@@ -168,6 +168,10 @@ def _declare(lib):
         "prt_frame_psf_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
         "prt_frame_psf": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_p, c_p, c_p, c_int, c_p, c_int, c_d,
                                   c_int, c_int, c_d, c_d, c_p, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_psf_focus_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+        "prt_frame_psf_focus": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_p, c_p, c_p, c_int, c_p, c_int,
+                                        c_d, c_int, c_int, c_d, c_d, c_p, c_p, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p,
+                                        c_p, c_p, c_p]),
         "prt_frame_vector_psf_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
         "prt_frame_vector_psf": (c_int, [c_int, c_p, c_i64, c_i64, c_d, c_d, c_d, c_int, c_p, c_p, c_p, c_int, c_p, c_int,
                                          c_d, c_int, c_int, c_d, c_d, c_p, c_p, c_i64, c_int, c_int, c_p, c_p, c_p, c_p,
@@ -249,6 +253,7 @@ EXPORTED_SYMBOLS = (
     "prt_frame_launch_sensitivity_workspace_bytes", "prt_frame_launch_sensitivity",
     "prt_frame_mtf_gradient_workspace_bytes", "prt_frame_mtf_gradient",
     "prt_frame_psf_gradient_workspace_bytes", "prt_frame_psf_gradient",
+    "prt_frame_psf_focus_workspace_bytes", "prt_frame_psf_focus",
 )
 
 

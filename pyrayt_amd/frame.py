@@ -548,7 +548,7 @@ class DeviceFrame:
     # --- diffraction PSF and Strehl ratio (no counterpart upstream) ---------------------------------------------------
     def psf(self, surface, *, world_unit_um, pixels=128, pixel_size=None, centre=(0.0, 0.0), weights="intensity",
             reference="centroid", radius=None, axis=None, basis=None, generation=None, rays_per_source=None,
-            n_groups=None, group=None, fresnel=None):
+            n_groups=None, group=None, fresnel=None, focus=None, track="chief"):
         """The diffraction image of a point at ``surface`` -- the Huygens PSF -- and its Strehl ratio, per group
         (``id // rays_per_source``).  Returns a ``PSF``.
 
@@ -578,7 +578,23 @@ class DeviceFrame:
         ``fresnel(polarization=None)`` follow each ray's own direction, which serves the per-ray transmittance but is
         not a state of the beam; they are first turned into two states that are uniform across the beam
         (``Fresnel.uniform_states()``; ``VectorPSF.fresnel`` is the Fresnel that was summed).  A ``Fresnel`` built by
-        hand is summed as it is.  Returns a ``VectorPSF``."""
+        hand is summed as it is.  Returns a ``VectorPSF``.
+
+        ``focus``: None, or 1 to 256 finite shifts delta along the axis, in world units, with the sign of ``mtf(focus=)``
+        and ``enclosed_energy(focus=)``: the image and the Strehl ratio on every plane through P + delta a, from the one
+        wavefront and in one call (``prt_frame_psf_focus``) -- a Huygens sum can be evaluated anywhere, so a scan needs
+        no re-trace.  Returns a ``PSFScan``.  The reference sphere stays where it is; the normalisation is that of
+        ``focus=None`` on every plane, and the plane 0.0 has its bits.  ``track`` (read only with ``focus``): "chief" --
+        each plane's grid is centred on the group's chief line, the line through P and the weighted mean of its rays'
+        points on the reference sphere, so the image of an off-axis field stays on the grid --, or None -- every grid is
+        centred at ``centre`` on the line through P parallel to the axis.  Not with ``fresnel=`` or ``group=``."""
+        if focus is not None:
+            if fresnel is not None or group is not None:
+                raise ValueError("psf: focus= does not go with fresnel= or group= (the polarised sum and sharded "
+                                 "frames have no through-focus pass yet)")
+            if track is not None and track != "chief":
+                raise ValueError(f'track: "chief" or None (got {track!r})')
+            focus = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
         import torch
 
         from . import engine
@@ -611,6 +627,9 @@ class DeviceFrame:
                 fresnel = fresnel.uniform_states()
             return self._vector_psf(fresnel, wave, rows, surface_id, n_groups, record, weights, generation,
                                     rays_per_source, wavelengths, unit, (nx, ny), step, uv0, f_number)
+        if focus is not None:
+            return self._psf_focus(focus, track, wave, rows, surface_id, n_groups, record, weights, rays_per_source,
+                                   wavelengths, unit, (nx, ny), step, uv0, f_number)
         image = torch.empty((n_groups, n_w, nx, ny), dtype=torch.float64, device=dev)
         strehl = torch.empty(n_groups, dtype=torch.float64, device=dev)
         out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
@@ -629,6 +648,40 @@ class DeviceFrame:
             out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
         return PSF(engine.to_host(image).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(), wavelengths,
                    unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave)
+
+    def _psf_focus(self, focus, track, wave, rows, surface_id, n_groups, record, weights, rays_per_source, wavelengths,
+                   unit, pixels, step, uv0, f_number):
+        """``psf(focus=)`` after the wavefront: the call, and the ``PSFScan``."""
+        import torch
+
+        from . import engine
+
+        dev = rows.device
+        n_rows, n_w, n_f, (nx, ny) = rows.shape[1], len(wavelengths), len(focus), pixels
+        image = torch.empty((n_groups, n_f, n_w, nx, ny), dtype=torch.float64, device=dev)
+        strehl = torch.empty((n_groups, n_f), dtype=torch.float64, device=dev)
+        out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
+        axial = torch.empty(max(n_rows, 1), dtype=torch.float64, device=dev)
+        line = torch.empty((n_groups, 2), dtype=torch.float64, device=dev)
+        centres = torch.empty((n_groups, n_f, 2), dtype=torch.float64, device=dev)
+        lib = engine.library()
+        work = torch.empty(int(engine._check(lib.prt_frame_psf_focus_workspace_bytes(n_rows, n_groups, n_w, n_f))),
+                           dtype=torch.uint8, device=dev)
+        lam = np.ascontiguousarray(wavelengths, dtype=np.float64)
+        uv0 = np.ascontiguousarray(uv0)
+        axes = np.ascontiguousarray(wave._made_of["axes"], dtype=np.float64)
+        opd = wave.opd if wave.opd.numel() else torch.empty(1, dtype=torch.float64, device=dev)
+        pupil = wave.pupil if wave.pupil.numel() else torch.empty(2, dtype=torch.float64, device=dev)
+        engine._check(lib.prt_frame_psf_focus(
+            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
+            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
+            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), -1 if weights is None else _INDEX[weights],
+            lam.ctypes.data, n_w, unit, nx, ny, step[0], step[1], uv0.ctypes.data, axes.ctypes.data, focus.ctypes.data,
+            n_f, 0 if track is None else 1, image.data_ptr(), strehl.data_ptr(), out.data_ptr(), axial.data_ptr(),
+            line.data_ptr(), centres.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        return PSFScan(engine.to_host(image).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(),
+                       axial[:wave.opd.numel()], engine.to_host(line).copy(), engine.to_host(centres).copy(), focus,
+                       wavelengths, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave, track)
 
     def _vector_psf(self, fresnel, wave, rows, surface_id, n_groups, record, weights, generation, rays_per_source,
                     wavelengths, unit, pixels, step, uv0, f_number):
@@ -1493,6 +1546,66 @@ class PSF:
             otf[g, 0] = np.einsum("afi,ij,afj->af", along_u, image, along_v) / total
             record[g, 3:] = total, self.n_rays[g], self.n_missed[g]
         return MTF(otf, record, nu, theta, np.zeros(1))
+
+
+class PSFScan:
+    """What ``DeviceFrame.psf(focus=...)`` returns: the diffraction PSF and the Strehl ratio on F planes shifted along
+    the axis, G groups, L wavelengths (numpy arrays unless stated).  ``image_by_wavelength`` (G, F, L, nx, ny) and
+    ``image`` (G, F, nx, ny), normalised as ``PSF.image`` is, by the same denominator on every plane; ``strehl`` (G, F):
+    the normalised intensity at the chief line's point of plane f, P + delta_f (t1 e1 + t2 e2 + a) -- on the axis line
+    with ``track=None`` --, whatever ``centre`` and the grid; ``focus`` (F); ``line`` (G, 2): the chief line's slopes
+    (t1, t2), 0 with ``track=None``; ``centres`` (G, F, 2): each grid's centre, (u0 + delta t1, v0 + delta t2); ``u`` (nx)
+    and ``v`` (ny): the pixel centres as offsets from a plane's centre; ``record`` (G, L, 4) as ``PSF.record``, the same
+    for every plane, and ``n_rays`` / ``n_missed``; ``peak`` (G, F): the brightest pixel; ``wavelengths``, ``f_number``,
+    ``wavefront``; ``axial``: a device tensor like ``wavefront.pupil``, per selected row in the wavefront's order the
+    component (E - P).a of its point on the reference sphere, NaN where the ray misses it."""
+
+    def __init__(self, image_by_wavelength, strehl, record, axial, line, centres, focus, wavelengths, world_unit_um,
+                 pixels, pixel_size, centre, f_number, wavefront, track="chief"):
+        self.image_by_wavelength = image_by_wavelength
+        self.image = image_by_wavelength.sum(axis=2)
+        self.strehl, self.record, self.axial = np.asarray(strehl, dtype=float), record, axial
+        self.line, self.centres = np.asarray(line, dtype=float), np.asarray(centres, dtype=float)
+        self.focus, self.wavelengths = np.asarray(focus, dtype=float), np.asarray(wavelengths, dtype=float)
+        self.world_unit_um, self.pixels, self.pixel_size, self.centre = world_unit_um, pixels, pixel_size, centre
+        self.f_number, self.wavefront, self.track = f_number, wavefront, track
+        nx, ny = pixels
+        self.u = (np.arange(nx) - 0.5 * (nx - 1)) * pixel_size[0]
+        self.v = (np.arange(ny) - 0.5 * (ny - 1)) * pixel_size[1]
+        self.n_rays = record[:, :, 0].sum(axis=1).astype(np.int64)
+        self.n_missed = record[:, :, 1].sum(axis=1).astype(np.int64)
+        flat = self.image.reshape(self.image.shape[0], self.image.shape[1], -1)
+        with np.errstate(invalid="ignore"):
+            self.peak = np.where(np.all(np.isfinite(flat), axis=2), flat.max(axis=2, initial=-np.inf), np.nan)
+
+    def plane(self, delta, group=None):
+        """The ``PSF`` of one of ``focus``: its ``encircled_energy()``, ``mtf()`` and ``to_pandas()`` then work on that
+        plane, with the pixel centres about the plane's point on the axis line through P.  A ``PSF`` has one grid for
+        all its groups: where the groups' centres differ on this plane (tracked chief lines), give ``group`` -- the
+        result then holds that group alone."""
+        f = _positions(self.focus, [delta], "delta")[0]
+        groups = slice(None) if group is None else slice(int(group), int(group) + 1)
+        centres = self.centres[groups, f]
+        if len(centres) and not np.all((centres == centres[0]) | np.isnan(centres)):
+            raise ValueError("plane: the groups' grids have different centres on this plane; give group=")
+        finite = centres[np.all(np.isfinite(centres), axis=1)]
+        centre = tuple(float(x) for x in finite[0]) if len(finite) else self.centre
+        return PSF(self.image_by_wavelength[groups, f], self.strehl[groups, f], self.record[groups], self.wavelengths,
+                   self.world_unit_um, self.pixels, self.pixel_size, centre, np.asarray(self.f_number)[groups],
+                   self.wavefront)
+
+    def best_focus(self):
+        """Per group, the focus shift of the largest Strehl ratio: the best sampled plane, refined by the vertex of the
+        parabola through it and its two neighbours when it is not at an end of the scan (``MTF.best_focus``'s rule).
+        NaN for a group without rays."""
+        return _best_plane(self.focus, self.strehl)
+
+    def to_pandas(self):
+        """Long form: one row per (source_id, focus) with its strehl and peak."""
+        g, f = self.strehl.shape
+        index = np.indices((g, f)).reshape(2, -1)
+        return pd.DataFrame({"source_id": index[0], "focus": self.focus[index[1]], "strehl": self.strehl.reshape(-1),
+                             "peak": self.peak.reshape(-1)})
 
 
 class VectorPSF(PSF):
