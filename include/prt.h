@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them).  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -921,6 +921,65 @@ int prt_frame_psf_gradient(int device, const double* rows, int64_t ld, int64_t n
                            double world_unit_um, int nx, int ny, double du, double dv, const double* centre_uv,
                            double* amplitude_out, double* damplitude_out, double* image_out, double* dimage_out,
                            double* strehl_out, double* record_out, void* workspace, void* stream);
+
+/* Monte Carlo tolerancing of the wavefront: the Strehl ratio of many perturbed systems, and the second moments of the
+ * OPD and its derivatives, from the rows and the wavefront outputs of one prt_frame_opd_sensitivity (or
+ * prt_frame_launch_sensitivity) call, without a re-trace.  Under the linear ray model the OPD of every ray moves linearly
+ * in the parameters; the merit stays nonlinear in the OPDs (this is not Strehl + dStrehl . p).
+ *
+ * Definitions.
+ * Rays: the selected rows of the sensitivity call, in its order (selected, group_first, weight_column and the wavelength
+ *   as prt_frame_psf_gradient takes them).  opd DEVICE n_selected, that call's opd_out.  columns DEVICE (C, n_selected),
+ *   1 <= C <= 20: x_c, the change of a ray's OPD per unit of column c, in world units (dopd_k, dfield_k, or a column a
+ *   caller composed).
+ * Rays kept: OPD finite, w finite and >= 0, all C column values finite.  There is one kept set for all columns and
+ *   trials.  The others are counted per (group, wavelength): n_missed by the first two (the PSF's rule), n_unfollowed by
+ *   the third; they contribute exactly nothing.
+ * prt_frame_tolerance.  trials DEVICE (n_groups, M, C), 1 <= M <= 65536: p_gmc, the value of column c in trial m of group
+ *   g.  Staged per kept ray of bucket (g, l), s_l = 1 / (lambda_l / world_unit_um): a = sqrt(w), c0 = OPD s_l,
+ *   e_c = x_c s_l.  Per trial, in cycles, the columns in their order:
+ *     phi_rm  = fma(e_C, p_C, ... fma(e_2, p_2, fma(e_1, p_1, c0)))
+ *     U_glm   = s_l sum_r a exp(2 pi i phi_rm)      the turn fract(phi) in fp64, its cos and sin in fp32 (prt_frame_psf's
+ *                                                    phase path from there on)
+ *     Strehl_gm = sum_l |U_glm|^2 / D_g,  D_g = sum_l (s_l sum a)^2
+ *   which is prt_frame_psf's Strehl ratio on the moved OPDs with the reference sphere held fixed.
+ *   Out, DEVICE, overwritten: strehl_out (n_groups, M); amplitude_out (n_groups, n_wavelengths, M, 2), U_glm;
+ *   record_out (n_groups, n_wavelengths, 5): rays kept, n_missed, n_unfollowed, sum a, (s sum a)^2.  A group without
+ *   kept rays is NaN.  workspace: prt_frame_tolerance_workspace_bytes(n_selected, n_groups, C, n_wavelengths, M) device
+ *   bytes (-1 for arguments the call would refuse).
+ *   Passes: a stable counting sort of an index of the kept rays into (group, wavelength) buckets; the staged planes;
+ *   sum a per slice in a fixed tree; the sum, a grid of (trial tile, ray slice, bucket) workgroups whose threads own 2
+ *   trials each, coefficients in registers, the slice's rays read through LDS; partial sums into a slab (bucket,
+ *   slice, trial) of 16 bytes each under the 256 MiB cap, the trials in several launches past it; the fold in slice
+ *   order.  The slice count follows n_selected, the bucket count and the device's CU count, a slice's rays its bucket's
+ *   kept count -- never n_rows, the frame's other rows, M or C --, and a trial's arithmetic does not depend on the
+ *   other trials: every output is the same, bit for bit, on every run, on any frame that holds the same selected rows,
+ *   for a trial alone or among 65536 at any place, and with a finite column appended whose trial values are all 0.
+ * prt_frame_tolerance_moments.  With v = (1, y_0, .. y_C), y_0 = OPD and y_c = x_c (world units, not scaled by s), per
+ *   group over the kept rays (of every wavelength): moments_out DEVICE (n_groups, 3 + (C + 2)(C + 3) / 2): rays kept,
+ *   n_missed, n_unfollowed, sum w, sum w y_i (C + 1 values), then sum w y_i y_j for j <= i, the lower triangle by rows.
+ *   Every entry is owned by one thread, summed in row order over chunks of 2048 selected rows of the group, the chunks
+ *   added in order: no floating-point atomics, the same bits on every run.  workspace:
+ *   prt_frame_tolerance_moments_workspace_bytes(n_selected, n_groups, C, n_wavelengths) device bytes (-1 as above).
+ * Both: wavelengths_um, world_unit_um as prt_frame_psf takes them, with its refusals; n_groups * n_wavelengths <= 16383
+ * (the moments entry also n_groups <= 65535).  A selected row number outside [0, n_rows), or a selected row of a wavelength
+ * that is not listed: PRT_ERR_ARG once the passes have run.  All arguments are checked before a device is touched.
+ * Stream-ordered; a call reads one status word back and so returns when the stream has reached its end.
+ * Accuracy: tests/tolerance_reference.py derives the bound per ray, eps = EPS_TRIG + 2 pi F32_TURN + 2 pi u (C + 2)
+ * (|c0| + sum_c |e_c p_c|), and carries it to U and to the Strehl ratio. */
+int64_t prt_frame_tolerance_workspace_bytes(int64_t n_selected, int n_groups, int n_columns, int n_wavelengths,
+                                            int n_trials);
+int prt_frame_tolerance(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                        int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                        const double* opd, const double* columns, int n_columns, const double* wavelengths_um,
+                        int n_wavelengths, double world_unit_um, const double* trials, int n_trials,
+                        double* strehl_out, double* amplitude_out, double* record_out, void* workspace, void* stream);
+int64_t prt_frame_tolerance_moments_workspace_bytes(int64_t n_selected, int n_groups, int n_columns, int n_wavelengths);
+int prt_frame_tolerance_moments(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                                int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                                const double* opd, const double* columns, int n_columns, const double* wavelengths_um,
+                                int n_wavelengths, double world_unit_um, double* moments_out, void* workspace,
+                                void* stream);
 
 /* Ray-aberration curves of the frame: each ray's row at a surface joined by ray id with the row where the ray was
  * launched (examples/lens_design.ipynb cells 12-13 join the two cuts of the frame with isin(id)), its transverse and

@@ -218,6 +218,12 @@ def _declare(lib):
         "prt_frame_psf_gradient": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p,
                                            c_p, c_int, c_p, c_int, c_d, c_int, c_int, c_d, c_d, c_p, c_p, c_p, c_p, c_p,
                                            c_p, c_p, c_p, c_p]),
+        "prt_frame_tolerance_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_int]),
+        "prt_frame_tolerance": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_int, c_p,
+                                        c_int, c_d, c_p, c_int, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_tolerance_moments_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+        "prt_frame_tolerance_moments": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_int,
+                                                c_p, c_int, c_d, c_p, c_p, c_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
@@ -254,6 +260,8 @@ EXPORTED_SYMBOLS = (
     "prt_frame_mtf_gradient_workspace_bytes", "prt_frame_mtf_gradient",
     "prt_frame_psf_gradient_workspace_bytes", "prt_frame_psf_gradient",
     "prt_frame_psf_focus_workspace_bytes", "prt_frame_psf_focus",
+    "prt_frame_tolerance_workspace_bytes", "prt_frame_tolerance",
+    "prt_frame_tolerance_moments_workspace_bytes", "prt_frame_tolerance_moments",
 )
 
 

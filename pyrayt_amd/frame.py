@@ -12,6 +12,8 @@ done on the device, so that only what is looked at crosses PCIe.  The grouped re
 row selections that return a new frame are torch indexing -- plumbing around the result.
 """
 
+from types import SimpleNamespace
+
 import numpy as np
 import pandas as pd
 
@@ -2657,6 +2659,203 @@ class WavelengthChange:
         return f"WavelengthChange(rays={self.rays}, rate={self.rate})"
 
 
+class Tolerances:
+    """Manufacturing tolerances of the parameters of a ``sensitivity()`` call, one width per parameter, and the trials
+    drawn from them.  ``distribution``: "uniform" on [-width, width]; "normal" with sigma = width (not truncated);
+    "parabolic", the density 3 x^2 / (2 width^3) on [-width, width] that favours the ends of the range (a part made to
+    the edge of its tolerance), variance 3 width^2 / 5.  ``sample(M)`` draws on the host from
+    ``numpy.random.default_rng(seed)``: the same trials for the same seed, M and widths, call after call."""
+
+    DISTRIBUTIONS = ("uniform", "normal", "parabolic")
+
+    def __init__(self, widths, distribution="uniform", seed=0):
+        try:
+            w = np.asarray(widths, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            w = np.zeros(0)
+        if not len(w) or not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError(f"widths: one finite number >= 0 per parameter (got {widths!r})")
+        if distribution not in self.DISTRIBUTIONS:
+            raise ValueError('distribution: "uniform", "normal" or "parabolic"')
+        self.widths, self.distribution, self.seed = w, distribution, seed
+
+    def sample(self, trials):
+        """(trials, K) float64."""
+        M = int(trials)
+        if M != trials or M < 1:
+            raise ValueError("trials: a whole number >= 1")
+        rng = np.random.default_rng(self.seed)
+        if self.distribution == "normal":
+            unit = rng.standard_normal((M, len(self.widths)))
+        else:
+            unit = rng.uniform(-1.0, 1.0, (M, len(self.widths)))
+            if self.distribution == "parabolic":
+                unit = np.cbrt(unit)  # (the inverse of the distribution function (x^3 + 1) / 2)
+        return unit * self.widths
+
+    def sensitivity_table(self):
+        """(2 K + 1, K): the nominal system, then per parameter k the trials 1 + 2 k (-width_k alone) and 2 + 2 k
+        (+width_k alone): what ``ToleranceRun.table()`` reads."""
+        K = len(self.widths)
+        out = np.zeros((2 * K + 1, K))
+        for k in range(K):
+            out[1 + 2 * k, k], out[2 + 2 * k, k] = -self.widths[k], self.widths[k]
+        return out
+
+
+def moment_covariance(moments, n_columns):
+    """The (C + 1, C + 1) longdouble covariance of (y_0 = OPD, y_1 .. y_C) from one group's block of
+    ``prt_frame_tolerance_moments`` (rays kept, n_missed, n_unfollowed, sum w, sum w y_i, the lower triangle of
+    sum w y_i y_j); None for a group without weight."""
+    LD = np.longdouble
+    wide = np.asarray(moments, dtype=LD)
+    n = n_columns + 1
+    sw = wide[3]
+    if not sw > 0:
+        return None
+    mean = wide[4:4 + n] / sw
+    lower = np.zeros((n, n), dtype=LD)
+    lower[np.tril_indices(n)] = wide[4 + n:4 + n + n * (n + 1) // 2]
+    second = (lower + np.tril(lower, -1).T) / sw
+    return second - np.outer(mean, mean)
+
+
+def _symmetric_pinv(matrix, rcond=None):
+    """The pseudo-inverse of a symmetric positive semi-definite longdouble matrix (numpy.linalg stops at float64):
+    equilibrated by its diagonal, diagonalised by cyclic Jacobi rotations, eigenvalues under ``rcond`` (default
+    ``RANK_RCOND``) of the largest dropped.  Returns (pinv, rank)."""
+    LD = np.longdouble
+    rcond = RANK_RCOND if rcond is None else rcond
+    a = np.array(matrix, dtype=LD)
+    n = len(a)
+    if not n:
+        return a, 0
+    scale = np.array([1 / np.sqrt(a[i, i]) if a[i, i] > 0 else LD(0) for i in range(n)], dtype=LD)
+    a = a * scale[:, None] * scale[None, :]
+    vectors = np.eye(n, dtype=LD)
+    for _ in range(60):
+        off = np.sqrt(np.sum(np.tril(a, -1) ** 2))
+        if not off > np.finfo(LD).eps * max(np.sqrt(np.sum(np.diag(a) ** 2)), np.finfo(LD).tiny):
+            break
+        for i in range(n - 1):
+            for j in range(i + 1, n):
+                if a[i, j] == 0:
+                    continue
+                theta = (a[j, j] - a[i, i]) / (2 * a[i, j])
+                t = np.sign(theta) / (abs(theta) + np.sqrt(theta * theta + 1)) if theta != 0 else LD(1)
+                c = 1 / np.sqrt(t * t + 1)
+                rot = np.eye(n, dtype=LD)
+                rot[i, i] = rot[j, j] = c
+                rot[i, j], rot[j, i] = t * c, -t * c
+                a = rot.T @ a @ rot
+                vectors = vectors @ rot
+    values = np.diag(a)
+    top = values.max() if n else LD(0)
+    keep = values > rcond * top if top > 0 else np.zeros(n, dtype=bool)
+    inverse = np.where(keep, 1 / np.where(keep, values, 1), 0)
+    pinv = (vectors * inverse[None, :]) @ vectors.T
+    return pinv * scale[:, None] * scale[None, :], int(keep.sum())
+
+
+def solve_compensators(covariance, trials, free):
+    """The coefficients of every column per trial, the columns ``free`` set to the least-squares minimiser of the
+    variance of y_0 + sum_c q_c y_c.  ``covariance``: (C + 1, C + 1), of (y_0, y_1 .. y_C); ``trials``: (M, C), the
+    drawn coefficients (what stands in a free column is overwritten); ``free``: column numbers in 0..C-1.  With A the
+    free columns and N the others: q_A = -pinv(Cov_AA) (Cov_A0 + Cov_AN q_N), the minimum-norm one (in the columns
+    scaled to unit variance) where Cov_AA is singular.  Returns (q (M, C) longdouble, rank); longdouble throughout."""
+    LD = np.longdouble
+    cov = np.asarray(covariance, dtype=LD)
+    q = np.array(trials, dtype=LD)
+    C = q.shape[1]
+    free = np.asarray(sorted(free), dtype=np.int64)
+    if not len(free):
+        return q, 0
+    fixed = np.setdiff1d(np.arange(C), free)
+    pinv, rank = _symmetric_pinv(cov[np.ix_(1 + free, 1 + free)])
+    rhs = cov[1 + free, 0][None, :] + q[:, fixed] @ cov[np.ix_(1 + fixed, 1 + free)]
+    q[:, free] = -(rhs @ pinv.T)
+    return q, rank
+
+
+class ToleranceRun:
+    """What ``Sensitivity.tolerance`` returns (numpy arrays), G groups, M trials, K parameters.  ``trials`` (M, K) as
+    drawn; ``compensators`` and ``compensation`` (G, M, n_comp): what each compensator was set to, per trial and
+    group -- for a real parameter the change ON TOP of the drawn value --; ``rms_opd`` (G, M): the RMS wavefront error
+    of the trial after compensation, piston removed, in world units, from the quadratic form of the device's moments;
+    ``strehl`` (G, M) and ``amplitude`` (G, L, M) complex: the Strehl ratio and U_l of include/prt.h
+    (``prt_frame_tolerance``), the merit fully nonlinear in the moved OPDs; ``rms_radius`` (G, M): the RMS spot radius
+    from the landing points' quadratic (``Sensitivity.mean_square``, its gradient and ``normal_matrix``) at the
+    compensated real parameters -- NaN throughout when "focus" is a compensator, since a focus shift moves a landing
+    point along its ray and that needs the slopes; "tilt" moves the evaluation point only and leaves the radius about
+    the centroid alone --; ``nominal``: the all-zero trial with the same compensators (``strehl``, ``rms_opd``,
+    ``rms_radius`` (G) and ``compensation`` (G, n_comp)); per group and wavelength ``n_rays``, ``n_missed``,
+    ``n_unfollowed``; ``record`` the device's (G, L, 5) block; ``moments`` its (G, ...) moments block."""
+
+    def __init__(self, trials, compensators, compensation, rms_opd, strehl, amplitude, rms_radius, record, moments,
+                 wavelengths, world_unit_um, parameters, follow):
+        self.compensators = tuple(compensators)
+        self.trials = np.asarray(trials, dtype=float)[:-1]
+        self.compensation, self.rms_opd, self.strehl = compensation[:, :-1], rms_opd[:, :-1], strehl[:, :-1]
+        self.amplitude, self.rms_radius = amplitude[:, :, :-1], rms_radius[:, :-1]
+        self.nominal = SimpleNamespace(compensation=compensation[:, -1], rms_opd=rms_opd[:, -1], strehl=strehl[:, -1],
+                                       rms_radius=rms_radius[:, -1], amplitude=amplitude[:, :, -1])
+        self.record, self.moments = np.asarray(record, dtype=float), np.asarray(moments, dtype=float)
+        self.n_rays, self.n_missed, self.n_unfollowed = (self.record[:, :, k].astype(np.int64) for k in (0, 1, 2))
+        self.wavelengths, self.world_unit_um = np.asarray(wavelengths, dtype=float), world_unit_um
+        self.parameters, self.follow = tuple(parameters), follow
+        self.n_parameters, self.n_trials = len(self.parameters), len(self.trials)
+
+    def yield_(self, strehl=0.8):
+        """(G): the share of the trials whose Strehl ratio is at least ``strehl``; NaN for a group without rays."""
+        with np.errstate(invalid="ignore"):
+            passed = np.mean(self.strehl >= strehl, axis=1)
+        return np.where(np.all(np.isfinite(self.strehl), axis=1), passed, np.nan)
+
+    def percentiles(self, q=(2, 10, 50, 90, 98)):
+        """Per merit a (G, len(q)) array of its percentiles over the trials: ``strehl``, ``rms_opd``, ``rms_radius``."""
+        q = np.atleast_1d(np.asarray(q, dtype=float))
+        with np.errstate(invalid="ignore"):
+            return {name: np.percentile(getattr(self, name), q, axis=1).T for name in ("strehl", "rms_opd", "rms_radius")}
+
+    def to_pandas(self):
+        """One row per (group, trial): the merits, the drawn parameters ``p_k`` and the compensation ``c_<name>``."""
+        G, M = self.strehl.shape
+        data = {"source_id": np.repeat(np.arange(G), M), "trial": np.tile(np.arange(M), G),
+                "strehl": self.strehl.ravel(), "rms_opd": self.rms_opd.ravel(), "rms_radius": self.rms_radius.ravel()}
+        for k in range(self.n_parameters):
+            data[f"p_{k}"] = np.tile(self.trials[:, k], G)
+        for j, name in enumerate(self._compensator_names()):
+            data[f"c_{name}"] = self.compensation[:, :, j].ravel()
+        return pd.DataFrame(data)
+
+    def _compensator_names(self):
+        names = []
+        for c in self.compensators:
+            names += ["tilt_u", "tilt_v"] if c == "tilt" else [str(c)]
+        return names
+
+    def table(self, group=0):
+        """For a run on ``Tolerances.sensitivity_table()``: per parameter the change of each merit against the nominal
+        trial at -width and +width (``dstrehl_minus``, ``dstrehl_plus``, ``drms_opd_*``, ``drms_radius_*``) and
+        ``worst``, the lower of the two Strehl changes; the rows sorted worst first.  ``ValueError`` for other trials."""
+        K = self.n_parameters
+        t = self.trials
+        one_at_a_time = t.shape == (2 * K + 1, K) and not np.any(t[0])
+        for k in range(K if one_at_a_time else 0):
+            hot = np.zeros(K, dtype=bool)
+            hot[k] = True
+            one_at_a_time &= (not np.any(t[1 + 2 * k][~hot]) and not np.any(t[2 + 2 * k][~hot])
+                              and t[1 + 2 * k, k] == -t[2 + 2 * k, k])
+        if not one_at_a_time:
+            raise ValueError("table: the trials are not Tolerances.sensitivity_table()'s")
+        rows = {"parameter": np.arange(K), "width": t[2::2][np.arange(K), np.arange(K)]}
+        for name in ("strehl", "rms_opd", "rms_radius"):
+            merit = getattr(self, name)[group]
+            rows[f"d{name}_minus"], rows[f"d{name}_plus"] = merit[1::2] - merit[0], merit[2::2] - merit[0]
+        rows["worst"] = np.fmin(rows["dstrehl_minus"], rows["dstrehl_plus"])
+        return pd.DataFrame(rows).sort_values("worst", kind="stable").reset_index(drop=True)
+
+
 class Sensitivity:
     """What ``DeviceFrame.sensitivity`` found.  ``jacobian``: device (K, 3, n_selected) float64, d(x1, y1, z1)/dp_k of the
     selected rows, which ``rows()`` names (frame row numbers, ordered by group, generation and id); NaN for a ray that
@@ -2898,6 +3097,155 @@ class Sensitivity:
                            engine.to_host(image).copy(), engine.to_host(dimage).copy(), engine.to_host(strehl).copy(),
                            engine.to_host(record).copy(), values, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])),
                            f_number, wave, self.parameters, follow)
+
+    def rms_radius_at(self, parameters):
+        """(groups, M): the RMS spot radius with the parameters changed by ``parameters`` (groups, M, K) under the linear
+        ray model, every landing point moved by ``jacobian . p``: the quadratic
+        ``mean_square + mean_square_gradient . p + p^T normal_matrix p`` of this object's sums, on the host -- about the
+        moved centroid for ``reference="centroid"``, about the fixed point otherwise."""
+        p = np.asarray(parameters, dtype=float)
+        with np.errstate(invalid="ignore"):
+            square = (self.mean_square[:, None] + np.einsum("gk,gmk->gm", self.mean_square_gradient, p)
+                      + np.einsum("gmj,gjk,gmk->gm", p, self.normal_matrix, p))
+            return np.sqrt(np.maximum(square, 0.0))
+
+    def tolerance(self, trials, *, world_unit_um, compensators=(), follow="ray"):
+        """Monte Carlo tolerancing from this one trace: the Strehl ratio and the RMS wavefront error of M perturbed
+        systems, a ``ToleranceRun``.  Needs ``sensitivity(wavefront=)``.  Under the linear ray model every ray's OPD moves
+        linearly in the parameters, ``OPD_r + sum_k dopd_rk p_k`` (``follow="ray"``, each ray followed; "pupil":
+        ``dfield``, the pupil points held), while the merit stays fully nonlinear in the OPDs: the Strehl ratio of a
+        trial is ``psf()``'s coherent sum on the moved OPDs, the sphere held fixed (``prt_frame_tolerance``;
+        include/prt.h states the formulas) -- not ``strehl + dstrehl . p``.
+
+        ``trials``: an (M, K) array of parameter changes, or a ``(Tolerances, M)`` pair to draw them; M <= 65535.
+        ``compensators``: what is re-adjusted per trial and group so that the variance of the OPD over the pupil is
+        least -- the index of a real parameter, or the pseudo-parameters "tilt" (the evaluation point moved by (du, dv)
+        across the axis) and "focus" (by d delta along it), the extra columns ``-p1 / R``, ``-p2 / R`` and ``-p3 / R``
+        with (p1, p2) = pupil * rho and p3 = -sign(u.a) sqrt(R^2 - p1^2 - p2^2) (``psf(focus=)``'s convention): the first-
+        order change of d_r - R.  The minimiser comes from the covariance of the device's moments
+        (``prt_frame_tolerance_moments``), solved on the host in longdouble (``solve_compensators``); the trial handed
+        to the Strehl kernel carries it.  A ray is summed if ``psf()`` would keep it and every column is finite there;
+        the others are counted (``n_missed``, ``n_unfollowed``).  A ``WavelengthChange`` among the parameters is refused.
+        Second-order terms and rays whose path changes under a perturbation are out of scope."""
+        self._need_wave("tolerance")
+        import torch
+
+        from . import engine
+
+        if follow not in ("ray", "pupil"):
+            raise ValueError('follow: "ray" or "pupil"')
+        if any(isinstance(m, WavelengthChange) for m in self.parameters):
+            raise ValueError("tolerance: a WavelengthChange among the parameters moves a ray between wavelengths; "
+                             "tolerances are taken for the other kinds of parameter")
+        unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
+        K = self.n_parameters
+        if isinstance(trials, tuple) and len(trials) == 2 and isinstance(trials[0], Tolerances):
+            if len(trials[0].widths) != K:
+                raise ValueError(f"trials: the Tolerances have {len(trials[0].widths)} widths for {K} parameters")
+            trials = trials[0].sample(trials[1])
+        try:
+            drawn = np.array(trials, dtype=np.float64)
+        except (TypeError, ValueError):
+            drawn = np.zeros(0)
+        if drawn.ndim != 2 or drawn.shape[1] != K or not 1 <= drawn.shape[0] <= 65535 or not np.all(np.isfinite(drawn)):
+            raise ValueError(f"trials: a finite (M, {K}) array, 1 <= M <= 65535, or a (Tolerances, M) pair")
+        if isinstance(compensators, (str, int, np.integer)):
+            compensators = (compensators,)
+        compensators = tuple(compensators)
+        free, pseudo = [], []
+        for c in compensators:
+            if c in ("tilt", "focus"):
+                pseudo.append(c)
+            elif isinstance(c, (int, np.integer)) and not isinstance(c, bool) and 0 <= c < K:
+                free.append(int(c))
+            else:
+                raise ValueError(f'compensators: indices of parameters (0..{K - 1}), "tilt" or "focus" (got {c!r})')
+        if len(set(compensators)) != len(compensators):
+            raise ValueError("compensators: each one once")
+        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        dev = rows.device
+        n_groups, n_rows, n_selected = len(first) - 1, rows.shape[1], int(self._selected.shape[0])
+        wave = self.wavefront
+        written = self._launch.get("written")
+        if written is not None and _INDEX["wavelength"] not in written:
+            raise ValueError("tolerance: the frame was recorded without the wavelength column (RecordPlan(columns=...))")
+        if not n_selected:
+            raise ValueError("tolerance: no row is selected at this surface")
+        values = _distinct_wavelengths(
+            rows[_INDEX["wavelength"]][self._selected].unique().cpu().numpy().astype(np.float64), "tolerance")
+        # the columns: the K parameters, then the pseudo-parameters' (torch, on the device)
+        columns = [(self.dopd if follow == "ray" else self.dfield)]
+        if pseudo:
+            first_t = torch.as_tensor(np.asarray(first, dtype=np.int64), device=dev)
+            group = torch.repeat_interleave(torch.arange(n_groups, device=dev), first_t[1:] - first_t[:-1])
+            radius = torch.as_tensor(np.asarray(wave.radius, dtype=np.float64), device=dev)[group]
+            rho = torch.as_tensor(np.asarray(wave.pupil_radius, dtype=np.float64), device=dev)[group]
+            p = self.pupil * rho[:, None]
+            for c in pseudo:
+                if c == "tilt":
+                    columns.append((-p / radius[:, None]).T)
+                else:
+                    axis = torch.as_tensor(np.asarray(wave._made_of["axes"], dtype=np.float64).reshape(3, 3)[0], device=dev)
+                    along = axis @ rows[_INDEX["x_tilt"]:_INDEX["z_tilt"] + 1][:, self._selected]
+                    p3 = -torch.sign(along) * torch.sqrt(radius * radius - (p * p).sum(dim=1))
+                    columns.append((-p3 / radius)[None, :])
+        columns = torch.cat(columns, dim=0).contiguous()
+        C = int(columns.shape[0])
+        slots, at = [], K  # (the column of every compensator value, in the compensators' order)
+        for c in compensators:
+            if c == "tilt":
+                slots += [at, at + 1]
+                at += 2
+            elif c == "focus":
+                slots.append(at)
+                at += 1
+            else:
+                slots.append(c)
+        lib = engine.library()
+        lam = np.ascontiguousarray(values, dtype=np.float64)
+        n_w = len(lam)
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        opd = self.opd.contiguous()
+        empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+        head = (dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, self._selected.data_ptr(),
+                n_selected, first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], opd.data_ptr(),
+                columns.data_ptr(), C, lam.ctypes.data, n_w, unit)
+        moments = empty(n_groups, 3 + (C + 2) * (C + 3) // 2)
+        work = torch.empty(int(engine._check(lib.prt_frame_tolerance_moments_workspace_bytes(n_selected, n_groups, C, n_w))),
+                           dtype=torch.uint8, device=dev)
+        engine._check(lib.prt_frame_tolerance_moments(*head, moments.data_ptr(), work.data_ptr(),
+                                                      engine._stream_ptr(torch, dev)))
+        moments = engine.to_host(moments).copy()
+        # per group: the covariance, the compensators of every trial (the nominal one last), the RMS of its OPD
+        LD = np.longdouble
+        M = len(drawn) + 1
+        plain = np.zeros((M, C))
+        plain[:-1, :K] = drawn
+        q = np.full((n_groups, M, C), np.nan)
+        rms_opd = np.full((n_groups, M), np.nan)
+        for g in range(n_groups):
+            covariance = moment_covariance(moments[g], C)
+            if covariance is None:
+                q[g] = plain
+                continue
+            qg, _ = solve_compensators(covariance, plain, slots)
+            v = np.concatenate([np.ones((M, 1), dtype=LD), qg], axis=1)
+            rms_opd[g] = np.sqrt(np.maximum(np.einsum("mi,ij,mj->m", v, covariance, v), 0)).astype(float)
+            q[g] = qg.astype(float)
+        handed = torch.as_tensor(np.ascontiguousarray(q), device=dev)
+        strehl, amplitude, record = empty(n_groups, M), empty(n_groups, n_w, M, 2), empty(n_groups, n_w, 5)
+        work = torch.empty(int(engine._check(lib.prt_frame_tolerance_workspace_bytes(n_selected, n_groups, C, n_w, M))),
+                           dtype=torch.uint8, device=dev)
+        engine._check(lib.prt_frame_tolerance(*head, handed.data_ptr(), M, strehl.data_ptr(), amplitude.data_ptr(),
+                                              record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        pair = engine.to_host(amplitude)
+        compensation = np.zeros((n_groups, M, len(slots)))
+        for j, slot in enumerate(slots):  # (a real parameter: what was added to the drawn value)
+            compensation[:, :, j] = q[:, :, slot] - (plain[:, slot] if slot < K else 0.0)
+        rms_radius = np.full((n_groups, M), np.nan) if "focus" in pseudo else self.rms_radius_at(q[:, :, :K])
+        return ToleranceRun(plain[:, :K], compensators, compensation, rms_opd, engine.to_host(strehl).copy(),
+                            pair[..., 0] + 1j * pair[..., 1], rms_radius, engine.to_host(record).copy(), moments, values,
+                            unit, self.parameters, follow)
 
     def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
         """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the
