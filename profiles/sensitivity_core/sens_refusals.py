@@ -12,7 +12,8 @@ import numpy as np  # noqa: E402
 
 import launch_scenes  # noqa: E402
 from pyrayt_amd import engine  # noqa: E402
-from pyrayt_amd.frame import _SENS_FORMS, _sens_pointer  # noqa: E402
+from pyrayt_amd.engine import _pointer as _sens_pointer  # noqa: E402
+from pyrayt_amd.frame import _SENS_FORMS  # noqa: E402
 from pyrayt_amd.scene import PRIM_DTYPE, SceneSnapshot  # noqa: E402
 
 engine.LIB_PATH = os.path.abspath(sys.argv[1])
@@ -104,17 +105,18 @@ PAIRS = [("K=0", "n_groups=0"), ("pivots nan", "type 99"), ("twists nan", "param
          ("index_first 70 ids", "linear nan"), ("material -1", "colour rate nan")]
 
 for name, mutations in itertools.chain(((n, [n]) for n in ONE), ((" + ".join(p), list(p)) for p in PAIRS)):
-    for form, (_, _, entry, order) in _SENS_FORMS.items():
+    for form, (_, entry, order) in _SENS_FORMS.items():
         pieces = base()
         for m in mutations:
             ONE[m](pieces)
-        rc = getattr(lib, entry)(*(_sens_pointer(pieces[q]) for q in order))
+        rc = getattr(lib, entry)(*(_sens_pointer(pieces[q]) for q in order + ("work", "stream")))
         text = lib.prt_last_error().decode("utf-8", "replace") if rc else ""
         print(json.dumps({"what": name, "form": form, "rc": rc, "text": text}))
 
 sizes = list(itertools.product((0, 1, 600, 1 << 40), (0, 4, (1 << 20) + 1), (0, 1, 5, 16, 17), (0, 1, 2, 65535, 65536),
                                (-1, 0, 1, 256, 257, 300, 1 << 33, 1 << 40)))
-for form, (size, extra, _, _) in _SENS_FORMS.items():
+for form, (extra, entry, _) in _SENS_FORMS.items():
+    size = entry + "_workspace_bytes"
     for args in sizes:
         for n_terms in ((-1, 0, 1, 15, 36, 37) if extra else (None,)):
             more = () if n_terms is None else (n_terms,)

@@ -91,9 +91,10 @@ class EngineUnavailable(RuntimeError):
     pass
 
 
-def _declare(lib):
+def _signatures():
+    """Every function of include/prt.h this binding binds: name -> (result type, argument types)."""
     c_int, c_i64, c_p, c_d = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_double
-    sig = {
+    return {
         "prt_version": (c_int, []),
         "prt_last_error": (ctypes.c_char_p, []),
         "prt_device_count": (c_int, []),
@@ -225,44 +226,18 @@ def _declare(lib):
         "prt_frame_tolerance_moments": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_int,
                                                 c_p, c_int, c_d, c_p, c_p, c_p]),
     }
-    for name, (res, args) in sig.items():
+
+
+SIGNATURES = _signatures()
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
+
+
+def _declare(lib):
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)  # AttributeError here = the library does not match prt.h
         fn.restype = res
         fn.argtypes = args
     return lib
-
-
-EXPORTED_SYMBOLS = (
-    "prt_version", "prt_last_error", "prt_device_count", "prt_scene_create", "prt_scene_destroy", "prt_scene_update",
-    "prt_scene_component_rows", "prt_scene_info", "prt_intersect", "prt_propagate", "prt_world_normals",
-    "prt_material_trace", "prt_interact_workspace_bytes", "prt_interact", "prt_scene_set_index_tables",
-    "prt_gather_hits", "prt_scatter_shaded", "prt_unique_workspace_bytes", "prt_unique_values",
-    "prt_trace_workspace_bytes", "prt_trace", "prt_trace_begin", "prt_trace_end", "prt_trace_batch", "prt_trace_batch_busy", "prt_trace_set_plan", "prt_trace_stats", "prt_trace_telemetry", "prt_trace_shortcut_counts", "prt_generate_rays",
-    "prt_camera_rays", "prt_render_hits", "prt_gooch_shade", "prt_gooch_mix", "prt_render",
-    "prt_edge_workspace_bytes", "prt_edge_canvas", "prt_reflect", "prt_refract", "prt_binomial_root",
-    "prt_smallest_positive_root", "prt_dot", "prt_array_csg", "prt_primitive_intersect",
-    "prt_primitive_normal", "prt_comm_unique_id", "prt_comm_create", "prt_comm_destroy", "prt_comm_info",
-    "prt_allgather_counts", "prt_allgather_workspace_bytes", "prt_allgather_rows",
-    "prt_place_workspace_bytes", "prt_place_rows", "prt_frame_reduce", "prt_frame_stats_workspace_bytes",
-    "prt_frame_stats", "prt_frame_stats_sharded", "prt_frame_pivots", "prt_frame_finish", "prt_frame_mean_square",
-    "prt_frame_range", "prt_frame_histogram_workspace_bytes", "prt_frame_histogram",
-    "prt_frame_optical_path", "prt_frame_wavefront_workspace_bytes", "prt_frame_wavefront",
-    "prt_frame_psf_workspace_bytes", "prt_frame_psf", "prt_frame_vector_psf_workspace_bytes", "prt_frame_vector_psf",
-    "prt_frame_mtf_workspace_bytes", "prt_frame_mtf",
-    "prt_frame_launch_index", "prt_frame_ray_aberrations_workspace_bytes", "prt_frame_ray_aberrations",
-    "prt_frame_energy_workspace_bytes", "prt_frame_energy", "prt_frame_paths_workspace_bytes", "prt_frame_paths",
-    "prt_frame_fresnel_workspace_bytes", "prt_frame_fresnel",
-    "prt_frame_fresnel_coated_workspace_bytes", "prt_frame_fresnel_coated",
-    "prt_frame_sensitivity_workspace_bytes", "prt_frame_sensitivity",
-    "prt_frame_design_sensitivity_workspace_bytes", "prt_frame_design_sensitivity",
-    "prt_frame_opd_sensitivity_workspace_bytes", "prt_frame_opd_sensitivity",
-    "prt_frame_launch_sensitivity_workspace_bytes", "prt_frame_launch_sensitivity",
-    "prt_frame_mtf_gradient_workspace_bytes", "prt_frame_mtf_gradient",
-    "prt_frame_psf_gradient_workspace_bytes", "prt_frame_psf_gradient",
-    "prt_frame_psf_focus_workspace_bytes", "prt_frame_psf_focus",
-    "prt_frame_tolerance_workspace_bytes", "prt_frame_tolerance",
-    "prt_frame_tolerance_moments_workspace_bytes", "prt_frame_tolerance_moments",
-)
 
 
 def library():
@@ -338,6 +313,47 @@ def to_host(tensor):
 
 def _stream_ptr(torch, device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _pointer(piece):
+    """What the library is given for a piece of a call: the address of a device tensor (NULL for one without elements)
+    or of a host array; None is NULL; a number, or an address the caller worked out, as it is."""
+    kind = type(piece)
+    if piece is None or kind is int or kind is float:  # (most of a call: tried first, a call costs microseconds)
+        return piece
+    if kind is np.ndarray:
+        return piece.ctypes.data
+    if hasattr(piece, "data_ptr"):
+        return piece.data_ptr() if piece.numel() else None
+    return piece
+
+
+def call(entry, *args, device, size=None, sized_by=None):
+    """One call of a frame pass of the library on the current stream of ``device``: ``args`` in the order of
+    include/prt.h without the workspace and the stream, each through ``_pointer``.  ``size``: the arguments of the size
+    function ``<sized_by or entry>_workspace_bytes`` of a pass that takes a workspace, which is allocated here and handed
+    over before the stream, always the last argument.  The size and the return code are checked (``_check``)."""
+    import torch
+
+    lib = library()
+    pieces = list(map(_pointer, args))
+    if size is not None:
+        # (the workspace dies with this frame: the allocator hands its block on in stream order, behind the work queued here)
+        work = torch.empty(int(_check(getattr(lib, (sized_by or entry) + "_workspace_bytes")(*size))), dtype=torch.uint8,
+                           device=device)
+        pieces.append(work.data_ptr())
+    return _check(getattr(lib, entry)(*pieces, _stream_ptr(torch, device)))
+
+
+def host(tensor):
+    """A device tensor as a host array of its own (``to_host`` gives a view of pinned memory that is taken back)."""
+    return to_host(tensor).copy()
+
+
+def host_complex(pair):
+    """A device tensor of (..., 2) real and imaginary parts as a complex host array."""
+    pair = to_host(pair)
+    return pair[..., 0] + 1j * pair[..., 1]
 
 
 _TICKET_STREAMS = {}  # device -> the process's ticket streams on it (DeviceScene.ticket_streams)

@@ -12,6 +12,7 @@ done on the device, so that only what is looked at crosses PCIe.  The grouped re
 row selections that return a new frame are torch indexing -- plumbing around the result.
 """
 
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -152,15 +153,9 @@ class DeviceFrame:
         rows = self.rows
         if rows.stride(1) != 1:
             rows = rows.contiguous()
-        dev = rows.device
-        lib = engine.library()
-        out = torch.empty((n_groups, 8), dtype=torch.float64, device=dev)
-        work = torch.empty(int(lib.prt_frame_stats_workspace_bytes(n_groups)), dtype=torch.uint8, device=dev)
-        nan = float("nan")
-        engine._check(lib.prt_frame_stats(
-            dev.index or 0, rows.data_ptr(), rows.stride(0), rows.shape[1],
-            nan if surface is None else float(surface), nan if generation is None else float(generation),
-            float(rays_per_source or 0), n_groups, out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+        out = torch.empty((n_groups, 8), dtype=torch.float64, device=rows.device)
+        engine.call("prt_frame_stats", *_row_head(rows), *_row_filter(surface, generation, rays_per_source, n_groups), out,
+                    device=rows.device, size=(n_groups,))
         return out.cpu().numpy()
 
     def _reduce_pass(self, surface, generation, rays_per_source, n_groups, pivots):
@@ -170,14 +165,9 @@ class DeviceFrame:
         from . import engine
 
         rows = self._contiguous_rows()
-        dev = rows.device
-        sums = torch.empty((n_groups, 9), dtype=torch.float64, device=dev)
-        nan = float("nan")
-        engine._check(engine.library().prt_frame_reduce(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), 1), rows.shape[1],
-            nan if surface is None else float(surface), nan if generation is None else float(generation),
-            float(rays_per_source or 0), n_groups, pivots.data_ptr() if pivots is not None else None,
-            sums.data_ptr(), engine._stream_ptr(torch, dev)))
+        sums = torch.empty((n_groups, 9), dtype=torch.float64, device=rows.device)
+        engine.call("prt_frame_reduce", *_row_head(rows), *_row_filter(surface, generation, rays_per_source, n_groups),
+                    pivots, sums, device=rows.device)
         return sums
 
     def _stats_sharded(self, surface, generation, rays_per_source, n_groups, group, comm):
@@ -186,17 +176,12 @@ class DeviceFrame:
 
         from . import engine
 
-        lib = engine.library()
-        nan = float("nan")
         if comm is not None:  # one library call: both passes, two ncclAllReduce of (n_groups, 9) doubles
             rows = self._contiguous_rows()
-            dev = rows.device
-            out = torch.empty((n_groups, 8), dtype=torch.float64, device=dev)
-            work = torch.empty(int(lib.prt_frame_stats_workspace_bytes(n_groups)), dtype=torch.uint8, device=dev)
-            engine._check(lib.prt_frame_stats_sharded(
-                comm._handle, rows.data_ptr(), max(rows.stride(0), 1), rows.shape[1],
-                nan if surface is None else float(surface), nan if generation is None else float(generation),
-                float(rays_per_source or 0), n_groups, out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
+            out = torch.empty((n_groups, 8), dtype=torch.float64, device=rows.device)
+            engine.call("prt_frame_stats_sharded", comm._handle, *_row_head(rows)[1:],
+                        *_row_filter(surface, generation, rays_per_source, n_groups), out, device=rows.device,
+                        size=(n_groups,), sized_by="prt_frame_stats")
             return out.cpu().numpy()
         # another transport adds the sums: the passes and the two small steps are separate library calls
         sums = _all_reduce_sum(self._reduce_pass(surface, generation, rays_per_source, n_groups, None), group)
@@ -211,8 +196,7 @@ class DeviceFrame:
         from . import engine
 
         pivots = torch.empty((n_groups, 3), dtype=torch.float64, device=sums.device)
-        engine._check(engine.library().prt_frame_pivots(sums.device.index or 0, sums.data_ptr(), n_groups, pivots.data_ptr(),
-                                                        engine._stream_ptr(torch, sums.device)))
+        engine.call("prt_frame_pivots", sums.device.index or 0, sums, n_groups, pivots, device=sums.device)
         return pivots
 
     def _finish(self, sums, pivots, n_groups):
@@ -222,8 +206,7 @@ class DeviceFrame:
         from . import engine
 
         out = torch.empty((n_groups, 8), dtype=torch.float64, device=sums.device)
-        engine._check(engine.library().prt_frame_finish(sums.device.index or 0, sums.data_ptr(), pivots.data_ptr(), n_groups,
-                                                        out.data_ptr(), engine._stream_ptr(torch, sums.device)))
+        engine.call("prt_frame_finish", sums.device.index or 0, sums, pivots, n_groups, out, device=sums.device)
         return out
 
     def mean_square(self, quantity, about=0.0, transform=None, surface=None, generation=None, rays_per_source=None,
@@ -265,14 +248,9 @@ class DeviceFrame:
         else:
             n_groups = 1
         rows = self._contiguous_rows()
-        dev = rows.device
-        sums = torch.empty((n_groups, 3), dtype=torch.float64, device=dev)
-        nan = float("nan")
-        engine._check(engine.library().prt_frame_mean_square(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), 1), rows.shape[1],
-            nan if surface is None else float(surface), nan if generation is None else float(generation),
-            float(rays_per_source or 0), n_groups, column, how, float(about), sums.data_ptr(),
-            engine._stream_ptr(torch, dev)))
+        sums = torch.empty((n_groups, 3), dtype=torch.float64, device=rows.device)
+        engine.call("prt_frame_mean_square", *_row_head(rows), *_row_filter(surface, generation, rays_per_source, n_groups),
+                    column, how, float(about), sums, device=rows.device)
         if group is not None:
             sums = _all_reduce_sum(sums, group)
         sums = sums.cpu().numpy()
@@ -343,8 +321,7 @@ class DeviceFrame:
                 generation = 0
         if generation is not None:
             if self.rows_per_generation:  # (generation-major: one generation's rows are a slice, no filter needed)
-                start = sum(self.rows_per_generation[:int(generation)])
-                size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+                _, start, size = self._generation_slice(generation)
                 frame = DeviceFrame(self.rows[:, start:start + size], None, self.written)
                 generation = None
             else:
@@ -359,17 +336,12 @@ class DeviceFrame:
             n_groups = 1
         rows = frame._contiguous_rows()
         dev = rows.device
-        ld, n_rows = max(rows.stride(0), rows.shape[1], 1), rows.shape[1]
-        nan = float("nan")
-        surface = nan if surface is None else float(surface)
-        generation = nan if generation is None else float(generation)
-        stream = engine._stream_ptr(torch, dev)
-        lib = engine.library()
+        head, which = _row_head(rows), _row_filter(surface, generation, rays_per_source, n_groups)
+        surface, generation = which[:2]  # (as the passes read them: the range takes no groups)
 
         def finite_range(axis):
             box = torch.empty(2, dtype=torch.float64, device=dev)
-            engine._check(lib.prt_frame_range(dev.index or 0, rows.data_ptr(), ld, n_rows, surface, generation,
-                                              codes[axis], box.data_ptr(), stream))
+            engine.call("prt_frame_range", *head, surface, generation, codes[axis], box, device=dev)
             if group is not None:
                 box[1:].neg_()
                 box = _all_reduce_min(box, group)
@@ -383,15 +355,9 @@ class DeviceFrame:
         shape = (n_groups, nx, max(ny, 1))
         counts = torch.empty(shape, dtype=torch.int64, device=dev)
         sums = torch.empty(shape, dtype=torch.float64, device=dev) if weights is not None else None
-        work = torch.empty(int(engine._check(lib.prt_frame_histogram_workspace_bytes(n_groups, nx, ny, sums is not None))),
-                           dtype=torch.uint8, device=dev)
-        y_edges = edges[1] if ny else None
-        engine._check(lib.prt_frame_histogram(
-            dev.index or 0, rows.data_ptr(), ld, n_rows, surface, generation, float(rays_per_source or 0), n_groups,
-            codes[0], edges[0].ctypes.data, nx, int(uniform[0]),
-            codes[1] if ny else -1, None if y_edges is None else y_edges.ctypes.data, ny, int(ny and uniform[1]),
-            -1 if weights is None else _INDEX[weights], counts.data_ptr(), None if sums is None else sums.data_ptr(),
-            work.data_ptr(), stream))
+        engine.call("prt_frame_histogram", *head, *which, codes[0], edges[0], nx, int(uniform[0]),
+                    codes[1] if ny else -1, edges[1] if ny else None, ny, int(ny and uniform[1]),
+                    _weight_column(weights), counts, sums, device=dev, size=(n_groups, nx, ny, sums is not None))
         out = counts if sums is None else sums
         if group is not None:
             out = _all_reduce_sum(out, group)
@@ -419,6 +385,14 @@ class DeviceFrame:
         """The rows as the library reads them: contiguous along the row axis."""
         rows = self.rows
         return rows if rows.stride(1) == 1 or rows.shape[1] <= 1 else rows.contiguous()
+
+    def _generation_slice(self, generation):
+        """``(generation, start, size)``: the number of the generation ("last": the highest that recorded rows), where
+        its rows begin in the generation-major block and how many they are -- none past the last generation."""
+        if generation == "last":
+            generation = self.last_generation_number() or 0
+        size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+        return generation, sum(self.rows_per_generation[:int(generation)]), size
 
     def _id_range(self, what, rows):
         """``(id0, n_ids, top)``: the smallest id of ``rows``, the length of the dense per-id arrays of a join by ray id,
@@ -459,9 +433,7 @@ class DeviceFrame:
             return opl
         id0, n_ids, _ = self._id_range("optical_path", rows)
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
-        engine._check(engine.library().prt_frame_optical_path(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), rows.shape[1], 1), counts.ctypes.data, len(counts),
-            id0, n_ids, opl.data_ptr(), engine._stream_ptr(torch, dev)))
+        engine.call("prt_frame_optical_path", *_row_head(rows)[:3], counts, len(counts), id0, n_ids, opl, device=dev)
         return opl
 
     def wavefront(self, surface, reference="centroid", radius=None, axis=None, basis=None, pupil_radius=None,
@@ -515,31 +487,20 @@ class DeviceFrame:
             radii = torch.as_tensor(np.broadcast_to(np.asarray(radius, dtype=float), (n_groups,)).copy()).to(dev)
         opl = self._optical_path()
         rows = self._contiguous_rows()
-        if generation == "last":
-            generation = self.last_generation_number() or 0
         if generation is not None:  # (generation-major: one generation's rows are a slice)
-            start = sum(self.rows_per_generation[:int(generation)])
-            size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+            generation, start, size = self._generation_slice(generation)
             rows, opl = rows[:, start:start + size], opl[start:start + size]
         n_rows = rows.shape[1]
         entries = terms * (terms + 1) // 2 + terms + 3
-        lib = engine.library()
         opd = torch.empty(n_rows, dtype=torch.float64, device=dev)
         pupil = torch.empty((n_rows, 2), dtype=torch.float64, device=dev)
         record = torch.empty((n_groups, 12), dtype=torch.float64, device=dev)
         normal = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
-        work = torch.empty(int(engine._check(lib.prt_frame_wavefront_workspace_bytes(n_rows, n_groups, terms,
-                                                                                     weights is not None))),
-                           dtype=torch.uint8, device=dev)
-        engine._check(lib.prt_frame_wavefront(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, opl.data_ptr(),
-            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
-            None if centres is None else centres.data_ptr(), None if radii is None else radii.data_ptr(),
-            axes.ctypes.data, float(pupil_radius or 0.0), terms, -1 if weights is None else _INDEX[weights],
-            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), normal.data_ptr(), work.data_ptr(),
-            engine._stream_ptr(torch, dev)))
-        record_host = engine.to_host(record).copy()
-        normal_host = engine.to_host(normal).copy()
+        engine.call("prt_frame_wavefront", *_row_head(rows), opl, *_row_filter(surface_id, None, rays_per_source, n_groups),
+                    centres, radii, axes, float(pupil_radius or 0.0), terms, _weight_column(weights), opd, pupil, record,
+                    normal, device=dev, size=(n_rows, n_groups, terms, weights is not None))
+        record_host = engine.host(record)
+        normal_host = engine.host(normal)
         n_selected = int(record_host[:, 6].sum())
         wave = Wavefront(opd[:n_selected], pupil[:n_selected], record_host, normal_host, terms)
         # (what sensitivity(wavefront=) holds a Wavefront to: the frame, the selection, the weights and the pupil's basis)
@@ -624,76 +585,57 @@ class DeviceFrame:
         dev = rows.device
         n_rows = rows.shape[1]
         n_w = len(wavelengths)
-        if fresnel is not None:
-            if fresnel.launch_states == "per_ray":  # (the pass's own two states: made uniform across the beam first)
-                fresnel = fresnel.uniform_states()
-            return self._vector_psf(fresnel, wave, rows, surface_id, n_groups, record, weights, generation,
-                                    rays_per_source, wavelengths, unit, (nx, ny), step, uv0, f_number)
-        if focus is not None:
-            return self._psf_focus(focus, track, wave, rows, surface_id, n_groups, record, weights, rays_per_source,
-                                   wavelengths, unit, (nx, ny), step, uv0, f_number)
-        image = torch.empty((n_groups, n_w, nx, ny), dtype=torch.float64, device=dev)
-        strehl = torch.empty(n_groups, dtype=torch.float64, device=dev)
-        out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_psf_workspace_bytes(n_rows, n_groups, n_w))),
-                           dtype=torch.uint8, device=dev)
         lam = np.ascontiguousarray(wavelengths, dtype=np.float64)
         uv0 = np.ascontiguousarray(uv0)
         opd = wave.opd if wave.opd.numel() else torch.empty(1, dtype=torch.float64, device=dev)
         pupil = wave.pupil if wave.pupil.numel() else torch.empty(2, dtype=torch.float64, device=dev)
-        engine._check(lib.prt_frame_psf(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
-            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
-            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), -1 if weights is None else _INDEX[weights],
-            lam.ctypes.data, n_w, unit, nx, ny, step[0], step[1], uv0.ctypes.data, image.data_ptr(), strehl.data_ptr(),
-            out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        return PSF(engine.to_host(image).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(), wavelengths,
-                   unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave)
+        # the twenty leading arguments of the three Huygens sums, and what their results are told of the grid
+        head = (*_row_head(rows), *_row_filter(surface_id, None, rays_per_source, n_groups), opd, pupil, record,
+                _weight_column(weights), lam, n_w, unit, nx, ny, step[0], step[1], uv0)
+        made = _HuygensGrid(wavelengths, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave)
+        if fresnel is not None:
+            if fresnel.launch_states == "per_ray":  # (the pass's own two states: made uniform across the beam first)
+                fresnel = fresnel.uniform_states()
+            return self._vector_psf(fresnel, generation, rows, n_groups, head, made)
+        if focus is not None:
+            return self._psf_focus(focus, track, rows, n_groups, head, made)
+        image = torch.empty((n_groups, n_w, nx, ny), dtype=torch.float64, device=dev)
+        strehl = torch.empty(n_groups, dtype=torch.float64, device=dev)
+        out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
+        engine.call("prt_frame_psf", *head, image, strehl, out, device=dev, size=(n_rows, n_groups, n_w))
+        return PSF(engine.host(image), engine.host(strehl), engine.host(out), *made)
 
-    def _psf_focus(self, focus, track, wave, rows, surface_id, n_groups, record, weights, rays_per_source, wavelengths,
-                   unit, pixels, step, uv0, f_number):
-        """``psf(focus=)`` after the wavefront: the call, and the ``PSFScan``."""
+    def _psf_focus(self, focus, track, rows, n_groups, head, made):
+        """``psf(focus=)`` after the wavefront (``head``, ``made``: see ``psf``): the call, and the ``PSFScan``."""
         import torch
 
         from . import engine
 
-        dev = rows.device
-        n_rows, n_w, n_f, (nx, ny) = rows.shape[1], len(wavelengths), len(focus), pixels
+        wavelengths, (nx, ny), wave = made.wavelengths, made.pixels, made.wave
+        dev, n_rows = rows.device, rows.shape[1]
+        n_w, n_f = len(wavelengths), len(focus)
         image = torch.empty((n_groups, n_f, n_w, nx, ny), dtype=torch.float64, device=dev)
         strehl = torch.empty((n_groups, n_f), dtype=torch.float64, device=dev)
         out = torch.empty((n_groups, n_w, 4), dtype=torch.float64, device=dev)
         axial = torch.empty(max(n_rows, 1), dtype=torch.float64, device=dev)
         line = torch.empty((n_groups, 2), dtype=torch.float64, device=dev)
         centres = torch.empty((n_groups, n_f, 2), dtype=torch.float64, device=dev)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_psf_focus_workspace_bytes(n_rows, n_groups, n_w, n_f))),
-                           dtype=torch.uint8, device=dev)
-        lam = np.ascontiguousarray(wavelengths, dtype=np.float64)
-        uv0 = np.ascontiguousarray(uv0)
         axes = np.ascontiguousarray(wave._made_of["axes"], dtype=np.float64)
-        opd = wave.opd if wave.opd.numel() else torch.empty(1, dtype=torch.float64, device=dev)
-        pupil = wave.pupil if wave.pupil.numel() else torch.empty(2, dtype=torch.float64, device=dev)
-        engine._check(lib.prt_frame_psf_focus(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
-            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
-            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), -1 if weights is None else _INDEX[weights],
-            lam.ctypes.data, n_w, unit, nx, ny, step[0], step[1], uv0.ctypes.data, axes.ctypes.data, focus.ctypes.data,
-            n_f, 0 if track is None else 1, image.data_ptr(), strehl.data_ptr(), out.data_ptr(), axial.data_ptr(),
-            line.data_ptr(), centres.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        return PSFScan(engine.to_host(image).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(),
-                       axial[:wave.opd.numel()], engine.to_host(line).copy(), engine.to_host(centres).copy(), focus,
-                       wavelengths, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave, track)
+        engine.call("prt_frame_psf_focus", *head, axes, focus, n_f, 0 if track is None else 1, image, strehl, out, axial,
+                    line, centres, device=dev, size=(n_rows, n_groups, n_w, n_f))
+        return PSFScan(engine.host(image), engine.host(strehl), engine.host(out), axial[:wave.opd.numel()],
+                       engine.host(line), engine.host(centres), focus, *made, track)
 
-    def _vector_psf(self, fresnel, wave, rows, surface_id, n_groups, record, weights, generation, rays_per_source,
-                    wavelengths, unit, pixels, step, uv0, f_number):
-        """``psf(fresnel=)`` after the wavefront: the field planes as the library reads them, and the call."""
+    def _vector_psf(self, fresnel, generation, rows, n_groups, head, made):
+        """``psf(fresnel=)`` after the wavefront (``head``, ``made``: see ``psf``): the field planes as the library reads
+        them, and the call."""
         import torch
 
         from . import engine
 
-        dev = rows.device
-        n_rows, n_w, (nx, ny) = rows.shape[1], len(wavelengths), pixels
+        wavelengths, (nx, ny), wave = made.wavelengths, made.pixels, made.wave
+        dev, n_rows = rows.device, rows.shape[1]
+        n_w = len(wavelengths)
         n_states = 1 if fresnel.polarization is not None else 2
         field = fresnel.field
         if tuple(field.shape) != (6, len(self)):
@@ -702,40 +644,23 @@ class DeviceFrame:
         planes = torch.cat([field.real, field.imag]) if field.is_complex() else field
         planes = planes.to(dev, torch.float64).contiguous()
         start = 0
-        if generation == "last":
-            generation = self.last_generation_number() or 0
         if generation is not None:  # (the rows are that generation's slice: the planes are read from the same offset)
-            start = sum(self.rows_per_generation[:int(generation)])
+            start = self._generation_slice(generation)[1]
         field_ld = max(planes.shape[1], 1)
         stokes = torch.empty((n_groups, n_w, 5, nx, ny), dtype=torch.float64, device=dev)
         strehl = torch.empty((n_groups, 4), dtype=torch.float64, device=dev)
         out = torch.empty((n_groups, n_w, n_states, 6), dtype=torch.float64, device=dev)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_vector_psf_workspace_bytes(n_rows, n_groups, n_w, n_states))),
-                           dtype=torch.uint8, device=dev)
-        lam = np.ascontiguousarray(wavelengths, dtype=np.float64)
-        uv0 = np.ascontiguousarray(uv0)
         axes = np.ascontiguousarray(wave._made_of["axes"], dtype=np.float64)
-        opd = wave.opd if wave.opd.numel() else torch.empty(1, dtype=torch.float64, device=dev)
-        pupil = wave.pupil if wave.pupil.numel() else torch.empty(2, dtype=torch.float64, device=dev)
-        engine._check(lib.prt_frame_vector_psf(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
-            float("nan") if surface_id is None else surface_id, float("nan"), float(rays_per_source or 0), n_groups,
-            opd.data_ptr(), pupil.data_ptr(), record.data_ptr(), -1 if weights is None else _INDEX[weights],
-            lam.ctypes.data, n_w, unit, nx, ny, step[0], step[1], uv0.ctypes.data,
-            planes.data_ptr() + 8 * start if n_rows else None, field_ld, int(planes.shape[0]), n_states, axes.ctypes.data,
-            stokes.data_ptr(), strehl.data_ptr(), out.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        return VectorPSF(engine.to_host(stokes).copy(), engine.to_host(strehl).copy(), engine.to_host(out).copy(),
-                         wavelengths, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])), f_number, wave, fresnel)
+        engine.call("prt_frame_vector_psf", *head, planes.data_ptr() + 8 * start if n_rows else None, field_ld,
+                    int(planes.shape[0]), n_states, axes, stokes, strehl, out, device=dev,
+                    size=(n_rows, n_groups, n_w, n_states))
+        return VectorPSF(engine.host(stokes), engine.host(strehl), engine.host(out), *made, fresnel)
 
     def _psf_wavelengths(self, surface_id, generation):
         """The distinct wavelengths of the rows the wavefront selects (sorted), found where the rows are."""
         rows = self.rows
-        if generation == "last":
-            generation = self.last_generation_number() or 0
         if generation is not None:
-            start = sum(self.rows_per_generation[:int(generation)])
-            size = self.rows_per_generation[int(generation)] if int(generation) < len(self.rows_per_generation) else 0
+            _, start, size = self._generation_slice(generation)
             rows = rows[:, start:start + size]
         lam = rows[_INDEX["wavelength"]]
         if surface_id is not None:
@@ -807,19 +732,10 @@ class DeviceFrame:
         n_rows = rows.shape[1]
         otf = torch.empty((n_groups, len(planes), len(theta), len(nu), 2), dtype=torch.float64, device=dev)
         record = torch.empty((n_groups, 6), dtype=torch.float64, device=dev)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_mtf_workspace_bytes(n_rows, n_groups, len(nu), len(theta),
-                                                                               len(planes)))),
-                           dtype=torch.uint8, device=dev)
-        engine._check(lib.prt_frame_mtf(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
-            float("nan") if surface_id is None else surface_id,
-            float("nan") if generation is None else float(generation), float(rays_per_source or 0), n_groups,
-            None if centres is None else centres.data_ptr(), axes.ctypes.data, -1 if weights is None else _INDEX[weights],
-            nu.ctypes.data, len(nu), theta.ctypes.data, len(theta), planes.ctypes.data, len(planes), otf.data_ptr(),
-            record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        pair = engine.to_host(otf)
-        return MTF(pair[..., 0] + 1j * pair[..., 1], engine.to_host(record).copy(), nu, theta, planes)
+        engine.call("prt_frame_mtf", *_row_head(rows), *_row_filter(surface_id, generation, rays_per_source, n_groups),
+                    centres, axes, _weight_column(weights), nu, len(nu), theta, len(theta), planes, len(planes), otf, record,
+                    device=dev, size=(n_rows, n_groups, len(nu), len(theta), len(planes)))
+        return MTF(engine.host_complex(otf), engine.host(record), nu, theta, planes)
 
     # --- geometric encircled / ensquared energy through focus (no counterpart upstream) -------------------------------
     def enclosed_energy(self, surface, radii=None, *, fractions=(0.5, 0.8, 0.9), shape="circle", focus=(0.0,),
@@ -872,21 +788,12 @@ class DeviceFrame:
         energy = torch.empty((n_groups, len(planes), len(edges)), dtype=torch.float64, device=dev)
         radius = torch.empty((n_groups, len(planes), len(phi)), dtype=torch.float64, device=dev)
         record = torch.empty((n_groups, 10), dtype=torch.float64, device=dev)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_energy_workspace_bytes(n_rows, n_groups, len(edges), len(phi),
-                                                                                  len(planes)))),
-                           dtype=torch.uint8, device=dev)
-        engine._check(lib.prt_frame_energy(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows,
-            float("nan") if surface_id is None else surface_id,
-            float("nan") if generation is None else float(generation), float(rays_per_source or 0), n_groups,
-            None if centres is None else centres.data_ptr(), axes.ctypes.data, -1 if weights is None else _INDEX[weights],
-            _ENERGY_SHAPES[shape], 1 if follow_centroid else 0, edges.ctypes.data if len(edges) else None, len(edges),
-            phi.ctypes.data if len(phi) else None, len(phi), planes.ctypes.data, len(planes),
-            energy.data_ptr() if len(edges) else None, radius.data_ptr() if len(phi) else None, record.data_ptr(),
-            work.data_ptr(), engine._stream_ptr(torch, dev)))
-        return EnclosedEnergy(engine.to_host(energy).copy(), engine.to_host(radius).copy(),
-                              engine.to_host(record).copy(), edges, phi, planes, shape)
+        # (radii or fractions that were not asked for are NULL, and so is the output that would hold them: it is empty)
+        engine.call("prt_frame_energy", *_row_head(rows), *_row_filter(surface_id, generation, rays_per_source, n_groups),
+                    centres, axes, _weight_column(weights), _ENERGY_SHAPES[shape], 1 if follow_centroid else 0,
+                    edges if len(edges) else None, len(edges), phi if len(phi) else None, len(phi), planes, len(planes),
+                    energy, radius, record, device=dev, size=(n_rows, n_groups, len(edges), len(phi), len(planes)))
+        return EnclosedEnergy(engine.host(energy), engine.host(radius), engine.host(record), edges, phi, planes, shape)
 
     # --- ray-aberration curves: the frame joined by ray id (examples/lens_design.ipynb cells 12-13) ---------------------
     def launch_index(self):
@@ -909,9 +816,8 @@ class DeviceFrame:
         if rows.shape[1] == 0:
             return index
         id0, n_ids, _ = self._id_range("launch_index", rows)
-        engine._check(engine.library().prt_frame_launch_index(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), rows.shape[1], 1), rows.shape[1],
-            int(self.rows_per_generation[0]), id0, n_ids, index.data_ptr(), engine._stream_ptr(torch, dev)))
+        engine.call("prt_frame_launch_index", *_row_head(rows), int(self.rows_per_generation[0]), id0, n_ids, index,
+                    device=dev)
         return index
 
     def _selection(self, surface, generation):
@@ -990,32 +896,23 @@ class DeviceFrame:
         index = self._launch_index()
         n_rows = rows.shape[1]
         if generation is not None:  # (generation-major: at most one generation's rows are selected)
-            g = int(generation)
-            capacity = self.rows_per_generation[g] if 0 <= g < len(self.rows_per_generation) else 0
+            capacity = self._generation_slice(generation)[2] if int(generation) >= 0 else 0
         elif surface_id is not None:
             capacity = int((rows[_INDEX["surface"]] == surface_id).sum())
         else:
             capacity = n_rows
         entries = terms * (terms + 1) // 2 + 4 * terms + 1
-        lib = engine.library()
         rays = torch.empty((capacity, 7), dtype=torch.float64, device=dev)
         row_numbers = torch.empty(capacity, dtype=torch.int64, device=dev)
         record = torch.empty((n_groups, 16), dtype=torch.float64, device=dev)
         normal = torch.empty((n_groups, entries), dtype=torch.float64, device=dev)
         zone = torch.empty((n_groups, zones, 6), dtype=torch.float64, device=dev)
-        work = torch.empty(int(engine._check(lib.prt_frame_ray_aberrations_workspace_bytes(capacity, n_groups, terms,
-                                                                                           zones))),
-                           dtype=torch.uint8, device=dev)
-        engine._check(lib.prt_frame_ray_aberrations(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, index.data_ptr(),
-            float("nan") if surface_id is None else surface_id,
-            float("nan") if generation is None else float(generation), float(rays_per_source or 0), n_groups,
-            None if centres is None else centres.data_ptr(), mode, axes.ctypes.data, 0 if pupil == "position" else 1,
-            origin.ctypes.data, float(pupil_radius or 0.0), terms, zones, -1 if weights is None else _INDEX[weights],
-            capacity, rays.data_ptr() if capacity else None, row_numbers.data_ptr() if capacity else None,
-            record.data_ptr(), normal.data_ptr(), zone.data_ptr() if zones else None, work.data_ptr(),
-            engine._stream_ptr(torch, dev)))
-        record_host = engine.to_host(record).copy()
+        engine.call("prt_frame_ray_aberrations", *_row_head(rows), index,
+                    *_row_filter(surface_id, generation, rays_per_source, n_groups), centres, mode, axes,
+                    0 if pupil == "position" else 1, origin, float(pupil_radius or 0.0), terms, zones,
+                    _weight_column(weights), capacity, rays, row_numbers, record, normal, zone, device=dev,
+                    size=(capacity, n_groups, terms, zones))
+        record_host = engine.host(record)
         used = int(record_host[:, 4].sum())
         row_numbers = row_numbers[:used]
         # the launch coordinate itself, gathered from the launch rows (p * rho would round twice)
@@ -1030,8 +927,8 @@ class DeviceFrame:
         groups = None
         if rays_per_source:
             groups = torch.floor(rows[_INDEX["id"]][row_numbers] / float(rays_per_source)).to(torch.int64)
-        return RayAberrations(rays[:used], row_numbers, record_host, engine.to_host(normal).copy(),
-                              engine.to_host(zone).copy(), terms, h=torch.stack(h, 1), group=groups)
+        return RayAberrations(rays[:used], row_numbers, record_host, engine.host(normal), engine.host(zone), terms,
+                              h=torch.stack(h, 1), group=groups)
 
     # --- ray paths: which surfaces every ray met, in order (the frame joined by ray id, for every ray at once) -----------
     def paths(self, weights="intensity", rays_per_source=None, n_groups=None, max_paths=4096):
@@ -1076,8 +973,6 @@ class DeviceFrame:
         else:
             n_groups = 1
         n_groups, max_paths = int(n_groups), int(max_paths)
-        lib = engine.library()
-        work_bytes = int(engine._check(lib.prt_frame_paths_workspace_bytes(n_rows, n_ids, n_groups, max_paths)))
         row_node = torch.empty(n_rows, dtype=torch.int32, device=dev)
         ray_node = torch.empty(n_ids, dtype=torch.int32, device=dev)
         ray_last_row = torch.empty(n_ids, dtype=torch.int64, device=dev)
@@ -1085,18 +980,14 @@ class DeviceFrame:
         count = torch.empty((n_groups, max_paths, 3), dtype=torch.int64, device=dev)
         energy = torch.empty((n_groups, max_paths, 2), dtype=torch.float64, device=dev)
         record = np.zeros(4, dtype=np.int64)
-        work = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
-        engine._check(lib.prt_frame_paths(
-            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
-            len(counts), id0, n_ids, float(rays_per_source or 0), n_groups, -1 if weights is None else _INDEX[weights],
-            max_paths, row_node.data_ptr() if n_rows else None, ray_node.data_ptr(), ray_last_row.data_ptr(),
-            node.data_ptr(), count.data_ptr(), energy.data_ptr(), record.ctypes.data, work.data_ptr(),
-            engine._stream_ptr(torch, dev)))
+        engine.call("prt_frame_paths", *_row_head(rows)[:3], counts, len(counts), id0, n_ids, float(rays_per_source or 0),
+                    n_groups, _weight_column(weights), max_paths, row_node, ray_node, ray_last_row, node, count, energy,
+                    record, device=dev, size=(n_rows, n_ids, n_groups, max_paths))
         n_nodes = int(record[0])
-        node_host = engine.to_host(node[:n_nodes]).copy()
-        count_host = engine.to_host(count[:, :n_nodes].contiguous()).copy()
-        energy_host = engine.to_host(energy[:, :n_nodes].contiguous()).copy()
+        node_host = engine.host(node[:n_nodes])
+        count_host = engine.host(count[:, :n_nodes].contiguous())
+        energy_host = engine.host(energy[:, :n_nodes].contiguous())
         return Paths(node_host[:, 0], node_host[:, 1], node_host[:, 2], node_host[:, 3], count_host[:, :, 0],
                      count_host[:, :, 1], count_host[:, :, 2], energy_host[:, :, 0], energy_host[:, :, 1],
                      row_node=row_node, ray_node=ray_node, ray_last_row=ray_last_row, id0=id0,
@@ -1163,26 +1054,19 @@ class DeviceFrame:
         dev = rows.device
         n_rows = rows.shape[1]
         id0, n_ids, _ = self._id_range("fresnel", rows)
-        lib = engine.library()
-        tables, arrays = (), ()  # (arrays: what the table arguments point into, alive over the call)
-        entry, workspace_bytes, planes, counters = lib.prt_frame_fresnel, lib.prt_frame_fresnel_workspace_bytes, 6, 4
+        entry, tables, planes, counters = "prt_frame_fresnel", (), 6, 4
         if is_complex:
-            entry, workspace_bytes, planes, counters = (lib.prt_frame_fresnel_coated,
-                                                        lib.prt_frame_fresnel_coated_workspace_bytes, 12, 6)
-            tables, arrays = _coating_tables(stacks, surface_coating, rows if n_rows else None)
-        work = torch.empty(int(engine._check(workspace_bytes(n_rows, n_ids))), dtype=torch.uint8, device=dev)
+            entry, planes, counters = "prt_frame_fresnel_coated", 12, 6
+            tables = _coating_tables(stacks, surface_coating, rows if n_rows else None)
         transmittance = torch.empty(n_rows, dtype=torch.float64, device=dev)
         field = torch.empty((planes, n_rows), dtype=torch.float64, device=dev) if fields else None
         record = np.zeros(counters, dtype=np.int64)
         counts = np.ascontiguousarray(self.rows_per_generation, dtype=np.int64)
         lossless_ids = np.ascontiguousarray(ids_lossless, dtype=np.int64)
         parts = None if v is None else np.ascontiguousarray(np.concatenate([v.real, v.imag]) if is_complex else v)
-        engine._check(entry(
-            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), counts.ctypes.data,
-            len(counts), id0, n_ids, None if parts is None else parts.ctypes.data,
-            lossless_ids.ctypes.data if len(lossless_ids) else None, len(lossless_ids), *tables,
-            transmittance.data_ptr() if n_rows else None, field.data_ptr() if field is not None and n_rows else None,
-            record.ctypes.data, work.data_ptr(), engine._stream_ptr(torch, dev)))
+        engine.call(entry, *_row_head(rows)[:3], counts, len(counts), id0, n_ids, parts,
+                    lossless_ids if len(lossless_ids) else None, len(lossless_ids), *tables, transmittance, field, record,
+                    device=dev, size=(n_rows, n_ids))
         if not is_complex:
             out = Fresnel(self, transmittance, field, record, polarization=v, lossless=tuple(ids_lossless))
         else:
@@ -1288,19 +1172,19 @@ class DeviceFrame:
         if name == "launch" and wavefront is not None and not n_rows:
             # (the entry point reads opl == NULL as "no wavefront": there is no path to point at)
             raise ValueError("sensitivity: wavefront= with a SourceMotion, a WavelengthChange or slopes=True needs a frame with rows")
-        size, size_extra, entry, order = _SENS_FORMS[name]
+        size_extra, entry, order = _SENS_FORMS[name]
         empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
         jacobian, sums = empty(K, 3, n_selected), empty(n_groups, 6 + 4 * K + K * (K + 1) // 2)
         directions = empty(K, 3, n_selected) if name == "launch" else None
         record = np.zeros(4, dtype=np.int64)
         pieces = dict.fromkeys(_SENS_WAVE_IN + _SENS_WAVE_OUT)  # (the launch form without wavefront= passes these as NULL)
-        pieces.update(_sens_host_arrays(motions, name, snapshot.materials), n_terms=0, device=dev.index or 0, rows=rows,
-                      ld=max(rows.stride(0), n_rows, 1), counts=counts, n_generations=len(counts), id0=id0, n_ids=n_ids,
-                      prims=prims, n_prims=len(prims), K=K,
+        device, _, ld, _ = _row_head(rows)
+        pieces.update(_sens_host_arrays(motions, name, snapshot.materials), n_terms=0,
+                      device=device, rows=rows, ld=ld, counts=counts, n_generations=len(counts),
+                      id0=id0, n_ids=n_ids, prims=prims, n_prims=len(prims), K=K,
                       row_slot=row_slot, selected=selected, n_selected=n_selected, group_first=group_first,
-                      n_groups=n_groups, weight_column=-1 if weights is None else _INDEX[weights], pivots=pivots,
-                      jacobian=jacobian, sums=sums, slopes=directions, record=record,
-                      stream=engine._stream_ptr(torch, dev))
+                      n_groups=n_groups, weight_column=_weight_column(weights), pivots=pivots,
+                      jacobian=jacobian, sums=sums, slopes=directions, record=record)
         wave = None
         if wavefront is not None:
             J = wavefront.terms
@@ -1313,18 +1197,14 @@ class DeviceFrame:
                                                                        wavefront.pivot, wavefront.pupil_radius]),
                                                       dtype=np.float64),
                           axes=np.ascontiguousarray(made["axes"], dtype=np.float64))
-        lib = engine.library()
-        pieces["work"] = torch.empty(int(engine._check(getattr(lib, size)(
-            n_ids, len(prims), K, n_groups, int(np.diff(group_first).max()), *(pieces[q] for q in size_extra)))),
-            dtype=torch.uint8, device=dev)
-        engine._check(getattr(lib, entry)(*(_sens_pointer(pieces[q]) for q in order)))
+        engine.call(entry, *(pieces[q] for q in order), device=dev, size=(
+            n_ids, len(prims), K, n_groups, int(np.diff(group_first).max()), *(pieces[q] for q in size_extra)))
         if wave is not None:
-            wave.update(sums=engine.to_host(wave["sums"]).copy(), wavefront=wavefront)
+            wave.update(sums=engine.host(wave["sums"]), wavefront=wavefront)
         launch = None
         if name in ("wavefront", "launch"):
             launch = dict(slopes=directions, rows=rows, weights=weights, group_first=group_first, written=self.written)
-        return Sensitivity(jacobian, selected, engine.to_host(sums).copy(), pivots, centred, record, motions, wave=wave,
-                           launch=launch)
+        return Sensitivity(jacobian, selected, engine.host(sums), pivots, centred, record, motions, wave=wave, launch=launch)
 
     def axis_intercept(self):
         """x where each ray's line crosses the optical (x) axis in the xy plane, from the segment's start point as the
@@ -2977,6 +2857,14 @@ class Sensitivity:
             out[:, k, :] = solve_normal_equations(packed, J)[0]
         return out
 
+    def _selected_rows(self):
+        """The nine leading arguments of the passes over the selected rows (``mtf_gradient``, ``psf_gradient``,
+        ``tolerance``): the frame's rows, the selection in its order, where every group begins, the weights' column."""
+        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        first = np.ascontiguousarray(first, dtype=np.int64)
+        return _SelectedRows(*_row_head(rows), self._selected, int(self._selected.shape[0]), first, len(first) - 1,
+                             _weight_column(weights))
+
     def _need_slopes(self, what):
         if self.slopes is None:
             raise ValueError(f"{what}: this Sensitivity has no slopes (they come with sensitivity(slopes=True), or with a "
@@ -3006,29 +2894,18 @@ class Sensitivity:
             raise ValueError('reference: "fixed" or "centroid"')
         nu, theta, planes = _mtf_sampling(frequencies, azimuths, focus)
         axes = pupil_axes(axis, basis)
-        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
-        dev = rows.device
-        n_groups, K, n_rows, n_selected = len(first) - 1, self.n_parameters, rows.shape[1], int(self._selected.shape[0])
+        head = self._selected_rows()
+        dev, n_selected, n_groups, K = head.rows.device, head.n_selected, head.n_groups, self.n_parameters
         centres = None if centre is None else _group_points(centre, n_groups, dev, "centre: None, a point")
         shape = (len(planes), len(theta), len(nu))
         otf = torch.empty((n_groups,) + shape + (2,), dtype=torch.float64, device=dev)
         dotf = torch.empty((n_groups, K + 1) + shape + (2,), dtype=torch.float64, device=dev)
         record = torch.empty((n_groups, 7 + 3 * K), dtype=torch.float64, device=dev)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_mtf_gradient_workspace_bytes(n_selected, n_groups, K, len(nu),
-                                                                                        len(theta), len(planes)))),
-                           dtype=torch.uint8, device=dev)
-        jacobian, slopes = self.jacobian.contiguous(), self.slopes.contiguous()
-        engine._check(lib.prt_frame_mtf_gradient(
-            dev.index or 0, rows.data_ptr() if n_rows else None, max(rows.stride(0), n_rows, 1), n_rows,
-            self._selected.data_ptr() if n_selected else None, n_selected, first.ctypes.data, n_groups,
-            -1 if weights is None else _INDEX[weights], jacobian.data_ptr() if n_selected else None,
-            slopes.data_ptr() if n_selected else None, K, None if centres is None else centres.data_ptr(),
-            axes.ctypes.data, nu.ctypes.data, len(nu), theta.ctypes.data, len(theta), planes.ctypes.data, len(planes),
-            otf.data_ptr(), dotf.data_ptr(), record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        pair, dpair = engine.to_host(otf), engine.to_host(dotf)
-        return MTFGradient(pair[..., 0] + 1j * pair[..., 1], dpair[..., 0] + 1j * dpair[..., 1],
-                           engine.to_host(record).copy(), nu, theta, planes, axes, self.parameters, reference)
+        engine.call("prt_frame_mtf_gradient", *head, self.jacobian.contiguous(), self.slopes.contiguous(), K, centres, axes,
+                    nu, len(nu), theta, len(theta), planes, len(planes), otf, dotf, record, device=dev,
+                    size=(n_selected, n_groups, K, len(nu), len(theta), len(planes)))
+        return MTFGradient(engine.host_complex(otf), engine.host_complex(dotf), engine.host(record), nu, theta, planes, axes,
+                           self.parameters, reference)
 
     def psf_gradient(self, *, world_unit_um, pixels=64, pixel_size=None, centre=(0.0, 0.0), follow="ray"):
         """d(PSF)/d(parameter) and d(Strehl)/d(parameter) of the diffraction image of the selected rows, per group, from
@@ -3058,9 +2935,9 @@ class Sensitivity:
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         nx, ny = _pixel_counts(pixels)
         step, uv0 = _pixel_grid(pixel_size, centre)
-        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        head = self._selected_rows()
+        rows, n_selected, n_groups, K = head.rows, head.n_selected, head.n_groups, self.n_parameters
         dev = rows.device
-        n_groups, K, n_rows, n_selected = len(first) - 1, self.n_parameters, rows.shape[1], int(self._selected.shape[0])
         wave = self.wavefront
         written = self._launch.get("written")
         if written is not None and _INDEX["wavelength"] not in written:
@@ -3077,26 +2954,16 @@ class Sensitivity:
         amplitude, damplitude = empty(n_groups, n_w, nx, ny, 2), empty(n_groups, K, n_w, nx, ny, 2)
         image, dimage = empty(n_groups, n_w, nx, ny), empty(n_groups, K, n_w, nx, ny)
         strehl, record = empty(n_groups, 1 + K), empty(n_groups, n_w, 5)
-        lib = engine.library()
-        work = torch.empty(int(engine._check(lib.prt_frame_psf_gradient_workspace_bytes(n_selected, n_groups, K, n_w))),
-                           dtype=torch.uint8, device=dev)
         lam = np.ascontiguousarray(values, dtype=np.float64)
         uv0 = np.ascontiguousarray(uv0)
-        first = np.ascontiguousarray(first, dtype=np.int64)
         dphase = (self.dopd if follow == "ray" else self.dfield).contiguous()
         dpoint = self.dpupil.contiguous() if follow == "ray" else None
-        opd, pupil = self.opd.contiguous(), self.pupil.contiguous()
-        engine._check(lib.prt_frame_psf_gradient(
-            dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, self._selected.data_ptr(), n_selected,
-            first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], opd.data_ptr(), pupil.data_ptr(),
-            groups.ctypes.data, dphase.data_ptr(), None if dpoint is None else dpoint.data_ptr(), K, lam.ctypes.data, n_w,
-            unit, nx, ny, step[0], step[1], uv0.ctypes.data, amplitude.data_ptr(), damplitude.data_ptr(), image.data_ptr(),
-            dimage.data_ptr(), strehl.data_ptr(), record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        pair, dpair = engine.to_host(amplitude), engine.to_host(damplitude)
-        return PSFGradient(pair[..., 0] + 1j * pair[..., 1], dpair[..., 0] + 1j * dpair[..., 1],
-                           engine.to_host(image).copy(), engine.to_host(dimage).copy(), engine.to_host(strehl).copy(),
-                           engine.to_host(record).copy(), values, unit, (nx, ny), step, (float(uv0[0]), float(uv0[1])),
-                           f_number, wave, self.parameters, follow)
+        engine.call("prt_frame_psf_gradient", *head, self.opd.contiguous(), self.pupil.contiguous(), groups, dphase, dpoint,
+                    K, lam, n_w, unit, nx, ny, step[0], step[1], uv0, amplitude, damplitude, image, dimage, strehl, record,
+                    device=dev, size=(n_selected, n_groups, K, n_w))
+        return PSFGradient(engine.host_complex(amplitude), engine.host_complex(damplitude), engine.host(image),
+                           engine.host(dimage), engine.host(strehl), engine.host(record), values, unit, (nx, ny), step,
+                           (float(uv0[0]), float(uv0[1])), f_number, wave, self.parameters, follow)
 
     def rms_radius_at(self, parameters):
         """(groups, M): the RMS spot radius with the parameters changed by ``parameters`` (groups, M, K) under the linear
@@ -3162,9 +3029,10 @@ class Sensitivity:
                 raise ValueError(f'compensators: indices of parameters (0..{K - 1}), "tilt" or "focus" (got {c!r})')
         if len(set(compensators)) != len(compensators):
             raise ValueError("compensators: each one once")
-        rows, weights, first = (self._launch[k] for k in ("rows", "weights", "group_first"))
+        selected_rows = self._selected_rows()
+        rows, n_selected, first, n_groups = (selected_rows.rows, selected_rows.n_selected, selected_rows.first,
+                                             selected_rows.n_groups)
         dev = rows.device
-        n_groups, n_rows, n_selected = len(first) - 1, rows.shape[1], int(self._selected.shape[0])
         wave = self.wavefront
         written = self._launch.get("written")
         if written is not None and _INDEX["wavelength"] not in written:
@@ -3201,21 +3069,13 @@ class Sensitivity:
                 at += 1
             else:
                 slots.append(c)
-        lib = engine.library()
         lam = np.ascontiguousarray(values, dtype=np.float64)
         n_w = len(lam)
-        first = np.ascontiguousarray(first, dtype=np.int64)
-        opd = self.opd.contiguous()
         empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
-        head = (dev.index or 0, rows.data_ptr(), max(rows.stride(0), n_rows, 1), n_rows, self._selected.data_ptr(),
-                n_selected, first.ctypes.data, n_groups, -1 if weights is None else _INDEX[weights], opd.data_ptr(),
-                columns.data_ptr(), C, lam.ctypes.data, n_w, unit)
+        head = (*selected_rows, self.opd.contiguous(), columns, C, lam, n_w, unit)
         moments = empty(n_groups, 3 + (C + 2) * (C + 3) // 2)
-        work = torch.empty(int(engine._check(lib.prt_frame_tolerance_moments_workspace_bytes(n_selected, n_groups, C, n_w))),
-                           dtype=torch.uint8, device=dev)
-        engine._check(lib.prt_frame_tolerance_moments(*head, moments.data_ptr(), work.data_ptr(),
-                                                      engine._stream_ptr(torch, dev)))
-        moments = engine.to_host(moments).copy()
+        engine.call("prt_frame_tolerance_moments", *head, moments, device=dev, size=(n_selected, n_groups, C, n_w))
+        moments = engine.host(moments)
         # per group: the covariance, the compensators of every trial (the nominal one last), the RMS of its OPD
         LD = np.longdouble
         M = len(drawn) + 1
@@ -3234,18 +3094,15 @@ class Sensitivity:
             q[g] = qg.astype(float)
         handed = torch.as_tensor(np.ascontiguousarray(q), device=dev)
         strehl, amplitude, record = empty(n_groups, M), empty(n_groups, n_w, M, 2), empty(n_groups, n_w, 5)
-        work = torch.empty(int(engine._check(lib.prt_frame_tolerance_workspace_bytes(n_selected, n_groups, C, n_w, M))),
-                           dtype=torch.uint8, device=dev)
-        engine._check(lib.prt_frame_tolerance(*head, handed.data_ptr(), M, strehl.data_ptr(), amplitude.data_ptr(),
-                                              record.data_ptr(), work.data_ptr(), engine._stream_ptr(torch, dev)))
-        pair = engine.to_host(amplitude)
+        engine.call("prt_frame_tolerance", *head, handed, M, strehl, amplitude, record, device=dev,
+                    size=(n_selected, n_groups, C, n_w, M))
         compensation = np.zeros((n_groups, M, len(slots)))
         for j, slot in enumerate(slots):  # (a real parameter: what was added to the drawn value)
             compensation[:, :, j] = q[:, :, slot] - (plain[:, slot] if slot < K else 0.0)
         rms_radius = np.full((n_groups, M), np.nan) if "focus" in pseudo else self.rms_radius_at(q[:, :, :K])
-        return ToleranceRun(plain[:, :K], compensators, compensation, rms_opd, engine.to_host(strehl).copy(),
-                            pair[..., 0] + 1j * pair[..., 1], rms_radius, engine.to_host(record).copy(), moments, values,
-                            unit, self.parameters, follow)
+        return ToleranceRun(plain[:, :K], compensators, compensation, rms_opd, engine.host(strehl),
+                            engine.host_complex(amplitude), rms_radius, engine.host(record), moments, values, unit,
+                            self.parameters, follow)
 
     def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
         """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the
@@ -3391,8 +3248,9 @@ class Sensitivity:
 
 
 # --- what DeviceFrame.sensitivity() is made of ---------------------------------------------------------------------------
-# The arguments of the four entry points, by name and in the order of include/prt.h: each form is its size function and
-# what that takes after (n_ids, n_surfaces, K, n_groups, max_group_rows), its entry point, and the pieces of its call.
+# The arguments of the four entry points, by name and in the order of include/prt.h: each form is what its size function
+# takes after (n_ids, n_surfaces, K, n_groups, max_group_rows), its entry point, and the pieces of its call, which
+# engine.call ends with the workspace and the stream.
 _SENS_COMMON = ("device", "rows", "ld", "counts", "n_generations", "id0", "n_ids", "prims", "n_prims", "twists",
               "parameter_ids", "parameter_first")
 _SENS_DESIGN = ("linear", "index_rates", "index_ids", "index_first")
@@ -3400,27 +3258,42 @@ _SENS_SELECTION = ("K", "row_slot", "selected", "n_selected", "group_first", "n_
 _SENS_WAVE_IN = ("opl", "groups", "axes", "n_terms")
 _SENS_LAUNCH_IN = ("ranges", "flags", "colour_rates", "materials", "n_materials")
 _SENS_WAVE_OUT = ("dfield", "dopd", "dpupil", "opd", "pupil", "opd_sums")
-_SENS_LAST = ("record", "work", "stream")
 _SENS_FORMS = {
-    "rigid": ("prt_frame_sensitivity_workspace_bytes", (), "prt_frame_sensitivity",
-              _SENS_COMMON + _SENS_SELECTION + ("jacobian", "sums") + _SENS_LAST),
-    "design": ("prt_frame_design_sensitivity_workspace_bytes", (), "prt_frame_design_sensitivity",
-               _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + ("jacobian", "sums") + _SENS_LAST),
-    "wavefront": ("prt_frame_opd_sensitivity_workspace_bytes", ("n_terms",), "prt_frame_opd_sensitivity",
+    "rigid": ((), "prt_frame_sensitivity", _SENS_COMMON + _SENS_SELECTION + ("jacobian", "sums", "record")),
+    "design": ((), "prt_frame_design_sensitivity",
+               _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + ("jacobian", "sums", "record")),
+    "wavefront": (("n_terms",), "prt_frame_opd_sensitivity",
                   _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + _SENS_WAVE_IN + ("jacobian", "sums") + _SENS_WAVE_OUT
-                  + _SENS_LAST),
-    "launch": ("prt_frame_launch_sensitivity_workspace_bytes", ("n_terms",), "prt_frame_launch_sensitivity",
+                  + ("record",)),
+    "launch": (("n_terms",), "prt_frame_launch_sensitivity",
                _SENS_COMMON + _SENS_DESIGN + _SENS_SELECTION + _SENS_WAVE_IN + _SENS_LAUNCH_IN
-               + ("jacobian", "sums", "slopes") + _SENS_WAVE_OUT + _SENS_LAST),
+               + ("jacobian", "sums", "slopes") + _SENS_WAVE_OUT + ("record",)),
 }
 
 
-def _sens_pointer(piece):
-    """What the library is given for a piece of a call: the address of a device tensor (NULL for one without elements)
-    or of a host array; a number as it is."""
-    if hasattr(piece, "data_ptr"):
-        return piece.data_ptr() if piece.numel() else None
-    return piece.ctypes.data if isinstance(piece, np.ndarray) else piece
+# --- how a pass reaches the library: engine.call, after these leading arguments -------------------
+def _row_head(rows):
+    """``(device index, rows, ld, n_rows)`` of a (15, n) block, contiguous along the row axis: what every pass over rows
+    begins with.  A contiguous block has the stride n (1 when it is empty), a view of a larger one the larger stride."""
+    n_rows = rows.shape[1]
+    return rows.device.index or 0, rows, max(rows.stride(0), n_rows, 1), n_rows
+
+
+def _row_filter(surface, generation, rays_per_source, n_groups):
+    """``(surface, generation, rays_per_source, n_groups)`` as the passes read the selection: NaN for a surface or a
+    generation that does not filter, 0 rays a source for one group."""
+    surface, generation = [float("nan") if value is None else float(value) for value in (surface, generation)]
+    return surface, generation, float(rays_per_source or 0), n_groups
+
+
+def _weight_column(weights):
+    """The column the weights are read from, -1 for ones."""
+    return -1 if weights is None else _INDEX[weights]
+
+
+# (what psf() tells the results of its three sums of the grid, and the leading arguments of Sensitivity._selected_rows)
+_HuygensGrid = namedtuple("_HuygensGrid", "wavelengths unit pixels step centre f_number wave")
+_SelectedRows = namedtuple("_SelectedRows", "device rows ld n_rows selected n_selected first n_groups weight_column")
 
 
 def _sens_parameters(parameters, rays_per_source, slopes):
@@ -3591,8 +3464,8 @@ def _coating_stacks(coatings, ids_lossless):
 
 
 def _coating_tables(stacks, surface_coating, rows):
-    """The table arguments of ``prt_frame_fresnel_coated``, in its order, and the arrays they point into: the
-    materials on the distinct wavelengths of the frame (as DeviceScene.ensure_tables does for table glasses)."""
+    """The table arguments of ``prt_frame_fresnel_coated``, in its order: the materials on the distinct wavelengths of
+    the frame (as DeviceScene.ensure_tables does for table glasses)."""
     import torch
 
     from . import engine
@@ -3614,10 +3487,8 @@ def _coating_tables(stacks, surface_coating, rows):
     has_substrate = np.array([c.substrate is not None for c in stacks] or [0], dtype=np.int32)
     coated_ids = np.array(sorted(surface_coating) or [0], dtype=np.int64)
     coating_of = np.array([surface_coating[sid] for sid in sorted(surface_coating)] or [0], dtype=np.int32)
-    arguments = (coated_ids.ctypes.data, coating_of.ctypes.data, len(surface_coating), len(stacks), layer_counts.ctypes.data,
-                 has_substrate.ctypes.data, thickness.ctypes.data, wavelengths.ctypes.data if len(wavelengths) else None,
-                 len(wavelengths), table.ctypes.data)
-    return arguments, (coated_ids, coating_of, layer_counts, has_substrate, thickness, wavelengths, table)
+    return (coated_ids, coating_of, len(surface_coating), len(stacks), layer_counts, has_substrate, thickness,
+            wavelengths if len(wavelengths) else None, len(wavelengths), table)
 
 
 def _lossless_ids(items):
