@@ -102,10 +102,10 @@ HOST_RULES = {
 }
 
 
-def header_constants():
-    """The static const ints of the two headers, by name."""
+def header_constants(names=None):
+    """The static const ints of the headers ``names`` (default: the two of HOST_RULES), by name."""
     found = {}
-    for name in HOST_RULES:
+    for name in (HOST_RULES if names is None else names):
         text = open(os.path.join(ROOT, "pyrayt_amd", "csrc", name)).read()
         for key, value in re.findall(r"static const (?:int|size_t) (k\w+) = ([^;]+);", text):
             try:
