@@ -8,10 +8,10 @@
 //                          rays left out (integer atomics on order-preserving images)
 //   k_aberration_count     per wave: the rays kept per (group, zone) bucket and in all; the chief ray's row (the
 //                          smallest row among the rays that attain the smallest |h|^2: an integer atomic)
-//   k_aberration_positions one workgroup: the waves' totals scanned into each wave's place in the row-order outputs
-//   (k_mtf_offsets, k_mtf_starts of prt_mtf.hpp: the waves' counts scanned per bucket; bucket and chunk starts)
+//   (k_sort_positions, k_sort_offsets of prt_sort.hpp: the waves' totals scanned into each wave's place in the row-order
+//   outputs, the waves' counts scanned per bucket; k_mtf_starts of prt_mtf.hpp: bucket and chunk starts)
 //   k_aberration_scatter   the stable counting sort: every wave writes its rays, in row order, at its offsets
-//   k_aberration_centre    per (bucket, chunk of 4096 rays): sum w and sum w Q in a fixed tree
+//   (k_mtf_centre<AbRaw> of prt_mtf.hpp: per (bucket, chunk of 4096 rays) sum w and sum w Q in a fixed tree)
 //   k_aberration_record    per group: the chunks folded in order into the centroid (or the given point, or the chief
 //                          ray's Q), rho, the counts
 //   k_aberration_stage     per (bucket, chunk): each ray's (p, eps, s, la) into ray_out / row_out at its row-order
@@ -26,6 +26,7 @@
 
 enum { AB_RECORD = 16, AB_RAY = 7, AB_ZONE = 6, AB_MAX_ZONES = 1024, AB_SUMS = 12 };
 static const int kAbBlock = 256;                  // threads of a chunk workgroup = rays of its LDS tile
+static_assert(kAbBlock == kMtfBlock, "k_mtf_centre<AbRaw> sums a chunk of this pass's rays");
 static const size_t kAbCountBytes = 64u << 20;    // cap on the sort's (wave, bucket) counts
 static const size_t kAbSlabBytes = 256u << 20;    // cap on the chunks' partial sums
 static const int kAbEntriesPerThread = (WF_MAX_TERMS * (WF_MAX_TERMS + 1) / 2 + 4 * WF_MAX_TERMS + 1 + kAbBlock - 1) / kAbBlock;
@@ -172,25 +173,19 @@ __global__ void __launch_bounds__(PRT_BLOCK)
 k_aberration_extent(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const int64_t* __restrict__ launch,
                     AbSelect a, int64_t per_wave, unsigned long long* __restrict__ extent,
                     unsigned long long* __restrict__ hmin, unsigned long long* __restrict__ missed) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
-  for (int64_t base = first; base < last; base += 64) {
-    const int64_t j = base + lane;
+  const SortRun run = sort_run(per_wave, n_rows);
+  for (int64_t base = run.first; base < run.last; base += 64) {
+    const int64_t j = base + run.lane;
     AbRaw r;
     bool used;
-    const int group = ab_select(rows, ld, n_rows, j, last, launch, a, r, used);
+    const int group = ab_select(rows, ld, n_rows, j, run.last, launch, a, r, used);
     if (group >= 0 && !used) atomicAdd(missed + group, 1ull);  // (integer: the same total in any order)
     const int kept = used ? group : -1;
     // (a non-negative double's bits order as the double does)
     const double hh = used ? r.h1 * r.h1 + r.h2 * r.h2 : 0.0;
     const unsigned long long e_bits = used ? (unsigned long long)__double_as_longlong(sqrt(hh)) : 0ull;
     const unsigned long long m_bits = used ? (unsigned long long)__double_as_longlong(hh) : ~0ull;
-    unsigned long long pending = __ballot(kept >= 0);
-    while (pending) {  // one turn per group present in the slice: almost always exactly one
-      const int leader = __ffsll((long long)pending) - 1;
-      const int g = __shfl(kept, leader);
+    sort_turns(kept, [&](int g, unsigned long long) {
       const bool take = kept == g;
       unsigned long long e = take ? e_bits : 0ull, m = take ? m_bits : ~0ull;
 #pragma unroll
@@ -199,12 +194,11 @@ k_aberration_extent(const double* __restrict__ rows, int64_t ld, int64_t n_rows,
         e = eo > e ? eo : e;
         m = mo < m ? mo : m;
       }
-      if (lane == 0) {
+      if (run.lane == 0) {
         atomicMax(extent + g, e);
         atomicMin(hmin + g, m);
       }
-      pending &= ~__ballot(take);
-    }
+    });
   }
 }
 
@@ -213,31 +207,24 @@ k_aberration_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, 
                    AbSelect a, int64_t per_wave, const unsigned long long* __restrict__ extent,
                    const unsigned long long* __restrict__ hmin, int n_buckets, int64_t* __restrict__ counts,
                    int64_t* __restrict__ wave_total, long long* __restrict__ chief) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const SortRun run = sort_run(per_wave, n_rows);
   const int nz = a.n_zones < 1 ? 1 : a.n_zones;
-  int64_t* const mine = counts + wave * n_buckets;  // (only this wave writes here)
+  int64_t* const mine = counts + run.wave * n_buckets;  // (only this wave writes here)
   int64_t total = 0;
-  for (int64_t base = first; base < last; base += 64) {
-    const int64_t j = base + lane;
+  for (int64_t base = run.first; base < run.last; base += 64) {
+    const int64_t j = base + run.lane;
     AbRaw r;
     bool used;
-    const int group = ab_select(rows, ld, n_rows, j, last, launch, a, r, used);
+    const int group = ab_select(rows, ld, n_rows, j, run.last, launch, a, r, used);
     int bucket = -1;
     long long candidate = 0x7fffffffffffffffll;
     if (used) {
       bucket = group * nz + ab_zone(r.h1, r.h2, ab_rho(a.pupil_radius, extent[group]), a.n_zones);
       if ((unsigned long long)__double_as_longlong(r.h1 * r.h1 + r.h2 * r.h2) == hmin[group]) candidate = j;
     }
-    unsigned long long pending = __ballot(bucket >= 0);
-    total += __popcll(pending);
+    total += __popcll(__ballot(bucket >= 0));
     const bool candidates = __ballot(candidate != 0x7fffffffffffffffll) != 0ull;  // (wave-uniform; rarely true)
-    while (pending) {  // one turn per bucket present in the slice
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
+    sort_turns(bucket, [&](int b, unsigned long long take) {
       long long c = bucket == b ? candidate : 0x7fffffffffffffffll;
       if (candidates) {
 #pragma unroll
@@ -246,22 +233,13 @@ k_aberration_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, 
           c = o < c ? o : c;
         }
       }
-      if (lane == 0) {
+      if (run.lane == 0) {
         mine[b] += __popcll(take);
         if (candidates && c != 0x7fffffffffffffffll) atomicMin(chief + b / nz, c);  // (integer: the same in any order)
       }
-      pending &= ~take;
-    }
+    });
   }
-  if (lane == 0) wave_total[wave] = total;
-}
-
-// one workgroup: wave_total[w] -> the number of rays used in the waves before w (in place)
-__global__ void __launch_bounds__(kMtfScanBlock)
-k_aberration_positions(int waves, int64_t* __restrict__ wave_total) {
-  __shared__ int64_t scan[kMtfScanBlock];
-  mtf_scan(
-      waves, [&](int64_t w) { return wave_total[w]; }, [&](int64_t w, int64_t before) { wave_total[w] = before; }, scan);
+  if (run.lane == 0) wave_total[run.wave] = total;
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
@@ -269,10 +247,7 @@ k_aberration_scatter(const double* __restrict__ rows, int64_t ld, int64_t n_rows
                      AbSelect a, int64_t per_wave, const unsigned long long* __restrict__ extent, int n_buckets,
                      int64_t* __restrict__ offsets, const int64_t* __restrict__ wave_pos,
                      const int64_t* __restrict__ bucket_start, int64_t capacity, AbRaw* __restrict__ sorted) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   if (first >= last) return;
   const int nz = a.n_zones < 1 ? 1 : a.n_zones;
   int64_t* const mine = offsets + wave * n_buckets;  // (only this wave reads and writes here)
@@ -284,49 +259,13 @@ k_aberration_scatter(const double* __restrict__ rows, int64_t ld, int64_t n_rows
     const int group = ab_select(rows, ld, n_rows, j, last, launch, a, r, used);
     int bucket = -1;
     if (used) bucket = group * nz + ab_zone(r.h1, r.h2, ab_rho(a.pupil_radius, extent[group]), a.n_zones);
-    unsigned long long pending = __ballot(bucket >= 0);
-    r.pos = pos + __popcll(pending & ((1ull << lane) - 1ull));
-    pos += __popcll(pending);
-    while (pending) {
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      int64_t at = lane == 0 ? mine[b] : 0;
-      at = __shfl(at, 0);
-      const int64_t slot = bucket_start[b] + at + __popcll(take & ((1ull << lane) - 1ull));
-      if (bucket == b && slot < capacity) sorted[slot] = r;  // (the host has checked the total against the capacity)
-      if (lane == 0) mine[b] = at + __popcll(take);
-      pending &= ~take;
-    }
+    const unsigned long long kept = __ballot(bucket >= 0);
+    r.pos = pos + __popcll(kept & ((1ull << lane) - 1ull));
+    pos += __popcll(kept);
+    sort_place(lane, bucket, mine, bucket_start, [&](int64_t slot) {
+      if (slot < capacity) sorted[slot] = r;  // (the host has checked the total against the capacity)
+    });
   }
-}
-
-// per (bucket, chunk): [0] sum w  [1..3] sum w Q -- each thread over its strided rays in order, then a fixed tree
-__global__ void __launch_bounds__(kAbBlock)
-k_aberration_centre(int n_buckets, const int64_t* __restrict__ chunk_start, const int64_t* __restrict__ bucket_total,
-                    const int64_t* __restrict__ bucket_start, const AbRaw* __restrict__ sorted,
-                    double* __restrict__ slab) {
-  __shared__ double red[4][kAbBlock];
-  const int t = threadIdx.x;
-  const int64_t chunk = blockIdx.x;
-  const int b = mtf_owner(chunk_start, n_buckets, chunk);
-  if (b < 0) return;
-  int64_t lo, hi;
-  mtf_chunk(chunk_start, bucket_total, bucket_start, b, chunk, lo, hi);
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int64_t r = lo + t; r < hi; r += kAbBlock) {
-    const double w = sorted[r].w;
-    s[0] += w;
-    for (int k = 0; k < 3; ++k) s[1 + k] = fma(w, sorted[r].q[k], s[1 + k]);
-  }
-  for (int k = 0; k < 4; ++k) red[k][t] = s[k];
-  for (int half = kAbBlock / 2; half > 0; half >>= 1) {
-    __syncthreads();
-    if (t < half)
-      for (int k = 0; k < 4; ++k) red[k][t] += red[k][t + half];
-  }
-  __syncthreads();
-  if (t < 4) slab[chunk * 4 + t] = red[t][0];
 }
 
 // per group: C_g (reference_mode 0: the chunks folded in order; 1: the given point; 2: the chief ray's Q), rho, counts
@@ -407,14 +346,7 @@ k_aberration_stage(int n_buckets, int nz, const int64_t* __restrict__ chunk_star
   }
 #pragma unroll
   for (int k = 0; k < AB_SUMS; ++k) red[k][t] = s[k];
-  for (int half = kAbBlock / 2; half > 0; half >>= 1) {
-    __syncthreads();
-    if (t < half) {
-#pragma unroll
-      for (int k = 0; k < AB_SUMS; ++k) red[k][t] += red[k][t + half];
-    }
-  }
-  __syncthreads();
+  sort_tree(red, t);
   if (t < AB_SUMS) slab[chunk * AB_SUMS + t] = red[t][0];
 }
 
@@ -580,14 +512,12 @@ extern "C" int prt_frame_ray_aberrations(int device, const double* rows, int64_t
     return fail(PRT_ERR_ARG, "reference_mode: 0 centroid, 1 the given points, 2 chief ray");
   if (!(pupil_radius == pupil_radius) || pupil_radius < 0 || !(pupil_radius < PRT_INF))
     return fail(PRT_ERR_ARG, "pupil_radius: > 0, or 0 for the largest extent");
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(axes[k])) return fail(PRT_ERR_ARG, "axes: finite");
   AbSelect a;
+  if (const int rc = mtf_axes(axes, a.ax)) return rc;
   a.surface = surface; a.generation = generation; a.rays_per_source = rays_per_source; a.pupil_radius = pupil_radius;
   for (int k = 0; k < 3; ++k) {
     a.origin[k] = launch_origin ? launch_origin[k] : 0.0;
     if (!std::isfinite(a.origin[k])) return fail(PRT_ERR_ARG, "launch_origin: finite");
-    a.ax.a[k] = axes[k]; a.ax.e1[k] = axes[3 + k]; a.ax.e2[k] = axes[6 + k];
   }
   a.n_groups = n_groups; a.n_zones = n_zones; a.weight_column = weight_column; a.pupil_mode = pupil_mode;
   const int nz = n_zones < 1 ? 1 : n_zones;
@@ -608,13 +538,10 @@ extern "C" int prt_frame_ray_aberrations(int device, const double* rows, int64_t
   unsigned long long* missed = (unsigned long long*)(chief + n_groups);
   AbRaw* sorted = (AbRaw*)(((uintptr_t)(missed + n_groups) + 31) & ~(uintptr_t)31);
   // row passes: waves of contiguous rows, as many as the (wave, bucket) counts allow
-  int64_t waves = (n_rows + kWfRowsPerWave - 1) / kWfRowsPerWave;
-  waves = std::min<int64_t>(std::max<int64_t>(waves, 1), kWfMaxWaves);
-  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kAbCountBytes / ((size_t)n_buckets * 8))));
-  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  const size_t count_bytes = (size_t)all_waves * n_buckets * 8, total_bytes = (size_t)all_waves * 8;
+  const SortPlan plan = sort_plan(n_rows, n_buckets, 8, kAbCountBytes);
+  const int64_t per_wave = plan.per_wave, all_waves = plan.all_waves;
+  const unsigned grid = plan.grid;
+  const size_t count_bytes = plan.count_bytes, total_bytes = (size_t)all_waves * 8;
   char* scratch = nullptr;
   HIP_TRY(hipMallocAsync((void**)&scratch, count_bytes + total_bytes, st));
   int64_t* counts = (int64_t*)scratch;
@@ -628,10 +555,10 @@ extern "C" int prt_frame_ray_aberrations(int device, const double* rows, int64_t
                      per_wave, extent, hmin, missed);
   hipLaunchKernelGGL(k_aberration_count, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, launch_index, a, per_wave,
                      extent, hmin, n_buckets, counts, wave_pos, chief);
-  hipLaunchKernelGGL(k_aberration_positions, dim3(1), dim3(kMtfScanBlock), 0, st, (int)all_waves, wave_pos);
-  hipLaunchKernelGGL(k_mtf_offsets, dim3((unsigned)n_buckets), dim3(kMtfScanBlock), 0, st, (int)all_waves, n_buckets,
+  hipLaunchKernelGGL(k_sort_positions, dim3(1), dim3(kSortScanBlock), 0, st, (int)all_waves, wave_pos, wave_pos);
+  hipLaunchKernelGGL(k_sort_offsets, dim3((unsigned)n_buckets), dim3(kSortScanBlock), 0, st, (int)all_waves, n_buckets,
                      counts, bucket_total);
-  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kMtfScanBlock), 0, st, n_buckets, (int64_t)1, bucket_total,
+  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kSortScanBlock), 0, st, n_buckets, (int64_t)1, bucket_total,
                      bucket_start, chunk_start, slice_start);
   // the rays used and the chunks they make: read back, so that the slabs are sized by the chunks there are
   int64_t used = 0, chunks = 0;
@@ -653,7 +580,7 @@ extern "C" int prt_frame_ray_aberrations(int device, const double* rows, int64_t
   hipLaunchKernelGGL(k_aberration_scatter, dim3(grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, launch_index, a,
                      per_wave, extent, n_buckets, counts, wave_pos, bucket_start, capacity, sorted);
   if (chunks && reference_mode == 0)
-    hipLaunchKernelGGL(k_aberration_centre, dim3((unsigned)chunks), dim3(kAbBlock), 0, st, n_buckets, chunk_start,
+    hipLaunchKernelGGL(k_mtf_centre<AbRaw>, dim3((unsigned)chunks), dim3(kMtfBlock), 0, st, n_buckets, chunk_start,
                        bucket_total, bucket_start, sorted, centre_slab);
   hipLaunchKernelGGL(k_aberration_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0,
                      st, rows, ld, n_rows, n_groups, nz, reference_mode, pupil_radius, chunk_start, bucket_start,

@@ -81,14 +81,7 @@ k_energy_centre(int n_groups, const int64_t* __restrict__ chunk_start, const int
   }
   for (int k = 0; k < 5; ++k) red[k][t] = s[k];
   red[5][t] = top;
-  for (int half = kEnergyBlock / 2; half > 0; half >>= 1) {
-    __syncthreads();
-    if (t < half) {
-      for (int k = 0; k < 5; ++k) red[k][t] += red[k][t + half];
-      red[5][t] = red[5][t + half] > red[5][t] ? red[5][t + half] : red[5][t];
-    }
-  }
-  __syncthreads();
+  sort_tree(red, t, [](int k, double& a, double b) { a = k < 5 ? a + b : (b > a ? b : a); });  // (five sums, one max)
   if (t < 5) slab[chunk * 5 + t] = red[t][0];
   // (weights are >= 0: the order of their bit images is their own)
   if (t == 5 && red[5][0] > 0.0) atomicMax(w_max + g, (u64)__double_as_longlong(red[5][0]));
@@ -123,7 +116,7 @@ __global__ void __launch_bounds__(kEnergyBlock)
 k_energy_scale(int n_groups, const int64_t* __restrict__ chunk_start, const int64_t* __restrict__ bucket_total,
                const int64_t* __restrict__ bucket_start, const MtfRay* __restrict__ stage, const int* __restrict__ shift,
                u64* __restrict__ q, u64* __restrict__ total) {
-  __shared__ u64 red[kEnergyBlock];
+  __shared__ u64 red[1][kEnergyBlock];
   const int t = threadIdx.x;
   const int64_t chunk = blockIdx.x;
   const int g = mtf_owner(chunk_start, n_groups, chunk);
@@ -137,12 +130,9 @@ k_energy_scale(int n_groups, const int64_t* __restrict__ chunk_start, const int6
     q[r] = v;
     mine += v;
   }
-  red[t] = mine;
-  for (int half = kEnergyBlock / 2; half > 0; half >>= 1) {
-    __syncthreads();
-    if (t < half) red[t] += red[t + half];
-  }
-  if (t == 0 && red[0]) atomicAdd(total + g, red[0]);
+  red[0][t] = mine;
+  sort_tree(red, t);
+  if (t == 0 && red[0][0]) atomicAdd(total + g, red[0][0]);
 }
 
 // per (ray slice, plane tile): bins[(g, plane, j)] += q of the rays with R_(j-1) < d <= R_j

@@ -5,11 +5,12 @@
 // The first part is the core that the geometric image passes stand on (this one, the MTF sensitivities, the enclosed
 // energy): on the host the checks and the plan of the outputs (mtf_plan), the plan of the row passes (mtf_row_plan), the
 // staging pass (mtf_stage_rows: the seven launches k_mtf_count to k_mtf_stage) and an entry's tail (mtf_finish); on the
-// device the rule for keeping a ray, the scan, a chunk's and a slice's rays, a ray about its centre and the fp32 phasor.
+// device the rule for keeping a ray, a chunk's and a slice's rays, a ray about its centre and the fp32 phasor.  The
+// stable counting sort under the staging pass (the runs, the ballot loop, the scan, the tree) is prt_sort.hpp's.
 //
 //   k_mtf_count     per wave of a contiguous run of rows: the rays kept per group; rays left out counted per group
 //                   (integer atomics)
-//   k_mtf_offsets   per group: the waves' counts scanned in parallel into each wave's offset inside the group's bucket
+//   (k_sort_offsets of prt_sort.hpp: the waves' counts scanned per group into each wave's offset inside the bucket)
 //   k_mtf_starts    one workgroup: each bucket's start, and where each group's centre chunks and sum slices begin
 //   k_mtf_scatter   the stable counting sort: every wave writes its rays (Q, u, w), in row order, at its offsets
 //   k_mtf_centre    per (group, chunk of 4096 rays): sum w and sum w Q in a fixed tree
@@ -31,7 +32,6 @@ static const int kMtfOut = 4;                     // outputs a thread owns (fp64
 static const int kMtfChunk = 4096;                // rays of a centroid / staging chunk
 static const int kMtfMinSlice = 2048;             // rays a sum slice holds at least (while the group has them)
 static const int kMtfMaxSlices = 256;             // slices of a group at most (the fold walks them in series)
-static const int kMtfScanBlock = 512;
 static const size_t kMtfSlabBytes = 256u << 20;   // cap on the (slice, output) partial sums
 static const size_t kMtfCountBytes = 64u << 20;   // cap on the sort's (wave, group) counts
 
@@ -105,12 +105,8 @@ struct MtfRowPlan {
 };
 static MtfRowPlan mtf_row_plan(int64_t n_rows, int n_groups, int64_t max_slices) {
   MtfRowPlan p;
-  int64_t waves = wf_waves(n_rows, 1);
-  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kMtfCountBytes / ((size_t)n_groups * 8))));
-  p.per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  p.grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  p.all_waves = (int64_t)p.grid * (PRT_BLOCK / 64);
-  p.count_bytes = (size_t)p.all_waves * n_groups * 8;
+  const SortPlan sort = sort_plan(n_rows, n_groups, 8, kMtfCountBytes);
+  p.per_wave = sort.per_wave, p.grid = sort.grid, p.all_waves = sort.all_waves, p.count_bytes = sort.count_bytes;
   p.chunk_grid = (n_rows + kMtfChunk - 1) / kMtfChunk + n_groups;
   p.slice_grid = std::min<int64_t>((int64_t)n_groups * max_slices, n_rows / kMtfMinSlice + n_groups);
   p.centre_bytes = (size_t)p.chunk_grid * 4 * sizeof(double);
@@ -157,32 +153,6 @@ __device__ __forceinline__ bool mtf_ray(const double* __restrict__ rows, int64_t
   const double s1 = (r.u[0] * ax.e1[0] + r.u[1] * ax.e1[1] + r.u[2] * ax.e1[2]) / ua;
   const double s2 = (r.u[0] * ax.e2[0] + r.u[1] * ax.e2[1] + r.u[2] * ax.e2[2]) / ua;
   return ok && ua != 0.0 && fabs(s1) < PRT_INF && fabs(s2) < PRT_INF;
-}
-
-// an exclusive scan of n int64 values by one workgroup of kMtfScanBlock threads, each owning a contiguous run:
-// get(k) reads value k, put(k, before) receives the sum of the values before it; returns the total
-template <class Get, class Put>
-__device__ int64_t mtf_scan(int64_t n, Get get, Put put, int64_t* __restrict__ scan) {
-  const int64_t per = (n + kMtfScanBlock - 1) / kMtfScanBlock;
-  const int64_t lo = threadIdx.x * per, hi = lo + per < n ? lo + per : n;
-  int64_t mine = 0;
-  for (int64_t k = lo; k < hi; ++k) mine += get(k);
-  __syncthreads();  // (scan may still be read by a previous call)
-  scan[threadIdx.x] = mine;
-  __syncthreads();
-  for (int off = 1; off < kMtfScanBlock; off <<= 1) {
-    const int64_t add = (int)threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-    __syncthreads();
-    scan[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int64_t at = scan[threadIdx.x] - mine;
-  for (int64_t k = lo; k < hi; ++k) {
-    const int64_t v = get(k);
-    put(k, at);
-    at += v;
-  }
-  return scan[kMtfScanBlock - 1];
 }
 
 // the slices of a group of `count` rays: at least kMtfMinSlice rays each while the group has them, max_slices at most
@@ -251,10 +221,7 @@ __global__ void __launch_bounds__(PRT_BLOCK)
 k_mtf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
             double rays_per_source, int n_groups, MtfAxes ax, int weight_column, int64_t per_wave,
             int64_t* __restrict__ counts, unsigned long long* __restrict__ missed) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   int64_t* const mine = counts + wave * n_groups;  // (only this wave writes here)
   for (int64_t base = first; base < last; base += 64) {
     const int64_t j = base + lane;
@@ -266,39 +233,21 @@ k_mtf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
       if (mtf_ray(rows, ld, j, ax, weight_column, r)) kept = group;
       else atomicAdd(missed + group, 1ull);  // (integer: the same total in any order)
     }
-    unsigned long long pending = __ballot(kept >= 0);
-    while (pending) {  // one turn per group present in the slice: almost always exactly one
-      const int leader = __ffsll((long long)pending) - 1;
-      const int g = __shfl(kept, leader);
-      const unsigned long long take = __ballot(kept == g);
-      if (lane == 0) mine[g] += __popcll(take);
-      pending &= ~take;
-    }
+    sort_tally(lane, kept, mine);
   }
 }
 
-// per group (one workgroup each): counts[wave][g] -> the wave's first position inside the bucket, in place
-__global__ void __launch_bounds__(kMtfScanBlock)
-k_mtf_offsets(int waves, int n_groups, int64_t* __restrict__ counts, int64_t* __restrict__ bucket_total) {
-  __shared__ int64_t scan[kMtfScanBlock];
-  const int g = blockIdx.x;
-  const int64_t total = mtf_scan(
-      waves, [&](int64_t w) { return counts[w * n_groups + g]; },
-      [&](int64_t w, int64_t before) { counts[w * n_groups + g] = before; }, scan);
-  if (threadIdx.x == 0) bucket_total[g] = total;
-}
-
 // one workgroup: bucket starts, and the first centre chunk and first sum slice of each group (n_groups + 1 entries)
-__global__ void __launch_bounds__(kMtfScanBlock)
+__global__ void __launch_bounds__(kSortScanBlock)
 k_mtf_starts(int n_groups, int64_t max_slices, const int64_t* __restrict__ bucket_total,
              int64_t* __restrict__ bucket_start, int64_t* __restrict__ chunk_start, int64_t* __restrict__ slice_start) {
-  __shared__ int64_t scan[kMtfScanBlock];
-  const int64_t rays = mtf_scan(
+  __shared__ int64_t scan[kSortScanBlock];
+  const int64_t rays = sort_scan(
       n_groups, [&](int64_t g) { return bucket_total[g]; }, [&](int64_t g, int64_t v) { bucket_start[g] = v; }, scan);
-  const int64_t chunks = mtf_scan(
+  const int64_t chunks = sort_scan(
       n_groups, [&](int64_t g) { return (bucket_total[g] + kMtfChunk - 1) / kMtfChunk; },
       [&](int64_t g, int64_t v) { chunk_start[g] = v; }, scan);
-  const int64_t slices = mtf_scan(
+  const int64_t slices = sort_scan(
       n_groups, [&](int64_t g) { return mtf_slices(bucket_total[g], max_slices); },
       [&](int64_t g, int64_t v) { slice_start[g] = v; }, scan);
   if (threadIdx.x == 0) {
@@ -312,10 +261,7 @@ __global__ void __launch_bounds__(PRT_BLOCK)
 k_mtf_scatter(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
               double rays_per_source, int n_groups, MtfAxes ax, int weight_column, int64_t per_wave,
               int64_t* __restrict__ offsets, const int64_t* __restrict__ bucket_start, MtfRaw* __restrict__ sorted) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   int64_t* const mine = offsets + wave * n_groups;  // (only this wave reads and writes here)
   for (int64_t base = first; base < last; base += 64) {
     const int64_t j = base + lane;
@@ -323,24 +269,16 @@ k_mtf_scatter(const double* __restrict__ rows, int64_t ld, int64_t n_rows, doubl
     MtfRaw r;
     if (j < last && wf_selected(rows, ld, j, surface, generation)) group = wf_group(rows, ld, j, rays_per_source, n_groups);
     if (group >= 0 && mtf_ray(rows, ld, j, ax, weight_column, r)) kept = group;
-    unsigned long long pending = __ballot(kept >= 0);
-    while (pending) {
-      const int leader = __ffsll((long long)pending) - 1;
-      const int g = __shfl(kept, leader);
-      const unsigned long long take = __ballot(kept == g);
-      int64_t at = lane == 0 ? mine[g] : 0;
-      at = __shfl(at, 0);
-      if (kept == g) sorted[bucket_start[g] + at + __popcll(take & ((1ull << lane) - 1ull))] = r;
-      if (lane == 0) mine[g] = at + __popcll(take);
-      pending &= ~take;
-    }
+    sort_place(lane, kept, mine, bucket_start, [&](int64_t slot) { sorted[slot] = r; });
   }
 }
 
-// per (group, chunk): [0] sum w  [1..3] sum w Q -- each thread over its strided rays in order, then a fixed tree
+// per (group, chunk): [0] sum w  [1..3] sum w Q -- each thread over its strided rays in order, then a fixed tree.
+// Ray: the sorted rays of the pass, with a weight .w and an end point .q (MtfRaw; the aberrations' AbRaw)
+template <class Ray>
 __global__ void __launch_bounds__(kMtfBlock)
 k_mtf_centre(int n_groups, const int64_t* __restrict__ chunk_start, const int64_t* __restrict__ bucket_total,
-             const int64_t* __restrict__ bucket_start, const MtfRaw* __restrict__ sorted, double* __restrict__ slab) {
+             const int64_t* __restrict__ bucket_start, const Ray* __restrict__ sorted, double* __restrict__ slab) {
   __shared__ double red[4][kMtfBlock];
   const int t = threadIdx.x;
   const int64_t chunk = blockIdx.x;
@@ -350,17 +288,12 @@ k_mtf_centre(int n_groups, const int64_t* __restrict__ chunk_start, const int64_
   mtf_chunk(chunk_start, bucket_total, bucket_start, g, chunk, lo, hi);
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   for (int64_t r = lo + t; r < hi; r += kMtfBlock) {
-    const MtfRaw ray = sorted[r];
-    s[0] += ray.w;
-    for (int k = 0; k < 3; ++k) s[1 + k] = fma(ray.w, ray.q[k], s[1 + k]);
+    const double w = sorted[r].w;
+    s[0] += w;
+    for (int k = 0; k < 3; ++k) s[1 + k] = fma(w, sorted[r].q[k], s[1 + k]);
   }
   for (int k = 0; k < 4; ++k) red[k][t] = s[k];
-  for (int half = kMtfBlock / 2; half > 0; half >>= 1) {
-    __syncthreads();
-    if (t < half)
-      for (int k = 0; k < 4; ++k) red[k][t] += red[k][t + half];
-  }
-  __syncthreads();
+  sort_tree(red, t);
   if (t < 4) slab[chunk * 4 + t] = red[t][0];
 }
 
@@ -413,14 +346,14 @@ static int mtf_stage_rows(hipStream_t st, const MtfRowPlan& p, const MtfStaging&
   HIP_TRY(hipMemsetAsync(s.missed, 0, cleared, st));
   hipLaunchKernelGGL(k_mtf_count, dim3(p.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, ax, weight_column, p.per_wave, s.counts, s.missed);
-  hipLaunchKernelGGL(k_mtf_offsets, dim3((unsigned)n_groups), dim3(kMtfScanBlock), 0, st, (int)p.all_waves, n_groups,
+  hipLaunchKernelGGL(k_sort_offsets, dim3((unsigned)n_groups), dim3(kSortScanBlock), 0, st, (int)p.all_waves, n_groups,
                      s.counts, s.bucket_total);
-  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kMtfScanBlock), 0, st, n_groups, max_slices, s.bucket_total,
+  hipLaunchKernelGGL(k_mtf_starts, dim3(1), dim3(kSortScanBlock), 0, st, n_groups, max_slices, s.bucket_total,
                      s.bucket_start, s.chunk_start, s.slice_start);
   hipLaunchKernelGGL(k_mtf_scatter, dim3(p.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, ax, weight_column, p.per_wave, s.counts, s.bucket_start, s.sorted);
   if (!reference)
-    hipLaunchKernelGGL(k_mtf_centre, dim3((unsigned)p.chunk_grid), dim3(kMtfBlock), 0, st, n_groups, s.chunk_start,
+    hipLaunchKernelGGL(k_mtf_centre<MtfRaw>, dim3((unsigned)p.chunk_grid), dim3(kMtfBlock), 0, st, n_groups, s.chunk_start,
                        s.bucket_total, s.bucket_start, s.sorted, s.centre_slab);
   hipLaunchKernelGGL(k_mtf_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
                      n_groups, s.chunk_start, s.centre_slab, reference, s.centre, s.record);

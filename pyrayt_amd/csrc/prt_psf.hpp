@@ -4,14 +4,15 @@
 //
 // The first part is the Huygens core that every diffraction pass stands on (this one, the polarised one and the
 // sensitivities): on the host the wavelength list, the grid checks, the plan of the sort and of the slices, the scratch
-// and the status word; on the device the wavelength of a row, the rule for keeping a ray, the two ballot loops of the
-// stable counting sort, a pixel's constants, the phase path, the tree reduction and the fold of the Strehl slab.
+// and the status word; on the device the wavelength of a row, the rule for keeping a ray, a wave's staged rays into
+// their places (psf_place), a pixel's constants, the phase path and the fold of the Strehl slab.  The stable counting
+// sort under it -- the runs of the row passes, the ballot loop, the scans, the tree -- is prt_sort.hpp's.
 //
 //   k_psf_count       per wave of a contiguous run of rows: how many rows the wavefront's filter selects
-//   k_psf_scan        one workgroup: the waves' output offsets (the order of the wavefront's opd_out / pupil_out)
+//   (k_sort_positions: the waves' output offsets, the order of the wavefront's opd_out / pupil_out)
 //   k_psf_stage       per selected row, in row order: p1, p2, c = (OPD - R) s, a = sqrt(w) and its (group, wavelength)
 //                     bucket; per wave and bucket the rays kept; rays left out counted per bucket (integer atomics)
-//   k_psf_offsets     one workgroup: each bucket's start, and each wave's offset inside each bucket
+//   (k_sort_offsets, k_sort_starts: each wave's offset inside each bucket, each bucket's total and start)
 //   k_psf_scatter     the stable counting sort: every wave writes its rays, in order, at its offsets
 //   k_psf_strehl      per (ray slice, bucket, quantity): sum a, sum a cos / sin (2 pi OPD s) in fp64, a fixed tree order;
 //                     with K parameters, quantity 1 + k: sum a e_k cos / sin (here K = 0)
@@ -78,11 +79,8 @@ static PsfPlan psf_plan(int cus, int64_t n_items, int64_t sort_buckets, int64_t 
                         int64_t tile_pixels, size_t pixel_bytes, size_t stored_bytes, size_t strehl_sums) {
   PsfPlan p;
   // row passes: waves of contiguous rows, as many as the (wave, bucket) counts allow
-  int64_t waves = wf_waves(n_items, 1);
-  waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kPsfCountBytes / ((size_t)sort_buckets * 8))));
-  p.per_wave = ((n_items + waves - 1) / waves + 63) / 64 * 64;
-  p.grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  p.all_waves = (int64_t)p.grid * (PRT_BLOCK / 64);
+  const SortPlan sort = sort_plan(n_items, sort_buckets, 8, kPsfCountBytes);
+  p.per_wave = sort.per_wave, p.grid = sort.grid, p.all_waves = sort.all_waves, p.count_bytes = sort.count_bytes;
   // ray slices: enough workgroups to fill the CUs, slices of at least kPsfMinSlice items of an average sort bucket
   const int64_t tiles = (npix + tile_pixels - 1) / tile_pixels;
   int64_t slices = (4 * (int64_t)cus + tiles * buckets - 1) / (tiles * buckets);
@@ -91,7 +89,6 @@ static PsfPlan psf_plan(int cus, int64_t n_items, int64_t sort_buckets, int64_t 
   slices = std::max<int64_t>(1, std::min<int64_t>(slices, kPsfMaxSlices));
   p.tiles = tiles;
   p.slices = slices;
-  p.count_bytes = (size_t)p.all_waves * sort_buckets * 8;
   p.strehl_bytes = (size_t)buckets * slices * strehl_sums * sizeof(double);
   p.slab_bytes = (size_t)buckets * slices * npix * stored_bytes;
   return p;
@@ -139,38 +136,14 @@ __device__ __forceinline__ bool psf_keep(double o, double x, double y, double w)
   return o == o && x == x && y == y && w >= 0.0 && w < PRT_INF;
 }
 
-// a wave's 64 rows, `bucket` < 0 for a row left out: mine[b] += the rows of bucket b
-__device__ __forceinline__ void psf_tally(int lane, int bucket, int64_t* mine) {
-  unsigned long long pending = __ballot(bucket >= 0);
-  while (pending) {  // one turn per bucket present in the 64 rows: almost always exactly one
-    const int leader = __ffsll((long long)pending) - 1;
-    const int b = __shfl(bucket, leader);
-    const unsigned long long take = __ballot(bucket == b);
-    if (lane == 0) mine[b] += __popcll(take);
-    pending &= ~take;
-  }
-}
-
-// a wave's staged rays [from, to): move(r, pos) for every ray r kept, pos its place in its bucket -- the wave's offset
-// mine[b], advanced as it goes, so that the rays of a bucket keep their order
+// a wave's staged rays [from, to): move(r, pos) for every ray r kept, pos its place in the sorted rays (sort_place)
 template <class Move>
 __device__ __forceinline__ void psf_place(int64_t from, int64_t to, const int* __restrict__ bucket_of, int64_t* mine,
-                                          Move move) {
+                                          const int64_t* __restrict__ bucket_start, Move move) {
   const int lane = threadIdx.x & 63;
   for (int64_t base = from; base < to; base += 64) {
     const int64_t r = base + lane;
-    const int bucket = r < to ? bucket_of[r] : -1;
-    unsigned long long pending = __ballot(bucket >= 0);
-    while (pending) {
-      const int leader = __ffsll((long long)pending) - 1;
-      const int b = __shfl(bucket, leader);
-      const unsigned long long take = __ballot(bucket == b);
-      int64_t at = lane == 0 ? mine[b] : 0;
-      at = __shfl(at, 0);
-      if (bucket == b) move(r, at + __popcll(take & ((1ull << lane) - 1ull)));
-      if (lane == 0) mine[b] = at + __popcll(take);
-      pending &= ~take;
-    }
+    sort_place(lane, r < to ? bucket_of[r] : -1, mine, bucket_start, [&](int64_t pos) { move(r, pos); });
   }
 }
 
@@ -232,17 +205,6 @@ __device__ __forceinline__ void psf_chief_phase(double radius, double s, double 
   sincospi(2.0 * (phase - rint(phase)), &sn, &cs);
 }
 
-// red[k][0] = the sum of red[k][0 .. kPsfBlock) for every k, a fixed tree
-template <int N>
-__device__ __forceinline__ void psf_tree(double (&red)[N][kPsfBlock], int t) {
-  for (int half = kPsfBlock / 2; half > 0; half >>= 1) {
-    __syncthreads();
-    if (t < half)
-      for (int k = 0; k < N; ++k) red[k][t] += red[k][t + half];
-  }
-  __syncthreads();
-}
-
 // strehl_slab: (bucket, slice, 1 + K, 3).  The slices of (bucket b, quantity) added in slice order
 __device__ __forceinline__ void psf_strehl_fold(const double* __restrict__ strehl_slab, int slices, int K, int b,
                                                 int quantity, double& a, double& c, double& s) {
@@ -264,10 +226,7 @@ __device__ __forceinline__ bool psf_row(const double* __restrict__ rows, int64_t
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_psf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
             double rays_per_source, int n_groups, int64_t per_wave, int64_t* __restrict__ wave_rows) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   int64_t selected = 0;
   for (int64_t base = first; base < last; base += 64) {
     const int64_t j = base + lane;
@@ -277,26 +236,6 @@ k_psf_count(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
   if (lane == 0) wave_rows[wave] = selected;
 }
 
-static const int kPsfScanBlock = 512;
-__global__ void __launch_bounds__(kPsfScanBlock)
-k_psf_scan(int waves, const int64_t* __restrict__ wave_rows, int64_t* __restrict__ wave_offset) {
-  __shared__ int64_t scan[kPsfScanBlock];
-  const int per = (waves + kPsfScanBlock - 1) / kPsfScanBlock;
-  const int lo = threadIdx.x * per, hi = lo + per < waves ? lo + per : waves;
-  int64_t mine = 0;
-  for (int k = lo; k < hi; ++k) mine += wave_rows[k];
-  scan[threadIdx.x] = mine;
-  __syncthreads();
-  for (int off = 1; off < kPsfScanBlock; off <<= 1) {
-    const int64_t add = (int)threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-    __syncthreads();
-    scan[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int64_t at = scan[threadIdx.x] - mine;
-  for (int k = lo; k < hi; ++k) { wave_offset[k] = at; at += wave_rows[k]; }
-}
-
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_psf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double surface, double generation,
             double rays_per_source, int n_groups, int64_t per_wave, const int64_t* __restrict__ wave_offset,
@@ -304,10 +243,7 @@ k_psf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
             int weight_column, PsfLambda lambda, PsfRay* __restrict__ stage, int* __restrict__ bucket_of,
             int64_t* __restrict__ counts, int buckets, unsigned long long* __restrict__ skipped,
             int* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   if (first >= last) return;
   int64_t* const mine = counts + wave * buckets;  // (only this wave writes here)
   int64_t at = wave_offset[wave];
@@ -337,42 +273,17 @@ k_psf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double 
       bucket_of[pos] = bucket;
     }
     at += __popcll(ballot);
-    psf_tally(lane, bucket, mine);
-  }
-}
-
-// one workgroup: counts (waves, buckets) -> each wave's first position inside each bucket, in place
-__global__ void __launch_bounds__(kPsfScanBlock)
-k_psf_offsets(int waves, int buckets, int64_t* __restrict__ counts, int64_t* __restrict__ bucket_total,
-              int64_t* __restrict__ bucket_start) {
-  for (int b = threadIdx.x; b < buckets; b += kPsfScanBlock) {
-    int64_t sum = 0;
-    for (int w = 0; w < waves; ++w) sum += counts[(int64_t)w * buckets + b];
-    bucket_total[b] = sum;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t at = 0;
-    for (int b = 0; b < buckets; ++b) { bucket_start[b] = at; at += bucket_total[b]; }
-  }
-  __syncthreads();
-  for (int b = threadIdx.x; b < buckets; b += kPsfScanBlock) {
-    int64_t at = bucket_start[b];
-    for (int w = 0; w < waves; ++w) {
-      const int64_t c = counts[(int64_t)w * buckets + b];
-      counts[(int64_t)w * buckets + b] = at;
-      at += c;
-    }
+    sort_tally(lane, bucket, mine);
   }
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_psf_scatter(const int64_t* __restrict__ wave_rows, const int64_t* __restrict__ wave_offset,
               const int* __restrict__ bucket_of, const PsfRay* __restrict__ stage, int64_t* __restrict__ offsets,
-              int buckets, PsfRay* __restrict__ sorted) {
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
+              const int64_t* __restrict__ bucket_start, int buckets, PsfRay* __restrict__ sorted) {
+  const int64_t wave = sort_wave();
   const int64_t from = wave_offset[wave];  // (offsets + wave * buckets: only this wave reads and writes there)
-  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets,
+  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets, bucket_start,
             [&](int64_t r, int64_t pos) { sorted[pos] = stage[r]; });
 }
 
@@ -405,7 +316,7 @@ k_psf_strehl(const PsfRay* __restrict__ sorted, const PsfPar* __restrict__ par, 
     }
   }
   red[0][t] = sum_a; red[1][t] = sum_c; red[2][t] = sum_s;
-  psf_tree(red, t);
+  sort_tree(red, t);
   if (t < 3) strehl_slab[(((size_t)b * slices + slice) * (1 + K) + quantity) * 3 + t] = red[t][0];
 }
 
@@ -553,14 +464,13 @@ extern "C" int prt_frame_psf(int device, const double* rows, int64_t ld, int64_t
   if (rc) return rc;
   hipLaunchKernelGGL(k_psf_count, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, plan.per_wave, wave_rows);
-  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, wave_rows, wave_offset);
+  hipLaunchKernelGGL(k_sort_positions, dim3(1), dim3(kSortScanBlock), 0, st, all_waves, wave_rows, wave_offset);
   hipLaunchKernelGGL(k_psf_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, plan.per_wave, wave_offset, opd, pupil, group_record, weight_column,
                      lambda, stage, bucket_of, scratch.counts, (int)buckets, skipped, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, (int)buckets, scratch.counts,
-                     bucket_total, bucket_start);
+  sort_offsets(st, all_waves, (int)buckets, scratch.counts, bucket_total, bucket_start);
   hipLaunchKernelGGL(k_psf_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
-                     scratch.counts, (int)buckets, sorted);
+                     scratch.counts, bucket_start, (int)buckets, sorted);
   hipLaunchKernelGGL(k_psf_strehl, dim3((unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st, sorted,
                      (const PsfPar*)nullptr, n_rows, bucket_total, bucket_start, group_record, lambda, (int)WF_GROUP,
                      slices, 0, scratch.strehl_slab);

@@ -1,13 +1,13 @@
 // prt_psf_focus.hpp -- the diffraction PSF and the Strehl ratio through focus, on the device.
 // It stands on the Huygens core of prt_psf.hpp: psf_lambda, psf_grid, psf_plan, the count, scan, offsets and place
-// pieces, psf_sqrt, psf_chief_phase, psf_tree and the folds.  Definitions: include/prt.h.
+// pieces, psf_sqrt, psf_chief_phase, the folds, and prt_sort.hpp's tree.  Definitions: include/prt.h.
 //
 // A pixel of plane delta lies at x = P + u e1 + v e2 + delta a, and a ray's point on the reference sphere at
 // E = P + p1 e1 + p2 e2 + p3 a, so |x - E|^2 = R^2 + u^2 + v^2 + delta^2 - 2 (u p1 + v p2 + delta p3): the sum of
 // prt_frame_psf with one more term.  p3 is not kept by the wavefront pass, and its sign follows the ray's direction,
 // so the staging pass extends the row to the sphere again.
 //
-//   k_psf_count, k_psf_scan, k_psf_offsets, k_psf_strehl, k_psf_record   prt_psf.hpp's, as prt_frame_psf launches them
+//   k_psf_count, k_psf_strehl, k_psf_record and the scans of prt_sort.hpp, as prt_frame_psf launches them
 //   k_psff_stage      k_psf_stage, and p3 = (E - P).a of the row extended to the sphere (axial_out, in the wavefront's order)
 //   k_psff_scatter    the stable counting sort, p3 moved beside its PsfRay into an array of its own
 //   k_psff_line       per (ray slice, bucket): sum w p1, w p2, w p3, a fixed tree
@@ -43,10 +43,7 @@ k_psff_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
              int weight_column, PsfLambda lambda, WfAxes axes, PsfRay* __restrict__ stage, double* __restrict__ axial,
              int* __restrict__ bucket_of, int64_t* __restrict__ counts, int buckets,
              unsigned long long* __restrict__ skipped, int* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   if (first >= last) return;
   int64_t* const mine = counts + wave * buckets;  // (only this wave writes here)
   int64_t at = wave_offset[wave];
@@ -83,17 +80,18 @@ k_psff_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
       bucket_of[pos] = bucket;
     }
     at += __popcll(ballot);
-    psf_tally(lane, bucket, mine);
+    sort_tally(lane, bucket, mine);
   }
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_psff_scatter(const int64_t* __restrict__ wave_rows, const int64_t* __restrict__ wave_offset,
                const int* __restrict__ bucket_of, const PsfRay* __restrict__ stage, const double* __restrict__ axial,
-               int64_t* __restrict__ offsets, int buckets, PsfRay* __restrict__ sorted, double* __restrict__ sorted3) {
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
+               int64_t* __restrict__ offsets, const int64_t* __restrict__ bucket_start, int buckets,
+               PsfRay* __restrict__ sorted, double* __restrict__ sorted3) {
+  const int64_t wave = sort_wave();
   const int64_t from = wave_offset[wave];  // (offsets + wave * buckets: only this wave reads and writes there)
-  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets, [&](int64_t r, int64_t pos) {
+  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets, bucket_start, [&](int64_t r, int64_t pos) {
     sorted[pos] = stage[r];
     sorted3[pos] = axial[r];
   });
@@ -117,7 +115,7 @@ k_psff_line(const PsfRay* __restrict__ sorted, const double* __restrict__ sorted
     s3 += w * sorted3[r];
   }
   red[0][t] = s1; red[1][t] = s2; red[2][t] = s3;
-  psf_tree(red, t);
+  sort_tree(red, t);
   if (t < 3) line_slab[((size_t)b * slices + slice) * 3 + t] = red[t][0];
 }
 
@@ -176,7 +174,7 @@ k_psff_strehl(const PsfRay* __restrict__ sorted, const double* __restrict__ sort
     sum_s += ray.a * sn;
   }
   red[0][t] = sum_c; red[1][t] = sum_s;
-  psf_tree(red, t);
+  sort_tree(red, t);
   if (t < 2) plane_slab[((((size_t)b * slices + slice) * n_focus) + f) * 2 + t] = red[t][0];
 }
 
@@ -355,14 +353,13 @@ extern "C" int prt_frame_psf_focus(int device, const double* rows, int64_t ld, i
   HIP_TRY(hipMemcpyAsync(focus_dev, focus, (size_t)n_focus * sizeof(double), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_psf_count, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, plan.per_wave, wave_rows);
-  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, wave_rows, wave_offset);
+  hipLaunchKernelGGL(k_sort_positions, dim3(1), dim3(kSortScanBlock), 0, st, all_waves, wave_rows, wave_offset);
   hipLaunchKernelGGL(k_psff_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, plan.per_wave, wave_offset, opd, pupil, group_record, weight_column,
                      lambda, ax, stage, axial_out, bucket_of, scratch.counts, (int)buckets, skipped, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, (int)buckets, scratch.counts,
-                     bucket_total, bucket_start);
+  sort_offsets(st, all_waves, (int)buckets, scratch.counts, bucket_total, bucket_start);
   hipLaunchKernelGGL(k_psff_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
-                     axial_out, scratch.counts, (int)buckets, sorted, sorted3);
+                     axial_out, scratch.counts, bucket_start, (int)buckets, sorted, sorted3);
   hipLaunchKernelGGL(k_psf_strehl, dim3((unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st, sorted,
                      (const PsfPar*)nullptr, n_rows, bucket_total, bucket_start, group_record, lambda, (int)WF_GROUP,
                      slices, 0, scratch.strehl_slab);

@@ -1,12 +1,12 @@
 // prt_psf_gradient.hpp -- d(PSF)/d(parameter) and d(Strehl)/d(parameter) of the diffraction PSF, on the device
 // (DESIGN.md section 4.5), from the rows, the OPD, the pupil points and their derivatives that a wavefront sensitivity
-// pass left there.  It stands on prt_psf.hpp: the Huygens core, k_psf_offsets and the Strehl kernel itself -- the scalar
+// pass left there.  It stands on prt_psf.hpp: the Huygens core, the sort of prt_sort.hpp and the Strehl kernel itself -- the scalar
 // PSF's is its case without parameters.  Definitions: include/prt.h.
 //
 //   k_psfg_stage      per selected row, in the selection's order: kept / missed / unfollowed, (p1, p2, c, a) and the
 //                     row's (group, wavelength) bucket; per wave and bucket the rays kept; the others counted per bucket
 //                     (integer atomics)
-//   k_psf_offsets     (prt_psf.hpp) each bucket's start, and each wave's offset inside each bucket
+//   (k_sort_offsets, k_sort_starts of prt_sort.hpp: each wave's offset inside each bucket, each bucket's total and start)
 //   k_psfg_scatter    the stable counting sort of an index: every wave writes its rays' slots, in order, at its offsets,
 //                     and the staged ray beside them
 //   k_psfg_stage_par  per sorted ray and parameter, gathered through the index: (e_k, q_k1, q_k2)
@@ -39,10 +39,7 @@ k_psfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const 
              PsfRay* __restrict__ stage, int* __restrict__ bucket_of, int64_t* __restrict__ counts, int buckets,
              unsigned long long* __restrict__ missed, unsigned long long* __restrict__ unfollowed,
              int* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_selected ? first + per_wave : n_selected;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_selected);
   if (first >= last) return;
   int64_t* const mine = counts + wave * buckets;  // (only this wave writes here)
   for (int64_t base = first; base < last; base += 64) {
@@ -84,21 +81,20 @@ k_psfg_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const 
       }
       bucket_of[r] = bucket;
     }
-    psf_tally(lane, bucket, mine);
+    sort_tally(lane, bucket, mine);
   }
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_psfg_scatter(int64_t n_selected, int64_t per_wave, const int* __restrict__ bucket_of,
-               const PsfRay* __restrict__ stage, int64_t* __restrict__ offsets, int buckets,
-               PsfRay* __restrict__ sorted, int64_t* __restrict__ order) {
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t from = wave * per_wave;  // (offsets + wave * buckets: only this wave reads and writes there)
-  psf_place(from, from + per_wave < n_selected ? from + per_wave : n_selected, bucket_of, offsets + wave * buckets,
-            [&](int64_t r, int64_t pos) {
-              sorted[pos] = stage[r];
-              order[pos] = r;
-            });
+               const PsfRay* __restrict__ stage, int64_t* __restrict__ offsets,
+               const int64_t* __restrict__ bucket_start, int buckets, PsfRay* __restrict__ sorted,
+               int64_t* __restrict__ order) {
+  const SortRun run = sort_run(per_wave, n_selected);  // (offsets + wave * buckets: only this wave reads and writes)
+  psf_place(run.first, run.last, bucket_of, offsets + run.wave * buckets, bucket_start, [&](int64_t r, int64_t pos) {
+    sorted[pos] = stage[r];
+    order[pos] = r;
+  });
 }
 
 // per sorted ray i, slot = order[i]: e_k = dphase_k s, q_k = dpoint_k rho s (zeros without dpoint), at par[k * n_selected + i]
@@ -369,10 +365,9 @@ extern "C" int prt_frame_psf_gradient(int device, const double* rows, int64_t ld
   hipLaunchKernelGGL(k_psfg_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, selected, n_selected,
                      n_groups, d_group, opd, pupil, groups, weight_column, lambda, dphase, dpoint, K, plan.per_wave, stage,
                      bucket_of, scratch.counts, (int)buckets, missed, unfollowed, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)plan.all_waves, (int)buckets,
-                     scratch.counts, bucket_total, bucket_start);
+  sort_offsets(st, (int)plan.all_waves, (int)buckets, scratch.counts, bucket_total, bucket_start);
   hipLaunchKernelGGL(k_psfg_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, n_selected, plan.per_wave, bucket_of,
-                     stage, scratch.counts, (int)buckets, sorted, order);
+                     stage, scratch.counts, bucket_start, (int)buckets, sorted, order);
   if (n_selected)
     hipLaunchKernelGGL(k_psfg_stage_par, dim3((unsigned)((n_selected + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0,
                        st, rows, ld, selected, n_selected, n_groups, d_group, groups, lambda, bucket_total, bucket_start,

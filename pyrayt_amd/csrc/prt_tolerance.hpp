@@ -2,12 +2,12 @@
 // the Strehl ratio of many perturbed systems under the linear ray model, OPD_r + sum_c x_rc p_c the phase of ray r, the
 // merit itself not linearised; and the second moments of the OPD and its derivative columns, from which the host takes
 // the RMS wavefront error of a trial and the least-squares compensators.  It stands on the Huygens core of prt_psf.hpp
-// (the wavelength list, the rule for keeping a ray, the ballot loops of the stable counting sort, k_psf_offsets, the
+// (the wavelength list, the rule for keeping a ray, the stable counting sort of prt_sort.hpp under it, the
 // slices, the tree, the scratch and the status word).  Definitions: include/prt.h.
 //
 //   k_tol_rows          per selected row, in the selection's order: kept / missed / unfollowed and its (group,
 //                       wavelength) bucket; per wave and bucket the rays kept; the others counted (integer atomics)
-//   k_psf_offsets       (prt_psf.hpp) each bucket's start, and each wave's offset inside each bucket
+//   (k_sort_offsets, k_sort_starts of prt_sort.hpp: each wave's offset inside each bucket, each bucket's total and start)
 //   k_tol_scatter       the stable counting sort of an index of the kept rays
 //   k_tol_stage         per sorted ray, gathered through the index: a = sqrt(w), c0 = OPD s, e_c = x_c s, one plane each
 //   k_tol_weight        per (ray slice, bucket): sum a, a fixed tree
@@ -78,10 +78,7 @@ k_tol_rows(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const in
            int* __restrict__ bucket_of, int64_t* __restrict__ counts, int buckets,
            unsigned long long* __restrict__ missed, unsigned long long* __restrict__ unfollowed,
            int* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_selected ? first + per_wave : n_selected;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_selected);
   if (first >= last) return;
   int64_t* const mine = counts + wave * buckets;  // (only this wave writes here)
   for (int64_t base = first; base < last; base += 64) {
@@ -95,16 +92,15 @@ k_tol_rows(const double* __restrict__ rows, int64_t ld, int64_t n_rows, const in
       else if (row.state == TOL_UNFOLLOWED) atomicAdd(unfollowed + row.bucket, 1ull);
       bucket_of[r] = bucket;
     }
-    psf_tally(lane, bucket, mine);
+    sort_tally(lane, bucket, mine);
   }
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_tol_scatter(int64_t n_selected, int64_t per_wave, const int* __restrict__ bucket_of, int64_t* __restrict__ offsets,
-              int buckets, int64_t* __restrict__ order) {
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t from = wave * per_wave;  // (offsets + wave * buckets: only this wave reads and writes there)
-  psf_place(from, from + per_wave < n_selected ? from + per_wave : n_selected, bucket_of, offsets + wave * buckets,
+              const int64_t* __restrict__ bucket_start, int buckets, int64_t* __restrict__ order) {
+  const SortRun run = sort_run(per_wave, n_selected);  // (offsets + wave * buckets: only this wave reads and writes)
+  psf_place(run.first, run.last, bucket_of, offsets + run.wave * buckets, bucket_start,
             [&](int64_t r, int64_t pos) { order[pos] = r; });
 }
 
@@ -137,7 +133,7 @@ k_tol_weight(const double* __restrict__ stage, const int64_t* __restrict__ bucke
   double sum = 0.0;
   for (int64_t r = lo + t; r < hi; r += kPsfBlock) sum += stage[r];
   red[0][t] = sum;
-  psf_tree(red, t);
+  sort_tree(red, t);
   if (t == 0) weight_slab[(size_t)b * slices + slice] = red[0][0];
 }
 
@@ -475,10 +471,9 @@ extern "C" int prt_frame_tolerance(int device, const double* rows, int64_t ld, i
   hipLaunchKernelGGL(k_tol_rows, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, selected, n_selected,
                      n_groups, d_group, opd, columns, C, weight_column, lambda, plan.per_wave, bucket_of, scratch.counts,
                      (int)buckets, missed, unfollowed, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, (int)plan.all_waves, (int)buckets,
-                     scratch.counts, bucket_total, bucket_start);
+  sort_offsets(st, (int)plan.all_waves, (int)buckets, scratch.counts, bucket_total, bucket_start);
   hipLaunchKernelGGL(k_tol_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, n_selected, plan.per_wave, bucket_of,
-                     scratch.counts, (int)buckets, order);
+                     scratch.counts, bucket_start, (int)buckets, order);
   if (n_selected)
     hipLaunchKernelGGL(k_tol_stage, dim3((unsigned)((n_selected + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
                        rows, ld, selected, n_selected, n_groups, d_group, weight_column, lambda, bucket_total,

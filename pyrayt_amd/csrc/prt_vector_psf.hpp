@@ -1,7 +1,7 @@
 // prt_vector_psf.hpp -- the polarised diffraction PSF: the Huygens sum of prt_psf.hpp with the complex field vectors of
 // prt_fresnel.hpp / prt_coatings.hpp as the rays' amplitudes.  Definitions: include/prt.h.
-// It stands on prt_psf.hpp's Huygens core (the wavelength list, the plan, the scratch, psf_wavelength, psf_keep, psf_tally,
-// psf_place, psf_slice, psf_pixel, psf_phase, psf_tree) and reuses k_psf_count, k_psf_scan and k_psf_offsets; the rays are
+// It stands on prt_psf.hpp's Huygens core (the wavelength list, the plan, the scratch, psf_wavelength, psf_keep, psf_place,
+// psf_slice, psf_pixel, psf_phase), reuses k_psf_count and sorts by prt_sort.hpp as the scalar pass does; the rays are
 // sorted into (group, wavelength) buckets exactly as there, and the one or two states of a ray lie in planes of n_rows
 // rays, so a (group, wavelength, state) bucket is the bucket's range in the state's plane.
 //
@@ -35,10 +35,7 @@ k_vpsf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
              int n_states, VpsfAxes axes, VpsfRay* __restrict__ stage, VpsfSide* __restrict__ stage_side,
              int* __restrict__ bucket_of, int64_t* __restrict__ counts, int buckets,
              unsigned long long* __restrict__ skipped, int* __restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
-  const int64_t first = wave * per_wave;
-  const int64_t last = first + per_wave < n_rows ? first + per_wave : n_rows;
+  const auto [lane, wave, first, last] = sort_run(per_wave, n_rows);
   if (first >= last) return;
   int64_t* const mine = counts + wave * buckets;  // (only this wave writes here)
   int64_t at = wave_offset[wave];
@@ -95,18 +92,19 @@ k_vpsf_stage(const double* __restrict__ rows, int64_t ld, int64_t n_rows, double
       bucket_of[pos] = bucket;
     }
     at += __popcll(ballot);
-    psf_tally(lane, bucket, mine);
+    sort_tally(lane, bucket, mine);
   }
 }
 
 __global__ void __launch_bounds__(PRT_BLOCK)
 k_vpsf_scatter(const int64_t* __restrict__ wave_rows, const int64_t* __restrict__ wave_offset,
                const int* __restrict__ bucket_of, const VpsfRay* __restrict__ stage,
-               const VpsfSide* __restrict__ stage_side, int64_t* __restrict__ offsets, int buckets, int64_t n_rows,
+               const VpsfSide* __restrict__ stage_side, int64_t* __restrict__ offsets,
+               const int64_t* __restrict__ bucket_start, int buckets, int64_t n_rows,
                int n_states, VpsfRay* __restrict__ sorted, VpsfSide* __restrict__ sorted_side) {
-  const int64_t wave = (int64_t)blockIdx.x * (PRT_BLOCK / 64) + (threadIdx.x >> 6);
+  const int64_t wave = sort_wave();
   const int64_t from = wave_offset[wave];  // (offsets + wave * buckets: only this wave reads and writes there)
-  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets, [&](int64_t r, int64_t pos) {
+  psf_place(from, from + wave_rows[wave], bucket_of, offsets + wave * buckets, bucket_start, [&](int64_t r, int64_t pos) {
     for (int s = 0; s < n_states; ++s) {
       sorted[(int64_t)s * n_rows + pos] = stage[(int64_t)s * n_rows + r];
       sorted_side[(int64_t)s * n_rows + pos] = stage_side[(int64_t)s * n_rows + r];
@@ -144,7 +142,7 @@ k_vpsf_strehl(const VpsfRay* __restrict__ sorted, const VpsfSide* __restrict__ s
     sum[9] += side.a * side.a;
   }
   for (int k = 0; k < VPSF_SUMS; ++k) red[k][t] = sum[k];
-  psf_tree(red, t);
+  sort_tree(red, t);
   if (t < VPSF_SUMS) strehl_slab[((size_t)b * slices + slice) * VPSF_SUMS + t] = red[t][0];
 }
 
@@ -354,15 +352,14 @@ extern "C" int prt_frame_vector_psf(int device, const double* rows, int64_t ld, 
   if (rc) return rc;
   hipLaunchKernelGGL(k_psf_count, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, plan.per_wave, wave_rows);
-  hipLaunchKernelGGL(k_psf_scan, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, wave_rows, wave_offset);
+  hipLaunchKernelGGL(k_sort_positions, dim3(1), dim3(kSortScanBlock), 0, st, all_waves, wave_rows, wave_offset);
   hipLaunchKernelGGL(k_vpsf_stage, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, rows, ld, n_rows, surface, generation,
                      rays_per_source, n_groups, plan.per_wave, wave_offset, opd, pupil, group_record, weight_column, lambda,
                      field, field_ld, field_planes, n_states, frame, stage, stage_side, bucket_of, scratch.counts,
                      (int)group_waves, skipped, status);
-  hipLaunchKernelGGL(k_psf_offsets, dim3(1), dim3(kPsfScanBlock), 0, st, all_waves, (int)group_waves, scratch.counts,
-                     bucket_total, bucket_start);
+  sort_offsets(st, all_waves, (int)group_waves, scratch.counts, bucket_total, bucket_start);
   hipLaunchKernelGGL(k_vpsf_scatter, dim3(plan.grid), dim3(PRT_BLOCK), 0, st, wave_rows, wave_offset, bucket_of, stage,
-                     stage_side, scratch.counts, (int)group_waves, n_rows, n_states, sorted, sorted_side);
+                     stage_side, scratch.counts, bucket_start, (int)group_waves, n_rows, n_states, sorted, sorted_side);
   hipLaunchKernelGGL(k_vpsf_strehl, dim3((unsigned)slices, (unsigned)buckets), dim3(kPsfBlock), 0, st, sorted,
                      sorted_side, n_rows, n_states, bucket_total, bucket_start, group_record, lambda, slices,
                      scratch.strehl_slab);

@@ -13,7 +13,7 @@
 //   k_frame_wavefront_locate     pass 1: per wave, in-order sums of the rows' end and start points and the group's
 //                                first row, into a slab of its own; the wave's count of selected rows
 //   k_frame_wavefront_reference  folds the slab in wave order: the reference sphere (P, R) and the pivot per group;
-//                                one more workgroup scans the waves' counts into output offsets
+//                                one more workgroup scans the waves' counts into output offsets (sort_scan)
 //   k_frame_wavefront_pupil      pass 2: per row E, OPD and the pupil point, written compacted in row order; per
 //                                group the largest pupil radius, the OPD's range and the misses (integer atomics on
 //                                order-preserving images: the same on every run)
@@ -30,6 +30,7 @@ static const int kWfZBlock = 256;              // threads of a k_frame_zernike w
 static const int kWfMaxZBlocks = 512;
 static const size_t kWfSlabBytes = 64u << 20;  // cap on a slab of per-wave / per-workgroup partial sums
 enum { WF_LOC = 8, WF_GROUP = 12, WF_MAX_TERMS = 36 };
+#include "prt_sort.hpp"  // (the runs of the row passes and the scan: it reads kWfMaxWaves and kWfRowsPerWave)
 // group record (n_groups, 12) float64: [0..2] P  [3] R  [4] pivot  [5] pupil radius  [6] rows  [7] rows that miss
 // the sphere  [8] largest and [9] smallest OPD about the pivot  [10] first row  [11] largest radial extent
 // (during the passes [7] is an int64 count, [8] / [9] order-preserving keys, [11] the bits of a non-negative double)
@@ -179,6 +180,7 @@ __device__ __forceinline__ bool wf_extend(const double* __restrict__ rows, int64
 
 // ---- the reference sphere and the pivot; the output offsets ------------------------------------------------------
 static const int kWfRefBlock = 512;  // 8 waves: one per pass-1 statistic
+static_assert(kWfRefBlock == kSortScanBlock, "the last workgroup of k_frame_wavefront_reference runs sort_scan");
 __global__ void __launch_bounds__(kWfRefBlock)
 k_frame_wavefront_reference(const double* __restrict__ rows, int64_t ld, int64_t n_rows,
                             const double* __restrict__ opl, double surface, double generation, double rays_per_source,
@@ -190,21 +192,9 @@ k_frame_wavefront_reference(const double* __restrict__ rows, int64_t ld, int64_t
   __shared__ int64_t scan[kWfRefBlock];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if ((int)blockIdx.x == n_groups) {  // the last workgroup: exclusive scan of the waves' selected rows
-    const int per = (waves + kWfRefBlock - 1) / kWfRefBlock;
-    const int lo = threadIdx.x * per, hi = lo + per < waves ? lo + per : waves;
-    int64_t mine = 0;
-    for (int k = lo; k < hi; ++k) mine += wave_rows[k];
-    scan[threadIdx.x] = mine;
-    __syncthreads();
-    for (int off = 1; off < kWfRefBlock; off <<= 1) {
-      const int64_t add = threadIdx.x >= off ? scan[threadIdx.x - off] : 0;
-      __syncthreads();
-      scan[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (threadIdx.x == kWfRefBlock - 1) *total = scan[threadIdx.x];
-    int64_t at = scan[threadIdx.x] - mine;
-    for (int k = lo; k < hi; ++k) { wave_offset[k] = at; at += wave_rows[k]; }
+    const int64_t all = sort_scan(
+        waves, [&](int64_t k) { return wave_rows[k]; }, [&](int64_t k, int64_t before) { wave_offset[k] = before; }, scan);
+    if (threadIdx.x == 0) *total = all;
     return;
   }
   const int g = blockIdx.x;
@@ -565,13 +555,6 @@ extern "C" int prt_frame_optical_path(int device, const double* rows, int64_t ld
   return join_refusal(host_status, "optical path");
 }
 
-static int64_t wf_waves(int64_t n_rows, int n_groups) {
-  int64_t waves = (n_rows + kWfRowsPerWave - 1) / kWfRowsPerWave;
-  waves = std::min<int64_t>(std::max<int64_t>(waves, 1), kWfMaxWaves);
-  const int64_t cap = (int64_t)(kWfSlabBytes / ((size_t)n_groups * WF_LOC * sizeof(double)));
-  return std::max<int64_t>(1, std::min<int64_t>(waves, cap));
-}
-
 extern "C" int64_t prt_frame_wavefront_workspace_bytes(int64_t n_rows, int n_groups, int n_terms, int with_weights) {
   if (n_rows < 0 || n_groups < 1 || n_terms < 1 || n_terms > WF_MAX_TERMS) return PRT_ERR_ARG;
   return (int64_t)(2 * kWfMaxWaves + 1) * 8 + n_rows * (int64_t)(sizeof(int) + (with_weights ? sizeof(double) : 0)) + 8;
@@ -606,11 +589,11 @@ extern "C" int prt_frame_wavefront(int device, const double* rows, int64_t ld, i
   int* group_of = (int*)(total + 1);
   double* weight_of = nullptr;
   if (weight_column >= 0) weight_of = (double*)(((uintptr_t)(group_of + n_rows) + 7) & ~(uintptr_t)7);
-  const int64_t waves = wf_waves(n_rows, n_groups);
-  const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;
-  const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));
-  const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);
-  const size_t loc_bytes = (size_t)all_waves * n_groups * WF_LOC * sizeof(double);
+  // row passes: waves of contiguous rows, as many as the slab of pass 1, WF_LOC doubles a (wave, group), allows
+  const SortPlan plan = sort_plan(n_rows, n_groups, WF_LOC * sizeof(double), kWfSlabBytes);
+  const int64_t per_wave = plan.per_wave, all_waves = plan.all_waves;
+  const unsigned grid = plan.grid;
+  const size_t loc_bytes = plan.count_bytes;
   double* loc = nullptr;
   HIP_TRY(hipMallocAsync((void**)&loc, loc_bytes, st));
   HIP_TRY(hipMemsetAsync(loc, 0, loc_bytes, st));

@@ -5,7 +5,7 @@ arrays as there.
 
 1. The partition (``ab_waves`` .. ``ab_tiles``), from (n_rows, n_groups, n_zones): the rows are cut into waves as the
    wavefront's are, cut again so that the (wave, bucket) counts fit kAbCountBytes, a bucket being a (group, zone); the
-   waves' counts are scanned by one workgroup of kMtfScanBlock threads (``ab_scan_per`` items a thread); a bucket is cut
+   waves' counts are scanned by one workgroup of kSortScanBlock threads (``ab_scan_per`` items a thread); a bucket is cut
    into chunks of kMtfChunk rays, a chunk summed in tiles of kAbBlock.  tests/test_host_aberration_sums.py holds the
    named constants and the restated lines to the headers' text.
 
@@ -20,7 +20,7 @@ arrays as there.
 
 3. Bounds (``bounded_aberrations``), u = 2^-53, gamma(k) = k u / (1 - k u).  The per-ray chain (h, p, eps, s, la, the
    Zernike basis by the device's recurrence) is evaluated in longdouble with the running bound ``Err`` keeps of the
-   device's own operation sequence.  The sums of k_aberration_centre / k_aberration_stage move a term through at most
+   device's own operation sequence.  The sums of k_mtf_centre<AbRaw> / k_aberration_stage move a term through at most
    ceil(kMtfChunk / kAbBlock) = 16 additions in its thread, 8 in the tree of 256, and one per chunk of the group in the
    serial fold (of the bucket, for a zone's sums): ``stage_depth``.  k_aberration_normal adds an entry over a chunk's rays
    in series, then the fold: ``normal_depth`` = the rays of the group's largest chunk + its chunks.  A sum is then off by
@@ -56,28 +56,31 @@ DEFAULT_AXES = np.array([1.0, 0, 0, 0, 1, 0, 0, 0, 1])
 AB_BLOCK = 256                  # prt_aberrations.hpp: static const int kAbBlock = 256;
 AB_COUNT_BYTES = 64 << 20       # prt_aberrations.hpp: static const size_t kAbCountBytes = 64u << 20;
 MTF_CHUNK = 4096                # prt_mtf.hpp: static const int kMtfChunk = 4096;
-MTF_SCAN_BLOCK = 512            # prt_mtf.hpp: static const int kMtfScanBlock = 512;
+MTF_SCAN_BLOCK = 512            # prt_sort.hpp: static const int kSortScanBlock = 512;
 WF_MAX_WAVES = ref.WF_MAX_WAVES
 WF_ROWS_PER_WAVE = ref.WF_ROWS_PER_WAVE
 BLOCK = ref.BLOCK
 HEADER_NAMES = dict(kAbBlock="AB_BLOCK", kAbCountBytes="AB_COUNT_BYTES", kMtfChunk="MTF_CHUNK",
-                    kMtfScanBlock="MTF_SCAN_BLOCK", kWfMaxWaves="WF_MAX_WAVES", kWfRowsPerWave="WF_ROWS_PER_WAVE")
+                    kSortScanBlock="MTF_SCAN_BLOCK", kWfMaxWaves="WF_MAX_WAVES", kWfRowsPerWave="WF_ROWS_PER_WAVE")
 HOST_RULES = {
     "prt_aberrations.hpp": (
-        "int64_t waves = (n_rows + kWfRowsPerWave - 1) / kWfRowsPerWave;",
-        "waves = std::min<int64_t>(std::max<int64_t>(waves, 1), kWfMaxWaves);",
-        "waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(kAbCountBytes / ((size_t)n_buckets * 8))));",
-        "const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;",
-        "const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));",
-        "const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);",
+        "const SortPlan plan = sort_plan(n_rows, n_buckets, 8, kAbCountBytes);",
         "const int n_buckets = n_groups * nz;",
         "for (int64_t r = lo + t; r < hi; r += kAbBlock) {",
-        "for (int half = kAbBlock / 2; half > 0; half >>= 1) {",
+        "__shared__ double red[AB_SUMS][kAbBlock];",
         "for (int64_t q = chunk_start[g * nz]; q < chunk_start[(g + 1) * nz]; ++q) v += sums_slab[(size_t)q * AB_SUMS + k];",
         "for (int64_t q = chunk_start[b]; q < chunk_start[b + 1]; ++q) v += sums_slab[(size_t)q * AB_SUMS + k];",
         "for (int k = 0; k < rays_here; ++k) {"),
+    "prt_sort.hpp": (
+        "int64_t waves = (n_rows + kWfRowsPerWave - 1) / kWfRowsPerWave;",
+        "waves = std::min<int64_t>(std::max<int64_t>(waves, 1), kWfMaxWaves);",
+        "waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(cap_bytes / ((size_t)buckets * cell_bytes))));",
+        "const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;",
+        "const unsigned grid = (unsigned)((waves + PRT_BLOCK / 64 - 1) / (PRT_BLOCK / 64));",
+        "const int64_t all_waves = (int64_t)grid * (PRT_BLOCK / 64);",
+        "const int64_t per = (n + kSortScanBlock - 1) / kSortScanBlock;",
+        "for (int half = BLOCK / 2; half > 0; half >>= 1) {"),
     "prt_mtf.hpp": (
-        "const int64_t per = (n + kMtfScanBlock - 1) / kMtfScanBlock;",
         "n_groups, [&](int64_t g) { return (bucket_total[g] + kMtfChunk - 1) / kMtfChunk; },",
         "hi = lo + kMtfChunk < end ? lo + kMtfChunk : end;"),
     "prt_wavefront.hpp": (),
@@ -85,7 +88,7 @@ HOST_RULES = {
 
 
 def header_constants():
-    """The static const ints of the three headers, by name."""
+    """The static const ints of the four headers, by name."""
     found = {}
     for name in HOST_RULES:
         text = open(os.path.join(ROOT, "pyrayt_amd", "csrc", name)).read()
@@ -117,12 +120,12 @@ def ab_all_waves(n_rows, n_groups, n_zones):
 
 
 def ab_scan_per(n_rows, n_groups, n_zones):
-    """The waves one thread of mtf_scan owns in k_aberration_positions / k_mtf_offsets."""
+    """The waves one thread of sort_scan owns in k_sort_positions / k_sort_offsets."""
     return -(-ab_all_waves(n_rows, n_groups, n_zones) // MTF_SCAN_BLOCK)
 
 
 def ab_bucket_scan_per(n_groups, n_zones):
-    """The buckets one thread of mtf_scan owns in k_mtf_starts."""
+    """The buckets one thread of sort_scan owns in k_mtf_starts."""
     return -(-ab_buckets(n_groups, n_zones) // MTF_SCAN_BLOCK)
 
 

@@ -78,6 +78,8 @@ HOST_RULES = {
         "hi = lo + per < first[g] + count ? lo + per : first[g] + count;",
         "n_groups, [&](int64_t g) { return (bucket_total[g] + kMtfChunk - 1) / kMtfChunk; },",
         "hi = lo + kMtfChunk < end ? lo + kMtfChunk : end;"),
+    "prt_sort.hpp": (
+        "for (int half = BLOCK / 2; half > 0; half >>= 1) {",),
     "prt_energy.hpp": (
         "static const int kEnergyWidth[kEnergyPasses] = {11, 11, 11, 10, 10, 10};",
         "static const int kEnergyLow[kEnergyPasses] = {52, 41, 30, 20, 10, 0};",
@@ -89,7 +91,8 @@ HOST_RULES = {
         "if ((size_t)n_groups * n_focus * n_radii * 8 > kEnergySlabBytes)",
         "if ((size_t)n_groups * n_focus * n_fractions * kEnergyDigits * 8 > kEnergySlabBytes)",
         "for (int64_t r = lo + t; r < hi; r += kEnergyBlock) {",
-        "for (int half = kEnergyBlock / 2; half > 0; half >>= 1) {",
+        "__shared__ double red[6][kEnergyBlock];",
+        "sort_tree(red, t, [](int k, double& a, double b) { a = k < 5 ? a + b : (b > a ? b : a); });",
         "for (int64_t q = chunk_start[g]; q < chunk_start[g + 1]; ++q)",
         "return 62 - e - (64 - __clzll(count));",
         "shift[g] = energy_shift(w_max[g], (long long)bucket_total[g]);",

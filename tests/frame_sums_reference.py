@@ -85,17 +85,20 @@ BLOCK = 256                     # prt_device.hpp: #define PRT_BLOCK 256
 HEADER_NAMES = dict(kFrameRowsPerWave="FRAME_ROWS_PER_WAVE", kFrameSlots="FRAME_SLOTS", kFrameSlotGroups="FRAME_SLOT_GROUPS",
                     kWfMaxWaves="WF_MAX_WAVES", kWfRowsPerWave="WF_ROWS_PER_WAVE", kWfZBlock="WF_ZBLOCK",
                     kWfMaxZBlocks="WF_MAX_ZBLOCKS", kWfSlabBytes="WF_SLAB_BYTES", kWfRefBlock="WF_REF_BLOCK")
-# lines of the two headers the partition rules below restate
+# lines of the headers the partition rules below restate
 HOST_RULES = {
     "prt_frame.hpp": (
         "const int slots = (n_groups <= kFrameSlotGroups && waves / n_groups >= 256) ? kFrameSlots : 1;",
         "double* const mine = out + (size_t)(wave & (slots - 1)) * n_groups * FRAME_STATS;",
         "for (int k = 0; k < slots; ++k) v += partial[(size_t)k * n + e];"),
-    "prt_wavefront.hpp": (
+    "prt_sort.hpp": (
         "waves = std::min<int64_t>(std::max<int64_t>(waves, 1), kWfMaxWaves);",
-        "const int64_t cap = (int64_t)(kWfSlabBytes / ((size_t)n_groups * WF_LOC * sizeof(double)));",
+        "waves = std::max<int64_t>(1, std::min<int64_t>(waves, (int64_t)(cap_bytes / ((size_t)buckets * cell_bytes))));",
         "const int64_t per_wave = ((n_rows + waves - 1) / waves + 63) / 64 * 64;",
-        "const int per = (waves + kWfRefBlock - 1) / kWfRefBlock;",
+        "const int64_t per = (n + kSortScanBlock - 1) / kSortScanBlock;"),
+    "prt_wavefront.hpp": (
+        "const SortPlan plan = sort_plan(n_rows, n_groups, WF_LOC * sizeof(double), kWfSlabBytes);",
+        "static_assert(kWfRefBlock == kSortScanBlock,",
         "const int64_t tiles = (n_rows + kWfZBlock * 4 - 1) / (kWfZBlock * 4);",
         "int64_t zblocks = std::min<int64_t>(std::max<int64_t>(tiles, 1), std::min<int64_t>(kWfMaxZBlocks, 2 * (int64_t)cus));",
         "const int64_t per = ((n + gridDim.x - 1) / gridDim.x + kWfZBlock - 1) / kWfZBlock * kWfZBlock;"),
@@ -103,7 +106,7 @@ HOST_RULES = {
 
 
 def header_constants(names=None):
-    """The static const ints of the headers ``names`` (default: the two of HOST_RULES), by name."""
+    """The static const ints of the headers ``names`` (default: those of HOST_RULES), by name."""
     found = {}
     for name in (HOST_RULES if names is None else names):
         text = open(os.path.join(ROOT, "pyrayt_amd", "csrc", name)).read()

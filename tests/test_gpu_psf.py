@@ -280,6 +280,92 @@ def test_reproducible_at_a_million_rays_and_trace_psf():
     assert np.array_equal(tracer.trace().to_numpy(dtype=float), spot)
 
 
+# ---- the stable sort under the pass (prt_sort.hpp) ----------------------------------------------------------------------
+SORT_R = 105 / 8                    # the reference sphere's radius
+SORT_P = (1.0, 0.0, 0.0)            # ... and its centre
+SORT_RPS = 4096                     # ids a group
+
+
+def sort_points():
+    """Integer (y, z, root) with y^2 + z^2 + root^2 = 105^2: in units of 1/8 a ray along x through (y, z) meets the
+    sphere of radius 105 / 8 about a point of the axis at a distance that fp64 holds exactly."""
+    found = []
+    for y in range(-60, 61):
+        for z in range(-60, 61):
+            root = math.isqrt(105 * 105 - y * y - z * z)
+            if root * root == 105 * 105 - y * y - z * z and (y, z) != (0, 0):  # (a lone ray on the axis: no pupil radius)
+                found.append((y, z, root))
+    return np.array(found, dtype=float)
+
+
+def sort_frame(n, filler):
+    """One generation: 2 groups x 2 wavelengths, n rays a bucket at surface 5, row i in bucket i % 4, so that all four
+    buckets occur inside every 64-row step; ray n // 2 of bucket (1, 0.55) misses the sphere (its OPD is NaN).  With
+    ``filler`` a row of surface 2 follows every row.  Everything the wavefront adds up over these rows is exact: the rays
+    run along x through the points of ``sort_points`` and end on multiples of 1/8, so OPL, the sphere's root and the OPD
+    are multiples of 1/8 below 2^6, the weights are 1, 2 or 4, and sum w and sum w OPD (the piston that comes off the
+    OPD) are the same bits however k_frame_zernike cuts the rows -- it cuts them by n_rows, which the filler doubles.
+    The reference point and the radius are given, the slices are one in both frames (4 n and 8 n rows are below
+    4 buckets x kPsfMinSlice): what is left to differ is the order of a bucket's rays."""
+    points = sort_points()
+    assert len(points) >= 40
+    i = np.arange(4 * n)
+    bucket, ray = i % 4, i // 4
+    group, colour = bucket // 2, bucket % 2
+    at = points[(7 * ray + 3 * bucket) % len(points)]
+    frame = np.zeros((4 * n, 15))
+    frame[:, IX["intensity"]] = 2.0 ** ((ray + bucket) % 3)
+    frame[:, IX["wavelength"]] = np.where(colour == 0, 0.55, 0.65)
+    frame[:, IX["index"]] = 1.0
+    frame[:, IX["id"]] = group * SORT_RPS + 2 * ray + colour
+    frame[:, IX["surface"]] = 5.0
+    frame[:, IX["x0"]], frame[:, IX["y0"]], frame[:, IX["z0"]] = -4.0, at[:, 0] / 8, at[:, 1] / 8
+    frame[:, IX["x1"]], frame[:, IX["y1"]], frame[:, IX["z1"]] = SORT_P[0] + (ray % 7) / 8, at[:, 0] / 8, at[:, 1] / 8
+    frame[:, IX["x_tilt"]] = 1.0
+    miss = 4 * (n // 2) + 2
+    frame[miss, IX["y0"]] = frame[miss, IX["y1"]] = 2 * SORT_R
+    if not filler:
+        return frame
+    other = frame.copy()
+    other[:, IX["surface"]] = 2.0
+    other[:, IX["id"]] = 2 * SORT_RPS + i
+    return np.stack([frame, other], 1).reshape(8 * n, 15)
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 300])
+def test_rows_of_another_surface_between_the_rays_change_no_bit(n):
+    """The sort's own promise, on (group, wavelength) buckets that all occur inside every 64-row step -- at 300 rays a
+    bucket the 1200 rows are two waves of the row passes (kWfRowsPerWave = 1024), three with the filler, so every
+    bucket crosses a wave's edge: image, Strehl ratio and record of ``sort_frame`` alone and with a row of another
+    surface after every row are the same uint64 bits, and the counts of rays kept and left out are numpy's."""
+    runs = []
+    for filler in (False, True):
+        frame = sort_frame(n, filler)
+        assert len(frame) == (8 if filler else 4) * n
+        selected = frame[frame[:, IX["surface"]] == 5.0]
+        for step in range(0, len(selected) - 63, 64):
+            assert len(set(selected[step:step + 64, IX["id"]] // SORT_RPS * 2 + (selected[step:step + 64, IX["wavelength"]] == 0.65))) == 4
+        got = device_frame(frame).psf(5.0, world_unit_um=1000.0, pixels=(9, 7), pixel_size=2e-3, centre=(1e-3, -2e-3),
+                                      reference=SORT_P, radius=SORT_R, rays_per_source=SORT_RPS, n_groups=2)
+        assert list(got.wavelengths) == [0.55, 0.65] and got.image_by_wavelength.shape == (2, 2, 9, 7)
+        # the wavefront's own sums are exact, as sort_frame says: OPDs on a grid of 1/8 about the piston that came off
+        opd = got.wavefront.opd.cpu().numpy()
+        assert np.isnan(opd).sum() == 1 and len(opd) == 4 * n
+        kept = np.full((2, 2), n)
+        kept[1, 0] -= 1
+        assert np.array_equal(got.record[:, :, 0], kept) and np.array_equal(got.record[:, :, 1], n - kept)
+        assert np.array_equal(got.record[:, :, 0], [[np.sum((selected[:, IX["id"]] // SORT_RPS == g) & (selected[:, IX["wavelength"]] == lam)
+                                                            & (np.abs(selected[:, IX["y1"]]) < SORT_R)) for lam in (0.55, 0.65)] for g in (0, 1)])
+        runs.append(got)
+    alone, among = runs
+    for name in ("image_by_wavelength", "strehl", "record"):
+        a, b = (np.ascontiguousarray(getattr(run, name), dtype=np.float64).view(np.uint64) for run in runs)
+        assert np.array_equal(a, b), (name, int((a != b).sum()))
+    assert np.array_equal(alone.wavefront.opd.cpu().numpy().view(np.uint64), among.wavefront.opd.cpu().numpy().view(np.uint64))
+    if n > 1:
+        assert np.all(np.isfinite(alone.strehl)) and np.all(np.isfinite(alone.image_by_wavelength))
+
+
 def test_errors_on_the_device():
     tracer, lens, det = config2_tracer(4096)
     frame = tracer.trace_device()

@@ -166,7 +166,13 @@ def test_mtf_kernels_use_no_scratch():
         pytest.skip("llvm-readelf not available")
     if not os.path.exists(engine.LIB_PATH):
         pytest.skip("libprt_hip.so is not built")
-    kernels = {name: res for name, res in mod.kernel_resources(engine.LIB_PATH).items() if "k_mtf_" in name}
-    assert len(kernels) == 9, sorted(kernels)
+    found = mod.kernel_resources(engine.LIB_PATH)
+    # (the staging pass's scan over the waves is k_sort_offsets of prt_sort.hpp; k_mtf_centre stands once for MtfRaw and
+    # once for the aberrations' AbRaw)
+    kernels = {name: res for name, res in found.items() if "k_mtf_" in name}
+    assert len(kernels) == 9 and sum("k_mtf_centre" in name for name in kernels) == 2, sorted(kernels)
+    sort = {name: res for name, res in found.items() if "k_sort_" in name}
+    assert len(sort) == 3 and all(any(f"k_sort_{k}" in name for name in sort) for k in ("positions", "offsets", "starts")), sorted(sort)
+    kernels.update(sort)
     for name, res in kernels.items():
         assert res["private_segment_fixed_size"] == 0 and res["vgpr_spill_count"] == 0, (name, res)
