@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -980,6 +980,69 @@ int prt_frame_tolerance_moments(int device, const double* rows, int64_t ld, int6
                                 const double* opd, const double* columns, int n_columns, const double* wavelengths_um,
                                 int n_wavelengths, double world_unit_um, double* moments_out, void* workspace,
                                 void* stream);
+
+/* Monte Carlo tolerancing of the geometric MTF: the OTF through focus, the second moments of the landing points and the
+ * least-squares focus of many perturbed systems, from the rows, jacobian_out and slopes_out of one
+ * prt_frame_launch_sensitivity call, without a re-trace.
+ *
+ * Definitions.  The rays, weights, kept set, centre C_g and staging are exactly prt_frame_mtf_gradient's:
+ *   - one kept set for all K: a ray the MTF keeps whose 6 K tangent entries are finite;
+ *   - the others are counted as n_missed / n_unfollowed and staged with w = 0 in place;
+ *   - s, p, ds_k, dp_k as defined there;
+ *   - C_g is the kept rays' centroid or a given point, held fixed.
+ * Under the linear ray model, trial m (parameter changes t_mk, k < K <= 16) moves a ray to
+ *     P_rm = p_r + sum_k t_mk dp_rk        S_rm = s_r + sum_k t_mk ds_rk        (2-vectors, accumulated in parameter order by fma)
+ * Moments, per (group, trial), over the kept rays:
+ *   - sum w; sum w P (2); sum w S (2); sum w P.P; sum w P.S; sum w S.S.
+ *   - From them, in the plane shifted by delta:
+ *     - the centroid is c_m(delta) = mean P + delta mean S;
+ *     - the mean-square radius about it is var_P + 2 delta cov_PS + delta^2 var_S;
+ *     - the least-squares focus is delta*_m = -cov_PS / var_S (0 where var_S is not > 0).
+ * OTF, per (group, trial, plane f, azimuth, frequency), with k = nu (cos theta, sin theta) and the trial's focus shift delta_m:
+ *     OTF_gm = sum w exp(-2 pi i k.(P_rm + (delta_f + delta_m) S_rm)) / sum w
+ *   - delta_m is 0 without the focus compensator, and delta*_m with it.
+ *   - The merit is fully nonlinear in the moved landing points.  This is the sensitivity-based Monte Carlo, as
+ *     prt_frame_tolerance is for the phase.
+ *   - The phasor is mtf_phasor of prt_mtf.hpp, applied to the moved ray {fma(delta_m, S, P), S, w} with the MTF's own
+ *     (kc, ks, kc delta_f, ks delta_f) table.
+ *   - With every t = 0 and delta_m = 0, each fma returns its addend.  The zero trial's per-ray phasors are therefore the
+ *     bits k_mtf_sum / k_mtfg_sum form.
+ *
+ * prt_frame_mtf_tolerance: the leading arguments up to n_focus as prt_frame_mtf_gradient takes them, with its refusals;
+ * trials DEVICE (n_groups, M, K), 1 <= M <= 65536, finite: t_gmk, the change of parameter k in trial m of group g;
+ * compensate_focus: 0, or non-zero for delta_m = delta*_m, formed on the device in fp64 from the folded moments.
+ * Out, DEVICE, overwritten: otf_out (n_groups, M, n_focus, n_azimuths, n_frequencies, 2); moments_out (n_groups, M, 8),
+ * the sums above in that order; focus_out (n_groups, M), delta_m as it was applied; record_out (n_groups, 7): C_g (3),
+ * sum w, rays kept, n_missed, n_unfollowed.  A group without kept rays, or with sum w = 0, is NaN in otf_out,
+ * moments_out, focus_out and C_g (unless given), with its counts.  workspace:
+ * prt_frame_mtf_tolerance_workspace_bytes(n_selected, n_groups, K, n_frequencies, n_azimuths, n_focus, M) device bytes
+ * (-1 for arguments the call would refuse).
+ * Passes: the centre, record and staging passes of prt_frame_mtf_gradient, its own kernels; then, per launch of whole
+ * tiles of 256 trials: the moments, a grid of (ray slice, trial tile) workgroups whose threads own one trial each, its
+ * coefficients in registers, the slice's rays read through LDS; the moments' fold in slice order with the focus shift;
+ * the sum, a grid of (ray slice, trial tile, chunk of 8 outputs) workgroups that move the ray once per chunk and form
+ * the phasor per output; the fold in slice order, normalised by the moments' sum w added in the same order, so the OTF
+ * at nu = 0 is exactly 1.  A launch's partial sums -- slices * trials * (64 + 16 outputs of the launch) bytes -- stay
+ * under the 256 MiB slab cap: the outputs run in launches of whole chunks of 8, as many as a tile of 256 trials leaves
+ * room for, the trials in launches of whole tiles, and a call whose single tile cannot fit with one chunk (65535 groups)
+ * is refused with PRT_ERR_ARG naming the cap: a result is never truncated.
+ * A group's slices follow its count of selected rows, n_groups and the device's CU count -- never n_rows, the frame's
+ * other rows, M, K, the outputs or the trial values --, a trial's arithmetic does not depend on the other trials, and
+ * there are no floating-point atomics: every output is the same, bit for bit, on every run, on any frame that holds the
+ * same selected rows, for a trial alone or among 65536 at any place, and with a finite parameter appended whose trial
+ * values are all 0 (where the kept set is the same).  The arguments are checked before any kernel is launched (the
+ * slab cap once the device's CU count is known).  Stream-ordered; the call returns when the stream has reached its end.
+ * Accuracy: tests/mtf_tolerance_reference.py derives the bound per ray -- the MTF's phasor budget over the moved ray
+ * plus 2 pi u times the counted roundings of the (4 K + 2)-term chains -- and a gamma_n bound for the moments. */
+int64_t prt_frame_mtf_tolerance_workspace_bytes(int64_t n_selected, int n_groups, int n_parameters, int n_frequencies,
+                                                int n_azimuths, int n_focus, int n_trials);
+int prt_frame_mtf_tolerance(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                            int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                            const double* jacobian, const double* slopes, int n_parameters, const double* reference,
+                            const double* axes, const double* frequencies, int n_frequencies, const double* azimuths_deg,
+                            int n_azimuths, const double* focus, int n_focus, const double* trials, int n_trials,
+                            int compensate_focus, double* otf_out, double* moments_out, double* focus_out,
+                            double* record_out, void* workspace, void* stream);
 
 /* Ray-aberration curves of the frame: each ray's row at a surface joined by ray id with the row where the ray was
  * launched (examples/lens_design.ipynb cells 12-13 join the two cuts of the frame with isin(id)), its transverse and

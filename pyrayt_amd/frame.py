@@ -2736,6 +2736,128 @@ class ToleranceRun:
         return pd.DataFrame(rows).sort_values("worst", kind="stable").reset_index(drop=True)
 
 
+class MTFToleranceRun:
+    """What ``Sensitivity.mtf_tolerance`` returns (numpy arrays), G groups, M trials, K parameters, F focus shifts, A
+    azimuths, N frequencies.  ``trials`` (M, K) as drawn; ``otf`` (G, M, F, A, N) complex and ``mtf`` = |otf|: the
+    geometric OTF of every trial under the linear ray model, the merit fully nonlinear in the moved landing points
+    (``prt_frame_mtf_tolerance``; include/prt.h states the formulas), at the planes ``focus[f] + focus_shift``;
+    ``focus_shift`` (G, M): the plane shift the trial was evaluated at on top of ``focus`` -- the device's least-squares
+    refocus with the "focus" compensator, zeros without --; ``best_focus`` (G, M): the least-squares focus
+    -cov(P, S) / var(S) of the trial from its moments, whether compensated or not (0 where var(S) is not > 0);
+    ``rms_radius`` (G, M, F): the RMS spot radius about the trial's own centroid in each of those planes, and
+    ``centroid`` (G, M, 2): that centroid in the first plane, ``focus[0] + focus_shift``, as (e1, e2) coordinates about
+    the centre C_g (``centroid_at(plane)`` for another) -- both from the device's moments, in longdouble on the host.
+    ``reference``: "fixed", the kernel's numbers about the held centre, or "centroid", each trial's OTF about its own
+    centroid, what ``frame.mtf()`` of the perturbed system reports; ``mtf`` is the same under both.  ``nominal``: the
+    same fields for the all-zero trial.  Per group ``centre`` (G, 3), ``sum_weights``, ``n_rays``, ``n_missed``,
+    ``n_unfollowed``; ``moments`` the device's (G, M + 1, 8) block (sum w, sum w P (2), sum w S (2), sum w P.P,
+    sum w P.S, sum w S.S; the nominal trial last), ``record`` its (G, 7) block.  A group without rays is NaN."""
+
+    FIELDS = ("otf", "mtf", "focus_shift", "centroid", "rms_radius", "best_focus")
+
+    def __init__(self, trials, otf, moments, focus_shift, record, frequencies, azimuths, focus, parameters,
+                 compensators=(), reference="fixed"):
+        LD = np.longdouble
+        self.frequencies = np.asarray(frequencies, dtype=float)
+        self.azimuths = np.asarray(azimuths, dtype=float)
+        self.focus = np.asarray(focus, dtype=float)
+        self.parameters, self.compensators, self.reference = tuple(parameters), tuple(compensators), reference
+        self.moments, self.record = np.asarray(moments, dtype=float), np.asarray(record, dtype=float)
+        self.centre, self.sum_weights = self.record[:, :3], self.record[:, 3]
+        self.n_rays, self.n_missed, self.n_unfollowed = (np.nan_to_num(self.record[:, k]).astype(np.int64) for k in (4, 5, 6))
+        shift = np.asarray(focus_shift, dtype=float)
+        wide = self.moments.astype(LD)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sw = np.where(wide[..., 0] > 0, wide[..., 0], np.nan)
+            mean_p, mean_s = wide[..., 1:3] / sw[..., None], wide[..., 3:5] / sw[..., None]
+            var_p = wide[..., 5] / sw - np.sum(mean_p * mean_p, axis=-1)
+            cov = wide[..., 6] / sw - np.sum(mean_p * mean_s, axis=-1)
+            var_s = wide[..., 7] / sw - np.sum(mean_s * mean_s, axis=-1)
+            best = np.where(var_s > 0, -cov / np.where(var_s > 0, var_s, 1), np.where(np.isnan(sw), np.nan, 0))
+            planes = self.focus.astype(LD)[None, None, :] + shift.astype(LD)[:, :, None]  # (G, M, F)
+            self._mean_p, self._mean_s, self._planes = mean_p, mean_s, planes
+            square = var_p[..., None] + 2 * planes * cov[..., None] + planes * planes * var_s[..., None]
+            rms_radius = np.sqrt(np.maximum(square, 0)).astype(float)
+        otf = np.asarray(otf)
+        if reference == "centroid":  # (about each trial's own centroid in each plane: the phase of the shift back)
+            angle = np.radians(self.azimuths)
+            kc, ks = np.cos(angle)[:, None] * self.frequencies, np.sin(angle)[:, None] * self.frequencies  # (A, N)
+            c = (mean_p[:, :, None, :] + planes[..., None] * mean_s[:, :, None, :]).astype(float)  # (G, M, F, 2)
+            otf = otf * np.exp(2j * np.pi * (c[..., 0, None, None] * kc + c[..., 1, None, None] * ks))
+        centroid = self.centroid_at(0)
+        whole = dict(otf=otf, mtf=np.abs(otf), focus_shift=shift, centroid=centroid, rms_radius=rms_radius,
+                     best_focus=best.astype(float))
+        for name, value in whole.items():
+            setattr(self, name, value[:, :-1])
+        self.nominal = SimpleNamespace(**{name: value[:, -1] for name, value in whole.items()})
+        self.trials = np.asarray(trials, dtype=float)[:-1]
+        self.n_parameters, self.n_trials = len(self.parameters), len(self.trials)
+
+    def centroid_at(self, plane):
+        """(G, M + 1, 2): every trial's centroid (the nominal trial last) in the plane ``focus[plane] + focus_shift``."""
+        return (self._mean_p + self._planes[:, :, plane, None] * self._mean_s).astype(float)
+
+    def _outputs(self, frequency, azimuth, plane):
+        """``mtf`` (G, M, ...) cut to the selected plane (an index), azimuths and frequencies (indices, or None: all)."""
+        cut = self.mtf[:, :, plane]
+        cut = cut if azimuth is None else cut[:, :, np.atleast_1d(azimuth)]
+        return cut if frequency is None else cut[:, :, :, np.atleast_1d(frequency)]
+
+    def yield_(self, threshold, frequency=None, azimuth=None, plane=0):
+        """(G): the share of the trials whose MTF is at least ``threshold`` at every selected output of the plane
+        ``plane``; ``frequency`` and ``azimuth`` are indices (or lists of them), None for all; NaN for a group
+        without rays."""
+        cut = self._outputs(frequency, azimuth, plane)
+        cut = cut.reshape(cut.shape[0], cut.shape[1], -1)
+        with np.errstate(invalid="ignore"):
+            passed = np.mean(np.all(cut >= threshold, axis=2), axis=1)
+        return np.where(np.all(np.isfinite(cut), axis=(1, 2)), passed, np.nan)
+
+    def percentiles(self, q=(2, 10, 50, 90, 98), frequency=-1, azimuth=0, plane=0):
+        """(G, len(q)): the percentiles over the trials of the MTF at one output (indices)."""
+        q = np.atleast_1d(np.asarray(q, dtype=float))
+        with np.errstate(invalid="ignore"):
+            return np.percentile(self.mtf[:, :, plane, azimuth, frequency], q, axis=1).T
+
+    def to_pandas(self):
+        """One row per (group, trial): ``focus_shift``, ``best_focus``, per plane ``rms_radius_<f>``, per output
+        ``mtf_<f>_<a>_<n>`` (indices of plane, azimuth, frequency) and the drawn parameters ``p_k``."""
+        G, M = self.focus_shift.shape
+        data = {"source_id": np.repeat(np.arange(G), M), "trial": np.tile(np.arange(M), G),
+                "focus_shift": self.focus_shift.ravel(), "best_focus": self.best_focus.ravel()}
+        for f in range(len(self.focus)):
+            data[f"rms_radius_{f}"] = self.rms_radius[:, :, f].ravel()
+        for f in range(len(self.focus)):
+            for a in range(len(self.azimuths)):
+                for n in range(len(self.frequencies)):
+                    data[f"mtf_{f}_{a}_{n}"] = self.mtf[:, :, f, a, n].ravel()
+        for k in range(self.n_parameters):
+            data[f"p_{k}"] = np.tile(self.trials[:, k], G)
+        return pd.DataFrame(data)
+
+    def table(self, group=0, frequency=-1, plane=0):
+        """For a run on ``Tolerances.sensitivity_table()``: per parameter the change of the MTF at one frequency and
+        plane (indices) against the nominal trial at -width and +width, each the worst (lowest) over the azimuths
+        (``dmtf_minus``, ``dmtf_plus``), and ``worst``, the lower of the two; the rows sorted worst first.
+        ``ValueError`` for other trials."""
+        K = self.n_parameters
+        t = self.trials
+        one_at_a_time = t.shape == (2 * K + 1, K) and not np.any(t[0])
+        for k in range(K if one_at_a_time else 0):
+            hot = np.zeros(K, dtype=bool)
+            hot[k] = True
+            one_at_a_time &= (not np.any(t[1 + 2 * k][~hot]) and not np.any(t[2 + 2 * k][~hot])
+                              and t[1 + 2 * k, k] == -t[2 + 2 * k, k])
+        if not one_at_a_time:
+            raise ValueError("table: the trials are not Tolerances.sensitivity_table()'s")
+        merit = self.mtf[group, :, plane, :, frequency]  # (M, A)
+        change = (merit[1:] - merit[0]).min(axis=1)
+        rows = {"parameter": np.arange(K), "width": t[2::2][np.arange(K), np.arange(K)], "dmtf_minus": change[0::2],
+                "dmtf_plus": change[1::2]}
+        rows["worst"] = np.fmin(rows["dmtf_minus"], rows["dmtf_plus"])
+        return pd.DataFrame(rows).sort_values("worst", kind="stable").reset_index(drop=True)
+
+
 class Sensitivity:
     """What ``DeviceFrame.sensitivity`` found.  ``jacobian``: device (K, 3, n_selected) float64, d(x1, y1, z1)/dp_k of the
     selected rows, which ``rows()`` names (frame row numbers, ordered by group, generation and id); NaN for a ray that
@@ -3103,6 +3225,60 @@ class Sensitivity:
         return ToleranceRun(plain[:, :K], compensators, compensation, rms_opd, engine.host(strehl),
                             engine.host_complex(amplitude), rms_radius, engine.host(record), moments, values, unit,
                             self.parameters, follow)
+
+    def mtf_tolerance(self, trials, frequencies, *, azimuths=(0.0, 90.0), focus=(0.0,), compensators=(),
+                      reference="centroid", centre=None, axis=None, basis=None):
+        """Monte Carlo tolerancing of the geometric MTF from this one trace: the OTF through focus of M perturbed
+        systems, an ``MTFToleranceRun``.  Needs ``slopes`` (``sensitivity(slopes=True)``).  Under the linear ray model a
+        ray lands at ``p + sum_k t_k dp_k`` with the slope ``s + sum_k t_k ds_k`` (``mtf_gradient()``'s staged
+        quantities, about the same held centre, over the same kept rays), while the merit stays fully nonlinear in the
+        moved points: the OTF of a trial is ``mtf()``'s sum on them (``prt_frame_mtf_tolerance``; include/prt.h states
+        the formulas) -- not ``mtf + dmtf . t``.
+
+        ``trials``: an (M, K) array of parameter changes, or a ``(Tolerances, M)`` pair to draw them; M <= 65535; the
+        nominal all-zero trial is appended (``MTFToleranceRun.nominal``).  ``frequencies``, ``azimuths``, ``focus``,
+        ``axis``, ``basis`` and ``centre`` as in ``mtf_gradient``.  ``compensators``: ``()`` or ``("focus",)``, the
+        least-squares refocus of every trial from its own second moments, found on the device (a real parameter is
+        compensated by the caller's own ``trials``).  ``reference="fixed"``: the kernel's numbers, about the held centre;
+        ``"centroid"``: every trial about its own centroid, composed on the host as
+        ``OTF exp(+2 pi i k.c_m(delta_f + delta_m))`` from the trial's moments -- what ``frame.mtf()`` of the perturbed
+        system reports; |OTF| is the same under both.  A ``WavelengthChange`` may be among the parameters.  Second-order
+        terms and rays whose path changes under a perturbation are out of scope."""
+        self._need_slopes("mtf_tolerance")
+        from . import mtf_tolerance
+
+        if reference not in ("fixed", "centroid"):
+            raise ValueError('reference: "fixed" or "centroid"')
+        if isinstance(compensators, str):
+            compensators = (compensators,)
+        try:
+            compensators = tuple(compensators)
+        except TypeError:
+            compensators = (compensators,)
+        if compensators not in ((), ("focus",)):
+            raise ValueError(f'compensators: () or ("focus",) (got {compensators!r})')
+        K = self.n_parameters
+        if isinstance(trials, tuple) and len(trials) == 2 and isinstance(trials[0], Tolerances):
+            if len(trials[0].widths) != K:
+                raise ValueError(f"trials: the Tolerances have {len(trials[0].widths)} widths for {K} parameters")
+            trials = trials[0].sample(trials[1])
+        try:
+            drawn = np.array(trials, dtype=np.float64)
+        except (TypeError, ValueError):
+            drawn = np.zeros(0)
+        if drawn.ndim != 2 or drawn.shape[1] != K or not 1 <= drawn.shape[0] <= 65535 or not np.all(np.isfinite(drawn)):
+            raise ValueError(f"trials: a finite (M, {K}) array, 1 <= M <= 65535, or a (Tolerances, M) pair")
+        nu, theta, planes = _mtf_sampling(frequencies, azimuths, focus)
+        axes = pupil_axes(axis, basis)
+        head = self._selected_rows()
+        dev, n_groups = head.rows.device, head.n_groups
+        centres = None if centre is None else _group_points(centre, n_groups, dev, "centre: None, a point")
+        plain = np.concatenate([drawn, np.zeros((1, K))])
+        trials = np.array(np.broadcast_to(plain[None], (n_groups,) + plain.shape), order="C")  # (the same for every group)
+        otf, moments, shift, record = mtf_tolerance.device_run(head, self.jacobian, self.slopes, centres, axes, nu, theta,
+                                                               planes, trials, bool(compensators))
+        return MTFToleranceRun(plain, otf, moments, shift, record, nu, theta, planes, self.parameters, compensators,
+                               reference)
 
     def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
         """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the
