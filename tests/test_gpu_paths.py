@@ -7,13 +7,13 @@ import pytest
 
 import helpers
 import paths_reference as ref
+from paths_partitions import check
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 IX = ref.IX
-EPS = np.finfo(np.float64).eps
 FIXTURES = ["config1", "config2", "config3", "config4", "config5", "mirrors_and_stops", "adv_prism", "adv_lens",
             "two_mirrors", "tutorial", "stopped_lens", "stale_box", "adv_short_b"]
 _CACHE = {}
@@ -25,28 +25,6 @@ def device_frame(frame):
     counts = np.bincount(frame[:, 0].astype(int)).tolist() if len(frame) else []
     rows = torch.from_numpy(np.ascontiguousarray(np.asarray(frame, dtype=np.float64).T)).to("cuda:0")
     return DeviceFrame(rows, counts)
-
-
-def check(got, want):
-    """Exact, but for the energies of weights that are not integers: there every row's weight is truncated to a multiple
-    of the unit 2^-(62 - E - B) (w_max = f 2^E, B = bit_length(n_rows): include/prt.h), so a cell of n rows lies below
-    math.fsum's value by less than n units, and the one conversion to a double rounds by half an ulp."""
-    assert got.sequences == want["sequences"]
-    for name in ("parent", "surface", "depth", "subtree_size", "through", "ended", "dark"):
-        assert np.array_equal(getattr(got, name), want[name]), name
-    for name in ("row_node", "ray_node", "ray_last_row"):
-        assert np.array_equal(getattr(got, name).cpu().numpy(), want[name]), name
-    assert got.row_node.dtype == torch.int32 and got.ray_node.dtype == torch.int32 and got.ray_last_row.dtype == torch.int64
-    assert got.id0 == want["id0"] and got.n_bad_weight == want["n_bad_weight"] and got.n_rays == want["n_rays"]
-    for name, rows in (("energy_through", "through"), ("energy_ended", "ended")):
-        if want["integer_weights"]:
-            assert np.array_equal(getattr(got, name), want[name]), name
-        else:
-            unit = 2.0 ** -want["shift"]
-            short = want[name] - getattr(got, name)
-            ulp = EPS * want[name]
-            print(name, "largest shortfall in units of a row's truncation:", (short / np.maximum(want[rows], 1) / unit).max())
-            assert np.all(short >= -ulp) and np.all(short <= want[rows] * unit + ulp), name
 
 
 def synthetic_frame():
