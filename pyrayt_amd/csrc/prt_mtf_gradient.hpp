@@ -15,6 +15,7 @@
 // w = 0.  Every partition of the rays (chunks, slices, tiles) depends only on the group's count of selected rows, on the
 // output count and on n_groups, never on the frame's other rows and never on K; a parameter's arithmetic does not depend
 // on its place in the call.  No floating-point atomics: every output is the same, bit for bit, on every run.
+// The staging (MtfgStaging, mtfg_stage) serves prt_frame_mtf_tolerance too; the selection's checks are prt_selection.hpp's.
 // The checks and the plan of the outputs (mtf_plan), the slice rule (mtf_slices, mtf_slice), a ray about its centre
 // (mtf_stage_ray), the phase with its fp32 phasor (mtf_phasor) and the tail (mtf_finish) are the core's, in prt_mtf.hpp.
 #pragma once
@@ -310,6 +311,48 @@ k_mtfg_fold(int n_groups, int K, int64_t n_out, const int64_t* __restrict__ slic
   }
 }
 
+// ---- the staging of prt_frame_mtf_gradient and prt_frame_mtf_tolerance: a group's share follows from its own count of
+// selected rows and max_slices; a pass makes it, refuses what is too large, allocates its scratch and calls mtfg_stage
+struct MtfgStaging {
+  std::vector<int64_t> starts;           // group, chunk and slice starts, n_groups + 1 each (they outlive their copy)
+  int64_t chunk_grid, slice_grid, centre_bytes;  // chunks and slices of all groups; the centre slab, first in the scratch
+  int64_t *d_group, *d_chunk, *d_slice;  // the starts in the workspace, then
+  double *centre, *rest;                 // the centres (n_groups, 3), then what is the pass's own
+  MtfgStaging(const int64_t* group_first, int n_groups, int K, int64_t max_slices, void* workspace)
+      : starts(3 * ((size_t)n_groups + 1)) {
+    int64_t *const h_group = starts.data(), *const h_chunk = h_group + n_groups + 1, *const h_slice = h_chunk + n_groups + 1;
+    for (int g = 0; g <= n_groups; ++g) h_group[g] = group_first[g];
+    for (int g = 0; g < n_groups; ++g) {  // (h_chunk[0] and h_slice[0] are 0)
+      const int64_t count = group_first[g + 1] - group_first[g];
+      h_chunk[g + 1] = h_chunk[g] + (count + kMtfgChunk - 1) / kMtfgChunk;
+      h_slice[g + 1] = h_slice[g] + mtf_slices(count, max_slices);
+    }
+    chunk_grid = h_chunk[n_groups], slice_grid = h_slice[n_groups];
+    centre_bytes = std::max<int64_t>(chunk_grid, 1) * (MTFG_RECORD + 3 * K) * (int64_t)sizeof(double);
+    d_group = (int64_t*)workspace, d_chunk = d_group + (n_groups + 1), d_slice = d_chunk + (n_groups + 1);
+    centre = (double*)(d_slice + (n_groups + 1)), rest = centre + 3 * (size_t)n_groups;
+  }
+};
+// the starts copied, then the four staging kernels; record: (n_groups, MTFG_RECORD + 3 K); the caller refuses the sizes
+static int mtfg_stage(const MtfgStaging& s, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                      int64_t n_selected, int n_groups, int weight_column, const double* jacobian, const double* slopes,
+                      int K, const double* reference, const MtfPlan& plan, double* centre_slab, double* record,
+                      MtfRay* stage, MtfgPar* stage_par, hipStream_t st) {
+  HIP_TRY(hipMemcpyAsync(s.d_group, s.starts.data(), s.starts.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (s.chunk_grid)
+    hipLaunchKernelGGL(k_mtfg_centre, dim3((unsigned)s.chunk_grid), dim3(kMtfgBlock), 0, st, rows, ld, n_rows, selected,
+                       n_selected, n_groups, s.d_group, s.d_chunk, plan.ax, weight_column, jacobian, slopes, K, centre_slab);
+  hipLaunchKernelGGL(k_mtfg_centre_fold, dim3((unsigned)(n_groups * (MTFG_RECORD + 3 * K))), dim3(64), 0, st, n_groups, K,
+                     s.d_chunk, centre_slab, record);
+  hipLaunchKernelGGL(k_mtfg_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
+                     n_groups, K, reference, s.centre, record);
+  if (n_selected)
+    hipLaunchKernelGGL(k_mtfg_stage, dim3((unsigned)((n_selected + kMtfgBlock - 1) / kMtfgBlock)), dim3(kMtfgBlock), 0, st,
+                       rows, ld, n_rows, selected, n_selected, n_groups, s.d_group, s.centre, plan.ax, weight_column,
+                       jacobian, slopes, K, stage, stage_par);
+  return PRT_OK;
+}
+
 // ---- entry points ---------------------------------------------------------------------------------------------------
 extern "C" int64_t prt_frame_mtf_gradient_workspace_bytes(int64_t n_selected, int n_groups, int n_parameters,
                                                           int n_frequencies, int n_azimuths, int n_focus) {
@@ -338,12 +381,7 @@ extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld
   if (K < 1 || K > MTFG_MAX_PARAMETERS) return fail(PRT_ERR_ARG, "mtf_gradient: 1 to 16 parameters");
   if (n_selected && (!selected || !jacobian || !slopes))
     return fail(PRT_ERR_ARG, "mtf_gradient: selected, jacobian and slopes where rows are selected");
-  if (n_selected > n_rows) return fail(PRT_ERR_ARG, "mtf_gradient: more selected rows than rows");
-  if (group_first[0] != 0 || group_first[n_groups] != n_selected)
-    return fail(PRT_ERR_ARG, "mtf_gradient: group_first runs from 0 to n_selected");
-  for (int g = 0; g < n_groups; ++g)
-    if (group_first[g] > group_first[g + 1]) return fail(PRT_ERR_ARG, "mtf_gradient: group_first does not decrease");
-  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
+  if (int bad = selection_check("mtf_gradient", n_rows, n_selected, group_first, n_groups, weight_column)) return bad;
   // the slab is sized for 16 parameters whatever K is, so that the slices do not follow K
   MtfPlan plan;
   int rc = mtf_plan("mtf_gradient", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups,
@@ -351,56 +389,30 @@ extern "C" int prt_frame_mtf_gradient(int device, const double* rows, int64_t ld
   if (rc) return rc;
   const int n_k = plan.n_k, lanes = plan.lanes;
   const int64_t n_out = plan.n_out, tiles = plan.tiles;
-  // group, chunk and slice starts: each group's share follows from its own count of selected rows
-  std::vector<int64_t> starts(3 * ((size_t)n_groups + 1));
-  int64_t* const h_group = starts.data();
-  int64_t* const h_chunk = h_group + (n_groups + 1);
-  int64_t* const h_slice = h_chunk + (n_groups + 1);
-  h_chunk[0] = h_slice[0] = 0;
-  for (int g = 0; g <= n_groups; ++g) h_group[g] = group_first[g];
-  for (int g = 0; g < n_groups; ++g) {
-    const int64_t count = group_first[g + 1] - group_first[g];
-    h_chunk[g + 1] = h_chunk[g] + (count + kMtfgChunk - 1) / kMtfgChunk;
-    h_slice[g + 1] = h_slice[g] + mtf_slices(count, plan.max_slices);
-  }
-  const int64_t chunk_grid = h_chunk[n_groups], slice_grid = h_slice[n_groups];
-  if (chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff || tiles > 65535 ||
+  const MtfgStaging staging(group_first, n_groups, K, plan.max_slices, workspace);
+  const int64_t slice_grid = staging.slice_grid;
+  if (staging.chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff || tiles > 65535 ||
       (n_selected + kMtfgBlock - 1) / kMtfgBlock > 0x7fffffff)
     return fail(PRT_ERR_ARG, "mtf_gradient: too many rows or outputs for one launch");
   rc = ops_device(device);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // the workspace (prt_frame_mtf_gradient_workspace_bytes)
-  int64_t* d_group = (int64_t*)workspace;
-  int64_t* d_chunk = d_group + (n_groups + 1);
-  int64_t* d_slice = d_chunk + (n_groups + 1);
-  double* centre = (double*)(d_slice + (n_groups + 1));
-  double* table = centre + 3 * (size_t)n_groups;
+  // the workspace after the staging's head (prt_frame_mtf_gradient_workspace_bytes)
+  const int64_t *d_group = staging.d_group, *d_slice = staging.d_slice;
+  double* table = staging.rest;
   double* planes = table + 2 * (size_t)n_k;
   MtfRay* stage = (MtfRay*)(((uintptr_t)(planes + n_focus) + 31) & ~(uintptr_t)31);
   MtfgPar* stage_par = (MtfgPar*)(stage + n_selected);
-  const int n_q = MTFG_RECORD + 3 * K;
-  const size_t centre_bytes = (size_t)std::max<int64_t>(chunk_grid, 1) * n_q * sizeof(double);
-  const size_t weight_bytes = (size_t)slice_grid * sizeof(double);
+  const size_t centre_bytes = staging.centre_bytes, weight_bytes = (size_t)slice_grid * sizeof(double);
   const size_t slab_bytes = (size_t)slice_grid * (K + 2) * n_out * 2 * sizeof(double);
   char* scratch = nullptr;
   HIP_TRY(hipMallocAsync((void**)&scratch, centre_bytes + weight_bytes + slab_bytes, st));
-  double* centre_slab = (double*)scratch;
   double* weight_slab = (double*)(scratch + centre_bytes);
   double* slab = (double*)(scratch + centre_bytes + weight_bytes);
-  HIP_TRY(hipMemcpyAsync(d_group, starts.data(), starts.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(table, plan.host.data(), plan.host.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  if (chunk_grid)
-    hipLaunchKernelGGL(k_mtfg_centre, dim3((unsigned)chunk_grid), dim3(kMtfgBlock), 0, st, rows, ld, n_rows, selected,
-                       n_selected, n_groups, d_group, d_chunk, plan.ax, weight_column, jacobian, slopes, K, centre_slab);
-  hipLaunchKernelGGL(k_mtfg_centre_fold, dim3((unsigned)(n_groups * n_q)), dim3(64), 0, st, n_groups, K, d_chunk,
-                     centre_slab, record_out);
-  hipLaunchKernelGGL(k_mtfg_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
-                     n_groups, K, reference, centre, record_out);
-  if (n_selected)
-    hipLaunchKernelGGL(k_mtfg_stage, dim3((unsigned)((n_selected + kMtfgBlock - 1) / kMtfgBlock)), dim3(kMtfgBlock), 0, st,
-                       rows, ld, n_rows, selected, n_selected, n_groups, d_group, centre, plan.ax, weight_column, jacobian,
-                       slopes, K, stage, stage_par);
+  rc = mtfg_stage(staging, rows, ld, n_rows, selected, n_selected, n_groups, weight_column, jacobian, slopes, K, reference,
+                  plan, (double*)scratch, record_out, stage, stage_par, st);
+  if (rc) return rc;
   // whole chunks of kMtfgParams parameters in one launch, then the rest in the smallest instantiation that holds it
   const int whole = K / kMtfgParams, rest = K - whole * kMtfgParams;
   auto sum = [&](auto chunk, int chunks, int first) {

@@ -2,8 +2,8 @@
 // 4.5): the OTF through focus, the second moments of the landing points and the least-squares focus of many perturbed
 // systems under the linear ray model, P = p + sum_k t_k dp_k and S = s + sum_k t_k ds_k the landing point and the slope
 // of a ray in a trial, the merit itself not linearised.  It stands on the staging of the MTF sensitivities
-// (prt_mtf_gradient.hpp: k_mtfg_centre, k_mtfg_centre_fold, k_mtfg_record, k_mtfg_stage, launched here unchanged) and on
-// the MTF's core (prt_mtf.hpp: mtf_plan, mtf_slices, mtf_slice, mtf_phasor, mtf_finish).  Definitions: include/prt.h.
+// (prt_mtf_gradient.hpp: MtfgStaging and mtfg_stage, with this pass's own slice limit), on the MTF's core (prt_mtf.hpp:
+// mtf_plan, mtf_slices, mtf_slice, mtf_phasor, mtf_finish), on prt_selection.hpp and on prt_trials.hpp.  include/prt.h.
 //
 //   k_mtft_moments<CP>  per (ray slice of a group, trial tile): a thread owns one trial, its CP >= K coefficients in
 //                       registers (the rest zeros); the slice's rays go through an LDS tile (MtfRay + CP MtfgPar a ray)
@@ -21,7 +21,6 @@
 // of the call.  No floating-point atomics: every output is the same, bit for bit, on every run.
 #pragma once
 
-#include <type_traits>
 #include <vector>
 
 enum { MTFT_MAX_TRIALS = 65536, MTFT_RECORD = 7, MTFT_MOMENTS = 8 };
@@ -296,12 +295,7 @@ extern "C" int prt_frame_mtf_tolerance(int device, const double* rows, int64_t l
   if (M < 1 || M > MTFT_MAX_TRIALS) return fail(PRT_ERR_ARG, "mtf_tolerance: 1 to 65536 trials");
   if (n_selected && (!selected || !jacobian || !slopes))
     return fail(PRT_ERR_ARG, "mtf_tolerance: selected, jacobian and slopes where rows are selected");
-  if (n_selected > n_rows) return fail(PRT_ERR_ARG, "mtf_tolerance: more selected rows than rows");
-  if (group_first[0] != 0 || group_first[n_groups] != n_selected)
-    return fail(PRT_ERR_ARG, "mtf_tolerance: group_first runs from 0 to n_selected");
-  for (int g = 0; g < n_groups; ++g)
-    if (group_first[g] > group_first[g + 1]) return fail(PRT_ERR_ARG, "mtf_tolerance: group_first does not decrease");
-  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
+  if (int bad = selection_check("mtf_tolerance", n_rows, n_selected, group_first, n_groups, weight_column)) return bad;
   // the core's checks of the sampling, its axes and its (kc, ks) table; the slices and the tiles are this pass's own
   MtfPlan plan;
   int rc = mtf_plan("mtf_tolerance", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups,
@@ -324,20 +318,9 @@ extern "C" int prt_frame_mtf_tolerance(int device, const double* rows, int64_t l
   int cus = 1;
   rc = psf_device(device, &cus);
   if (rc) return rc;
-  // group, chunk and slice starts: each group's share follows from its own count of selected rows
-  const int64_t max_slices = mtft_max_slices(cus, n_groups);
-  std::vector<int64_t> starts(3 * ((size_t)n_groups + 1));
-  int64_t* const h_group = starts.data();
-  int64_t* const h_chunk = h_group + (n_groups + 1);
-  int64_t* const h_slice = h_chunk + (n_groups + 1);
-  h_chunk[0] = h_slice[0] = 0;
-  for (int g = 0; g <= n_groups; ++g) h_group[g] = group_first[g];
-  for (int g = 0; g < n_groups; ++g) {
-    const int64_t count = group_first[g + 1] - group_first[g];
-    h_chunk[g + 1] = h_chunk[g] + (count + kMtfgChunk - 1) / kMtfgChunk;
-    h_slice[g + 1] = h_slice[g] + mtf_slices(count, max_slices);
-  }
-  const int64_t chunk_grid = h_chunk[n_groups], slice_grid = h_slice[n_groups];
+  // the staging of prt_frame_mtf_gradient, the slices cut by this pass's own limit
+  const MtfgStaging staging(group_first, n_groups, K, mtft_max_slices(cus, n_groups), workspace);
+  const int64_t slice_grid = staging.slice_grid;
   // a launch's partial sums (the moments, and the outputs of the launch) stay under the cap: first the outputs of a
   // launch, whole chunks, as many as one tile of trials leaves room for; then the trials of a launch, whole tiles
   const int64_t tile_room = (int64_t)(kMtftSlabBytes / ((size_t)slice_grid * kMtftTile)) - MTFT_MOMENTS * 8;
@@ -346,46 +329,30 @@ extern "C" int prt_frame_mtf_tolerance(int device, const double* rows, int64_t l
   const size_t trial_bytes = (size_t)slice_grid * (MTFT_MOMENTS * 8 + (size_t)outputs * 16);
   int64_t most = (int64_t)(kMtftSlabBytes / trial_bytes) / kMtftTile * kMtftTile;
   most = std::min<int64_t>(most, ((int64_t)M + kMtftTile - 1) / kMtftTile * kMtftTile);
-  if (chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff || outputs / kMtftOut > 65535 ||
+  if (staging.chunk_grid > 0x7fffffff || slice_grid > 0x7fffffff || outputs / kMtftOut > 65535 ||
       (n_selected + kMtfgBlock - 1) / kMtfgBlock > 0x7fffffff ||
       ((int64_t)n_groups * most * outputs + PRT_BLOCK - 1) / PRT_BLOCK > 0x7fffffff)
     return fail(PRT_ERR_ARG, "mtf_tolerance: too many rows or outputs for one launch");
   hipStream_t st = (hipStream_t)stream;
-  // the workspace (prt_frame_mtf_tolerance_workspace_bytes)
-  int64_t* d_group = (int64_t*)workspace;
-  int64_t* d_chunk = d_group + (n_groups + 1);
-  int64_t* d_slice = d_chunk + (n_groups + 1);
-  double* centre = (double*)(d_slice + (n_groups + 1));
-  const int n_q = MTFG_RECORD + 3 * K;
-  double* staged_record = centre + 3 * (size_t)n_groups;
-  double* d_table = staged_record + (size_t)n_groups * n_q;
+  // the workspace after the staging's head (prt_frame_mtf_tolerance_workspace_bytes)
+  const int64_t *d_group = staging.d_group, *d_slice = staging.d_slice;
+  double* staged_record = staging.rest;
+  double* d_table = staged_record + (size_t)n_groups * (MTFG_RECORD + 3 * K);
   MtfRay* stage = (MtfRay*)(((uintptr_t)(d_table + 4 * (size_t)n_out) + 31) & ~(uintptr_t)31);
   MtfgPar* stage_par = (MtfgPar*)(stage + n_selected);
   const int64_t held = std::min<int64_t>(most, M);  // (trials of the largest launch)
-  const size_t centre_bytes = (size_t)std::max<int64_t>(chunk_grid, 1) * n_q * sizeof(double);
-  const size_t delta_bytes = (size_t)n_groups * held * sizeof(double);
+  const size_t centre_bytes = staging.centre_bytes, delta_bytes = (size_t)n_groups * held * sizeof(double);
   const size_t moment_bytes = (size_t)slice_grid * held * MTFT_MOMENTS * sizeof(double);
   const size_t slab_bytes = (size_t)slice_grid * held * std::min<int64_t>(outputs, n_out) * 2 * sizeof(double);
   char* scratch = nullptr;
   HIP_TRY(hipMallocAsync((void**)&scratch, centre_bytes + delta_bytes + moment_bytes + slab_bytes, st));
-  double* centre_slab = (double*)scratch;
   double* delta = (double*)(scratch + centre_bytes);
   double* moment_slab = (double*)(scratch + centre_bytes + delta_bytes);
   double* slab = (double*)(scratch + centre_bytes + delta_bytes + moment_bytes);
-  HIP_TRY(hipMemcpyAsync(d_group, starts.data(), starts.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, st));
-  // the staging of prt_frame_mtf_gradient: the same kernels, the same launches
-  if (chunk_grid)
-    hipLaunchKernelGGL(k_mtfg_centre, dim3((unsigned)chunk_grid), dim3(kMtfgBlock), 0, st, rows, ld, n_rows, selected,
-                       n_selected, n_groups, d_group, d_chunk, plan.ax, weight_column, jacobian, slopes, K, centre_slab);
-  hipLaunchKernelGGL(k_mtfg_centre_fold, dim3((unsigned)(n_groups * n_q)), dim3(64), 0, st, n_groups, K, d_chunk,
-                     centre_slab, staged_record);
-  hipLaunchKernelGGL(k_mtfg_record, dim3((unsigned)((n_groups + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK), 0, st,
-                     n_groups, K, reference, centre, staged_record);
-  if (n_selected)
-    hipLaunchKernelGGL(k_mtfg_stage, dim3((unsigned)((n_selected + kMtfgBlock - 1) / kMtfgBlock)), dim3(kMtfgBlock), 0, st,
-                       rows, ld, n_rows, selected, n_selected, n_groups, d_group, centre, plan.ax, weight_column, jacobian,
-                       slopes, K, stage, stage_par);
+  rc = mtfg_stage(staging, rows, ld, n_rows, selected, n_selected, n_groups, weight_column, jacobian, slopes, K, reference,
+                  plan, (double*)scratch, staged_record, stage, stage_par, st);
+  if (rc) return rc;
   // the smallest instantiation that holds the parameters; the trials in launches of at most `most`, and under each the
   // outputs in launches of at most `outputs`
   auto launch = [&](auto held_columns, int first, int n) {
@@ -406,12 +373,6 @@ extern "C" int prt_frame_mtf_tolerance(int device, const double* rows, int64_t l
                          otf_out);
     }
   };
-  for (int first = 0; first < M; first += (int)most) {
-    const int n = M - first < most ? M - first : (int)most;
-    if (K <= 4) launch(std::integral_constant<int, 4>(), first, n);
-    else if (K <= 8) launch(std::integral_constant<int, 8>(), first, n);
-    else if (K <= 12) launch(std::integral_constant<int, 12>(), first, n);
-    else launch(std::integral_constant<int, 16>(), first, n);
-  }
+  trial_launches(M, most, [&](int first, int n) { trial_columns<MTFG_MAX_PARAMETERS>(K, launch, first, n); });
   return mtf_finish(st, scratch);  // (it drains the stream: the host starts and table outlive their copies, too)
 }

@@ -1,7 +1,7 @@
 // prt_psf_gradient.hpp -- d(PSF)/d(parameter) and d(Strehl)/d(parameter) of the diffraction PSF, on the device
 // (DESIGN.md section 4.5), from the rows, the OPD, the pupil points and their derivatives that a wavefront sensitivity
 // pass left there.  It stands on prt_psf.hpp: the Huygens core, the sort of prt_sort.hpp and the Strehl kernel itself -- the scalar
-// PSF's is its case without parameters.  Definitions: include/prt.h.
+// PSF's is its case without parameters; the selection's checks are prt_selection.hpp's.  Definitions: include/prt.h.
 //
 //   k_psfg_stage      per selected row, in the selection's order: kept / missed / unfollowed, (p1, p2, c, a) and the
 //                     row's (group, wavelength) bucket; per wave and bucket the rays kept; the others counted per bucket
@@ -315,12 +315,7 @@ extern "C" int prt_frame_psf_gradient(int device, const double* rows, int64_t ld
   if (K < 1 || K > PSFG_MAX_PARAMETERS) return fail(PRT_ERR_ARG, "psf_gradient: 1 to 16 parameters");
   if (n_selected && (!selected || !opd || !pupil || !dphase))
     return fail(PRT_ERR_ARG, "psf_gradient: selected, opd, pupil and dphase where rows are selected");
-  if (n_selected > n_rows) return fail(PRT_ERR_ARG, "psf_gradient: more selected rows than rows");
-  if (group_first[0] != 0 || group_first[n_groups] != n_selected)
-    return fail(PRT_ERR_ARG, "psf_gradient: group_first runs from 0 to n_selected");
-  for (int g = 0; g < n_groups; ++g)
-    if (group_first[g] > group_first[g + 1]) return fail(PRT_ERR_ARG, "psf_gradient: group_first does not decrease");
-  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
+  if (int bad = selection_check("psf_gradient", n_rows, n_selected, group_first, n_groups, weight_column)) return bad;
   PsfLambda lambda;
   int rc = psf_lambda("psf_gradient", wavelengths_um, n_wavelengths, world_unit_um, lambda);
   if (!rc) rc = psf_grid("psf_gradient", nx, ny, du, dv, centre_uv);

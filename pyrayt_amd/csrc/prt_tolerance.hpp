@@ -2,8 +2,8 @@
 // the Strehl ratio of many perturbed systems under the linear ray model, OPD_r + sum_c x_rc p_c the phase of ray r, the
 // merit itself not linearised; and the second moments of the OPD and its derivative columns, from which the host takes
 // the RMS wavefront error of a trial and the least-squares compensators.  It stands on the Huygens core of prt_psf.hpp
-// (the wavelength list, the rule for keeping a ray, the stable counting sort of prt_sort.hpp under it, the
-// slices, the tree, the scratch and the status word).  Definitions: include/prt.h.
+// (the wavelength list, the rule for keeping a ray, the stable counting sort of prt_sort.hpp under it, the slices, the
+// tree, the scratch and the status word), on prt_selection.hpp and on prt_trials.hpp.  Definitions: include/prt.h.
 //
 //   k_tol_rows          per selected row, in the selection's order: kept / missed / unfollowed and its (group,
 //                       wavelength) bucket; per wave and bucket the rays kept; the others counted (integer atomics)
@@ -337,13 +337,8 @@ static int tol_arguments(const char* name, const double* rows, int64_t ld, int64
   if (n_columns < 1 || n_columns > TOL_MAX_COLUMNS) return fail(PRT_ERR_ARG, at + "1 to 20 columns");
   if (n_selected && (!selected || !opd || !columns))
     return fail(PRT_ERR_ARG, at + "selected, opd and columns where rows are selected");
-  if (n_selected > n_rows) return fail(PRT_ERR_ARG, at + "more selected rows than rows");
-  if (group_first[0] != 0 || group_first[n_groups] != n_selected)
-    return fail(PRT_ERR_ARG, at + "group_first runs from 0 to n_selected");
-  for (int g = 0; g < n_groups; ++g)
-    if (group_first[g] > group_first[g + 1]) return fail(PRT_ERR_ARG, at + "group_first does not decrease");
-  if (weight_column < -1 || weight_column >= PRT_RECORD_COLS) return fail(PRT_ERR_ARG, "weight_column: 0..14 or -1");
-  const int rc = psf_lambda(name, wavelengths_um, n_wavelengths, world_unit_um, lambda);
+  int rc = selection_check(name, n_rows, n_selected, group_first, n_groups, weight_column);
+  if (!rc) rc = psf_lambda(name, wavelengths_um, n_wavelengths, world_unit_um, lambda);
   if (rc) return rc;
   if ((int64_t)n_groups * n_wavelengths > 16383) return fail(PRT_ERR_ARG, at + "n_groups * n_wavelengths <= 16383");
   return PRT_OK;
@@ -489,16 +484,11 @@ extern "C" int prt_frame_tolerance(int device, const double* rows, int64_t ld, i
                        dim3(kTolBlock), 0, st, stage, n_selected, bucket_total, bucket_start, trials, n_wavelengths, M, C,
                        first, n, slices, scratch.slab);
   };
-  for (int first = 0; first < M; first += (int)chunk) {
-    const int n = M - first < chunk ? M - first : (int)chunk;
-    if (C <= 4) sum(std::integral_constant<int, 4>(), first, n);
-    else if (C <= 8) sum(std::integral_constant<int, 8>(), first, n);
-    else if (C <= 12) sum(std::integral_constant<int, 12>(), first, n);
-    else if (C <= 16) sum(std::integral_constant<int, 16>(), first, n);
-    else sum(std::integral_constant<int, 20>(), first, n);
+  trial_launches(M, chunk, [&](int first, int n) {
+    trial_columns<TOL_MAX_COLUMNS>(C, sum, first, n);
     hipLaunchKernelGGL(k_tol_fold, dim3((unsigned)(((int64_t)n_groups * n + PRT_BLOCK - 1) / PRT_BLOCK)), dim3(PRT_BLOCK),
                        0, st, scratch.slab, slices, n_groups, M, first, n, lambda, norm, strehl_out, amplitude_out);
-  }
+  });
   int host_status;
   rc = psf_finish(st, status, scratch, &host_status);
   if (rc) return rc;

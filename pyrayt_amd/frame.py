@@ -2987,6 +2987,22 @@ class Sensitivity:
         return _SelectedRows(*_row_head(rows), self._selected, int(self._selected.shape[0]), first, len(first) - 1,
                              _weight_column(weights))
 
+    def _wavelengths_for(self, what, follow, closing):
+        """What ``psf_gradient`` and ``tolerance`` (``what``) check before they allocate: ``follow``, no
+        ``WavelengthChange`` among the parameters (``closing`` ends the caller's sentence), a frame recorded with its
+        wavelengths and a selection that is not empty.  Returns the distinct wavelengths of the selected rows."""
+        if follow not in ("ray", "pupil"):
+            raise ValueError('follow: "ray" or "pupil"')
+        if any(isinstance(m, WavelengthChange) for m in self.parameters):
+            raise ValueError(f"{what}: a WavelengthChange among the parameters moves a ray between wavelengths; {closing}")
+        written = self._launch.get("written")
+        if written is not None and _INDEX["wavelength"] not in written:
+            raise ValueError(f"{what}: the frame was recorded without the wavelength column (RecordPlan(columns=...))")
+        if not len(self._selected):
+            raise ValueError(f"{what}: no row is selected at this surface")
+        wavelength = self._launch["rows"][_INDEX["wavelength"]][self._selected]
+        return _distinct_wavelengths(wavelength.unique().cpu().numpy().astype(np.float64), what)
+
     def _need_slopes(self, what):
         if self.slopes is None:
             raise ValueError(f"{what}: this Sensitivity has no slopes (they come with sensitivity(slopes=True), or with a "
@@ -3049,25 +3065,15 @@ class Sensitivity:
 
         from . import engine
 
-        if follow not in ("ray", "pupil"):
-            raise ValueError('follow: "ray" or "pupil"')
-        if any(isinstance(m, WavelengthChange) for m in self.parameters):
-            raise ValueError("psf_gradient: a WavelengthChange among the parameters moves a ray between wavelengths; "
-                             "the PSF's derivative is taken for the other kinds of parameter")
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         nx, ny = _pixel_counts(pixels)
         step, uv0 = _pixel_grid(pixel_size, centre)
+        values = self._wavelengths_for("psf_gradient", follow,
+                                       "the PSF's derivative is taken for the other kinds of parameter")
         head = self._selected_rows()
-        rows, n_selected, n_groups, K = head.rows, head.n_selected, head.n_groups, self.n_parameters
-        dev = rows.device
+        n_selected, n_groups, K = head.n_selected, head.n_groups, self.n_parameters
+        dev = head.rows.device
         wave = self.wavefront
-        written = self._launch.get("written")
-        if written is not None and _INDEX["wavelength"] not in written:
-            raise ValueError("psf_gradient: the frame was recorded without the wavelength column (RecordPlan(columns=...))")
-        if not n_selected:
-            raise ValueError("psf_gradient: no row is selected at this surface")
-        values = _distinct_wavelengths(
-            rows[_INDEX["wavelength"]][self._selected].unique().cpu().numpy().astype(np.float64), "psf_gradient")
         f_number, step = _f_number_and_step(wave, values, unit, step, "psf_gradient")
         groups = np.ascontiguousarray(np.column_stack([wave.reference, wave.radius, wave.pivot, wave.pupil_radius]),
                                       dtype=np.float64)
@@ -3121,23 +3127,9 @@ class Sensitivity:
 
         from . import engine
 
-        if follow not in ("ray", "pupil"):
-            raise ValueError('follow: "ray" or "pupil"')
-        if any(isinstance(m, WavelengthChange) for m in self.parameters):
-            raise ValueError("tolerance: a WavelengthChange among the parameters moves a ray between wavelengths; "
-                             "tolerances are taken for the other kinds of parameter")
         unit = _positive(world_unit_um, "world_unit_um: how many micrometres one world unit is (1000 for mm)")
         K = self.n_parameters
-        if isinstance(trials, tuple) and len(trials) == 2 and isinstance(trials[0], Tolerances):
-            if len(trials[0].widths) != K:
-                raise ValueError(f"trials: the Tolerances have {len(trials[0].widths)} widths for {K} parameters")
-            trials = trials[0].sample(trials[1])
-        try:
-            drawn = np.array(trials, dtype=np.float64)
-        except (TypeError, ValueError):
-            drawn = np.zeros(0)
-        if drawn.ndim != 2 or drawn.shape[1] != K or not 1 <= drawn.shape[0] <= 65535 or not np.all(np.isfinite(drawn)):
-            raise ValueError(f"trials: a finite (M, {K}) array, 1 <= M <= 65535, or a (Tolerances, M) pair")
+        drawn = _drawn_trials(trials, K)
         if isinstance(compensators, (str, int, np.integer)):
             compensators = (compensators,)
         compensators = tuple(compensators)
@@ -3151,18 +3143,12 @@ class Sensitivity:
                 raise ValueError(f'compensators: indices of parameters (0..{K - 1}), "tilt" or "focus" (got {c!r})')
         if len(set(compensators)) != len(compensators):
             raise ValueError("compensators: each one once")
+        values = self._wavelengths_for("tolerance", follow, "tolerances are taken for the other kinds of parameter")
         selected_rows = self._selected_rows()
         rows, n_selected, first, n_groups = (selected_rows.rows, selected_rows.n_selected, selected_rows.first,
                                              selected_rows.n_groups)
         dev = rows.device
         wave = self.wavefront
-        written = self._launch.get("written")
-        if written is not None and _INDEX["wavelength"] not in written:
-            raise ValueError("tolerance: the frame was recorded without the wavelength column (RecordPlan(columns=...))")
-        if not n_selected:
-            raise ValueError("tolerance: no row is selected at this surface")
-        values = _distinct_wavelengths(
-            rows[_INDEX["wavelength"]][self._selected].unique().cpu().numpy().astype(np.float64), "tolerance")
         # the columns: the K parameters, then the pseudo-parameters' (torch, on the device)
         columns = [(self.dopd if follow == "ray" else self.dfield)]
         if pseudo:
@@ -3245,8 +3231,6 @@ class Sensitivity:
         system reports; |OTF| is the same under both.  A ``WavelengthChange`` may be among the parameters.  Second-order
         terms and rays whose path changes under a perturbation are out of scope."""
         self._need_slopes("mtf_tolerance")
-        from . import mtf_tolerance
-
         if reference not in ("fixed", "centroid"):
             raise ValueError('reference: "fixed" or "centroid"')
         if isinstance(compensators, str):
@@ -3258,25 +3242,15 @@ class Sensitivity:
         if compensators not in ((), ("focus",)):
             raise ValueError(f'compensators: () or ("focus",) (got {compensators!r})')
         K = self.n_parameters
-        if isinstance(trials, tuple) and len(trials) == 2 and isinstance(trials[0], Tolerances):
-            if len(trials[0].widths) != K:
-                raise ValueError(f"trials: the Tolerances have {len(trials[0].widths)} widths for {K} parameters")
-            trials = trials[0].sample(trials[1])
-        try:
-            drawn = np.array(trials, dtype=np.float64)
-        except (TypeError, ValueError):
-            drawn = np.zeros(0)
-        if drawn.ndim != 2 or drawn.shape[1] != K or not 1 <= drawn.shape[0] <= 65535 or not np.all(np.isfinite(drawn)):
-            raise ValueError(f"trials: a finite (M, {K}) array, 1 <= M <= 65535, or a (Tolerances, M) pair")
+        drawn = _drawn_trials(trials, K)
         nu, theta, planes = _mtf_sampling(frequencies, azimuths, focus)
         axes = pupil_axes(axis, basis)
         head = self._selected_rows()
-        dev, n_groups = head.rows.device, head.n_groups
-        centres = None if centre is None else _group_points(centre, n_groups, dev, "centre: None, a point")
+        centres = None if centre is None else _group_points(centre, head.n_groups, head.rows.device, "centre: None, a point")
         plain = np.concatenate([drawn, np.zeros((1, K))])
-        trials = np.array(np.broadcast_to(plain[None], (n_groups,) + plain.shape), order="C")  # (the same for every group)
-        otf, moments, shift, record = mtf_tolerance.device_run(head, self.jacobian, self.slopes, centres, axes, nu, theta,
-                                                               planes, trials, bool(compensators))
+        trials = np.array(np.broadcast_to(plain[None], (head.n_groups,) + plain.shape), order="C")  # (the same for all)
+        otf, moments, shift, record = _mtf_tolerance_run(head, self.jacobian, self.slopes, centres, axes, nu, theta, planes,
+                                                         trials, bool(compensators))
         return MTFToleranceRun(plain, otf, moments, shift, record, nu, theta, planes, self.parameters, compensators,
                                reference)
 
@@ -3812,6 +3786,44 @@ def _distinct_wavelengths(values, name):
     if len(values) > 16:
         raise ValueError(f"{name}: at most 16 distinct wavelengths (the selected rows hold {len(values)})")
     return values
+
+
+def _mtf_tolerance_run(head, jacobian, slopes, centres, axes, frequencies, azimuths, planes, trials, compensate_focus):
+    """``prt_frame_mtf_tolerance`` on the selected rows ``head`` and host ``trials`` (groups, M, K), which may differ by
+    group.  Returns host arrays: otf (groups, M, F, A, N) complex, moments (groups, M, 8), focus_shift (groups, M), record
+    (groups, 7)."""
+    import torch
+
+    from . import engine
+
+    dev, n_groups = head.rows.device, head.n_groups
+    trials = np.ascontiguousarray(trials, dtype=np.float64)
+    M, K = trials.shape[1:]
+    assert trials.shape[0] == n_groups and K == jacobian.shape[0], (trials.shape, n_groups, jacobian.shape)
+    shape = (len(planes), len(azimuths), len(frequencies))
+    empty = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    otf, moments, shift, record = empty(n_groups, M, *shape, 2), empty(n_groups, M, 8), empty(n_groups, M), empty(n_groups, 7)
+    engine.call("prt_frame_mtf_tolerance", *head, jacobian.contiguous(), slopes.contiguous(), K, centres, axes, frequencies,
+                len(frequencies), azimuths, len(azimuths), planes, len(planes), torch.as_tensor(trials, device=dev), M,
+                int(bool(compensate_focus)), otf, moments, shift, record, device=dev,
+                size=(head.n_selected, n_groups, K, len(frequencies), len(azimuths), len(planes), M))
+    return engine.host_complex(otf), engine.host(moments), engine.host(shift), engine.host(record)
+
+
+def _drawn_trials(trials, K):
+    """``trials`` of ``tolerance`` and ``mtf_tolerance`` as a finite (M, K) float64 array, 1 <= M <= 65535: the array
+    itself, or M draws of a ``(Tolerances, M)`` pair."""
+    if isinstance(trials, tuple) and len(trials) == 2 and isinstance(trials[0], Tolerances):
+        if len(trials[0].widths) != K:
+            raise ValueError(f"trials: the Tolerances have {len(trials[0].widths)} widths for {K} parameters")
+        trials = trials[0].sample(trials[1])
+    try:
+        drawn = np.array(trials, dtype=np.float64)
+    except (TypeError, ValueError):
+        drawn = np.zeros(0)
+    if drawn.ndim != 2 or drawn.shape[1] != K or not 1 <= drawn.shape[0] <= 65535 or not np.all(np.isfinite(drawn)):
+        raise ValueError(f"trials: a finite (M, {K}) array, 1 <= M <= 65535, or a (Tolerances, M) pair")
+    return drawn
 
 
 def _f_number_and_step(wave, wavelengths, unit, step, name):

@@ -78,7 +78,8 @@ HOST_RULES = {
         "static_assert(kMtfgMinSlice == kMtfMinSlice && kMtfgMaxSlices == kMtfMaxSlices && kMtfgSlabBytes == kMtfSlabBytes,",
         'int rc = mtf_plan("mtf_gradient", frequencies, n_frequencies, azimuths_deg, n_azimuths, focus, n_focus, axes, n_groups,',
         "kMtfgQuantities * 16, kMtfgOut, kMtfgBlock, plan);",
-        "h_slice[g + 1] = h_slice[g] + mtf_slices(count, plan.max_slices);",
+        "const MtfgStaging staging(group_first, n_groups, K, plan.max_slices, workspace);",
+        "h_slice[g + 1] = h_slice[g] + mtf_slices(count, max_slices);",
         "h_chunk[g + 1] = h_chunk[g] + (count + kMtfgChunk - 1) / kMtfgChunk;",
         "const int whole = K / kMtfgParams, rest = K - whole * kMtfgParams;",
         "if (rest > 4) sum(std::integral_constant<int, 8>(), 1, whole * kMtfgParams);",

@@ -79,7 +79,7 @@ HOST_RULES = {
         "static const int kMtftTile = kMtftBlock * kMtftTrials;",
         "const int64_t s = ((int64_t)kMtftSlicesPerCu * cus + n_groups - 1) / n_groups;",
         "return s < 1 ? 1 : (s > kMtfMaxSlices ? kMtfMaxSlices : s);",
-        "h_slice[g + 1] = h_slice[g] + mtf_slices(count, max_slices);",
+        "const MtfgStaging staging(group_first, n_groups, K, mtft_max_slices(cus, n_groups), workspace);",
         "const int64_t n_out = plan.n_out, all_outputs = (n_out + kMtftOut - 1) / kMtftOut * kMtftOut;",
         "const int64_t tile_room = (int64_t)(kMtftSlabBytes / ((size_t)slice_grid * kMtftTile)) - MTFT_MOMENTS * 8;",
         "const int64_t outputs = std::min<int64_t>(all_outputs, tile_room / 16 / kMtftOut * kMtftOut);",
@@ -87,11 +87,17 @@ HOST_RULES = {
         "const size_t trial_bytes = (size_t)slice_grid * (MTFT_MOMENTS * 8 + (size_t)outputs * 16);",
         "int64_t most = (int64_t)(kMtftSlabBytes / trial_bytes) / kMtftTile * kMtftTile;",
         "most = std::min<int64_t>(most, ((int64_t)M + kMtftTile - 1) / kMtftTile * kMtftTile);",
-        "if (K <= 4) launch(std::integral_constant<int, 4>(), first, n);",
-        "else if (K <= 8) launch(std::integral_constant<int, 8>(), first, n);",
-        "else if (K <= 12) launch(std::integral_constant<int, 12>(), first, n);",
-        "else launch(std::integral_constant<int, 16>(), first, n);",
+        "trial_launches(M, most, [&](int first, int n) { trial_columns<MTFG_MAX_PARAMETERS>(K, launch, first, n); });",
         "for (int64_t base = lo; base < hi; base += kMtftRays) {"),
+    "prt_trials.hpp": (  # (the ladder and the loop over the launches, as prt_frame_mtf_tolerance calls them)
+        'static_assert(MAX == 16 || MAX == 20, "the ladder ends at 16 or at 20 columns");',
+        "if (K <= 4) launch(std::integral_constant<int, 4>(), more...);",
+        "else if (K <= 8) launch(std::integral_constant<int, 8>(), more...);",
+        "else if (K <= 12) launch(std::integral_constant<int, 12>(), more...);",
+        "else if (MAX == 16 || K <= 16) launch(std::integral_constant<int, 16>(), more...);",
+        "for (int first = 0; first < M; first += (int)most) launch(first, M - first < most ? M - first : (int)most);"),
+    "prt_mtf_gradient.hpp": (  # (the staging's slices, cut by the limit this pass hands it)
+        "h_slice[g + 1] = h_slice[g] + mtf_slices(count, max_slices);",),
     "prt_mtf.hpp": (
         "const int64_t s = (count + kMtfMinSlice - 1) / kMtfMinSlice;",
         "return s < 1 ? 1 : (s > max_slices ? max_slices : s);"),

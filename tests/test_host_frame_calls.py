@@ -221,6 +221,13 @@ def cases():
             np.array([[0.1, 0.0], [0.0, 0.1], [0.1, 0.1]]), world_unit_um=1000.0, follow=follow,
             compensators=("focus", "tilt", 1) if follow == "ray" else ()))
     add("psf_gradient-nothing", lambda f: f.sensitivity(7, rigid, system, wavefront=True).psf_gradient(**psf))
+    # (the three calls of tests/test_host_mtf_tolerance.py::test_the_pass_calls_the_library_as_the_header_declares_it)
+    trials, sampling = np.array([[0.1, 0.0], [0.0, 0.1], [0.1, 0.1]]), dict(azimuths=(0.0,), focus=(0.0, 0.1))
+    add("mtf_tolerance-centre", lambda f: sensitivity(rigid, slopes=True, rays_per_source=4)(f).mtf_tolerance(
+        trials, nu, compensators=("focus",), centre=point, **sampling))
+    add("mtf_tolerance", lambda f: sensitivity(rigid, slopes=True)(f).mtf_tolerance(trials, nu, **sampling))
+    add("mtf_tolerance-nothing", lambda f: f.sensitivity(7, rigid, system, slopes=True).mtf_tolerance(
+        trials, nu, reference="fixed", **sampling))
     return out
 
 
@@ -249,7 +256,7 @@ def test_the_golden_record_holds_every_entry_point_of_frame_py():
     seen = {name for case in golden.values() for name, _ in case["calls"]}
     table = signatures(engine)
     wanted = set(frame_entry_points())
-    assert len(wanted) >= 28 and wanted <= set(table)
+    assert len(wanted) >= 29 and wanted <= set(table)
     wanted |= {name + "_workspace_bytes" for name in wanted if name + "_workspace_bytes" in table}
     assert wanted <= seen, sorted(wanted - seen)
 

@@ -200,8 +200,8 @@ def test_mtf_tolerance_needs_slopes_and_refuses_what_it_cannot_serve():
 def test_the_pass_calls_the_library_as_the_header_declares_it(monkeypatch):
     """tests/test_host_frame_calls.py's stand-in library (every argument checked against the binding's ctypes kinds)
     under ``mtf_tolerance``: one size call, then the entry with 27 arguments, the workspace and the stream -- on a frame
-    with rows and on a selection of nothing, with the centroid and with a given centre.  The call lives in
-    pyrayt_amd/mtf_tolerance.py, beside frame.py whose entry points that file's golden record enumerates."""
+    with rows and on a selection of nothing, with the centroid and with a given centre.  The call is
+    frame.py's own, and that file's golden record holds these three cases too."""
     torch = pytest.importorskip("torch")
     import pyrayt_amd.frame as F
     from pyrayt_amd.scene import MATERIAL_DTYPE, PRIM_DTYPE

@@ -67,7 +67,13 @@ HOST_RULES = {
         "PsfPlan plan = psf_plan(cus, n_selected, buckets, buckets, 1, 1, 16, 0, 1);",
         "int64_t chunk = (int64_t)(kPsfSlabBytes / ((size_t)buckets * slices * 16)) / kTolTile * kTolTile;",
         "for (int64_t base = lo; base < hi; base += kTolRays) {",
-        "const int64_t chunks = (group_first[g + 1] - group_first[g] + kTolMomentChunk - 1) / kTolMomentChunk;"),
+        "const int64_t chunks = (group_first[g + 1] - group_first[g] + kTolMomentChunk - 1) / kTolMomentChunk;",
+        "trial_columns<TOL_MAX_COLUMNS>(C, sum, first, n);"),
+    "prt_trials.hpp": (  # (the instantiation and the launches, as prt_frame_tolerance calls them)
+        'static_assert(MAX == 16 || MAX == 20, "the ladder ends at 16 or at 20 columns");',
+        "else if (MAX == 16 || K <= 16) launch(std::integral_constant<int, 16>(), more...);",
+        "else if constexpr (MAX == 20) launch(std::integral_constant<int, 20>(), more...);",
+        "for (int first = 0; first < M; first += (int)most) launch(first, M - first < most ? M - first : (int)most);"),
     "prt_psf.hpp": G.HOST_RULES["prt_psf.hpp"],
 }
 
