@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own, prt_frame_energy_tolerance with its own.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -1043,6 +1043,84 @@ int prt_frame_mtf_tolerance(int device, const double* rows, int64_t ld, int64_t 
                             int n_azimuths, const double* focus, int n_focus, const double* trials, int n_trials,
                             int compensate_focus, double* otf_out, double* moments_out, double* focus_out,
                             double* record_out, void* workspace, void* stream);
+
+/* Monte Carlo tolerancing of the geometric enclosed energy: the energy within given radii and the radius that holds
+ * given fractions, through focus, of many perturbed systems, from the rows, jacobian_out and slopes_out of one
+ * prt_frame_launch_sensitivity call, without a re-trace.  It composes prt_frame_mtf_tolerance's moved ray with
+ * prt_frame_energy's exact integer count.
+ *
+ * Definitions.
+ * Rays, groups, staging: prt_frame_mtf_tolerance's -- rays, groups, axes, weights, the kept / missed / unfollowed rule,
+ *   the held centre C_g (the kept rays' centroid, or a given point), the staged (p, s, w) a ray and (dp_k, ds_k) a ray and
+ *   parameter.  The ray in trial m:
+ *     P_rm = p_r + sum_k t_mk dp_rk        S_rm = s_r + sum_k t_mk ds_rk
+ *   by the same fma chains in parameter order (mtft_move), so with the same bits as there.
+ * Moments and refocus: k_mtft_moments and k_mtft_focus run as they are on the same staging and slices, so moments_out,
+ *   focus_out and the first seven doubles of the record have the bits prt_frame_mtf_tolerance gives for the same
+ *   sensitivity, trials and compensate_focus.  delta_m is 0 without the focus compensator, and delta*_m with it.  Plane f of
+ *   trial m lies at delta = focus[f] + delta_m (one rounded sum).
+ * Centre in a plane: with follow_centroid != 0 the trial's own centroid there, from the trial's own moments,
+ *     c = m_P / m_0 + delta * (m_S / m_0)
+ *   per component, the two quotients, the product and the sum each rounded on their own, without fused multiply-add: a
+ *   float64 line on moments_out reproduces its bits.  This is what prt_frame_energy of the perturbed system measures
+ *   from.  With follow_centroid == 0, c = 0: distances are measured from the held centre C_g -- the pixel or the fibre
+ *   stays where it is while the spot walks off it.
+ * Distance: d_rm(delta) is prt_frame_energy's distance of the moved ray {P_rm, S_rm}: x = (P + delta S) - c per
+ *   component, product, sum and difference each rounded, then the shape's rule (PRT_ENERGY_CIRCLE, SQUARE, SLIT_E1,
+ *   SLIT_E2); a coordinate that comes out NaN counts as d = +inf.
+ * Integer weights: prt_frame_energy's power-of-two rule, once per call -- the weights do not change with the trial.  Per
+ *   group, count = the group's number of selected rows (kept or not, so the sum cannot overflow whatever is kept),
+ *   w_max = the largest staged weight = f 2^E with 0.5 <= f < 1 (an integer atomic max on the bit image),
+ *   B = bit_length(count); q_r = (uint64) floor(ldexp(w_r, 62 - E - B)) and W_g = sum q_r by integer adds.  A row that is
+ *   left out is staged with w = 0 and counts nothing.
+ * Outputs, per (group, trial, plane):
+ *     count[j]  = sum over d_r <= R_j of q_r, an exact uint64
+ *     energy[j] = (double) count[j] / (double) W
+ *     radius[k] = the smallest d among the trial's distances in that plane with sum over d_r <= d of q_r >= T_k,
+ *                 T_k = clamp((uint64) ceil(phi_k * (double) W), 1, W): a ray's own distance, as prt_frame_energy defines it
+ *   A group without weight (W = 0, or no kept rays) gives NaN in energy and radius, and counts of 0.
+ *
+ * prt_frame_energy_tolerance: the leading arguments up to axes as prt_frame_mtf_tolerance takes them, with its refusals;
+ * shape and follow_centroid as prt_frame_energy's; radii (HOST, 0..256, finite, >= 0, strictly ascending), fractions
+ * (HOST, 0..16, in (0, 1]), not both empty; focus (HOST, 1..256 finite shifts); trials DEVICE (n_groups, M, K),
+ * 1 <= M <= 65536; compensate_focus as prt_frame_mtf_tolerance's.  Out, DEVICE, overwritten: count_out and energy_out
+ * (n_groups, M, n_focus, n_radii) (may be NULL when n_radii == 0), radius_out (n_groups, M, n_focus, n_fractions) (may
+ * be NULL when n_fractions == 0), moments_out (n_groups, M, 8), focus_out (n_groups, M), record_out (n_groups, 8):
+ * prt_frame_mtf_tolerance's seven doubles, then W_g as its bit image (a uint64 below 2^62 read as a double: memcpy it
+ * back).  workspace: prt_frame_energy_tolerance_workspace_bytes(n_selected, n_groups, K, n_radii, n_fractions, n_focus, M)
+ * device bytes (-1 for arguments the call would refuse).
+ * Passes: the centre, record and staging passes of prt_frame_mtf_gradient; the largest weight and the integer weights
+ * over the staging's chunks; then, per launch of whole tiles of 256 trials: prt_frame_mtf_tolerance's moments and their
+ * fold with the focus shift; the curve, a grid of (ray slice, trial tile, chunk of 8 (plane, radius) outputs,
+ * plane-major) workgroups whose threads own one trial each, move the ray once, form the distance once per plane of the
+ * chunk and add q where d <= R into uint64 registers, and its fold over the slices; the select, 21 passes of a
+ * most-significant-bits-first multiway bisection on the 63-bit image of d (for non-negative doubles, bit order is
+ * numeric order): per (ray slice, trial tile, (plane, 4 fractions)) a thread counts, per fraction, sum q [key <=
+ * threshold_j] for the seven thresholds that split its prefix's interval in eight, and a fold over the slices appends
+ * three bits -- no atomics, no LDS windows; after the last pass the prefix is the radius.  A launch's partial counts
+ * -- slices * trials * 224 bytes at the least -- stay under the 256 MiB slab cap: the trials run in launches of whole
+ * tiles, under them the curve's outputs in launches of whole chunks and the select's (plane, 4 fractions) items in
+ * launches of as many as fit, and a call whose single tile cannot fit (more than 4681 groups) is refused with
+ * PRT_ERR_ARG naming the cap: a result is never truncated.
+ * A group's slices follow its count of selected rows, n_groups and the device's CU count -- never n_rows, the frame's
+ * other rows, M, K, the output counts or the trial values --, every sum that decides an output is an integer sum and
+ * there are no floating-point atomics: every output is the same, bit for bit, on every run, on any frame that holds the
+ * same selected rows, for a trial alone or among 65536 at any place, with a finite parameter appended whose trial values
+ * are all 0 (where the kept set is the same), and however the launches fall under the cap.  The arguments are checked
+ * before any kernel is launched (the slab cap once the device's CU count is known).  Stream-ordered; the call returns
+ * when the stream has reached its end.
+ * Accuracy: tests/energy_tolerance_reference.py derives the band of a ray's distance from the counted roundings of the
+ * moved point; every check of a count or a radius is then an exact integer inequality. */
+int64_t prt_frame_energy_tolerance_workspace_bytes(int64_t n_selected, int n_groups, int n_parameters, int n_radii,
+                                                   int n_fractions, int n_focus, int n_trials);
+int prt_frame_energy_tolerance(int device, const double* rows, int64_t ld, int64_t n_rows, const int64_t* selected,
+                               int64_t n_selected, const int64_t* group_first, int n_groups, int weight_column,
+                               const double* jacobian, const double* slopes, int n_parameters, const double* reference,
+                               const double* axes, int shape, int follow_centroid, const double* radii, int n_radii,
+                               const double* fractions, int n_fractions, const double* focus, int n_focus,
+                               const double* trials, int n_trials, int compensate_focus, uint64_t* count_out,
+                               double* energy_out, double* radius_out, double* moments_out, double* focus_out,
+                               double* record_out, void* workspace, void* stream);
 
 /* Ray-aberration curves of the frame: each ray's row at a surface joined by ray id with the row where the ray was
  * launched (examples/lens_design.ipynb cells 12-13 join the two cuts of the frame with isin(id)), its transverse and

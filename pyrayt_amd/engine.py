@@ -229,6 +229,10 @@ def _signatures():
         "prt_frame_mtf_tolerance": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_int, c_p,
                                             c_p, c_p, c_int, c_p, c_int, c_p, c_int, c_p, c_int, c_int, c_p, c_p, c_p, c_p,
                                             c_p, c_p]),
+        "prt_frame_energy_tolerance_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_int, c_int, c_int]),
+        "prt_frame_energy_tolerance": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_int,
+                                               c_p, c_p, c_int, c_int, c_p, c_int, c_p, c_int, c_p, c_int, c_p, c_int,
+                                               c_int, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     }
 
 

@@ -2736,7 +2736,53 @@ class ToleranceRun:
         return pd.DataFrame(rows).sort_values("worst", kind="stable").reset_index(drop=True)
 
 
-class MTFToleranceRun:
+class _TrialMoments:
+    """What ``MTFToleranceRun`` and ``EnergyToleranceRun`` read from the device's moments (G, M + 1, 8) and record, in
+    longdouble on the host: the two passes hand over the same block, so they share this arithmetic."""
+
+    def _read_moments(self, moments, record, focus_shift, focus):
+        """Sets ``focus``, ``moments``, ``record`` and the per-group fields; returns the whole (G, M + 1, ...) arrays
+        ``focus_shift``, ``centroid``, ``rms_radius`` and ``best_focus``, the nominal trial last."""
+        LD = np.longdouble
+        self.focus = np.asarray(focus, dtype=float)
+        self.moments, self.record = np.asarray(moments, dtype=float), np.asarray(record, dtype=float)
+        self.centre, self.sum_weights = self.record[:, :3], self.record[:, 3]
+        self.n_rays, self.n_missed, self.n_unfollowed = (np.nan_to_num(self.record[:, k]).astype(np.int64) for k in (4, 5, 6))
+        shift = np.asarray(focus_shift, dtype=float)
+        wide = self.moments.astype(LD)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sw = np.where(wide[..., 0] > 0, wide[..., 0], np.nan)
+            mean_p, mean_s = wide[..., 1:3] / sw[..., None], wide[..., 3:5] / sw[..., None]
+            var_p = wide[..., 5] / sw - np.sum(mean_p * mean_p, axis=-1)
+            cov = wide[..., 6] / sw - np.sum(mean_p * mean_s, axis=-1)
+            var_s = wide[..., 7] / sw - np.sum(mean_s * mean_s, axis=-1)
+            best = np.where(var_s > 0, -cov / np.where(var_s > 0, var_s, 1), np.where(np.isnan(sw), np.nan, 0))
+            planes = self.focus.astype(LD)[None, None, :] + shift.astype(LD)[:, :, None]  # (G, M, F)
+            self._mean_p, self._mean_s, self._planes = mean_p, mean_s, planes
+            square = var_p[..., None] + 2 * planes * cov[..., None] + planes * planes * var_s[..., None]
+            rms_radius = np.sqrt(np.maximum(square, 0)).astype(float)
+        return dict(focus_shift=shift, centroid=self.centroid_at(0), rms_radius=rms_radius, best_focus=best.astype(float))
+
+    def centroid_at(self, plane):
+        """(G, M + 1, 2): every trial's centroid (the nominal trial last) in the plane ``focus[plane] + focus_shift``."""
+        return (self._mean_p + self._planes[:, :, plane, None] * self._mean_s).astype(float)
+
+    def _one_at_a_time(self):
+        """K, for a run on ``Tolerances.sensitivity_table()``'s trials; ``ValueError`` for other trials."""
+        K = self.n_parameters
+        t = self.trials
+        one_at_a_time = t.shape == (2 * K + 1, K) and not np.any(t[0])
+        for k in range(K if one_at_a_time else 0):
+            hot = np.zeros(K, dtype=bool)
+            hot[k] = True
+            one_at_a_time &= (not np.any(t[1 + 2 * k][~hot]) and not np.any(t[2 + 2 * k][~hot])
+                              and t[1 + 2 * k, k] == -t[2 + 2 * k, k])
+        if not one_at_a_time:
+            raise ValueError("table: the trials are not Tolerances.sensitivity_table()'s")
+        return K
+
+
+class MTFToleranceRun(_TrialMoments):
     """What ``Sensitivity.mtf_tolerance`` returns (numpy arrays), G groups, M trials, K parameters, F focus shifts, A
     azimuths, N frequencies.  ``trials`` (M, K) as drawn; ``otf`` (G, M, F, A, N) complex and ``mtf`` = |otf|: the
     geometric OTF of every trial under the linear ray model, the merit fully nonlinear in the moved landing points
@@ -2757,45 +2803,24 @@ class MTFToleranceRun:
 
     def __init__(self, trials, otf, moments, focus_shift, record, frequencies, azimuths, focus, parameters,
                  compensators=(), reference="fixed"):
-        LD = np.longdouble
         self.frequencies = np.asarray(frequencies, dtype=float)
         self.azimuths = np.asarray(azimuths, dtype=float)
-        self.focus = np.asarray(focus, dtype=float)
         self.parameters, self.compensators, self.reference = tuple(parameters), tuple(compensators), reference
-        self.moments, self.record = np.asarray(moments, dtype=float), np.asarray(record, dtype=float)
-        self.centre, self.sum_weights = self.record[:, :3], self.record[:, 3]
-        self.n_rays, self.n_missed, self.n_unfollowed = (np.nan_to_num(self.record[:, k]).astype(np.int64) for k in (4, 5, 6))
-        shift = np.asarray(focus_shift, dtype=float)
-        wide = self.moments.astype(LD)
-        with np.errstate(invalid="ignore", divide="ignore"):
-            sw = np.where(wide[..., 0] > 0, wide[..., 0], np.nan)
-            mean_p, mean_s = wide[..., 1:3] / sw[..., None], wide[..., 3:5] / sw[..., None]
-            var_p = wide[..., 5] / sw - np.sum(mean_p * mean_p, axis=-1)
-            cov = wide[..., 6] / sw - np.sum(mean_p * mean_s, axis=-1)
-            var_s = wide[..., 7] / sw - np.sum(mean_s * mean_s, axis=-1)
-            best = np.where(var_s > 0, -cov / np.where(var_s > 0, var_s, 1), np.where(np.isnan(sw), np.nan, 0))
-            planes = self.focus.astype(LD)[None, None, :] + shift.astype(LD)[:, :, None]  # (G, M, F)
-            self._mean_p, self._mean_s, self._planes = mean_p, mean_s, planes
-            square = var_p[..., None] + 2 * planes * cov[..., None] + planes * planes * var_s[..., None]
-            rms_radius = np.sqrt(np.maximum(square, 0)).astype(float)
+        whole = self._read_moments(moments, record, focus_shift, focus)
+        mean_p, mean_s, planes = self._mean_p, self._mean_s, self._planes
         otf = np.asarray(otf)
         if reference == "centroid":  # (about each trial's own centroid in each plane: the phase of the shift back)
             angle = np.radians(self.azimuths)
             kc, ks = np.cos(angle)[:, None] * self.frequencies, np.sin(angle)[:, None] * self.frequencies  # (A, N)
-            c = (mean_p[:, :, None, :] + planes[..., None] * mean_s[:, :, None, :]).astype(float)  # (G, M, F, 2)
+            with np.errstate(invalid="ignore"):
+                c = (mean_p[:, :, None, :] + planes[..., None] * mean_s[:, :, None, :]).astype(float)  # (G, M, F, 2)
             otf = otf * np.exp(2j * np.pi * (c[..., 0, None, None] * kc + c[..., 1, None, None] * ks))
-        centroid = self.centroid_at(0)
-        whole = dict(otf=otf, mtf=np.abs(otf), focus_shift=shift, centroid=centroid, rms_radius=rms_radius,
-                     best_focus=best.astype(float))
+        whole = dict(otf=otf, mtf=np.abs(otf), **whole)
         for name, value in whole.items():
             setattr(self, name, value[:, :-1])
         self.nominal = SimpleNamespace(**{name: value[:, -1] for name, value in whole.items()})
         self.trials = np.asarray(trials, dtype=float)[:-1]
         self.n_parameters, self.n_trials = len(self.parameters), len(self.trials)
-
-    def centroid_at(self, plane):
-        """(G, M + 1, 2): every trial's centroid (the nominal trial last) in the plane ``focus[plane] + focus_shift``."""
-        return (self._mean_p + self._planes[:, :, plane, None] * self._mean_s).astype(float)
 
     def _outputs(self, frequency, azimuth, plane):
         """``mtf`` (G, M, ...) cut to the selected plane (an index), azimuths and frequencies (indices, or None: all)."""
@@ -2840,22 +2865,103 @@ class MTFToleranceRun:
         plane (indices) against the nominal trial at -width and +width, each the worst (lowest) over the azimuths
         (``dmtf_minus``, ``dmtf_plus``), and ``worst``, the lower of the two; the rows sorted worst first.
         ``ValueError`` for other trials."""
-        K = self.n_parameters
-        t = self.trials
-        one_at_a_time = t.shape == (2 * K + 1, K) and not np.any(t[0])
-        for k in range(K if one_at_a_time else 0):
-            hot = np.zeros(K, dtype=bool)
-            hot[k] = True
-            one_at_a_time &= (not np.any(t[1 + 2 * k][~hot]) and not np.any(t[2 + 2 * k][~hot])
-                              and t[1 + 2 * k, k] == -t[2 + 2 * k, k])
-        if not one_at_a_time:
-            raise ValueError("table: the trials are not Tolerances.sensitivity_table()'s")
+        K, t = self._one_at_a_time(), self.trials
         merit = self.mtf[group, :, plane, :, frequency]  # (M, A)
         change = (merit[1:] - merit[0]).min(axis=1)
         rows = {"parameter": np.arange(K), "width": t[2::2][np.arange(K), np.arange(K)], "dmtf_minus": change[0::2],
                 "dmtf_plus": change[1::2]}
         rows["worst"] = np.fmin(rows["dmtf_minus"], rows["dmtf_plus"])
         return pd.DataFrame(rows).sort_values("worst", kind="stable").reset_index(drop=True)
+
+
+class EnergyToleranceRun(_TrialMoments):
+    """What ``Sensitivity.energy_tolerance`` returns (numpy arrays), G groups, M trials, K parameters, F focus shifts, R
+    radii, N fractions.  ``trials`` (M, K) as drawn; ``energy`` (G, M, F, R): the share of the energy within each of
+    ``radii`` of every trial under the linear ray model, the merit fully nonlinear in the moved landing points, and
+    ``count`` (G, M, F, R) uint64, the exact integer count it is the quotient of (``energy = count / total``);
+    ``radius`` (G, M, F, N): the radius (half-width for a square or a slit) that holds each of ``fractions``, a ray's own
+    distance (the pass of include/prt.h under the energy tolerancing; it states the formulas) -- all at the planes
+    ``focus[f] + focus_shift``, about the trial's own centroid there (``follow_centroid``) or about the held centre.
+    ``focus_shift`` (G, M), ``best_focus`` (G, M), ``rms_radius`` (G, M, F), ``centroid`` (G, M, 2) and
+    ``centroid_at(plane)`` from the device's moments, as in ``MTFToleranceRun``.  ``nominal``: the same fields for the
+    all-zero trial.  Per group ``total`` (uint64: W, the sum of the integer weights), ``centre`` (G, 3), ``sum_weights``,
+    ``n_rays``, ``n_missed``, ``n_unfollowed``; ``moments`` the device's (G, M + 1, 8) block (the nominal trial last),
+    ``record`` its (G, 7) block, both with the bits ``mtf_tolerance`` gives.  A group without rays, or without weight,
+    is NaN, its counts 0."""
+
+    FIELDS = ("energy", "count", "radius", "focus_shift", "centroid", "rms_radius", "best_focus")
+
+    def __init__(self, trials, count, energy, radius, moments, focus_shift, record, radii, fractions, focus, parameters,
+                 shape="circle", compensators=(), follow_centroid=True):
+        self.radii, self.fractions = np.asarray(radii, dtype=float), np.asarray(fractions, dtype=float)
+        self.parameters, self.compensators = tuple(parameters), tuple(compensators)
+        self.shape, self.follow_centroid = shape, bool(follow_centroid)
+        record = np.ascontiguousarray(record, dtype=np.float64)
+        self.total = record[:, 7].copy().view(np.uint64)  # (the device hands W over as its bit image)
+        whole = self._read_moments(moments, record[:, :7], focus_shift, focus)
+        whole = dict(energy=np.asarray(energy, dtype=float), count=np.asarray(count).astype(np.uint64, copy=False),
+                     radius=np.asarray(radius, dtype=float), **whole)
+        for name, value in whole.items():
+            setattr(self, name, value[:, :-1])
+        self.nominal = SimpleNamespace(**{name: value[:, -1] for name, value in whole.items()})
+        self.trials = np.asarray(trials, dtype=float)[:-1]
+        self.n_parameters, self.n_trials = len(self.parameters), len(self.trials)
+
+    @staticmethod
+    def _share(cut, passed):
+        """(G): the mean of ``passed`` (G, M) over the trials, NaN for a group whose ``cut`` (G, M) is not finite."""
+        return np.where(np.all(np.isfinite(cut), axis=1), np.mean(passed, axis=1), np.nan)
+
+    def yield_(self, fraction_at_least, radius=0, plane=0):
+        """(G): the share of the trials that put at least ``fraction_at_least`` of the energy within ``radii[radius]``
+        in the plane ``plane`` (indices); NaN for a group without rays."""
+        cut = self.energy[:, :, plane, radius]
+        with np.errstate(invalid="ignore"):
+            return self._share(cut, cut >= fraction_at_least)
+
+    def yield_radius(self, at_most, fraction=-1, plane=0):
+        """(G): the share of the trials whose radius of ``fractions[fraction]`` is at most ``at_most`` in the plane
+        ``plane`` (indices); NaN for a group without rays."""
+        cut = self.radius[:, :, plane, fraction]
+        with np.errstate(invalid="ignore"):
+            return self._share(cut, cut <= at_most)
+
+    def percentiles(self, q=(2, 10, 50, 90, 98), fraction=-1, plane=0):
+        """(G, len(q)): the percentiles over the trials of the radius of one fraction in one plane (indices)."""
+        q = np.atleast_1d(np.asarray(q, dtype=float))
+        with np.errstate(invalid="ignore"):
+            return np.percentile(self.radius[:, :, plane, fraction], q, axis=1).T
+
+    def to_pandas(self):
+        """One row per (group, trial): ``focus_shift``, ``best_focus``, per plane ``rms_radius_<f>``, per output
+        ``energy_<f>_<j>`` and ``radius_<f>_<k>`` (indices of plane, radius, fraction) and the drawn parameters
+        ``p_k``."""
+        G, M = self.focus_shift.shape
+        data = {"source_id": np.repeat(np.arange(G), M), "trial": np.tile(np.arange(M), G),
+                "focus_shift": self.focus_shift.ravel(), "best_focus": self.best_focus.ravel()}
+        for f in range(len(self.focus)):
+            data[f"rms_radius_{f}"] = self.rms_radius[:, :, f].ravel()
+        for f in range(len(self.focus)):
+            for j in range(len(self.radii)):
+                data[f"energy_{f}_{j}"] = self.energy[:, :, f, j].ravel()
+            for k in range(len(self.fractions)):
+                data[f"radius_{f}_{k}"] = self.radius[:, :, f, k].ravel()
+        for k in range(self.n_parameters):
+            data[f"p_{k}"] = np.tile(self.trials[:, k], G)
+        return pd.DataFrame(data)
+
+    def table(self, group=0, fraction=-1, plane=0):
+        """For a run on ``Tolerances.sensitivity_table()``: per parameter the change of the radius of one fraction in
+        one plane (indices) against the nominal trial at -width and +width (``dradius_minus``, ``dradius_plus``), and
+        ``worst``, the larger of the two; the rows sorted worst (largest growth of the radius) first.  ``ValueError``
+        for other trials."""
+        K, t = self._one_at_a_time(), self.trials
+        merit = self.radius[group, :, plane, fraction]  # (M)
+        change = merit[1:] - merit[0]
+        rows = {"parameter": np.arange(K), "width": t[2::2][np.arange(K), np.arange(K)], "dradius_minus": change[0::2],
+                "dradius_plus": change[1::2]}
+        rows["worst"] = np.fmax(rows["dradius_minus"], rows["dradius_plus"])
+        return pd.DataFrame(rows).sort_values("worst", ascending=False, kind="stable").reset_index(drop=True)
 
 
 class Sensitivity:
@@ -3253,6 +3359,60 @@ class Sensitivity:
                                                          trials, bool(compensators))
         return MTFToleranceRun(plain, otf, moments, shift, record, nu, theta, planes, self.parameters, compensators,
                                reference)
+
+    def energy_tolerance(self, trials, radii=None, *, fractions=(0.5, 0.8, 0.9), shape="circle", focus=(0.0,),
+                         compensators=(), follow_centroid=True, centre=None, axis=None, basis=None):
+        """Monte Carlo tolerancing of the geometric enclosed energy from this one trace: the energy within ``radii`` and
+        the radius that holds each of ``fractions``, through focus, of M perturbed systems, an ``EnergyToleranceRun``.
+        Needs ``slopes`` (``sensitivity(slopes=True)``).  The rays move under the linear ray model exactly as in
+        ``mtf_tolerance`` (the same staged quantities, kept rays, held centre, moments and least-squares refocus, bit
+        for bit), while the merit stays fully nonlinear in the moved points: every trial's energy is counted exactly
+        with ``enclosed_energy``'s power-of-two integer weights, and its radius is a ray's own distance (the entry
+        point of include/prt.h under the energy tolerancing states the formulas).
+
+        ``trials``: an (M, K) array of parameter changes, or a ``(Tolerances, M)`` pair to draw them; M <= 65535; the
+        nominal all-zero trial is appended (``EnergyToleranceRun.nominal``).  ``radii``: None or 1 to 256 values,
+        finite, >= 0 and strictly ascending; ``fractions``: None or 1 to 16 values in (0, 1]; not both None; ``shape``
+        and ``focus`` as in ``enclosed_energy``; ``compensators``: ``()`` or ``("focus",)`` as in ``mtf_tolerance``;
+        ``centre``, ``axis`` and ``basis`` as in ``mtf_gradient``.  ``follow_centroid=True``: distances from the trial's
+        own centroid in each plane, what ``enclosed_energy()`` of the perturbed system reports; ``False``: from the
+        held centre -- the pixel or the fibre stays where it is while the spot walks off it, the case a decentre
+        tolerance is about.  Second-order terms and rays whose path changes under a perturbation are out of scope."""
+        self._need_slopes("energy_tolerance")
+        from . import energy_tolerance
+
+        if isinstance(compensators, str):
+            compensators = (compensators,)
+        try:
+            compensators = tuple(compensators)
+        except TypeError:
+            compensators = (compensators,)
+        if compensators not in ((), ("focus",)):
+            raise ValueError(f'compensators: () or ("focus",) (got {compensators!r})')
+        K = self.n_parameters
+        drawn = _drawn_trials(trials, K)
+        edges = np.zeros(0) if radii is None else _mtf_values(radii, "radii", 256, "finite, >= 0 and strictly ascending",
+                                                              non_negative=True)
+        if len(edges) > 1 and not np.all(np.diff(edges) > 0):
+            raise ValueError("radii: 1 to 256 numbers, finite, >= 0 and strictly ascending")
+        phi = np.zeros(0) if fractions is None else _mtf_values(fractions, "fractions", 16, "in (0, 1]")
+        if np.any(phi <= 0) or np.any(phi > 1):
+            raise ValueError("fractions: 1 to 16 numbers, in (0, 1]")
+        if not len(edges) and not len(phi):
+            raise ValueError("radii: give radii, fractions or both")
+        if not isinstance(shape, str) or shape not in _ENERGY_SHAPES:
+            raise ValueError(f"shape: one of {sorted(_ENERGY_SHAPES)} (got {shape!r})")
+        planes = _mtf_values(focus, "focus", 256, "finite shifts along the axis")
+        axes = pupil_axes(axis, basis)
+        head = self._selected_rows()
+        centres = None if centre is None else _group_points(centre, head.n_groups, head.rows.device, "centre: None, a point")
+        plain = np.concatenate([drawn, np.zeros((1, K))])
+        trials = np.array(np.broadcast_to(plain[None], (head.n_groups,) + plain.shape), order="C")  # (the same for all)
+        count, energy, radius, moments, shift, record = energy_tolerance.device_run(
+            head, self.jacobian, self.slopes, centres, axes, shape, follow_centroid, edges, phi, planes, trials,
+            bool(compensators))
+        return EnergyToleranceRun(plain, count, energy, radius, moments, shift, record, edges, phi, planes, self.parameters,
+                                  shape, compensators, follow_centroid)
 
     def focus_gradient(self, axis=(1.0, 0.0, 0.0)):
         """(groups, K): the derivative of the least-squares best-focus shift along ``axis``, per parameter.  Past the
