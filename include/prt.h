@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own, prt_frame_energy_tolerance with its own.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own, prt_frame_energy_tolerance with its own, prt_frame_ghosts_count and prt_frame_ghosts_emit with theirs.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -1453,6 +1453,65 @@ int prt_frame_fresnel_coated(int device, const double* rows, int64_t ld, const i
                              const int32_t* has_substrate, const double* thicknesses, const double* wavelengths,
                              int n_wavelengths, const double* indices, double* transmittance_out, double* field_out,
                              int64_t* record_out, void* workspace, void* stream);
+
+/* ---- Ghost rays: Fresnel reflections spawned from the frame (no counterpart upstream) ---------------------------------
+ * prt_frame_fresnel says how much energy every refracting surface takes from a ray; this pass says where it goes.  At
+ * every refraction a ray's rows describe, at the surfaces the caller lists, one reflected child ray leaves with the
+ * energy that did not go through.  The children are an ordinary (13, n) ray set for prt_trace, ordered so that every
+ * (parent group, surface) is a "source" of the per-source frame passes.  The trace is not touched.
+ *
+ * Definitions.
+ * Frame: whole and generation-major, ids as prt_frame_fresnel wants them; k = id - id0 is the ray's number.
+ * transmittance: n_rows doubles, what prt_frame_fresnel or prt_frame_fresnel_coated wrote for this frame.  The pass
+ *   takes 1 - T for R: it holds for the bare interface and for stacks of real layer indices, not for absorbing ones.
+ * Interface: for a ray's row j in generation g >= 1 and its row p in g - 1 (the join of prt_frame_fresnel: per id a stamp
+ *   and its last row), ni = index[p], nt = index[j], S = surface[p].  A child is spawned at the end of row p when the join
+ *   is good; ni and nt are finite, > 0 and unequal (a refraction: mirrors, total internal reflection and undeviated rays
+ *   spawn nothing); S is in the list; t[p] and t[j] are finite; and e = intensity[p] * (t[p] - t[j]) has e > 0 and
+ *   e >= min_intensity.
+ * Child, every product and sum rounded on its own (no FMA contraction), dot products as (x x' + y y') + z z':
+ *     ui = unit(tilt[p]); ut = unit(tilt[j]); m = ni ui - nt ut; N = unit(m); ci = dot(ui, N)
+ *     ur = ui - (2.0 ci) N                                    (not renormalised)
+ *     origin = (x1, y1, z1)[p] + ray_offset ur, w = 1; direction = (ur, 0)
+ *     generation 0, intensity e, wavelength[p], index ni
+ *   A child with a component that is not finite is not spawned and is counted (invalid).
+ * Buckets, groups, ids: bucket = parent_group * n_surfaces + (position of S in the list), parent_group =
+ *   floor(k / rays_per_group) (0 when rays_per_group <= 0, which needs n_groups = 1); a parent_group >= n_groups is
+ *   PRT_ERR_ARG.  The marked rows p are put in order of their buckets, in frame order inside a bucket, by the stable
+ *   counting sort of the image passes.  The non-empty buckets, numbered 0 .. G' - 1 in bucket order, are the groups of the
+ *   child set; stride = the largest bucket's count; a child's id = group * stride + (its rank in its bucket).  Child c
+ *   of the ray set stands at column c in that order.
+ * Open rows: a ray that leaves the system has no later row, so the interface at the end of its last row is not seen.
+ *   Rows that end on a listed surface and have no successor are counted as open.
+ * Counters (record_out, HOST 8 int64): spawned; dropped (0 < e < min_intensity); dark (e <= 0 at a listed refraction with
+ *   finite t); invalid; open; then G', stride, 0.
+ *
+ * prt_frame_ghosts_count: surfaces HOST n_surfaces in [1, 64] distinct ids; n_groups * n_surfaces <= 65535;
+ * min_intensity finite >= 0, ray_offset finite.  Out: bucket_count_out HOST n_groups * n_surfaces int64, the children of
+ * every bucket; record_out.  workspace: prt_frame_ghosts_count_workspace_bytes(n_rows, n_ids, n_buckets) device bytes
+ * (-1 for arguments the call would refuse); it keeps what prt_frame_ghosts_emit needs and must be handed to it unchanged.
+ * prt_frame_ghosts_emit: the same rows, n_rows (all generations), n_ids, transmittance, ray_offset and n_buckets; n_children
+ * = the sum of bucket_count_out (anything else: PRT_ERR_ARG, as is a count_workspace of another call).  Out, overwritten:
+ * rays_out DEVICE (13, ld_rays) doubles, ld_rays >= n_children; parent_row_out DEVICE n_children int64, the row p of
+ * every child.  workspace: prt_frame_ghosts_emit_workspace_bytes(n_rows, n_buckets) device bytes of its own; the count's
+ * workspace is only read, so it serves any number of emits.
+ * Guarantees: the marking is one launch per generation in order on the stream, one row a thread, 256 threads a
+ * workgroup; no two lanes write one row's mark; no floating-point atomics, no floating-point sums across rows; the
+ * counters are integers, summed by ballot and LDS and added with one atomic per workgroup: every output is the same
+ * bits on every run, and a permutation of the rows inside a generation permutes the children inside their buckets and
+ * changes nothing else.  Nothing is read or written out of bounds on a refused frame.  All arguments are checked before
+ * a device is touched.  Stream-ordered; both calls return when the stream has reached their end. */
+int64_t prt_frame_ghosts_count_workspace_bytes(int64_t n_rows, int64_t n_ids, int n_buckets);
+int prt_frame_ghosts_count(int device, const double* rows, int64_t ld, const int64_t* rows_per_generation,
+                           int n_generations, double id0, int64_t n_ids, const double* transmittance,
+                           const int64_t* surfaces, int n_surfaces, double rays_per_group, int n_groups,
+                           double min_intensity, double ray_offset, int64_t* bucket_count_out, int64_t* record_out,
+                           void* workspace, void* stream);
+int64_t prt_frame_ghosts_emit_workspace_bytes(int64_t n_rows, int n_buckets);
+int prt_frame_ghosts_emit(int device, const double* rows, int64_t ld, int64_t n_rows, int64_t n_ids,
+                          const double* transmittance, double ray_offset, int n_buckets, int64_t n_children,
+                          const void* count_workspace, double* rays_out, int64_t ld_rays, int64_t* parent_row_out,
+                          void* workspace, void* stream);
 
 /* ---- Sensitivities of the frame: differential ray tracing (no counterpart upstream) -----------------------------------
  * d(landing point)/d(parameter) of every ray, for K rigid motions of surfaces, from ONE trace: the rows of a ray, joined

@@ -98,6 +98,7 @@ static int raise_lds_limits() {
 #include "prt_paths.hpp"
 #include "prt_fresnel.hpp"
 #include "prt_coatings.hpp"
+#include "prt_ghosts.hpp"
 #include "prt_sensitivity.hpp"
 #include "prt_selection.hpp"
 #include "prt_trials.hpp"

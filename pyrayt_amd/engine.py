@@ -196,6 +196,12 @@ def _signatures():
         "prt_frame_fresnel_coated_workspace_bytes": (c_i64, [c_i64, c_i64]),
         "prt_frame_fresnel_coated": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_p, c_int, c_p, c_p, c_int,
                                              c_int, c_p, c_p, c_p, c_p, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),
+        "prt_frame_ghosts_count_workspace_bytes": (c_i64, [c_i64, c_i64, c_int]),
+        "prt_frame_ghosts_count": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_p, c_int, c_d, c_int, c_d, c_d,
+                                           c_p, c_p, c_p, c_p]),
+        "prt_frame_ghosts_emit_workspace_bytes": (c_i64, [c_i64, c_int]),
+        "prt_frame_ghosts_emit": (c_int, [c_int, c_p, c_i64, c_i64, c_i64, c_p, c_d, c_int, c_i64, c_p, c_p, c_i64, c_p, c_p,
+                                          c_p]),
         "prt_frame_sensitivity_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_i64]),
         "prt_frame_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p, c_int,
                                           c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),

@@ -1076,6 +1076,25 @@ class DeviceFrame:
         out.launch_states = "per_ray" if v is None else "polarised"
         return out
 
+    def ghosts(self, fresnel, surfaces=None, rays_per_source=None, n_groups=None, min_intensity=0.0, ray_offset=1e-6,
+               system=None):
+        """The ghost rays of the frame: at every refraction the rows describe, at ``surfaces``, one reflected child ray
+        with the energy ``fresnel`` (``self.fresnel(...)``, of this very frame) says did not go through,
+        ``intensity[p] * (T[p] - T[j])`` for a ray's consecutive rows p, j.  Returns a ``pyrayt_amd.ghosts.GhostRays``:
+        the (13, n) ray set, ordered by (parent group, surface) so that every ghost path is a source of the per-source
+        passes of its trace, per child the row it left, the groups' keys and the counters.  ``surfaces``: ids, objects
+        with ``get_id()`` or components, at most 64 ids; None: every refracting surface of ``system`` (components, a
+        tracer or a snapshot).  ``rays_per_source`` / ``n_groups``: the parent groups, ``id // rays_per_source`` (at
+        most 65535 groups x surfaces).  ``min_intensity``: children below it are dropped and counted.  ``ray_offset``:
+        how far a child starts off its surface.  A ray that leaves the system has no later row, so the reflection at
+        the end of its last row is not seen: ``n_open`` counts such rows (``pyrayt_amd.ghosts.housing``).  Refused: a
+        frame that is not whole, a ``Fresnel`` of another frame, coatings with an absorbing layer at a listed
+        surface (there R is not 1 - T).  One HIP launch per generation and the image passes' stable counting sort;
+        include/prt.h states the definitions."""
+        from . import ghosts
+
+        return ghosts.spawn(self, fresnel, surfaces, rays_per_source, n_groups, min_intensity, ray_offset, system)
+
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
                     rays_per_source=None, n_groups=None, wavefront=None, slopes=False):
