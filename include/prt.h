@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own, prt_frame_energy_tolerance with its own, prt_frame_ghosts_count and prt_frame_ghosts_emit with theirs.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
+#define PRT_VERSION 240 /* 0.2.4: prt_frame_optical_path, prt_frame_wavefront_workspace_bytes, prt_frame_wavefront; added since without a change to what was there: prt_frame_psf, prt_frame_vector_psf, prt_frame_mtf, prt_frame_launch_index, prt_frame_ray_aberrations, prt_frame_energy, prt_frame_paths, prt_frame_fresnel, prt_frame_fresnel_coated, prt_frame_sensitivity, prt_frame_design_sensitivity, prt_frame_opd_sensitivity, prt_frame_launch_sensitivity, prt_frame_mtf_gradient, prt_frame_psf_gradient, prt_frame_psf_focus and their workspace functions (prt_frame_psf_gradient_workspace_bytes and prt_frame_psf_focus_workspace_bytes among them), prt_frame_tolerance and prt_frame_tolerance_moments with theirs, prt_frame_mtf_tolerance with its own, prt_frame_energy_tolerance with its own, prt_frame_ghosts_count and prt_frame_ghosts_emit with theirs, prt_frame_scatter_count and prt_frame_scatter_emit with theirs.  0.2.3: prt_frame_range, prt_frame_histogram_workspace_bytes, prt_frame_histogram.  0.2.2: record plans (prt_record_plan, prt_trace_set_plan); per-tile records retired (PRT_TRACE_NO_TILE_RECORDS ignored, telemetry slots 8 / 9 count plan launches / misses). 0.2.1: prt_frame_mean_square, PRT_TRACE_BUSY / prt_trace_batch_busy, prt_comm_info.  0.2.0: prt_interact takes the caller-shaded state, PRT_MAT_TABLE / PRT_MAT_HOST,
                            prt_scene_set_index_tables, prt_gather_hits / prt_scatter_shaded, prt_unique_values,
                            prt_frame_stats_sharded / prt_frame_pivots / prt_frame_finish, prt_trace_telemetry fills 12 slots.  A caller built against another version must not load this library:
                            prt_version() is there to be compared with this constant (pyrayt_amd.engine.library does). */
@@ -1512,6 +1512,84 @@ int prt_frame_ghosts_emit(int device, const double* rows, int64_t ld, int64_t n_
                           const double* transmittance, double ray_offset, int n_buckets, int64_t n_children,
                           const void* count_workspace, double* rays_out, int64_t ld_rays, int64_t* parent_row_out,
                           void* workspace, void* stream);
+
+/* ---- Scattered rays: stray light spawned from the frame by BSDF (no counterpart upstream) --------------------------------
+ * The ghost pass follows the specular reflections of refracting surfaces; this pass follows surface scatter.  Every row
+ * that lands on a listed surface sends N = rays_per_hit child rays back into the half space it came from (reflective
+ * scatter, BRDF), each with the energy its surface's BSDF gives the direction drawn for it.  The children are an ordinary
+ * (13, n) ray set for prt_trace, ordered so that every (parent group, surface) is a "source" of the per-source frame
+ * passes.  The trace is not touched.
+ *
+ * Definitions.  Every product and sum is rounded on its own (no FMA contraction), in the order written; dot(a, b) =
+ * (ax bx + ay by) + az bz; unit(v) = v / sqrt(dot(v, v)) component by component.
+ * Which rows spawn: row p spawns when surface[p] is in the list, whatever happens to its ray afterwards (absorbed,
+ *   refracted, reflected): no join by ray id, no open rows.  id[p] and generation[p] of such a row are integers >= 0
+ *   (id < 2^53, generation < 2^31), PRT_ERR_ARG otherwise.  The frame need not be whole.
+ * Geometry of row p: x = (x1, y1, z1)[p]; ui = unit(tilt[p]); n = the world normal of the surface's primitive at
+ *   (x, 1) as the trace computes it (its 4x4 products are fma chains, the normalisations IEEE divisions by one length),
+ *   times normal_scale, negated when dot(n, ui) > 0; I = intensity[p].  The primitive is the entry of `prims` (HOST
+ *   n_prims prt_prim sorted by surface_id, ids distinct: the table of prt_frame_sensitivity) with the surface's id,
+ *   found by bisection; a listed surface that is not there is PRT_ERR_ARG.
+ * BSDF: shift-invariant, f(b), b = |beta - beta0|, beta and beta0 the projections of the scattered and of the specular
+ *   direction on the tangent plane; beta0 is the projection of ui, so with d = uo - ui, dn = dot(d, n),
+ *   w = d - dn n:  b = sqrt(dot(w, w)) in [0, 2].  A model is a table of T + 1 = 1025 doubles, finite and >= 0, uniform
+ *   in u = sqrt(b / 2):  q = sqrt(0.5 b) * 1024.0; k = (int)q when q < 1023.0, else 1023;
+ *   f = tab[k] + (q - k) * (tab[k + 1] - tab[k]); f = NaN when q is not >= 0 (b not a number).  tables: HOST
+ *   n_models x 1025 doubles, n_models in [1, 16]; models[s] in [0, n_models) is the model of surfaces[s].
+ * Random numbers: Philox4x32-10 (multipliers D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85) on the counter
+ *   (low 32 bits of id, high 32 bits of id, generation, child) under the key (low, high 32 bits of seed); from its
+ *   output words x0..x3:  u1 = (((x0 << 32) | x1) >> 11) * 2^-53, u2 likewise from x2, x3;  a = 2.0 u1 - 1.0,
+ *   b = 2.0 u2 - 1.0.  A child's sample depends on (seed, id, generation, child) alone.
+ * Sampling: s = a a + b b; a sample with s >= 1 (not s < 1) is rejected: counted, no child.  The basis of a unit vector
+ *   m (Duff et al. 2017):  sg = copysign(1.0, mz); h = -1.0 / (sg + mz); g = (mx my) h; sx = sg mx;
+ *   t1 = (1.0 + (sx mx) h, sg g, -sx); t2 = (g, sg + (my my) h, -my).
+ * target == NULL, the cosine-weighted hemisphere: c = sqrt(1.0 - s), rejected when c is not > 0; (t1, t2) of n;
+ *   uo = (a t1 + b t2) + c n per component (not renormalised); E = ((4.0 I) f) / N.  With the rejections the density is
+ *   cos(theta_o) / 4 per solid angle; for f = rho / pi the expected sum of the children's energies is rho I.
+ * target != NULL (HOST 13 doubles: centre (3), normal (3), e1 (3), e2 (3), radius R), a disk: (e1, e2) is the basis
+ *   above of the normal, formed by the caller; the normal is a unit vector to 1e-12, R > 0.
+ *   y = centre + R (a e1 + b e2) per component; v = y - x; r2 = dot(v, v); uo = v / sqrt(r2) per component;
+ *   cos_o = dot(n, uo); a child with cos_o <= 0 is below the horizon: counted, no child; cos_t = |dot(normal, uo)|;
+ *   E = ((((I f) cos_o) cos_t) (4.0 (R R))) / (N r2).
+ * Child: origin = x + ray_offset uo, w = 1; direction = (uo, 0); generation 0; intensity E; wavelength[p]; index[p]
+ *   (the medium the ray travelled in).  Fates, in this order: rejected; below; dark (E <= 0); dropped (E <
+ *   min_intensity); invalid (E, the wavelength, the index or a component of origin or direction is not finite: a cube
+ *   normal on an edge, a row without a direction); spawned.
+ * Items, buckets, groups, ids: item p N + c is child c of row p.  bucket = parent_group * n_surfaces + (place of the
+ *   surface in the list), parent_group = floor(id / rays_per_group) (0 when rays_per_group <= 0, which needs n_groups
+ *   = 1); a parent_group that is not below n_groups is PRT_ERR_ARG.  The spawned items are put in order of their
+ *   buckets, in item order (row, then child) inside a bucket, by the stable counting sort of the image passes.  The
+ *   non-empty buckets, numbered 0 .. G' - 1, are the groups of the child set; stride = the largest bucket's count; a
+ *   child's id = group * stride + (its rank in its bucket).
+ * Counters (record_out, HOST 8 int64): spawned, rejected, below, dark, dropped, invalid; then G', stride.
+ *
+ * prt_frame_scatter_count: rows DEVICE (15, ld), n_rows <= ld; rays_per_hit in [1, 64], n_rows * rays_per_hit < 2^31 - 1;
+ * surfaces HOST n_surfaces in [1, 64] distinct ids; n_groups * n_surfaces <= 65535; min_intensity finite >= 0,
+ * ray_offset finite.  Out: bucket_count_out HOST n_groups * n_surfaces int64, the children of every bucket; record_out.
+ * workspace: prt_frame_scatter_count_workspace_bytes(n_rows, rays_per_hit, n_buckets, n_models) device bytes (-1 for
+ * arguments the call would refuse); it keeps what prt_frame_scatter_emit needs -- the marks, the arguments, the listed
+ * primitives and the tables -- and must be handed to it unchanged.
+ * prt_frame_scatter_emit: the same rows, n_rows, rays_per_hit, n_buckets and n_models; n_children = the sum of
+ * bucket_count_out (anything else: PRT_ERR_ARG, as is a count_workspace of another call).  Out, overwritten: rays_out
+ * DEVICE (13, ld_rays) doubles, ld_rays >= n_children; parent_row_out DEVICE n_children int64 and child_out DEVICE
+ * n_children int32: the row p and the number c of every child.  workspace:
+ * prt_frame_scatter_emit_workspace_bytes(n_rows, rays_per_hit, n_buckets) device bytes of its own; the count's
+ * workspace is only read, so it serves any number of emits.
+ * Guarantees: one item a thread, 256 threads a workgroup; no floating-point atomics, no floating-point sums across
+ * items; the counters are integers, summed by ballot and LDS and added with one atomic per workgroup: every output is
+ * the same bits on every run, a child's bits (its id apart) do not depend on where its row stands in the frame or on
+ * the other rows, and its direction does not depend on N.  All arguments are checked before a device is touched.
+ * Stream-ordered; both calls return when the stream has reached their end. */
+int64_t prt_frame_scatter_count_workspace_bytes(int64_t n_rows, int rays_per_hit, int n_buckets, int n_models);
+int prt_frame_scatter_count(int device, const double* rows, int64_t ld, int64_t n_rows, const prt_prim* prims,
+                            int n_prims, const int64_t* surfaces, const int* models, int n_surfaces,
+                            const double* tables, int n_models, const double* target, int rays_per_hit, uint64_t seed,
+                            double rays_per_group, int n_groups, double min_intensity, double ray_offset,
+                            int64_t* bucket_count_out, int64_t* record_out, void* workspace, void* stream);
+int64_t prt_frame_scatter_emit_workspace_bytes(int64_t n_rows, int rays_per_hit, int n_buckets);
+int prt_frame_scatter_emit(int device, const double* rows, int64_t ld, int64_t n_rows, int rays_per_hit, int n_buckets,
+                           int n_models, int64_t n_children, const void* count_workspace, double* rays_out,
+                           int64_t ld_rays, int64_t* parent_row_out, int* child_out, void* workspace, void* stream);
 
 /* ---- Sensitivities of the frame: differential ray tracing (no counterpart upstream) -----------------------------------
  * d(landing point)/d(parameter) of every ray, for K rigid motions of surfaces, from ONE trace: the rows of a ray, joined

@@ -14,12 +14,13 @@ from . import materials
 from . import components
 from . import utils
 from . import ghosts
+from . import scatter
 from .rayset import RaySet
 from .tracer import RayTracer
 from .frame import Deformation, DeviceFrame, EnergyToleranceRun, IndexChange, Motion, MTFGradient, MTFToleranceRun, PSFGradient, PSFScan, Sensitivity, SourceMotion, ToleranceRun, Tolerances, WavelengthChange
 from .g3d.objects import pin
 from .utils import wavelength_to_rgb
 
-__all__ = ["RayTracer", "RaySet", "DeviceFrame", "Motion", "Deformation", "IndexChange", "SourceMotion", "WavelengthChange", "Sensitivity", "MTFGradient", "PSFGradient", "PSFScan", "Tolerances", "ToleranceRun", "MTFToleranceRun", "EnergyToleranceRun", "pin", "materials", "components", "g3d", "utils", "ghosts",
+__all__ = ["RayTracer", "RaySet", "DeviceFrame", "Motion", "Deformation", "IndexChange", "SourceMotion", "WavelengthChange", "Sensitivity", "MTFGradient", "PSFGradient", "PSFScan", "Tolerances", "ToleranceRun", "MTFToleranceRun", "EnergyToleranceRun", "pin", "materials", "components", "g3d", "utils", "ghosts", "scatter",
            "wavelength_to_rgb"]
 __version__ = "0.1.0"

@@ -12,7 +12,7 @@
 //   prt_abi_states.hpp      extern "C": per-state entry points (+ prt_host_shade.hpp: a caller's own Material.trace())
 //   prt_trace_runtime.hpp   extern "C": prt_trace*, the ticket runtime
 //   prt_abi_render_ops.hpp  extern "C": renderers, operations
-//   prt_gather.hpp, prt_join.hpp (the join by ray id of the passes after it), prt_frame.hpp, prt_histogram.hpp, prt_wavefront.hpp, prt_psf.hpp (first the Huygens core that prt_vector_psf.hpp and prt_psf_gradient.hpp stand on too), prt_psf_focus.hpp, prt_vector_psf.hpp, prt_mtf.hpp, prt_aberrations.hpp, prt_energy.hpp, prt_paths.hpp, prt_fresnel.hpp, prt_coatings.hpp, prt_sensitivity.hpp, prt_selection.hpp (the selected rows of a sensitivity call, as the five passes below check them), prt_trials.hpp (the trial core of the two Monte Carlo passes), prt_mtf_gradient.hpp, prt_psf_gradient.hpp, prt_tolerance.hpp, prt_mtf_tolerance.hpp, prt_energy_tolerance.hpp   extern "C" + kernels: frame
+//   prt_gather.hpp, prt_join.hpp (the join by ray id of the passes after it), prt_frame.hpp, prt_histogram.hpp, prt_wavefront.hpp, prt_psf.hpp (first the Huygens core that prt_vector_psf.hpp and prt_psf_gradient.hpp stand on too), prt_psf_focus.hpp, prt_vector_psf.hpp, prt_mtf.hpp, prt_aberrations.hpp, prt_energy.hpp, prt_paths.hpp, prt_fresnel.hpp, prt_coatings.hpp, prt_sensitivity.hpp, prt_scatter.hpp (scattered rays spawned from the frame: below the ghost pass and the surface table it reads), prt_selection.hpp (the selected rows of a sensitivity call, as the five passes below check them), prt_trials.hpp (the trial core of the two Monte Carlo passes), prt_mtf_gradient.hpp, prt_psf_gradient.hpp, prt_tolerance.hpp, prt_mtf_tolerance.hpp, prt_energy_tolerance.hpp   extern "C" + kernels: frame
 //                    re-assembly across ranks, reductions, histograms, optical path and wavefront over the frame
 //
 // Data layout in HBM
@@ -100,6 +100,7 @@ static int raise_lds_limits() {
 #include "prt_coatings.hpp"
 #include "prt_ghosts.hpp"
 #include "prt_sensitivity.hpp"
+#include "prt_scatter.hpp"
 #include "prt_selection.hpp"
 #include "prt_trials.hpp"
 #include "prt_mtf_gradient.hpp"

@@ -202,6 +202,12 @@ def _signatures():
         "prt_frame_ghosts_emit_workspace_bytes": (c_i64, [c_i64, c_int]),
         "prt_frame_ghosts_emit": (c_int, [c_int, c_p, c_i64, c_i64, c_i64, c_p, c_d, c_int, c_i64, c_p, c_p, c_i64, c_p, c_p,
                                           c_p]),
+        "prt_frame_scatter_count_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int]),
+        "prt_frame_scatter_count": (c_int, [c_int, c_p, c_i64, c_i64, c_p, c_int, c_p, c_p, c_int, c_p, c_int, c_p, c_int,
+                                            ctypes.c_uint64, c_d, c_int, c_d, c_d, c_p, c_p, c_p, c_p]),
+        "prt_frame_scatter_emit_workspace_bytes": (c_i64, [c_i64, c_int, c_int]),
+        "prt_frame_scatter_emit": (c_int, [c_int, c_p, c_i64, c_i64, c_int, c_int, c_int, c_i64, c_p, c_p, c_i64, c_p, c_p,
+                                           c_p, c_p]),
         "prt_frame_sensitivity_workspace_bytes": (c_i64, [c_i64, c_int, c_int, c_int, c_i64]),
         "prt_frame_sensitivity": (c_int, [c_int, c_p, c_i64, c_p, c_int, c_d, c_i64, c_p, c_int, c_p, c_p, c_p, c_int,
                                           c_p, c_p, c_i64, c_p, c_int, c_int, c_p, c_p, c_p, c_p, c_p, c_p]),

@@ -1095,6 +1095,25 @@ class DeviceFrame:
 
         return ghosts.spawn(self, fresnel, surfaces, rays_per_source, n_groups, min_intensity, ray_offset, system)
 
+    def scatter(self, models, system, toward=None, rays_per_hit=1, seed=0, rays_per_source=None, n_groups=None,
+                min_intensity=0.0, ray_offset=1e-6):
+        """The scattered rays of the frame: every row that lands on a surface of ``models`` -- a dict ``{surface |
+        component | tuple of them: pyrayt_amd.scatter.Scatter}``, at most 64 surfaces and 16 models -- sends
+        ``rays_per_hit`` (1 to 64) child rays back into the half space it came from, whatever happens to its ray
+        afterwards.  ``toward=None`` draws them cosine-weighted over the hemisphere, ``E = 4 I f / N`` each;
+        ``toward=Target.disk(centre, normal, radius)`` sends them to uniform points of the disk, ``E = I f cos_o cos_t
+        4 R^2 / (N r^2)``: importance sampling towards an imager.  ``system`` (components, a tracer or a snapshot)
+        gives the primitive behind every surface id and so the normal.  Random numbers are Philox4x32-10 on (``seed``,
+        ray id, generation, child): a child does not depend on where its row stands or on the other rows.  Returns a
+        ``pyrayt_amd.scatter.ScatterRays``, the interface of ``GhostRays``: the (13, n) ray set ordered by (source,
+        surface) with the children of a bucket in (row, child) order, ``parent_row``, ``child``, the groups' keys and
+        the counters.  To scatter what is left after Fresnel losses call it on ``fresnel.apply()``.  The frame need not
+        be whole.  One HIP pass and the image passes' stable counting sort; include/prt.h states the definitions."""
+        from . import scatter
+
+        return scatter.spawn(self, models, system, toward, rays_per_hit, seed, rays_per_source, n_groups, min_intensity,
+                             ray_offset)
+
     # --- sensitivities: differential ray tracing (no counterpart upstream) -------------------------------------------
     def sensitivity(self, surface, parameters, system, *, weights="intensity", reference="centroid", generation=None,
                     rays_per_source=None, n_groups=None, wavefront=None, slopes=False):

@@ -71,9 +71,13 @@ class GhostRays:
     on a listed surface and have no successor: their reflections are not seen)."""
 
     def __init__(self, frame, rays, parent_row, counts, record, surfaces, ray_offset):
+        self._children(frame, rays, parent_row, counts, surfaces, ray_offset)
+        self.n_spawned, self.n_dropped, self.n_dark, self.n_invalid, self.n_open = (int(v) for v in record[:5])
+
+    def _children(self, frame, rays, parent_row, counts, surfaces, ray_offset):
+        """The ray set, its buckets and its groups (what ``pyrayt_amd.scatter.ScatterRays`` has too)."""
         self.frame, self.rays, self.parent_row = frame, rays, parent_row
         self.counts, self.surfaces, self.ray_offset = np.asarray(counts, dtype=np.int64), tuple(surfaces), float(ray_offset)
-        self.n_spawned, self.n_dropped, self.n_dark, self.n_invalid, self.n_open = (int(v) for v in record[:5])
         self.bucket = np.flatnonzero(self.counts > 0)
         self.n_groups = len(self.bucket)
         self.stride = int(self.counts.max()) if len(self.counts) else 0
@@ -96,10 +100,10 @@ class GhostRays:
         scene = scene_or_tracer._device_scene() if hasattr(scene_or_tracer, "_device_scene") else scene_or_tracer
         if generation_limit is None:
             if not hasattr(scene_or_tracer, "get_generation_limit"):
-                raise ValueError("GhostRays.trace: generation_limit is needed with a DeviceScene")
+                raise ValueError(f"{type(self).__name__}.trace: generation_limit is needed with a DeviceScene")
             generation_limit = scene_or_tracer.get_generation_limit()
         if getattr(getattr(scene, "snapshot", None), "host_surfaces", None):
-            raise TypeError("GhostRays.trace: the scene has a material with a user-defined trace()")
+            raise TypeError(f"{type(self).__name__}.trace: the scene has a material with a user-defined trace()")
         if len(self) == 0:
             return DeviceFrame(torch.zeros((engine.RECORD_COLS, 0), dtype=torch.float64, device=self.rays.device), [0])
         rows, counts = scene.trace(self.rays, int(generation_limit), self.ray_offset, plan=None)
